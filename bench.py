@@ -7,6 +7,7 @@ masked-MSE + backward + (all-reduce) + Adam on one mini-batch already resident i
 Prints ONE JSON line on rank 0.
 """
 import argparse
+import gc
 import json
 import os
 import sys
@@ -1150,6 +1151,30 @@ def exchange_plan(n, ff_params, rnn_params, ff_step_ms, rnn_step_ms, rnn_small_s
     return plan
 
 
+def ff_step_outputs(model, loss):
+    """What the last timed train step handed its caller, copied to the host: the step's loss (this rank's share
+    of the global mean), the parameters it updated and the gradients it computed.  Weights are taken in the
+    reference's state-dict shape [N, K] (without the row-pitch padding of the flat buffers), so that two builds
+    with different layouts compare array for array.  float32 throughout; 4.6 MB for the 425-512-512-187 model."""
+    arrays = {"loss": loss}
+    for i in range(len(model.layout)):
+        arrays["layer%d_weight" % i] = model.weight(i)
+        arrays["layer%d_bias" % i] = model.bias(i)
+        arrays["layer%d_weight_grad" % i] = model.weight(i, model.grads)
+        arrays["layer%d_bias_grad" % i] = model.bias(i, model.grads)
+    return {k: np.ascontiguousarray(v.detach().cpu().numpy()) for k, v in arrays.items()}
+
+
+def write_outputs(out_dir, arrays):
+    """--dump-outputs: one <name>.npy per array."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": os.path.abspath(out_dir), "arrays": sorted(arrays),
+            "bytes": int(sum(a.nbytes for a in arrays.values()))}
+
+
 def visible_gpus():
     """Number of GPUs this process may use, WITHOUT touching HIP in this process: the compute nodes of
     the KFD topology (sysfs) that have SIMDs AND whose render node this user can open (a container or
@@ -1238,7 +1263,12 @@ def main():
                          "API on synthetic files in a temporary directory, ~3 GB at 1024; 0 = skip)")
     ap.add_argument("--bilstm-utts", type=int, default=64,
                     help="utterances per GPU of the BiLSTM / BiGRU (config 3) section (0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, updated parameters, gradients; rank 0) "
+                         "as DIR/<name>.npy, to compare two builds output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: start the N ranks ourselves, before this process
@@ -1326,15 +1356,22 @@ def main():
     # everything the timed region needs is created BEFORE the barrier
     stream = torch.cuda.current_stream()
     evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+    # After the barrier the device queue is empty, so a garbage-collector pass while the first timed step is being
+    # launched adds its ~0.1 ms to that step, and whether one falls there depends on how many objects the set-up
+    # happened to create.  Emptying generation 0 here (well under a millisecond) keeps the collector out of the
+    # timed steps.
+    gc.collect(0)
     barrier()
     t0 = time.perf_counter()
     evs[0].record(stream)
     for i in range(args.steps):
-        step(i)
+        loss = step(i)
         evs[i + 1].record(stream)
     t_launched = time.perf_counter() - t0
     barrier()
     dt = time.perf_counter() - t0
+    # taken before the GEMM replay and the clock sampling below overwrite the gradients and parameters
+    outputs = ff_step_outputs(model, loss) if args.dump_outputs and rank == 0 else None
     # GEMM-only replay of the six GEMM launches of a step, RIGHT BEHIND the timed region (same clocks, same
     # batches in the same order, events on the launch stream): how much of a step its dominant kernel is.
     # (Round 4 ran this replay after the RNN sections, on batch 0 only: its 1.022 ms per step exceeded the
@@ -1534,6 +1571,8 @@ def main():
         if args.force_dist:
             out["forced_collectives"] = ("RCCL initialised with {} rank(s); every collective of the "
                                          "N > 1 path was issued".format(world))
+        if outputs is not None:
+            out["dumped_outputs"] = write_outputs(args.dump_outputs, outputs)
         out.update(extra)
         print(json.dumps(out))
     if dist_on:

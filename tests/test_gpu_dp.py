@@ -184,16 +184,18 @@ def test_bench_starts_its_own_ranks(gpu):
     assert out["world"]["n_gpus"] == 2 and out["bilstm"]["n_gpus"] == 2
 
 
-def test_bench_with_eight_ranks_on_one_device(gpu):
-    """The driver's `bench.py --gpus 8` protocol with all eight ranks on this one device (gloo collectives; never a
-    measurement): rendezvous on 127.0.0.1, per-rank seeds, barrier + max-over-ranks timing, one JSON line from rank
-    0, both forms of BASELINE config 3 (64 utterances per GPU, and 64 in all = 8 per GPU) and the exchange plan the
+def test_bench_with_four_ranks_on_one_device(gpu):
+    """The driver's `bench.py --gpus N` protocol for N > 2 with all ranks on this one device (gloo collectives; never
+    a measurement): rendezvous on 127.0.0.1, per-rank seeds, barrier + max-over-ranks timing, one JSON line from rank
+    0, both forms of BASELINE config 3 (8 utterances per GPU, and 8 in all = 2 per GPU) and the exchange plan the
     first real SCALE record is to be checked against (reference hook: ModularModelHandlerPyTorch.py:732-735,
-    :757-763)."""
+    :757-763).  Four ranks, not eight: with this process they are five holding the one device, and a shared
+    device takes at most six processes at once."""
+    world = 4
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--share-gpu",
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--share-gpu",
                           "--steps", "2", "--warmup", "1", "--ramp-steps", "0", "--utts-per-gpu", "2",
                           "--world-utts", "0", "--bilstm-utts", "8", "--trainer-utts", "0", "--no-cpu-baseline"],
                          env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1500)
@@ -201,12 +203,12 @@ def test_bench_with_eight_ranks_on_one_device(gpu):
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
     out = json.loads(lines[0])
-    assert out["n_gpus"] == 8 and "shared_gpu" in out and out["value"] > 0 and out["scaling"] == "weak"
+    assert out["n_gpus"] == world and "shared_gpu" in out and out["value"] > 0 and out["scaling"] == "weak"
     assert out["config"]["utts_per_gpu"] == 2
-    assert out["bilstm"]["n_gpus"] == 8 and out["bilstm"]["utterances_global"] == 64
-    assert out["bilstm_global_batch"]["utterances_global"] == 8 and out["bilstm_global_batch"]["n_gpus"] == 8
+    assert out["bilstm"]["n_gpus"] == world and out["bilstm"]["utterances_global"] == 8 * world
+    assert out["bilstm_global_batch"]["utterances_global"] == 8 and out["bilstm_global_batch"]["n_gpus"] == world
     plan = out["exchange_plan"]
-    assert plan["n_gpus"] == 8 and plan["bilstm_bigru_step"]["bytes_per_rank_per_step"] > 60e6
+    assert plan["n_gpus"] == world and plan["bilstm_bigru_step"]["bytes_per_rank_per_step"] > 60e6
     assert 0 < plan["config_3_as_worded"]["predicted_speedup_at_8_gpus"]["64_utterances_in_all"] < 2.5
     assert plan["config_3_as_worded"]["predicted_speedup_at_8_gpus"]["64_utterances_per_gpu"] > 6
 
@@ -342,13 +344,15 @@ def test_bench_counts_devices_without_touching_hip():
     assert n == torch.cuda.device_count()
 
 
-def _native_comm_two_rank_worker(rank, port, ret_dir):
-    """One of two processes, each on its own GPU: the library's communicator against torch.distributed's."""
+def _native_comm_two_rank_worker(rank, port, ret_dir, device):
+    """One of two processes, on GPU `device`: the library's communicator against torch.distributed's."""
+    import faulthandler
     import torch.distributed as dist
     from idiaptts_amd import lib, parallel
+    faulthandler.dump_traceback_later(240, exit=True)      # a rank stuck in a collective says where, and ends
     lib.require_gpu()
-    torch.cuda.set_device(rank)
-    dev = torch.device("cuda", rank)
+    torch.cuda.set_device(device)
+    dev = torch.device("cuda", device)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("nccl", rank=rank, world_size=2, device_id=dev)
     out = {"version": int(lib.load().itts_comm_version())}
@@ -370,26 +374,37 @@ def _native_comm_two_rank_worker(rank, port, ret_dir):
 
 def test_native_comm_two_ranks_equal_torch_distributed(gpu, tmp_path):
     """a one-rank reduction is the identity and proves nothing about the id broadcast, the
-    multi-rank ncclCommInitRank, or the enum values the binding hard-codes.  Two processes on two GPUs: sum,
+    multi-rank ncclCommInitRank, or the enum values the binding hard-codes.  Two processes, two ranks: sum,
     average and maximum of float32 / float64 buffers through itts_allreduce_flat equal torch.distributed's
-    bit for bit.  Skipped where fewer than two GPUs are visible (the one-GPU boxes of the test pool)."""
-    if torch.cuda.device_count() < 2:
-        pytest.skip("needs two GPUs")
+    (RCCL as well) bit for bit.  With two GPUs every rank has its own; with one, both ranks share device 0:
+    RCCL refuses two ranks of one host on one device ("Duplicate GPU detected"), so each rank gets a host id of
+    its own (NCCL_HOSTID), becomes a one-GPU node, and the ranks talk over RCCL's socket transport on the
+    loopback interface -- the same communicator set-up and collective calls."""
     import socket
     with socket.socket() as sock:
         sock.bind(("127.0.0.1", 0))
         port = sock.getsockname()[1]
-    env = dict(os.environ)
-    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    shared = torch.cuda.device_count() < 2
     procs = []
-    for rank in range(2):
-        code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r); import test_gpu_dp as t; "
-                "t._native_comm_two_rank_worker(%d, %d, %r)" % (ROOT, os.path.join(ROOT, "tests"), rank, port, str(tmp_path)))
-        procs.append(subprocess.Popen([sys.executable, "-c", code], env=env, stdout=subprocess.PIPE,
-                                      stderr=subprocess.STDOUT, text=True))
-    for p in procs:
-        out, _ = p.communicate(timeout=600)
-        assert p.returncode == 0, out[-3000:]
+    try:
+        for rank in range(2):
+            env = dict(os.environ)
+            env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+            if shared:
+                env.update(NCCL_HOSTID="itts-test-rank%d" % rank, NCCL_SOCKET_IFNAME="lo", NCCL_IB_DISABLE="1")
+            code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r); import test_gpu_dp as t; "
+                    "t._native_comm_two_rank_worker(%d, %d, %r, %d)"
+                    % (ROOT, os.path.join(ROOT, "tests"), rank, port, str(tmp_path), 0 if shared else rank))
+            procs.append(subprocess.Popen([sys.executable, "-c", code], env=env, stdout=subprocess.PIPE,
+                                          stderr=subprocess.STDOUT, text=True))
+        for p in procs:
+            out, _ = p.communicate(timeout=300)
+            assert p.returncode == 0, out[-3000:]
+    finally:
+        for p in procs:
+            if p.poll() is None:
+                p.kill()
+                p.wait()
     for rank in range(2):
         res = json.load(open(os.path.join(str(tmp_path), "rank{}.json".format(rank))))
         assert res.pop("version") >= 21000
