@@ -1844,6 +1844,73 @@ static int mlpg_check_offsets(const int64_t* h_offsets, int n_utts, int64_t* t_m
   return ITTS_OK;
 }
 
+// ---- the choice of form (ITTS_MLPG_FORM_*, include/idiaptts_amd.h) --------------------------------------------------
+// The override: solve | width << 4 | nt << 8 in one word, read once per call (a relaxed load; the environment was
+// read by getenv once per process -- five calls were 2-3 us of every call).  The first use seeds it from the
+// environment, so a later itts_mlpg_set_override is never overwritten by the seed.
+static std::atomic<int>& mlpg_override() {
+  static std::atomic<int> word{[] {
+    const int solve = getenv("ITTS_MLPG_RING") ? ITTS_MLPG_FORM_RING : getenv("ITTS_MLPG_STREAM") ? ITTS_MLPG_FORM_STREAM : 0;
+    const int width = getenv("ITTS_MLPG_NARROW") ? ITTS_MLPG_FORCE_OFF : getenv("ITTS_MLPG_WIDE") ? ITTS_MLPG_FORCE_ON : 0;
+    const int nt = getenv("ITTS_MLPG_NO_NT") ? ITTS_MLPG_FORCE_OFF : 0;
+    return solve | width << 4 | nt << 8;
+  }()};
+  return word;
+}
+
+static thread_local int t_mlpg_last_form = 0;
+
+// The whole decision, from the shape and the override alone (the dispatcher and itts_mlpg_choose_form both call it).
+static int mlpg_choose(int n_utts, int dim, int64_t t_max, int64_t t_total, bool f32, int ovr) {
+  const int solve = ovr & 15, width = (ovr >> 4) & 15, nt = (ovr >> 8) & 15;
+  const int f32_bits = f32 ? ITTS_MLPG_FORM_F32_ROWS | ITTS_MLPG_FORM_WIDENED_COPY : 0;
+  if (t_max < MLPG_SEQ_BELOW) return ITTS_MLPG_FORM_SWEEPS | f32_bits;
+  const int64_t units = (int64_t)n_utts * ((dim + RING_LANES - 1) / RING_LANES);
+  // reduce -> scan -> solve with 16-frame chunks, two chunks per workgroup, input rows staged through LDS; from about
+  // half a chip's worth of (utterance, 64 dimensions) units the one-pass kernel with the right-hand side in LDS
+  // (mlpg_ring_kernel: a sequential sweep per unit -- 200 us for a 2 000-frame utterance however few there are -- so
+  // small batches stay with the form above, which also divides an utterance among workgroups: 16 utterances 132
+  // against 225 us, 64: 174 / 201, 256: 372 / 307, 4 096: 4 520 / 3 608)
+  const bool ring = n_utts <= 65535 &&          // (an utterance per blockIdx.y)
+                    (solve == ITTS_MLPG_FORM_RING || (solve != ITTS_MLPG_FORM_STREAM && units >= MLPG_RING_FROM));
+  if (!ring) return ITTS_MLPG_FORM_STREAM | f32_bits;
+  // two dimensions a lane in the helpers (half the memory instructions) where that is what the kernel waits for: float32
+  // rows in batches of many rounds of workgroups -- 4 096 utterances 2.68 against 3.23 ms.  With float64 rows the
+  // kernel moves 3.8 - 4.1 TB/s either way (3.62 / 3.61 ms), and at 256 utterances the exchange's extra arithmetic
+  // costs 3 - 5 % (317 / 301 us; float32 231 / 223).  Even dim only.
+  const bool wide = dim % 2 == 0 && width != ITTS_MLPG_FORCE_OFF && (width == ITTS_MLPG_FORCE_ON || (f32 && units >= 1024));
+  if (f32) return ITTS_MLPG_FORM_RING | ITTS_MLPG_FORM_F32_ROWS | (wide ? ITTS_MLPG_FORM_WIDE : 0);
+  if (wide) return ITTS_MLPG_FORM_RING | ITTS_MLPG_FORM_WIDE;
+  // (float64 rows, y small enough to wait in the memory-side cache: input rows non-temporal -- see RING_LD)
+  const bool nt_in = nt != ITTS_MLPG_FORCE_OFF && (nt == ITTS_MLPG_FORCE_ON || t_total * dim * 8 <= (int64_t)192 << 20);
+  return ITTS_MLPG_FORM_RING | (nt_in ? ITTS_MLPG_FORM_NT_IN : 0);
+}
+
+extern "C" int itts_mlpg_choose_form(int n_utts, int dim, int64_t t_max, int64_t t_total, int rows_f32) {
+  ITTS_REQUIRE(n_utts >= 0 && dim > 0 && t_max >= 0 && t_total >= t_max, "bad sizes");
+  return mlpg_choose(n_utts, dim, t_max, t_total, rows_f32 != 0, mlpg_override().load(std::memory_order_relaxed));
+}
+
+extern "C" int itts_mlpg_set_override(int solve, int width, int nt) {
+  ITTS_REQUIRE(solve == 0 || solve == ITTS_MLPG_FORM_STREAM || solve == ITTS_MLPG_FORM_RING, "solve: 0, stream or ring");
+  ITTS_REQUIRE(width >= 0 && width <= ITTS_MLPG_FORCE_ON, "width: 0, ITTS_MLPG_FORCE_OFF or ITTS_MLPG_FORCE_ON");
+  ITTS_REQUIRE(nt >= 0 && nt <= ITTS_MLPG_FORCE_ON, "nt: 0, ITTS_MLPG_FORCE_OFF or ITTS_MLPG_FORCE_ON");
+  mlpg_override().store(solve | width << 4 | nt << 8, std::memory_order_relaxed);
+  return ITTS_OK;
+}
+
+extern "C" int itts_mlpg_get_override(int* solve, int* width, int* nt) {
+  const int ovr = mlpg_override().load(std::memory_order_relaxed);
+  if (solve) *solve = ovr & 15;
+  if (width) *width = (ovr >> 4) & 15;
+  if (nt) *nt = (ovr >> 8) & 15;
+  return ITTS_OK;
+}
+
+extern "C" int itts_mlpg_last_form(void) {
+  return t_mlpg_last_form;
+}
+
 static int mlpg_generation_impl(const double* d_feat, const float* d_feat32, int64_t ld_feat, int col0, int dim,
                                 const double* d_var, const int64_t* h_offsets, int n_utts,
                                 double* d_out, int64_t ld_out, int ocol0, void* d_scratch,
@@ -1868,22 +1935,9 @@ static int mlpg_generation_impl(const double* d_feat, const float* d_feat32, int
   int64_t* d_off = reinterpret_cast<int64_t*>(scratch + 3 * t_total * (int64_t)dim);
   int* d_nconv = reinterpret_cast<int*>(d_off + (t_total + 2));
   MlpgArgs a{d_feat, ld_feat, col0, dim, d_var, d_off, d_out, ld_out, ocol0, scratch, t_total, d_nconv};
-  // reduce -> scan -> solve with 16-frame chunks, two chunks per workgroup, input rows staged through
-  // LDS (uploads its own tables and computes the factor in its first launch); batches of short
-  // utterances: the sequential sweeps are as fast
-  // .. or, from about half a chip's worth of (utterance, 64 dimensions) units, one pass with the right-hand side in LDS
-  // (mlpg_ring_kernel: a sequential sweep per unit -- 200 us for a 2 000-frame utterance however few there are --
-  // so small batches stay with the form above, which also divides an utterance among workgroups: 16 utterances 132
-  // against 225 us, 64: 174 / 201, 256: 372 / 307, 4 096: 4 520 / 3 608).  ITTS_MLPG_STREAM=1 / ITTS_MLPG_RING=1 force one.
-  const int nblk = (dim + RING_LANES - 1) / RING_LANES;
-  // (the environment is read once per process: five getenv calls were 2-3 us of every call)
-  static const char* const force_stream = getenv("ITTS_MLPG_STREAM");
-  static const char* const force_ring = getenv("ITTS_MLPG_RING");
-  static const bool env_narrow = getenv("ITTS_MLPG_NARROW") != nullptr, env_wide = getenv("ITTS_MLPG_WIDE") != nullptr,
-                    env_no_nt = getenv("ITTS_MLPG_NO_NT") != nullptr;
-  const bool ring = n_utts <= 65535 &&          // (an utterance per blockIdx.y)
-                    (force_ring ? true : (force_stream ? false : (int64_t)n_utts * nblk >= MLPG_RING_FROM));
-  if (d_feat32 && !(t_max >= MLPG_SEQ_BELOW && ring)) {
+  const int form = mlpg_choose(n_utts, dim, t_max, t_total, d_feat32 != nullptr, mlpg_override().load(std::memory_order_relaxed));
+  t_mlpg_last_form = form;
+  if (form & ITTS_MLPG_FORM_WIDENED_COPY) {
     // the other solves read doubles: widen the three column blocks once, behind the usual scratch
     double* wide = reinterpret_cast<double*>(reinterpret_cast<char*>(d_scratch) + itts_mlpg_scratch_bytes(t_total, dim));
     const int cols = 3 * dim;
@@ -1894,8 +1948,9 @@ static int mlpg_generation_impl(const double* d_feat, const float* d_feat32, int
     a.ld_feat = cols;
     a.col0 = 0;
   }
-  if (t_max >= MLPG_SEQ_BELOW && !ring) return mlpg_stream_launch<16, 2, true>(a, h_offsets, n_utts, dim, t_max, s);
-  if (t_max >= MLPG_SEQ_BELOW) {
+  if ((form & ITTS_MLPG_FORM_SOLVE_MASK) == ITTS_MLPG_FORM_STREAM)
+    return mlpg_stream_launch<16, 2, true>(a, h_offsets, n_utts, dim, t_max, s);
+  if ((form & ITTS_MLPG_FORM_SOLVE_MASK) == ITTS_MLPG_FORM_RING) {
     static std::atomic<uint64_t> attr_done{0};
     int dev = 0;
     ITTS_HIP_CHECK(hipGetDevice(&dev));
@@ -1918,19 +1973,19 @@ static int mlpg_generation_impl(const double* d_feat, const float* d_feat32, int
     }
     a.offsets = nullptr;          // (the kernel has its bounds in the table)
     RingArgs g{a, bounds, (int)t_max, d_feat32};
-    // two dimensions a lane in the helpers (half the memory instructions) where that is what the kernel waits for: float32
-    // rows in batches of many rounds of workgroups -- 4 096 utterances 2.68 against 3.23 ms.  With float64 rows the
-    // kernel moves 3.8 - 4.1 TB/s either way (3.62 / 3.61 ms), and at 256 utterances the exchange's extra arithmetic
-    // costs 3 - 5 % (317 / 301 us; float32 231 / 223).  ITTS_MLPG_WIDE=1 / ITTS_MLPG_NARROW=1 force one (even dim only).
-    const bool wide = dim % 2 == 0 && !env_narrow && (env_wide || (d_feat32 && (int64_t)n_utts * nblk >= 1024));
-    const dim3 rgrid((unsigned)nblk, (unsigned)n_utts), rblock(RING_THREADS);
-    // (float64 rows, y small enough to wait in the memory-side cache: input rows non-temporal -- see RING_LD)
-    const bool nt_in = !env_no_nt && (int64_t)t_total * dim * 8 <= (int64_t)192 << 20;
-    if (d_feat32 && wide) hipLaunchKernelGGL((mlpg_ring_kernel<float, true, false>), rgrid, rblock, RING_LDS_BYTES, s, g);
-    else if (d_feat32) hipLaunchKernelGGL((mlpg_ring_kernel<float, false, false>), rgrid, rblock, RING_LDS_BYTES, s, g);
-    else if (wide) hipLaunchKernelGGL((mlpg_ring_kernel<double, true, false>), rgrid, rblock, RING_LDS_BYTES, s, g);
-    else if (nt_in) hipLaunchKernelGGL((mlpg_ring_kernel<double, false, true>), rgrid, rblock, RING_LDS_BYTES, s, g);
-    else hipLaunchKernelGGL((mlpg_ring_kernel<double, false, false>), rgrid, rblock, RING_LDS_BYTES, s, g);
+    const dim3 rgrid((unsigned)((dim + RING_LANES - 1) / RING_LANES), (unsigned)n_utts), rblock(RING_THREADS);
+    switch (form & (ITTS_MLPG_FORM_WIDE | ITTS_MLPG_FORM_F32_ROWS | ITTS_MLPG_FORM_NT_IN)) {
+      case ITTS_MLPG_FORM_F32_ROWS | ITTS_MLPG_FORM_WIDE:
+        hipLaunchKernelGGL((mlpg_ring_kernel<float, true, false>), rgrid, rblock, RING_LDS_BYTES, s, g); break;
+      case ITTS_MLPG_FORM_F32_ROWS:
+        hipLaunchKernelGGL((mlpg_ring_kernel<float, false, false>), rgrid, rblock, RING_LDS_BYTES, s, g); break;
+      case ITTS_MLPG_FORM_WIDE:
+        hipLaunchKernelGGL((mlpg_ring_kernel<double, true, false>), rgrid, rblock, RING_LDS_BYTES, s, g); break;
+      case ITTS_MLPG_FORM_NT_IN:
+        hipLaunchKernelGGL((mlpg_ring_kernel<double, false, true>), rgrid, rblock, RING_LDS_BYTES, s, g); break;
+      default:
+        hipLaunchKernelGGL((mlpg_ring_kernel<double, false, false>), rgrid, rblock, RING_LDS_BYTES, s, g);
+    }
     const hipError_t launched = hipGetLastError();
     const int rc_table = plan && plan->table ? ITTS_OK : itts::pinned_table_end(&table, s);
     if (launched != hipSuccess) {
@@ -1955,6 +2010,7 @@ extern "C" int itts_mlpg_generation(const double* d_feat, int64_t ld_feat, int c
                                     const double* d_var, const int64_t* h_offsets, int n_utts,
                                     double* d_out, int64_t ld_out, int ocol0, void* d_scratch,
                                     void* stream) {
+  t_mlpg_last_form = 0;
   ITTS_REQUIRE(n_utts == 0 || d_feat, "null pointer");
   return mlpg_generation_impl(d_feat, nullptr, ld_feat, col0, dim, d_var, h_offsets, n_utts, d_out, ld_out, ocol0, d_scratch, stream);
 }
@@ -1968,6 +2024,7 @@ extern "C" int itts_mlpg_generation_f32(const float* d_feat, int64_t ld_feat, in
                                         const double* d_var, const int64_t* h_offsets, int n_utts,
                                         double* d_out, int64_t ld_out, int ocol0, void* d_scratch,
                                         void* stream) {
+  t_mlpg_last_form = 0;
   ITTS_REQUIRE(n_utts == 0 || d_feat, "null pointer");
   return mlpg_generation_impl(nullptr, d_feat, ld_feat, col0, dim, d_var, h_offsets, n_utts, d_out, ld_out, ocol0, d_scratch, stream);
 }
@@ -2005,6 +2062,7 @@ extern "C" int itts_mlpg_generation_planned(const void* plan, const void* d_feat
                                             int col0, int dim, const double* d_var, double* d_out, int64_t ld_out,
                                             int ocol0, void* d_scratch, void* stream) {
   const MlpgPlan* p = static_cast<const MlpgPlan*>(plan);
+  t_mlpg_last_form = 0;
   ITTS_REQUIRE(p && (p->n_utts == 0 || d_feat), "null pointer");
   // (a launch reads the plan's table in place: the plan must outlive the work queued on `stream`)
   return mlpg_generation_impl(feat_is_f32 ? nullptr : static_cast<const double*>(d_feat),

@@ -71,6 +71,10 @@ _SIGNATURES = {
     "itts_mlpg_plan_destroy": (None, [_P]),
     "itts_mlpg_plan_frames": (c_int64, [_P]),
     "itts_mlpg_generation_planned": (c_int, [_P, _P, c_int, c_int64, c_int, c_int, _P, _P, c_int64, c_int, _P, _P]),
+    "itts_mlpg_choose_form": (c_int, [c_int, c_int, c_int64, c_int64, c_int]),
+    "itts_mlpg_set_override": (c_int, [c_int, c_int, c_int]),
+    "itts_mlpg_get_override": (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "itts_mlpg_last_form": (c_int, []),
     "itts_sqrt_inplace_f64": (c_int, [_P, c_int64, _P]),
     "itts_square_inplace_f64": (c_int, [_P, c_int64, _P]),
     "itts_batch_pad_gather_f32": (c_int, [_P, c_int64, c_int64, _P, _P, c_int, c_int64, c_int, c_int, _P, c_int64, _P,

@@ -3,6 +3,7 @@
 Every function takes CUDA(HIP) tensors, passes raw device pointers + the current HIP stream to
 libidiaptts_amd.so and raises on any failure.  Nothing here computes on the CPU.
 """
+import contextlib
 import ctypes
 import threading
 
@@ -108,6 +109,59 @@ def mlpg_generation(feat, variances, dim, offsets, col0=0, out=None, ocol0=0, pl
                      offs, len(offsets) - 1, _ptr(out), ldo, ocol0,
                      _ptr(scratch), _stream()), "itts_mlpg_generation")
     return out
+
+
+# the form a call solves in (ITTS_MLPG_FORM_*, include/idiaptts_amd.h): one of the three solves, or-ed with flags
+MLPG_SWEEPS, MLPG_STREAM, MLPG_RING, MLPG_SOLVE_MASK = 1, 2, 3, 3
+MLPG_WIDE, MLPG_F32_ROWS, MLPG_NT_IN, MLPG_WIDENED_COPY = 4, 8, 16, 32
+_FORCE_OFF, _FORCE_ON = 1, 2
+_MLPG_SOLVES = {None: 0, "auto": 0, "stream": MLPG_STREAM, "ring": MLPG_RING}
+_MLPG_WIDTHS = {None: 0, "auto": 0, "narrow": _FORCE_OFF, "wide": _FORCE_ON}
+_MLPG_NT = {None: 0, "auto": 0, False: _FORCE_OFF, True: _FORCE_ON}
+
+
+def mlpg_form_name(form):
+    """'ring wide f32', 'stream f32 widened', ... for a form code."""
+    if form <= 0:
+        return "none" if form == 0 else "invalid"
+    words = [{MLPG_SWEEPS: "sweeps", MLPG_STREAM: "stream", MLPG_RING: "ring"}[form & MLPG_SOLVE_MASK]]
+    for bit, word in ((MLPG_WIDE, "wide"), (MLPG_F32_ROWS, "f32"), (MLPG_NT_IN, "nt-in"),
+                      (MLPG_WIDENED_COPY, "widened")):
+        if form & bit:
+            words.append(word)
+    return " ".join(words)
+
+
+def mlpg_choose_form(n_utts, dim, t_max, t_total, rows_f32=False):
+    """The form `mlpg_generation` takes for such a batch under the current override (itts_mlpg_choose_form)."""
+    form = _lib.load().itts_mlpg_choose_form(n_utts, dim, t_max, t_total, 1 if rows_f32 else 0)
+    if form < 0:
+        _lib.check(form, "itts_mlpg_choose_form")
+    return form
+
+
+def mlpg_last_form():
+    """The form of this thread's last `mlpg_generation` call (0: none, or nothing to solve)."""
+    return _lib.load().itts_mlpg_last_form()
+
+
+@contextlib.contextmanager
+def mlpg_forced(solve=None, width=None, nt=None):
+    """Forces parts of the choice of form for the calls inside (process-wide); the previous override comes back on
+    exit.  solve: None / "auto", "stream", "ring"; width: None / "auto", "narrow", "wide"; nt: None / "auto", False,
+    True (non-temporal input loads of the float64 ring).  None leaves that part to the library."""
+    L = _lib.load()
+    prev = [ctypes.c_int(), ctypes.c_int(), ctypes.c_int()]
+    _lib.check(L.itts_mlpg_get_override(*[ctypes.byref(p) for p in prev]), "itts_mlpg_get_override")
+    try:
+        codes = (_MLPG_SOLVES[solve], _MLPG_WIDTHS[width], _MLPG_NT[nt])
+    except KeyError:
+        raise ValueError("mlpg_forced(solve={!r}, width={!r}, nt={!r})".format(solve, width, nt))
+    _lib.check(L.itts_mlpg_set_override(*codes), "itts_mlpg_set_override")
+    try:
+        yield
+    finally:
+        _lib.check(L.itts_mlpg_set_override(*[p.value for p in prev]), "itts_mlpg_set_override")
 
 
 def lf0_vuv(f0, offsets, f0_silence_threshold=30.0, lf0_zero=0.0):

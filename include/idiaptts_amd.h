@@ -13,7 +13,8 @@
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream).  GPU entry points are
  *     asynchronous with respect to the host unless stated otherwise.
  *   - return value: 0 = ok, negative = error (ITTS_E_*); itts_last_error() gives a message.
- *   - no hidden global state besides read-only tables cached per device; HIP is not
+ *   - no hidden global state besides read-only tables cached per device (and the MLPG form override and
+ *     last-form record, itts_mlpg_set_override / itts_mlpg_last_form); HIP is not
  *     initialised before the first GPU entry point is called (fork-safe for DataLoader workers,
  *     src/neural_networks/pytorch/ModularModelHandlerPyTorch.py:528-548).
  */
@@ -179,6 +180,46 @@ int64_t itts_mlpg_plan_frames(const void* plan);
 int itts_mlpg_generation_planned(const void* plan, const void* d_feat, int feat_is_f32, int64_t ld_feat, int col0,
                                  int dim, const double* d_var, double* d_out, int64_t ld_out, int ocol0,
                                  void* d_scratch, void* stream);
+
+/* The form a call solves in, chosen from the batch's shape (all forms give the oracle's result to fp64 round-off):
+ *   ITTS_MLPG_FORM_SWEEPS   longest utterance under 194 frames: the shared factor + one sequential sweep per
+ *                           (utterance, dimension) (mlpg_factor_kernel, mlpg_kernel)
+ *   ITTS_MLPG_FORM_STREAM   reduce -> scan -> solve over 16-frame chunks (mlpg_prep/reduce/scan/solve_kernel): from
+ *                           194 frames with fewer than 128 (utterance, 64-dimension block) units, or more than
+ *                           65 535 utterances
+ *   ITTS_MLPG_FORM_RING     the one-pass kernel (mlpg_ring_kernel) otherwise
+ * or-ed with
+ *   ITTS_MLPG_FORM_WIDE          ring: two dimensions a lane in the helpers (float32 rows from 1 024 units, even D)
+ *   ITTS_MLPG_FORM_F32_ROWS      float32 input rows
+ *   ITTS_MLPG_FORM_NT_IN         ring, float64 rows, narrow: non-temporal input loads (rows of at most 192 MiB)
+ *   ITTS_MLPG_FORM_WIDENED_COPY  float32 rows widened into a float64 copy first (mlpg_widen_kernel): every form but
+ *                                the ring, which converts in its loads */
+#define ITTS_MLPG_FORM_SWEEPS 1
+#define ITTS_MLPG_FORM_STREAM 2
+#define ITTS_MLPG_FORM_RING 3
+#define ITTS_MLPG_FORM_SOLVE_MASK 3
+#define ITTS_MLPG_FORM_WIDE 4
+#define ITTS_MLPG_FORM_F32_ROWS 8
+#define ITTS_MLPG_FORM_NT_IN 16
+#define ITTS_MLPG_FORM_WIDENED_COPY 32
+/* The form itts_mlpg_generation* would take for U = n_utts utterances of D = dim dimensions, the longest t_max frames,
+ * t_total in all (float32 rows if rows_f32), under the current override.  No device work; -1 for bad sizes. */
+int itts_mlpg_choose_form(int n_utts, int dim, int64_t t_max, int64_t t_total, int rows_f32);
+/* Forces parts of the choice for every later call of the process (0 = the library's choice for that part):
+ *   solve  ITTS_MLPG_FORM_STREAM or ITTS_MLPG_FORM_RING (batches under 194 frames keep the sweeps; forced ring
+ *          with more than 65 535 utterances takes the stream form)
+ *   width  ITTS_MLPG_FORCE_OFF (narrow) or ITTS_MLPG_FORCE_ON (wide; odd D stays narrow) -- ring only
+ *   nt     ITTS_MLPG_FORCE_OFF or ITTS_MLPG_FORCE_ON -- ring with float64 rows, narrow, only
+ * ITTS_E_INVALID for any other value.  The first use of the override seeds it from the environment:
+ * ITTS_MLPG_RING / ITTS_MLPG_STREAM, ITTS_MLPG_NARROW / ITTS_MLPG_WIDE, ITTS_MLPG_NO_NT (set = forced). */
+#define ITTS_MLPG_FORCE_OFF 1
+#define ITTS_MLPG_FORCE_ON 2
+int itts_mlpg_set_override(int solve, int width, int nt);
+/* The override in force (any pointer may be NULL). */
+int itts_mlpg_get_override(int* solve, int* width, int* nt);
+/* The form (ITTS_MLPG_FORM_*) of the last itts_mlpg_generation* call on the calling thread; 0 when there was none,
+ * or it had nothing to solve, or failed before choosing. */
+int itts_mlpg_last_form(void);
 
 /* ---- frame utilities (misc/utils.py:40-105) --------------------------------------------- */
 /* compute_deltas == np.gradient(x, axis=0) in float32 (utils.py:103-105): part of

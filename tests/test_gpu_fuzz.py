@@ -1,4 +1,4 @@
-"""Random-shape sweeps as tests: MLPG (whichever solve the library picks for the batch) against the C
+"""Random-shape sweeps as tests: MLPG (the library's choice of solve and each form forced) against the C
 oracle utterance by utterance, the fp32 GEMM entry points against torch in float64
 (scripts/gemm_fuzz.py, a child process)."""
 import os
@@ -13,52 +13,67 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.mark.parametrize("solve", ["auto", "ring"])
-def test_mlpg_random_shapes(gpu, solve, monkeypatch):
-    """(under the library's own choice of solve, and with the one-pass ring kernel forced for every batch whose
-    longest utterance has 194 frames or more)
+@pytest.mark.parametrize("solve", ["auto", "stream", "ring", "ring-wide", "ring-plain"])
+def test_mlpg_random_shapes(gpu, solve):
+    """(under the library's own choice of solve, and with the stream form, the narrow and the wide one-pass ring
+    kernel and the ring with plain float64 loads forced -- ops.mlpg_forced -- for every batch whose longest utterance
+    has 194 frames or more; every batch asserts the form it recorded, tests/mlpg_forms.py)
     80 random batches: empty, one-frame and chunk-boundary lengths, 1 .. 129 dimensions (one to three
-    64-dimension blocks), input / output column offsets, slowly settling factors; untouched columns
-    of the output array must stay untouched (misc/mlpg.py:94-127 per utterance is the reference)."""
+    64-dimension blocks), input / output column offsets, slowly settling factors, float32 rows in about a third of
+    them; under the library's choice 12 more batches of 128+ utterances, so that its own choice reaches the ring;
+    untouched columns of the output array must stay untouched (misc/mlpg.py:94-127 per utterance is the reference)."""
     from idiaptts_amd import ops
+    from mlpg_forms import FORCED, check_form
     from oracle import capi
-    monkeypatch.delenv("ITTS_MLPG_STREAM", raising=False)
-    if solve == "ring":
-        monkeypatch.setenv("ITTS_MLPG_RING", "1")
-    else:
-        monkeypatch.delenv("ITTS_MLPG_RING", raising=False)
     rng = np.random.default_rng(5)
+    rng2 = np.random.default_rng(55)          # (the draws added to the original 80 cases: those stay as they were)
     worst = 0.0
-    for case in range(80):
-        n_utts = int(rng.integers(1, 24))
-        kind = rng.integers(0, 4)
-        hi = (40, 400, 2500, 5000)[kind]
-        lengths = rng.integers(0 if kind == 0 else 1, hi, size=n_utts)
-        if rng.random() < 0.3:
-            lengths[rng.integers(0, n_utts)] = int(rng.choice([1, 2, 3, 15, 16, 17, 31, 32, 33, 47, 48, 49, 64, 65]))
-        if lengths.sum() == 0:
-            lengths[0] = 5
-        dim = int(rng.choice([1, 2, 3, 7, 20, 60, 62, 64, 65, 70, 129]))
-        col0, extra, ocol0, oextra = (int(rng.integers(0, 4)) for _ in range(4))
-        off = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
-        T = int(off[-1])
-        feat = rng.normal(size=(T, col0 + 3 * dim + extra))
-        var = rng.uniform(0.01, 1.0, size=3 * dim)
-        if rng.random() < 0.25:
-            var[dim:] *= 10.0 ** rng.uniform(-6, 0)          # slowly settling factor
-        out = torch.full((T, ocol0 + dim + oextra), 3.5, dtype=torch.float64, device=gpu)
-        ops.mlpg_generation(torch.from_numpy(feat).to(gpu), torch.from_numpy(var).to(gpu), dim, off.tolist(),
-                            col0=col0, out=out, ocol0=ocol0)
-        got = out.cpu().numpy()
-        assert (got[:, :ocol0] == 3.5).all() and (got[:, ocol0 + dim:] == 3.5).all(), (case, "columns touched")
-        for u in range(n_utts):
-            a, b = off[u], off[u + 1]
-            if b == a:
-                continue
-            ref = capi.mlpg(feat[a:b], var, dim, col0=col0)
-            err = np.abs(got[a:b, ocol0:ocol0 + dim] - ref).max() / max(1.0, np.abs(ref).max())
-            assert np.isfinite(err) and err < 1e-9, (case, u, err, lengths.tolist()[:8], dim, col0, ocol0)
-            worst = max(worst, err)
+    seen = set()
+    with ops.mlpg_forced(**FORCED[solve]):
+        for case in range(80 + (12 if solve == "auto" else 0)):
+            if case >= 80:                     # batches of 128+ utterances: the library's choice reaches the ring
+                g, n_utts, kind, hi = rng2, int(rng2.integers(128, 160)), 1, 600
+            else:
+                g, n_utts = rng, int(rng.integers(1, 24))
+                kind = rng.integers(0, 4)
+                hi = (40, 400, 2500, 5000)[kind]
+            lengths = g.integers(0 if kind == 0 else 1, hi, size=n_utts)
+            if g.random() < 0.3:
+                lengths[g.integers(0, n_utts)] = int(g.choice([1, 2, 3, 15, 16, 17, 31, 32, 33, 47, 48, 49, 64, 65]))
+            if lengths.sum() == 0:
+                lengths[0] = 5
+            dim = int(g.choice([1, 2, 3, 7, 20, 60, 62, 64, 65, 70, 129]))
+            col0, extra, ocol0, oextra = (int(g.integers(0, 4)) for _ in range(4))
+            f32 = rng2.random() < 0.35
+            off = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+            T = int(off[-1])
+            feat = g.normal(size=(T, col0 + 3 * dim + extra))
+            if f32:
+                feat = feat.astype(np.float32).astype(np.float64)
+            var = g.uniform(0.01, 1.0, size=3 * dim)
+            if g.random() < 0.25:
+                # slowly settling factor (the added batches stop at 1e-4: at 1e-6 - 1e-7 an utterance of a few frames
+                # is so ill-conditioned that the float64 oracle itself is 0.4 - 3e-9 off the exact solution)
+                var[dim:] *= 10.0 ** g.uniform(-6 if case < 80 else -4, 0)
+            out = torch.full((T, ocol0 + dim + oextra), 3.5, dtype=torch.float64, device=gpu)
+            rows = torch.from_numpy(feat.astype(np.float32) if f32 else feat).to(gpu)
+            ops.mlpg_generation(rows, torch.from_numpy(var).to(gpu), dim, off.tolist(), col0=col0, out=out,
+                                ocol0=ocol0)
+            seen.add(check_form(solve, lengths, dim, f32, what="case %d" % case))
+            got = out.cpu().numpy()
+            assert (got[:, :ocol0] == 3.5).all() and (got[:, ocol0 + dim:] == 3.5).all(), (case, "columns touched")
+            for u in range(n_utts):
+                a, b = off[u], off[u + 1]
+                if b == a:
+                    continue
+                ref = capi.mlpg(feat[a:b], var, dim, col0=col0)
+                err = np.abs(got[a:b, ocol0:ocol0 + dim] - ref).max() / max(1.0, np.abs(ref).max())
+                assert np.isfinite(err) and err < 1e-9, (case, u, err, lengths.tolist()[:8], dim, col0, ocol0, f32)
+                worst = max(worst, err)
+    solves = {form & ops.MLPG_SOLVE_MASK for form in seen}
+    assert solves == ({ops.MLPG_SWEEPS, ops.MLPG_STREAM, ops.MLPG_RING} if solve == "auto" else
+                      {ops.MLPG_SWEEPS, ops.MLPG_STREAM if solve == "stream" else ops.MLPG_RING}), sorted(seen)
+    print("forms:", ", ".join(sorted(ops.mlpg_form_name(f) for f in seen)))
     print("worst relative difference to the oracle: %.1e" % worst)
 
 
