@@ -12,8 +12,6 @@
 // torch.nn.GRU cell, gate order r, z, n:
 //   r = sigmoid(gin_r + W_hr h + b_hr)      z = sigmoid(gin_z + W_hz h + b_hz)
 //   n = tanh(gin_n + r * (W_hn h + b_hn))   h' = (1 - z) * n + z * h
-#include <vector>
-
 #include "rnn_common.h"
 #include "rnn_persist.h"
 
@@ -42,6 +40,7 @@ struct GruArgs {
   int ksplit, kiter;
   int nact, nact_next;    // rows active at this step / at step + 1 (a prefix: rows are sorted)
   int row_base;           // row_off[step] from the host's copy of the lengths (no table read)
+  int row_base_prev;      // row_off[step - 1] (set by rnn_bwd_steps, not read by the GRU's step kernels)
 };
 
 __device__ __forceinline__ size_t gru_row_at(const GruArgs& a, int dir, int s, int b) {
@@ -302,21 +301,9 @@ extern "C" int itts_gru_layer_fwd(const float* d_gin, const float* d_whh, const 
   ITTS_LAUNCH_CHECK();
   a.ksplit = (H % 64 == 0) ? 4 : ((H % 32 == 0) ? 2 : 1);
   a.kiter = H / (16 * a.ksplit);
-  const dim3 grid(H / GRU_FW_UNITS, ndir);
-  int p = B;
-  int row_base = 0;
-  for (int step = 0; step < T; ++step) {
-    a.step = step;
-    a.nact = rnn_active_rows(h_lengths, B, step, &p);
-    a.row_base = row_base;          // row_off[step] = rows active in all earlier steps
-    row_base += a.nact;
-    switch (std::min((a.nact + 15) / 16, 4)) {
-      case 1: hipLaunchKernelGGL(gru_step_fwd_kernel<1>, grid, dim3(256), 0, s, a); break;
-      case 2: hipLaunchKernelGGL(gru_step_fwd_kernel<2>, grid, dim3(256), 0, s, a); break;
-      case 3: hipLaunchKernelGGL(gru_step_fwd_kernel<3>, grid, dim3(256), 0, s, a); break;
-      default: hipLaunchKernelGGL(gru_step_fwd_kernel<4>, grid, dim3(256), 0, s, a); break;
-    }
-  }
+  static void (*const step_kernels[4])(GruArgs) = {gru_step_fwd_kernel<1>, gru_step_fwd_kernel<2>,
+                                                   gru_step_fwd_kernel<3>, gru_step_fwd_kernel<4>};
+  rnn_fwd_steps(step_kernels, a, h_lengths, dim3(H / GRU_FW_UNITS, ndir), s);
   ITTS_LAUNCH_CHECK();
   if (d_hn) {
     hipLaunchKernelGGL(rnn_final_state_kernel, rnn_ew_grid(n), dim3(256), 0, s, a.hs, d_lengths, d_hn, ndir, B, H);
@@ -356,21 +343,7 @@ extern "C" int itts_gru_layer_bwd(const float* d_dy, const float* d_whh, const f
   ITTS_HIP_CHECK(hipMemsetAsync(a.hs, 0, st * 4, s));   // carry of not-yet-active rows
   a.ksplit = (H % 64 == 0) ? 12 : ((H % 32 == 0) ? 6 : 3);   // waves per workgroup; 3H/16 k-steps in all
   a.kiter = (3 * H / 16) / a.ksplit;
-  int p = 0, nact_next = 0;
-  std::vector<int> row_off(T + 1, 0);      // host copy of the packed-row offsets
-  {
-    int q = B;
-    for (int t = 0; t < T; ++t) row_off[t + 1] = row_off[t] + rnn_active_rows(h_lengths, B, t, &q);
-  }
-  for (int step = T - 1; step >= 0; --step) {
-    a.step = step;
-    a.nact = rnn_active_rows(h_lengths, B, step, &p);
-    a.nact_next = nact_next;
-    nact_next = a.nact;
-    a.row_base = row_off[step];
-    hipLaunchKernelGGL(gru_step_bwd_kernel, dim3((H / GRU_BW_UNITS) * ((a.nact + 15) / 16), ndir),
-                       dim3(64 * a.ksplit), 0, s, a);
-  }
+  rnn_bwd_steps(gru_step_bwd_kernel, GRU_BW_UNITS, a, h_lengths, s);
   ITTS_LAUNCH_CHECK();
   // step 0 (all rows active) leaves dh * z in the parity-0 carry buffer [ndir][B][H]
   if (d_dh0)

@@ -29,9 +29,6 @@
 //     which costs ~0.2 us per load when it happens), and every operand load is a contiguous 1 KB
 //     wave access thanks to the K-blocked state / re-tiled W_hh layouts of rnn_common.h.
 // Gate order i, f, g, o and the two bias vectors follow torch.nn.LSTM.
-#include <atomic>
-#include <cstdio>
-#include <vector>
 
 #include "rnn_common.h"
 #include "rnn_persist.h"
@@ -369,21 +366,9 @@ extern "C" int itts_lstm_layer_fwd(const float* d_gin, const float* d_whh, const
   ITTS_LAUNCH_CHECK();
   a.ksplit = (H % 64 == 0) ? 4 : ((H % 32 == 0) ? 2 : 1);
   a.kiter = H / (16 * a.ksplit);
-  const dim3 grid(H / FW_UNITS, ndir);
-  int p = B;
-  int row_base = 0;
-  for (int step = 0; step < T; ++step) {
-    a.step = step;
-    a.nact = rnn_active_rows(h_lengths, B, step, &p);
-    a.row_base = row_base;          // row_off[step] = rows active in all earlier steps
-    row_base += a.nact;
-    switch (std::min((a.nact + 15) / 16, 4)) {
-      case 1: hipLaunchKernelGGL(lstm_step_fwd_kernel<1>, grid, dim3(256), 0, s, a); break;
-      case 2: hipLaunchKernelGGL(lstm_step_fwd_kernel<2>, grid, dim3(256), 0, s, a); break;
-      case 3: hipLaunchKernelGGL(lstm_step_fwd_kernel<3>, grid, dim3(256), 0, s, a); break;
-      default: hipLaunchKernelGGL(lstm_step_fwd_kernel<4>, grid, dim3(256), 0, s, a); break;
-    }
-  }
+  static void (*const step_kernels[4])(LstmArgs) = {lstm_step_fwd_kernel<1>, lstm_step_fwd_kernel<2>,
+                                                    lstm_step_fwd_kernel<3>, lstm_step_fwd_kernel<4>};
+  rnn_fwd_steps(step_kernels, a, h_lengths, dim3(H / FW_UNITS, ndir), s);
   ITTS_LAUNCH_CHECK();
   if (d_hn) hipLaunchKernelGGL(rnn_final_state_kernel, rnn_ew_grid(n), dim3(256), 0, s, a.hs, d_lengths, d_hn, ndir, B, H);
   if (d_cn) hipLaunchKernelGGL(rnn_final_state_kernel, rnn_ew_grid(n), dim3(256), 0, s, a.cs, d_lengths, d_cn, ndir, B, H);
@@ -425,22 +410,7 @@ extern "C" int itts_lstm_layer_bwd(const float* d_dy, const float* d_whh, const 
   ITTS_HIP_CHECK(hipMemsetAsync(a.cs, 0, st * 4, s));   // running dc of rows that are not active yet
   a.ksplit = (H % 64 == 0) ? 16 : ((H % 32 == 0) ? 8 : 4);   // waves per workgroup
   a.kiter = H / (4 * a.ksplit);
-  int p = 0, nact_next = 0;
-  std::vector<int> row_off(T + 1, 0);      // host copy of the packed-row offsets
-  {
-    int q = B;
-    for (int t = 0; t < T; ++t) row_off[t + 1] = row_off[t] + rnn_active_rows(h_lengths, B, t, &q);
-  }
-  for (int step = T - 1; step >= 0; --step) {
-    a.step = step;
-    a.nact = rnn_active_rows(h_lengths, B, step, &p);
-    a.nact_next = nact_next;
-    nact_next = a.nact;
-    a.row_base = row_off[step];
-    a.row_base_prev = step > 0 ? row_off[step - 1] : 0;
-    hipLaunchKernelGGL(lstm_step_bwd_kernel, dim3((H / BW_UNITS) * ((a.nact + 15) / 16), ndir),
-                       dim3(64 * a.ksplit), 0, s, a);
-  }
+  rnn_bwd_steps(lstm_step_bwd_kernel, BW_UNITS, a, h_lengths, s);
   ITTS_LAUNCH_CHECK();
   // step 0 has every row active and leaves dc * f, the gradient of the initial cell state, in the
   // parity-0 carry buffer [ndir][B][H]

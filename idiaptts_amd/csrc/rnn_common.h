@@ -14,6 +14,7 @@
 // These are private scratch layouts inside d_state; the C ABI keeps torch's layouts.
 #pragma once
 #include <algorithm>
+#include <vector>
 
 #include "common.h"
 
@@ -115,3 +116,43 @@ static inline int rnn_active_rows(const int* h_lengths, int B, int s, int* p) {
 }
 
 static inline dim3 rnn_ew_grid(int64_t n) { return dim3((unsigned)std::min<int64_t>((n + 255) / 256, 2048)); }
+
+// host copy of the packed-row offsets: row_off[t] = rows active in the steps before t, row_off[T] = N
+static inline std::vector<int> rnn_row_offsets(const int* h_lengths, int T, int B) {
+  std::vector<int> row_off(T + 1, 0);
+  int q = B;
+  for (int t = 0; t < T; ++t) row_off[t + 1] = row_off[t] + rnn_active_rows(h_lengths, B, t, &q);
+  return row_off;
+}
+
+// Forward recurrence on the step kernels: one launch per step, kernels[n - 1] taking n batch tiles of 16
+// rows per pass (the cell's step kernel for NT = 1 .. 4).
+template <class Args>
+static void rnn_fwd_steps(void (*const kernels[4])(Args), Args& a, const int* h_lengths, dim3 grid, hipStream_t s) {
+  int p = a.B;
+  int row_base = 0;
+  for (int step = 0; step < a.T; ++step) {
+    a.step = step;
+    a.nact = rnn_active_rows(h_lengths, a.B, step, &p);
+    a.row_base = row_base;          // row_off[step] = rows active in all earlier steps
+    row_base += a.nact;
+    hipLaunchKernelGGL(kernels[std::min((a.nact + 15) / 16, 4) - 1], grid, dim3(256), 0, s, a);
+  }
+}
+
+// Backward recurrence on the step kernels, steps T - 1 .. 0: workgroups of `units` hidden units x one
+// 16-row batch tile, 64 * a.ksplit threads each.
+template <class Args>
+static void rnn_bwd_steps(void (*kernel)(Args), int units, Args& a, const int* h_lengths, hipStream_t s) {
+  const std::vector<int> row_off = rnn_row_offsets(h_lengths, a.T, a.B);
+  int p = 0, nact_next = 0;
+  for (int step = a.T - 1; step >= 0; --step) {
+    a.step = step;
+    a.nact = rnn_active_rows(h_lengths, a.B, step, &p);
+    a.nact_next = nact_next;
+    nact_next = a.nact;
+    a.row_base = row_off[step];
+    a.row_base_prev = step > 0 ? row_off[step - 1] : 0;
+    hipLaunchKernelGGL(kernel, dim3((a.H / units) * ((a.nact + 15) / 16), a.ndir), dim3(64 * a.ksplit), 0, s, a);
+  }
+}

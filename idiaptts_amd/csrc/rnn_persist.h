@@ -346,15 +346,18 @@ struct PersistDevice {
   int next_cooldown = kPersistCooldown;
   int give_ups = 0;       // in a row
 };
+struct PersistDevices {   // one table per persistent kernel: the forward and backward cool-downs are independent
+  std::map<int, PersistDevice> map;
+  std::mutex mu;
+};
 // Returns 1 when the persistent kernel may be launched on the current device, 0 when the caller has to
 // take the step kernels (fewer than 256 CUs, cooling down, or the attribute could not be set).
-static int persist_device_ready(const void* kernel, int lds_bytes, std::map<int, PersistDevice>& table, std::mutex& mu,
-                                int* dev_out) {
+static int persist_device_ready(const void* kernel, int lds_bytes, PersistDevices& table, int* dev_out) {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return 0;
   *dev_out = dev;
-  std::lock_guard<std::mutex> lock(mu);
-  PersistDevice& d = table[dev];
+  std::lock_guard<std::mutex> lock(table.mu);
+  PersistDevice& d = table.map[dev];
   if (d.n_cu == 0) {
     if (hipDeviceGetAttribute(&d.n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { d.n_cu = 0; return 0; }
   }
@@ -371,40 +374,44 @@ static int persist_device_ready(const void* kernel, int lds_bytes, std::map<int,
 }
 // A launch gave up (or could not be made): returns the number of calls the step kernels take now, negative when the
 // message for it should not be printed any more.
-static int persist_cool_down(std::map<int, PersistDevice>& table, std::mutex& mu, int dev) {
-  std::lock_guard<std::mutex> lock(mu);
-  PersistDevice& d = table[dev];
+static int persist_cool_down(PersistDevices& table, int dev) {
+  std::lock_guard<std::mutex> lock(table.mu);
+  PersistDevice& d = table.map[dev];
   d.cooldown = d.next_cooldown;
   d.next_cooldown = std::min(2 * d.next_cooldown, kPersistCooldownCap);
   ++d.give_ups;
   return d.give_ups <= 3 ? d.cooldown : -d.cooldown;
 }
-static void persist_ran(std::map<int, PersistDevice>& table, std::mutex& mu, int dev) {
-  std::lock_guard<std::mutex> lock(mu);
-  PersistDevice& d = table[dev];
+static void persist_ran(PersistDevices& table, int dev) {
+  std::lock_guard<std::mutex> lock(table.mu);
+  PersistDevice& d = table.map[dev];
   d.next_cooldown = kPersistCooldown;
   d.give_ups = 0;
 }
 
-template <int G>
-static int rnn_persist_forward(RnnPersistArgs p, int H, hipStream_t s) {
-  static std::map<int, PersistDevice> devices;
-  static std::mutex devices_mu;
+// The host half of both persistent recurrences: 1 = done, 0 = run the step kernels, -1 = HIP error.  The scratch
+// block holds the exchange buffer (`xbytes`, cleared), the abort flag and -- when h_lengths is given (the backward
+// kernel reads them) -- a device copy of the lengths.
+template <class Args>
+static int persist_run(void (*kernel)(Args), int lds_bytes, size_t xbytes, Args p, const int* h_lengths, int H,
+                       PersistDevices& devices, const char* what, hipStream_t s) {
   const char* pe = getenv("ITTS_RNN_PERSISTENT");       // read per call: tests switch it
   if (pe && pe[0] == '0') return 0;
   p.ntiles = (p.B + 15) / 16;
   if (H != PH) return 0;
   int dev = 0;
-  if (!persist_device_ready(reinterpret_cast<const void*>(&rnn_persist_fwd_kernel<G>), persist_lds_bytes(G), devices,
-                            devices_mu, &dev))
-    return 0;
+  if (!persist_device_ready(reinterpret_cast<const void*>(kernel), lds_bytes, devices, &dev)) return 0;
   DeviceContext* ctx = get_context();
   if (!ctx) return 0;
-  const size_t xbytes = (size_t)8 * 4 * 32 * 64 * sizeof(uint4);
+  const size_t lbytes = h_lengths ? ((size_t)p.B * sizeof(int) + 63) / 64 * 64 : 0;
   char* blk = nullptr;
   itts::ScratchScope scope(s);
-  if (itts::scratch_malloc((void**)&blk, xbytes + 64, s) != hipSuccess) return -1;
+  if (itts::scratch_malloc((void**)&blk, xbytes + 64 + lbytes, s) != hipSuccess) return -1;
   if (hipMemsetAsync(blk, 0, xbytes + 64, s) != hipSuccess) return -1;
+  if (h_lengths) {
+    if (staged_upload(blk + xbytes + 64, h_lengths, (size_t)p.B * sizeof(int), s) != ITTS_OK) return -1;
+    p.lengths = reinterpret_cast<const int*>(blk + xbytes + 64);
+  }
   p.xchg = reinterpret_cast<uint4*>(blk);
   p.abort_flag = reinterpret_cast<int*>(blk + xbytes);
   if (getenv("ITTS_RNN_PERSIST_TEST_ABORT"))       // test hook: the launch finds the abort flag raised
@@ -416,23 +423,29 @@ static int rnn_persist_forward(RnnPersistArgs p, int H, hipStream_t s) {
   // therefore cleared between rounds)
   for (p.tile0 = 0; p.tile0 < p.ntiles; p.tile0 += 8 / p.ndir) {
     if (p.tile0 > 0 && hipMemsetAsync(blk, 0, xbytes, s) != hipSuccess) return -1;
-    hipLaunchKernelGGL(rnn_persist_fwd_kernel<G>, dim3(256), dim3(256), persist_lds_bytes(G), s, p);
+    hipLaunchKernelGGL(kernel, dim3(256), dim3(256), lds_bytes, s, p);
     if (hipGetLastError() != hipSuccess) {          // nothing of this round ran: the step kernels redo the layer
-      persist_cool_down(devices, devices_mu, dev);
+      persist_cool_down(devices, dev);
       return 0;
     }
   }
   const int gave_up = persist_read_flag(pinned_slot(ctx), p.abort_flag, s);
   if (gave_up < 0) return -1;
   if (itts::scratch_free(blk, s) != hipSuccess) return -1;
-  if (gave_up == 0) { persist_ran(devices, devices_mu, dev); return 1; }
-  const int calls = persist_cool_down(devices, devices_mu, dev);
+  if (gave_up == 0) { persist_ran(devices, dev); return 1; }
+  const int calls = persist_cool_down(devices, dev);
   if (calls > 0)
-    fprintf(stderr, "libidiaptts_amd: the persistent recurrence gave up waiting (are all 256 CUs available to "
-                    "this process?); per-step kernels for the next %d calls\n", calls);
+    fprintf(stderr, "libidiaptts_amd: the persistent %srecurrence gave up waiting (are all 256 CUs available to "
+                    "this process?); per-step kernels for the next %d calls\n", what, calls);
   return 0;
 }
 
+template <int G>
+static int rnn_persist_forward(RnnPersistArgs p, int H, hipStream_t s) {
+  static PersistDevices devices;
+  return persist_run(rnn_persist_fwd_kernel<G>, persist_lds_bytes(G), (size_t)8 * 4 * 32 * 64 * sizeof(uint4), p,
+                     nullptr, H, devices, "", s);
+}
 
 // ---- persistent backward recurrence, same placement (G = 4: LSTM, G = 3: GRU) ---------------------
 // Step s (T_tile - 1 ... 0) of row b:  dh = dy + dG(s + 1) W_hh (+ the GRU's dh z carry),  then the
@@ -700,48 +713,9 @@ __global__ __launch_bounds__(256) void rnn_persist_bwd_kernel(RnnPersistBwdArgs 
 // Backward counterpart of rnn_persist_forward: 1 = done, 0 = run the step kernels.
 template <int G>
 static int rnn_persist_backward(RnnPersistBwdArgs p, const int* h_lengths, int H, hipStream_t s) {
-  static std::map<int, PersistDevice> devices;
-  static std::mutex devices_mu;
-  const char* pe = getenv("ITTS_RNN_PERSISTENT");          // read per call: tests switch it
-  const char* pb = getenv("ITTS_RNN_PERSISTENT_BWD");      // ... and this one keeps the forward half on
-  if ((pe && pe[0] == '0') || (pb && pb[0] == '0')) return 0;
-  p.ntiles = (p.B + 15) / 16;
-  if (H != PH) return 0;
-  int dev = 0;
-  if (!persist_device_ready(reinterpret_cast<const void*>(&rnn_persist_bwd_kernel<G>), persist_bwd_lds_bytes(G),
-                            devices, devices_mu, &dev))
-    return 0;
-  DeviceContext* ctx = get_context();
-  if (!ctx) return 0;
-  const size_t xbytes = (size_t)8 * 2 * 32 * 32 * PT * sizeof(uint4);
-  const size_t lbytes = ((size_t)p.B * sizeof(int) + 63) / 64 * 64;
-  char* blk = nullptr;
-  itts::ScratchScope scope(s);
-  if (itts::scratch_malloc((void**)&blk, xbytes + 64 + lbytes, s) != hipSuccess) return -1;
-  if (hipMemsetAsync(blk, 0, xbytes + 64, s) != hipSuccess) return -1;
-  if (staged_upload(blk + xbytes + 64, h_lengths, (size_t)p.B * sizeof(int), s) != ITTS_OK) return -1;
-  p.xchg = reinterpret_cast<uint4*>(blk);
-  p.abort_flag = reinterpret_cast<int*>(blk + xbytes);
-  p.lengths = reinterpret_cast<const int*>(blk + xbytes + 64);
-  if (getenv("ITTS_RNN_PERSIST_TEST_ABORT"))       // test hook: the launch finds the abort flag raised
-    if (hipMemsetAsync(p.abort_flag, 1, sizeof(int), s) != hipSuccess) return -1;
-  for (p.tile0 = 0; p.tile0 < p.ntiles; p.tile0 += 8 / p.ndir) {
-    if (p.tile0 > 0 && hipMemsetAsync(blk, 0, xbytes, s) != hipSuccess) return -1;
-    hipLaunchKernelGGL(rnn_persist_bwd_kernel<G>, dim3(256), dim3(256), persist_bwd_lds_bytes(G), s, p);
-    if (hipGetLastError() != hipSuccess) {
-      persist_cool_down(devices, devices_mu, dev);
-      return 0;
-    }
-  }
-  const int gave_up = persist_read_flag(pinned_slot(ctx), p.abort_flag, s);
-  if (gave_up < 0) return -1;
-  if (itts::scratch_free(blk, s) != hipSuccess) return -1;
-  if (gave_up == 0) { persist_ran(devices, devices_mu, dev); return 1; }
-  const int calls = persist_cool_down(devices, devices_mu, dev);
-  if (calls > 0)
-    fprintf(stderr, "libidiaptts_amd: the persistent backward recurrence gave up waiting; per-step kernels for the "
-                    "next %d calls\n", calls);
-  return 0;
+  static PersistDevices devices;
+  return persist_run(rnn_persist_bwd_kernel<G>, persist_bwd_lds_bytes(G), (size_t)8 * 2 * 32 * 32 * PT * sizeof(uint4),
+                     p, h_lengths, H, devices, "backward ", s);
 }
 
 }  // namespace itts

@@ -1,7 +1,6 @@
 """torch.autograd glue for the HIP acoustic-model kernels (PyTorch-ROCm only provides autograd,
 device memory and streams; every forward / backward computation below is a C-ABI call)."""
 import collections
-import os
 import ctypes
 import threading
 
@@ -470,6 +469,53 @@ def _pad4_cols(t):
     return torch.nn.functional.pad(t, (0, 4 - F % 4))
 
 
+def _input_projection(x2, w_ih, b_ih, b_hh=None):
+    """The input projection of all frames of a recurrent layer, one GEMM on packed rows x2 [N, F] (they may arrive
+    with their rows already padded to 16-byte multiples) against w_ih [ndir, G*H, F] plus b_ih (+ b_hh: the LSTM
+    adds both biases here, the GRU's b_hh stays inside its reset gate).
+    -> (x2 and w_ih [ndir*G*H, F] with 4-column rows, gin [N, ndir*G*H], pre_padded)"""
+    F = w_ih.shape[-1]
+    pre_padded = x2.shape[1] != F
+    x2 = _pad4_cols(x2.contiguous())
+    w_ih_cat = _pad4_cols(w_ih.reshape(-1, F))
+    gin = ops.linear_fwd(x2, w_ih_cat, (b_ih if b_hh is None else b_ih + b_hh).reshape(-1), ops.ACT_NONE)
+    return x2, w_ih_cat, gin, pre_padded
+
+
+def _initial_state_grad(dg, w_hh, pb, ndir):
+    """Trainable initial states (RNNWrapper train_hidden_init): one vector per direction shared by all rows, so
+    the rows' W_hh^T dG at their first processed frame, summed over the rows -> [ndir, H]."""
+    G = dg.shape[1] // ndir
+    return torch.stack([ops.linear_bwd_input(
+        ops.rows_gather(dg[:, d * G:(d + 1) * G], pb.first_rows(d)).sum(0, keepdim=True), w_hh[d])[0]
+        for d in range(ndir)], dim=0)
+
+
+def _weight_grads(dgi, dgh, x2, hprev, F, ndir, want_hh_bias):
+    """dW_hh (+ db_hh) from the gradient wrt the hidden projections dgh [N, ndir*G*H] and the states that entered
+    each step hprev [N, ndir*H], then dW_ih [ndir, G*H, F] and db_ih [ndir*G*H] from dgi and the layer's input x2.
+    The launch right behind a recurrence runs 20-25 % slow (the chip comes back from light load: LABNOTES 12g):
+    the small products W_hh' take that place, the large one follows (95.9 -> 95.6 ms per 3 x 512 BiLSTM step,
+    two A/B pairs against dW_ih first).  -> (dw_ih, db_ih, dw_hh, db_hh or None)"""
+    H = hprev.shape[1] // ndir
+    G = dgh.shape[1] // ndir
+    dw_hh = torch.empty((ndir, G, H), dtype=torch.float32, device=dgh.device)
+    db_hh = torch.empty((ndir, G), dtype=torch.float32, device=dgh.device) if want_hh_bias else None
+    for d in range(ndir):
+        _, db = ops.linear_bwd_weight(dgh[:, d * G:(d + 1) * G], hprev[:, d * H:(d + 1) * H],
+                                      dw=dw_hh[d], want_bias=want_hh_bias)
+        if want_hh_bias:
+            db_hh[d] = db
+    dw_ih, db_ih = ops.linear_bwd_weight(dgi, x2)                 # [ndir*G*H, F (padded)], [ndir*G*H]
+    return dw_ih[:, :F].reshape(ndir, G, F), db_ih, dw_hh, db_hh
+
+
+def _input_grad(dgi, w_ih_cat, F, pre_padded):
+    """dX = dG W_ih, cut back to the F columns the layer received unless its rows arrived padded"""
+    dx = ops.linear_bwd_input(dgi, w_ih_cat)
+    return dx if pre_padded else dx[:, :F]
+
+
 class LSTMLayerFunction(torch.autograd.Function):
     """One (bi)directional LSTM layer on packed rows x [N, F] (see PackedBatch)."""
 
@@ -477,13 +523,10 @@ class LSTMLayerFunction(torch.autograd.Function):
     def forward(ctx, x2, pb, w_ih, w_hh, b_ih, b_hh, h0, c0, training):
         L = _lib.load()
         N = x2.shape[0]
-        F = w_ih.shape[-1]               # x2 may arrive with its rows already padded to 16-byte multiples
+        F = w_ih.shape[-1]
         ndir, G4, H = w_hh.shape
         T, B = pb.T, pb.B
-        pre_padded = x2.shape[1] != F
-        x2 = _pad4_cols(x2.contiguous())
-        w_ih_cat = _pad4_cols(w_ih.reshape(ndir * G4, F))
-        gin = ops.linear_fwd(x2, w_ih_cat, (b_ih + b_hh).reshape(-1), ops.ACT_NONE)
+        x2, w_ih_cat, gin, pre_padded = _input_projection(x2, w_ih, b_ih, b_hh)
         dev = x2.device
         y = torch.empty((N, ndir * H), dtype=torch.float32, device=dev)
         keep = bool(training)
@@ -536,34 +579,12 @@ class LSTMLayerFunction(torch.autograd.Function):
                                          _iptr(pb.d_row_off), _iptr(pb.d_rev_row), pb.T, pb.B, H, ndir,
                                          _iptr(dg), _iptr(dc0_rows), _iptr(state), ops._stream()),
                    "itts_lstm_layer_bwd")
-        # trainable initial states (RNNWrapper train_hidden_init): one vector per direction shared
-        # by all rows -> sum over the rows; dh0 = W_hh^T dG at the first processed frame
-        dh0 = dc0 = None
-        if want_h0:
-            dh0 = torch.stack([ops.linear_bwd_input(
-                ops.rows_gather(dg[:, d * G4:(d + 1) * G4], pb.first_rows(d)).sum(0, keepdim=True), w_hh[d])[0]
-                for d in range(ndir)], dim=0)
-        if want_c0:
-            dc0 = dc0_rows.sum(dim=1)
-        # The launch right behind a recurrence runs 20-25 % slow (the chip comes back from light load: LABNOTES 12g):
-        # the two small products W_hh' take that place, the large ones follow (95.9 -> 95.6 ms per 3 x 512 BiLSTM
-        # step, two A/B pairs; ITTS_RNN_BWD_SMALL_FIRST=0 for the old order)
-        small_first = os.environ.get("ITTS_RNN_BWD_SMALL_FIRST", "1") != "0"
-        if not small_first:
-            dw_ih, db = ops.linear_bwd_weight(dg, x2)                      # [ndir*4H, F], [ndir*4H]
-        dw_hh = torch.empty((ndir, G4, H), dtype=torch.float32, device=dev)
-        for d in range(ndir):
-            ops.linear_bwd_weight(dg[:, d * G4:(d + 1) * G4], hprev[:, d * H:(d + 1) * H],
-                                  dw=dw_hh[d], want_bias=False)
-        if small_first:
-            dw_ih, db = ops.linear_bwd_weight(dg, x2)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = ops.linear_bwd_input(dg, w_ih_cat)
-            if not pre_padded:
-                dx = dx[:, :F]
+        dh0 = _initial_state_grad(dg, w_hh, pb, ndir) if want_h0 else None
+        dc0 = dc0_rows.sum(dim=1) if want_c0 else None
+        dw_ih, db, dw_hh, _ = _weight_grads(dg, dg, x2, hprev, F, ndir, want_hh_bias=False)
+        dx = _input_grad(dg, w_ih_cat, F, pre_padded) if ctx.needs_input_grad[0] else None
         db = db.reshape(ndir, G4)
-        return dx, None, dw_ih[:, :F].reshape(ndir, G4, F), dw_hh, db, db.clone(), dh0, dc0, None
+        return dx, None, dw_ih, dw_hh, db, db.clone(), dh0, dc0, None
 
 
 class GRULayerFunction(torch.autograd.Function):
@@ -574,13 +595,10 @@ class GRULayerFunction(torch.autograd.Function):
     def forward(ctx, x2, pb, w_ih, w_hh, b_ih, b_hh, h0, training):
         L = _lib.load()
         N = x2.shape[0]
-        F = w_ih.shape[-1]               # x2 may arrive with its rows already padded to 16-byte multiples
+        F = w_ih.shape[-1]
         ndir, G3, H = w_hh.shape
         T, B = pb.T, pb.B
-        pre_padded = x2.shape[1] != F
-        x2 = _pad4_cols(x2.contiguous())
-        w_ih_cat = _pad4_cols(w_ih.reshape(ndir * G3, F))
-        gin = ops.linear_fwd(x2, w_ih_cat, b_ih.reshape(-1), ops.ACT_NONE)
+        x2, w_ih_cat, gin, pre_padded = _input_projection(x2, w_ih, b_ih)
         dev = x2.device
         y = torch.empty((N, ndir * H), dtype=torch.float32, device=dev)
         keep = bool(training)
@@ -631,24 +649,7 @@ class GRULayerFunction(torch.autograd.Function):
                    "itts_gru_layer_bwd")
         dh0 = None
         if want_h0:      # direct part dh * z from the kernel + recurrent part W_hh^T dGh, summed over rows
-            dh0 = dh0_rows.sum(dim=1) + torch.stack([ops.linear_bwd_input(
-                ops.rows_gather(dgh[:, d * G3:(d + 1) * G3], pb.first_rows(d)).sum(0, keepdim=True), w_hh[d])[0]
-                for d in range(ndir)], dim=0)
-        small_first = os.environ.get("ITTS_RNN_BWD_SMALL_FIRST", "1") != "0"     # (as in the LSTM's backward)
-        if not small_first:
-            dw_ih, db_ih = ops.linear_bwd_weight(dgi, x2)                  # [ndir*3H, F], [ndir*3H]
-        dw_hh = torch.empty((ndir, G3, H), dtype=torch.float32, device=dev)
-        db_hh = torch.empty((ndir, G3), dtype=torch.float32, device=dev)
-        for d in range(ndir):
-            _, db = ops.linear_bwd_weight(dgh[:, d * G3:(d + 1) * G3], hprev[:, d * H:(d + 1) * H],
-                                          dw=dw_hh[d])
-            db_hh[d] = db
-        if small_first:
-            dw_ih, db_ih = ops.linear_bwd_weight(dgi, x2)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = ops.linear_bwd_input(dgi, w_ih_cat)
-            if not pre_padded:
-                dx = dx[:, :F]
-        return dx, None, dw_ih[:, :F].reshape(ndir, G3, F), dw_hh, db_ih.reshape(ndir, G3), db_hh, \
-            dh0, None
+            dh0 = dh0_rows.sum(dim=1) + _initial_state_grad(dgh, w_hh, pb, ndir)
+        dw_ih, db_ih, dw_hh, db_hh = _weight_grads(dgi, dgh, x2, hprev, F, ndir, want_hh_bias=True)
+        dx = _input_grad(dgi, w_ih_cat, F, pre_padded) if ctx.needs_input_grad[0] else None
+        return dx, None, dw_ih, dw_hh, db_ih.reshape(ndir, G3), db_hh, dh0, None

@@ -88,12 +88,11 @@ def _shared_initial_state(h):
                                   "hx must be equal (expand one [layers*dirs, 1, H] state).")
 
 
-class LSTM(nn.Module):
-    """Drop-in for torch.nn.LSTM(input_size, hidden_size, num_layers, bidirectional, batch_first)
-    as RNNWrapper uses it (rnn_dyn/RNNWrapper.py:45-54).  forward takes the padded tensor and
-    the sequence lengths instead of a PackedSequence:
-        output, (h_n, c_n) = lstm(padded, (h_0, c_0), lengths)
-    with output zero-padded to the input's time extent (pad_packed_sequence(total_length=...))."""
+class _RNNBase(nn.Module):
+    """What LSTM, GRU and RNN share: torch.nn's parameters (weight_ih_l0[_reverse], weight_hh_.., bias_ih_..,
+    bias_hh_.. per layer and direction, in torch.nn's order -- the checkpoints' and the Adam arena's layout) with
+    `_gates` blocks of hidden_size rows, their initialisation, packing and inter-layer dropout."""
+    _gates = 1
 
     def __init__(self, input_size, hidden_size, num_layers=1, bias=True, batch_first=False,
                  dropout=0.0, bidirectional=False):
@@ -102,14 +101,15 @@ class LSTM(nn.Module):
         self.input_size, self.hidden_size, self.num_layers = input_size, hidden_size, num_layers
         self.batch_first, self.dropout, self.bidirectional = batch_first, dropout, bidirectional
         ndir = 2 if bidirectional else 1
+        G = self._gates * hidden_size
         for layer in range(num_layers):
             in_size = input_size if layer == 0 else hidden_size * ndir
             for d in range(ndir):
                 sfx = "_l{}{}".format(layer, "_reverse" if d == 1 else "")
-                self.register_parameter("weight_ih" + sfx, nn.Parameter(torch.empty(4 * hidden_size, in_size)))
-                self.register_parameter("weight_hh" + sfx, nn.Parameter(torch.empty(4 * hidden_size, hidden_size)))
-                self.register_parameter("bias_ih" + sfx, nn.Parameter(torch.empty(4 * hidden_size)))
-                self.register_parameter("bias_hh" + sfx, nn.Parameter(torch.empty(4 * hidden_size)))
+                self.register_parameter("weight_ih" + sfx, nn.Parameter(torch.empty(G, in_size)))
+                self.register_parameter("weight_hh" + sfx, nn.Parameter(torch.empty(G, hidden_size)))
+                self.register_parameter("bias_ih" + sfx, nn.Parameter(torch.empty(G)))
+                self.register_parameter("bias_hh" + sfx, nn.Parameter(torch.empty(G)))
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -122,20 +122,27 @@ class LSTM(nn.Module):
         return torch.stack([getattr(self, "{}_l{}{}".format(name, layer, "_reverse" if d else ""))
                             for d in range(ndir)], dim=0)
 
-    def forward(self, input_, hx=None, lengths=None):
-        ndir = 2 if self.bidirectional else 1
+    def _pack(self, input_, lengths, pad_cols):
+        """-> (PackedBatch, the valid frames as packed rows, sorted by length)"""
         time_dim, batch_dim = (1, 0) if self.batch_first else (0, 1)
         if lengths is None:
             lengths = torch.full((input_.shape[batch_dim],), input_.shape[time_dim])
-        # pack once (valid frames only, rows sorted by length), run all layers on packed rows
         pb = PackedBatch.get(lengths, input_.shape[time_dim], self.batch_first, input_.device)
-        x = pb.pack(input_, pad_cols=True)
-        h0 = c0 = None
-        if hx is not None:
-            h0, c0 = hx      # [num_layers*ndir, B, H]; RNNWrapper expands one vector per row
-            _shared_initial_state(h0)
-            _shared_initial_state(c0)
-        hn_all, cn_all = [], []
+        return pb, pb.pack(input_, pad_cols=pad_cols)
+
+    def _dropout(self, x, layer):
+        if self.dropout > 0 and self.training and layer < self.num_layers - 1:
+            x = torch.nn.functional.dropout(x, self.dropout, True)
+        return x
+
+    def _recurrent_forward(self, input_, h0s, lengths):
+        """LSTM / GRU on the recurrence kernels: h0s = the initial states ((h_0, c_0) / (h_0,), each
+        [num_layers*ndir, B, H] or None) -> (output, the final states, each [num_layers*ndir, B, H] in the
+        caller's row order)."""
+        ndir = 2 if self.bidirectional else 1
+        pb, x = self._pack(input_, lengths, pad_cols=True)
+        for h in h0s:
+            _shared_initial_state(h)
         H = self.hidden_size
         # Every layer's operands are put together BEFORE the first recurrence is launched: the host waits for each
         # recurrence's verdict (rnn_persist.h), and what it still has to queue after that wait -- the stacking of
@@ -143,91 +150,49 @@ class LSTM(nn.Module):
         # layer's product on an idle device (90 us a layer boundary in the step's timeline).
         operands = []
         for layer in range(self.num_layers):
-            hl = cl = None
-            if h0 is not None:
-                # all rows share the initial state (init_hidden expands [.., 1, H]); use row 0
-                hl = h0[layer * ndir:(layer + 1) * ndir, 0, :]
-                cl = c0[layer * ndir:(layer + 1) * ndir, 0, :]
+            # all rows share the initial state (init_hidden expands [.., 1, H]); use row 0
+            states = [h[layer * ndir:(layer + 1) * ndir, 0, :] if h is not None else None for h in h0s]
             operands.append(_pad_hidden(
                 self._stack("weight_ih", layer), self._stack("weight_hh", layer),
-                [self._stack("bias_ih", layer), self._stack("bias_hh", layer)], [hl, cl], 4, H, rows=pb.B))
-        for layer in range(self.num_layers):
-            w_ih, w_hh, (b_ih, b_hh), (hl, cl), Hp = operands[layer]
-            x, hn, cn = LSTMLayerFunction.apply(x, pb, w_ih, w_hh, b_ih, b_hh, hl, cl,
-                                                torch.is_grad_enabled())
-            x = _unpad_rows(x, ndir, H, Hp)
-            if self.dropout > 0 and self.training and layer < self.num_layers - 1:
-                x = torch.nn.functional.dropout(x, self.dropout, True)
-            hn_all.append(hn)
-            cn_all.append(cn)
+                [self._stack("bias_ih", layer), self._stack("bias_hh", layer)], states, self._gates, H, rows=pb.B))
+        finals = []
+        for layer, (w_ih, w_hh, (b_ih, b_hh), states, Hp) in enumerate(operands):
+            x, *fin = self._layer_function.apply(x, pb, w_ih, w_hh, b_ih, b_hh, *states, torch.is_grad_enabled())
+            x = self._dropout(_unpad_rows(x, ndir, H, Hp), layer)
+            finals.append(fin)
         out = pb.unpack(x, input_.shape)
         # back to the caller's row order, stacked over the layers
-        return out, (StatesToCallerOrder.apply(pb.inv_perm, pb.perm, self.hidden_size, *hn_all),
-                     StatesToCallerOrder.apply(pb.inv_perm, pb.perm, self.hidden_size, *cn_all))
+        return out, [StatesToCallerOrder.apply(pb.inv_perm, pb.perm, H, *[f[i] for f in finals])
+                     for i in range(len(h0s))]
 
 
-class GRU(nn.Module):
+class LSTM(_RNNBase):
+    """Drop-in for torch.nn.LSTM(input_size, hidden_size, num_layers, bidirectional, batch_first)
+    as RNNWrapper uses it (rnn_dyn/RNNWrapper.py:45-54).  forward takes the padded tensor and
+    the sequence lengths instead of a PackedSequence:
+        output, (h_n, c_n) = lstm(padded, (h_0, c_0), lengths)
+    with output zero-padded to the input's time extent (pad_packed_sequence(total_length=...))."""
+    _gates = 4
+    _layer_function = LSTMLayerFunction
+
+    def forward(self, input_, hx=None, lengths=None):
+        out, (hn, cn) = self._recurrent_forward(input_, hx if hx is not None else (None, None), lengths)
+        return out, (hn, cn)
+
+
+class GRU(_RNNBase):
     """Drop-in for torch.nn.GRU(input_size, hidden_size, num_layers, bidirectional, batch_first)
     as RNNWrapper uses it; same parameter names (weight_ih_l0[_reverse], ...), gate order r, z, n.
         output, h_n = gru(padded, h_0, lengths)"""
-
-    def __init__(self, input_size, hidden_size, num_layers=1, bias=True, batch_first=False,
-                 dropout=0.0, bidirectional=False):
-        super().__init__()
-        assert bias, "bias=False is not supported"
-        self.input_size, self.hidden_size, self.num_layers = input_size, hidden_size, num_layers
-        self.batch_first, self.dropout, self.bidirectional = batch_first, dropout, bidirectional
-        ndir = 2 if bidirectional else 1
-        for layer in range(num_layers):
-            in_size = input_size if layer == 0 else hidden_size * ndir
-            for d in range(ndir):
-                sfx = "_l{}{}".format(layer, "_reverse" if d == 1 else "")
-                self.register_parameter("weight_ih" + sfx, nn.Parameter(torch.empty(3 * hidden_size, in_size)))
-                self.register_parameter("weight_hh" + sfx, nn.Parameter(torch.empty(3 * hidden_size, hidden_size)))
-                self.register_parameter("bias_ih" + sfx, nn.Parameter(torch.empty(3 * hidden_size)))
-                self.register_parameter("bias_hh" + sfx, nn.Parameter(torch.empty(3 * hidden_size)))
-        self.reset_parameters()
-
-    def reset_parameters(self):
-        stdv = 1.0 / math.sqrt(self.hidden_size)
-        for w in self.parameters():
-            nn.init.uniform_(w, -stdv, stdv)
-
-    def _stack(self, name, layer):
-        ndir = 2 if self.bidirectional else 1
-        return torch.stack([getattr(self, "{}_l{}{}".format(name, layer, "_reverse" if d else ""))
-                            for d in range(ndir)], dim=0)
+    _gates = 3
+    _layer_function = GRULayerFunction
 
     def forward(self, input_, hx=None, lengths=None):
-        ndir = 2 if self.bidirectional else 1
-        time_dim, batch_dim = (1, 0) if self.batch_first else (0, 1)
-        if lengths is None:
-            lengths = torch.full((input_.shape[batch_dim],), input_.shape[time_dim])
-        pb = PackedBatch.get(lengths, input_.shape[time_dim], self.batch_first, input_.device)
-        x = pb.pack(input_, pad_cols=True)
-        _shared_initial_state(hx)
-        hn_all = []
-        H = self.hidden_size
-        operands = []            # (all layers' operands before the first recurrence: see LSTM.forward)
-        for layer in range(self.num_layers):
-            # all rows share the initial state (init_hidden expands [.., 1, H]); use row 0
-            hl = hx[layer * ndir:(layer + 1) * ndir, 0, :] if hx is not None else None
-            operands.append(_pad_hidden(
-                self._stack("weight_ih", layer), self._stack("weight_hh", layer),
-                [self._stack("bias_ih", layer), self._stack("bias_hh", layer)], [hl], 3, H, rows=pb.B))
-        for layer in range(self.num_layers):
-            w_ih, w_hh, (b_ih, b_hh), (hl,), Hp = operands[layer]
-            x, hn = GRULayerFunction.apply(x, pb, w_ih, w_hh, b_ih, b_hh, hl,
-                                           torch.is_grad_enabled())
-            x = _unpad_rows(x, ndir, H, Hp)
-            if self.dropout > 0 and self.training and layer < self.num_layers - 1:
-                x = torch.nn.functional.dropout(x, self.dropout, True)
-            hn_all.append(hn)
-        out = pb.unpack(x, input_.shape)
-        return out, StatesToCallerOrder.apply(pb.inv_perm, pb.perm, self.hidden_size, *hn_all)
+        out, (hn,) = self._recurrent_forward(input_, (hx,), lengths)
+        return out, hn
 
 
-class RNN(nn.Module):
+class RNN(_RNNBase):
     """Drop-in for torch.nn.RNN(input_size, hidden_size, num_layers, nonlinearity, bidirectional,
     batch_first) as RNNWrapper builds it for 'RNNTANH' / 'RNNRELU' groups (rnn_dyn/RNNWrapper.py:
     45-54, RNNDyn.py:268-272); same parameter names.
@@ -240,28 +205,10 @@ class RNN(nn.Module):
 
     def __init__(self, input_size, hidden_size, num_layers=1, nonlinearity='tanh', bias=True,
                  batch_first=False, dropout=0.0, bidirectional=False):
-        super().__init__()
-        assert bias, "bias=False is not supported"
         if nonlinearity.lower() not in ("tanh", "relu"):
             raise ValueError("Unknown nonlinearity '{}'".format(nonlinearity))
-        self.input_size, self.hidden_size, self.num_layers = input_size, hidden_size, num_layers
+        super().__init__(input_size, hidden_size, num_layers, bias, batch_first, dropout, bidirectional)
         self.nonlinearity = nonlinearity.lower()
-        self.batch_first, self.dropout, self.bidirectional = batch_first, dropout, bidirectional
-        ndir = 2 if bidirectional else 1
-        for layer in range(num_layers):
-            in_size = input_size if layer == 0 else hidden_size * ndir
-            for d in range(ndir):
-                sfx = "_l{}{}".format(layer, "_reverse" if d == 1 else "")
-                self.register_parameter("weight_ih" + sfx, nn.Parameter(torch.empty(hidden_size, in_size)))
-                self.register_parameter("weight_hh" + sfx, nn.Parameter(torch.empty(hidden_size, hidden_size)))
-                self.register_parameter("bias_ih" + sfx, nn.Parameter(torch.empty(hidden_size)))
-                self.register_parameter("bias_hh" + sfx, nn.Parameter(torch.empty(hidden_size)))
-        self.reset_parameters()
-
-    def reset_parameters(self):
-        stdv = 1.0 / math.sqrt(self.hidden_size)
-        for w in self.parameters():
-            nn.init.uniform_(w, -stdv, stdv)
 
     def _direction(self, x, pb, layer, d, h0):
         """x [N, F] packed rows -> (y [N, H] packed, h_n [B, H] in sorted row order)"""
@@ -299,11 +246,8 @@ class RNN(nn.Module):
 
     def forward(self, input_, hx=None, lengths=None):
         ndir = 2 if self.bidirectional else 1
-        time_dim, batch_dim = (1, 0) if self.batch_first else (0, 1)
-        if lengths is None:
-            lengths = torch.full((input_.shape[batch_dim],), input_.shape[time_dim])
-        pb = PackedBatch.get(lengths, input_.shape[time_dim], self.batch_first, input_.device)
-        x = pb.pack(input_)
+        pb, x = self._pack(input_, lengths, pad_cols=False)
+        _shared_initial_state(hx)
         hn_all = []
         for layer in range(self.num_layers):
             outs = []
@@ -312,7 +256,5 @@ class RNN(nn.Module):
                 y, h_n = self._direction(x, pb, layer, d, h0)
                 outs.append(y)
                 hn_all.append(h_n.index_select(0, pb.inv_perm))
-            x = outs[0] if ndir == 1 else torch.cat(outs, dim=1)
-            if self.dropout > 0 and self.training and layer < self.num_layers - 1:
-                x = torch.nn.functional.dropout(x, self.dropout, True)
+            x = self._dropout(outs[0] if ndir == 1 else torch.cat(outs, dim=1), layer)
         return pb.unpack(x, input_.shape), torch.stack(hn_all, 0)

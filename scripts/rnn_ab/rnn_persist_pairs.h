@@ -668,8 +668,7 @@ template <int G>
 static int rnn_persist_backward(RnnPersistBwdArgs p, const int* h_lengths, int H, hipStream_t s) {
   static std::atomic<bool> usable{true};
   const char* pe = getenv("ITTS_RNN_PERSISTENT");          // read per call: tests switch it
-  const char* pb = getenv("ITTS_RNN_PERSISTENT_BWD");      // ... and this one keeps the forward half on
-  if ((pe && pe[0] == '0') || (pb && pb[0] == '0') || !usable.load()) return 0;
+  if ((pe && pe[0] == '0') || !usable.load()) return 0;
   p.ntiles = (p.B + 15) / 16;
   if (H != PH) return 0;
   static int n_cu = 0;

@@ -145,6 +145,8 @@ def test_vanilla_rnn_matches_torch(gpu, nonlin, bidir, layers, batch_first):
     for (n, pr), (_, pm) in zip(ref.named_parameters(), mine.named_parameters()):
         err = (pm.grad.cpu().double() - pr.grad).abs().max().item()
         assert err < 1e-4 * max(1.0, pr.grad.abs().max().item()), (n, err)
+    with pytest.raises(NotImplementedError):        # one initial state per row: refused, not replaced by row 0's
+        mine(x.to(gpu), torch.randn(layers * ndir, B, H, device=gpu), lengths)
 
 
 def test_rnntanh_group_in_rnndyn(gpu):

@@ -47,6 +47,19 @@ def test_bilstm_3x512_parameter_count():
     assert tuple(model.state_dict()["1.h_0"].shape) == (6, 1, 512)
 
 
+@pytest.mark.parametrize("cell", ["LSTM", "GRU", "RNN"])
+@pytest.mark.parametrize("layers,bidir", [(1, False), (1, True), (3, False), (3, True)])
+def test_recurrent_parameters_follow_torch_nn(cell, layers, bidir):
+    """Names, shapes and order of named_parameters() equal torch.nn's: they fix the checkpoint layout and the
+    Adam arena's."""
+    from idiaptts_amd import nn as inn
+    mine = getattr(inn, cell)(11, 16, layers, bidirectional=bidir)
+    ref = getattr(torch.nn, cell)(11, 16, layers, bidirectional=bidir)
+    assert [(n, tuple(p.shape)) for n, p in mine.named_parameters()] == \
+        [(n, tuple(p.shape)) for n, p in ref.named_parameters()]
+    assert all(float(p.detach().abs().max()) <= 0.25 for p in mine.parameters())     # U(-1/sqrt(H), 1/sqrt(H))
+
+
 def test_legacy_string_errors():
     with pytest.raises(NotImplementedError):
         _wrapped("RNNDYN-1_Conv1dRELU_32_5-1_FC_3", 5)
