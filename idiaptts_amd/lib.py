@@ -96,6 +96,14 @@ _SIGNATURES = {
                                        _P, c_int, _P]),
     "itts_linear_bwd": (c_int, [_P, c_int64, _P, c_int64, _P, _P, _P, _P, c_int64, _P, c_int64, c_int,
                                 c_int64, c_int, c_int, _P, c_int, _P]),
+    "itts_conv1d_fwd": (c_int, [_P, c_int64, _P, _P, _P, c_int64, c_int, c_int, c_int, c_int, c_int,
+                                c_int, c_int, c_int, c_int, _P]),
+    "itts_conv1d_bwd_input": (c_int, [_P, c_int64, _P, _P, c_int64, _P, c_int64, c_int, c_int, c_int,
+                                      c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "itts_conv1d_bwd_weight_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int,
+                                                         c_int]),
+    "itts_conv1d_bwd_weight": (c_int, [_P, c_int64, _P, c_int64, _P, _P, c_int, c_int, c_int, c_int,
+                                       c_int, c_int, c_int, c_int, _P, c_int, _P]),
     "itts_masked_mse_workspace_bytes": (c_int64, [c_int64, c_int]),
     "itts_masked_mse": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, c_int, c_double, c_float,
                                 _P, _P, c_int64, _P, _P]),

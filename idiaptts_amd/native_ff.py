@@ -75,7 +75,7 @@ class FlatFFModel:
     def from_module(model, device=None):
         """Mirror of a drop-in module stack (NamedForwardWrapper / RNNDyn) that consists of Linear
         groups only: same weights, flat buffers.  Returns None when the model has anything else
-        (recurrent groups, dropout) -- those train through the module path."""
+        (recurrent groups, Conv1d groups, dropout) -- those train through the module path."""
         from .nn.modules import LinearAct
         inner = getattr(model, "model", model)
         layers, acts = [], []
@@ -87,7 +87,7 @@ class FlatFFModel:
                 if isinstance(m, LinearAct):
                     layers.append((m.weight.detach(), m.bias.detach()))
                     acts.append({ops.ACT_NONE: None, ops.ACT_TANH: "tanh", ops.ACT_RELU: "relu"}[m.act])
-                elif isinstance(m, torch.nn.Dropout):
+                elif isinstance(m, (torch.nn.Dropout, torch.nn.Conv1d)):
                     return None
                 elif type(m).__name__ != "FusedActivation":
                     return None

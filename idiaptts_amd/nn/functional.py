@@ -90,6 +90,50 @@ class LinearActFunction(torch.autograd.Function):
         return dx, dw, (db if ctx.has_bias else None), None
 
 
+def _conv_pitch4(t):
+    """t ([B, T, C] / [T, B, C]) itself when its rows have a 16-byte pitch, else a view of a copy whose rows do:
+    the conv1d kernels then take 16-byte loads (the pad floats are read and masked, never used)."""
+    C = t.shape[2]
+    if C % 4 == 0 and t.is_contiguous():
+        return t
+    full = torch.empty(t.shape[:2] + ((C + 3) // 4 * 4,), dtype=torch.float32, device=t.device)
+    full[:, :, C:] = 0
+    full[:, :, :C] = t
+    return full[:, :, :C]
+
+
+class Conv1dActFunction(torch.autograd.Function):
+    """y = act(conv1d(x, w, b)) over time on channels-last activations ([B, T, C] batch_first, else [T, B, C]);
+    rnn_dyn/CNNWrapper.py:55-61 (torch.nn.Conv1d + Tanh / ReLU).  Saves x and y; backward applies act' through y
+    and returns dx, dw, db (csrc/conv1d.hip)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, padding, dilation, batch_first, act):
+        x = _conv_pitch4(x)
+        w = weight.contiguous()
+        y = ops.conv1d_fwd(x, w, bias, padding, dilation, batch_first, act)
+        ctx.save_for_backward(x, w, y)
+        ctx.geometry = (int(padding), int(dilation), bool(batch_first))
+        ctx.act = act
+        ctx.has_bias = bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, y = ctx.saved_tensors
+        padding, dilation, batch_first = ctx.geometry
+        dz = ops.act_bwd(dy, y, ctx.act) if ctx.act != ops.ACT_NONE else dy
+        dz = _conv_pitch4(dz)
+        dx = dw = db = None
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            dw, db = ops.conv1d_bwd_weight(dz, x, w.shape[2], padding, dilation, batch_first,
+                                           want_bias=ctx.has_bias)
+        if ctx.needs_input_grad[0]:
+            T_in = x.shape[1 if batch_first else 0]
+            dx = ops.conv1d_bwd_input(dz, w, T_in, padding, dilation, batch_first)
+        return dx, dw, (db if ctx.has_bias else None), None, None, None, None
+
+
 def _rows_padded(M, N, device):
     """[M, N] view of a fresh buffer whose row pitch is N rounded up to four floats, pad columns zero"""
     Np = (N + 3) // 4 * 4

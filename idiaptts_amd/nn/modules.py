@@ -8,7 +8,8 @@ import torch
 from torch import nn
 
 from .. import ops
-from .functional import GRULayerFunction, LinearActFunction, LSTMLayerFunction, PackedBatch, StatesToCallerOrder
+from .functional import (Conv1dActFunction, GRULayerFunction, LinearActFunction, LSTMLayerFunction, PackedBatch,
+                         StatesToCallerOrder)
 
 
 class LinearAct(nn.Linear):
@@ -21,6 +22,45 @@ class LinearAct(nn.Linear):
 
     def forward(self, input_):
         return LinearActFunction.apply(input_, self.weight, self.bias, self.act)
+
+
+class Conv1dAct(nn.Conv1d):
+    """torch.nn.Conv1d (same parameters, same initialisation, same RNG draws) whose forward/backward run the
+    fp32-MFMA implicit-GEMM kernels of csrc/conv1d.hip; `act` fuses the following Tanh / ReLU into the epilogue.
+    Activations are channels-last and keep the model's layout: input [B, T, Cin] when `batch_first`, else
+    [T, B, Cin]; output [B, T_out, Cout] / [T_out, B, Cout] (torch's Conv1d takes [B, Cin, T]).
+    Built: stride 1, groups 1, padding_mode 'zeros', integer padding; anything else raises NotImplementedError."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1,
+                 bias=True, padding_mode="zeros", act=None, batch_first=True):
+        if isinstance(padding, str):
+            raise NotImplementedError("Conv1d padding={!r}: only integer padding is implemented".format(padding))
+        for name, value in (("kernel_size", kernel_size), ("stride", stride), ("padding", padding),
+                            ("dilation", dilation)):
+            if isinstance(value, (tuple, list)) and len(value) != 1:
+                raise NotImplementedError("Conv1d {}={}: only 1-D convolutions are implemented".format(name, value))
+        if _first(stride) != 1:
+            raise NotImplementedError("Conv1d stride={}: only stride 1 is implemented".format(stride))
+        if groups != 1:
+            raise NotImplementedError("Conv1d groups={}: only groups=1 is implemented".format(groups))
+        if padding_mode != "zeros":
+            raise NotImplementedError("Conv1d padding_mode={!r}: only 'zeros' is implemented".format(padding_mode))
+        super().__init__(in_channels, out_channels, kernel_size, stride=stride, padding=padding, dilation=dilation,
+                         groups=groups, bias=bias, padding_mode=padding_mode)
+        self.act = ops.ACT_BY_NAME[act.lower() if isinstance(act, str) else act]
+        self.batch_first = batch_first
+
+    def forward(self, input_):
+        return Conv1dActFunction.apply(input_, self.weight, self.bias, self.padding[0], self.dilation[0],
+                                       self.batch_first, self.act)
+
+    def output_length(self, lengths):
+        """T_out of inputs of T_in steps (tensor or int)"""
+        return lengths + 2 * self.padding[0] - self.dilation[0] * (self.kernel_size[0] - 1)
+
+
+def _first(v):
+    return v[0] if isinstance(v, (tuple, list)) else v
 
 
 _cu_count = {}

@@ -517,6 +517,139 @@ def linear_bwd_weight(dz, x, dw=None, db=None, accumulate=False, want_bias=True)
     return dw, db
 
 
+# ------------------------------------------------------------------------------ Conv1d groups
+# Activations stay in the model's layout: [B, T, C] (batch_first) or [T, B, C], channels last, so that
+# row (b, t) of the padded batch is one row of a 2-D [B*T, ld] view; no transpose to torch's [B, C, T].
+def conv1d_out_len(T_in, kernel_size, padding, dilation):
+    """T_out of a stride-1 Conv1d (rnn_dyn/CNNWrapper.py:get_output_length)"""
+    return T_in + 2 * padding - dilation * (kernel_size - 1)
+
+
+def _conv_rows(t, name):
+    """(t, ld): t as a [B, T, C] / [T, B, C] tensor whose row (i, j) sits at (i * shape[1] + j) * ld, copied
+    when its strides do not allow that; a 16-byte pitch wider than C is kept only when the storage holds the
+    last row's pad floats (the kernels read them, see the pitch rule in include/idiaptts_amd.h)."""
+    if t.dim() != 3:
+        raise ValueError("{} must be 3-D [B, T, C] (batch_first) or [T, B, C]".format(name))
+    C = t.shape[2]
+    ld = t.stride(1) if t.shape[1] > 1 else (t.stride(0) if t.shape[0] > 1 else C)
+    ok = (t.stride(2) == 1 or C == 1) and ld >= C and (t.shape[0] == 1 or t.stride(0) == t.shape[1] * ld)
+    if ok and ld != C and ld % 4 == 0:
+        ok = t.storage_offset() + t.shape[0] * t.shape[1] * ld <= t.untyped_storage().nbytes() // 4
+    if ok:
+        return t, ld
+    return t.clone(memory_format=torch.contiguous_format), C
+
+
+def _conv_dims(x, batch_first):
+    return (x.shape[0], x.shape[1]) if batch_first else (x.shape[1], x.shape[0])
+
+
+def _conv_geometry(w, padding, dilation, T_in):
+    if w.dim() != 3 or not w.is_contiguous():
+        raise ValueError("w must be contiguous [Cout, Cin, Kw]")
+    Cout, Cin, Kw = w.shape
+    padding, dilation = int(padding), int(dilation)
+    if padding < 0 or dilation < 1:
+        raise ValueError("padding must be >= 0 and dilation >= 1, got {} / {}".format(padding, dilation))
+    T_out = conv1d_out_len(T_in, Kw, padding, dilation)
+    if T_out <= 0:
+        raise ValueError("Conv1d output length T_in + 2 padding - dilation (kernel_size - 1) = {} + 2 * {} - {} * {} "
+                         "= {} is not positive".format(T_in, padding, dilation, Kw - 1, T_out))
+    return Cout, Cin, Kw, padding, dilation, T_out
+
+
+def _conv_out(like, batch_first, B, T, C):
+    shape = (B, T, C) if batch_first else (T, B, C)
+    return torch.empty(shape, dtype=torch.float32, device=like.device)
+
+
+def conv1d_fwd(x, w, b, padding, dilation, batch_first, act=ACT_NONE, out=None):
+    """y = act(conv1d(x, w, b, padding, dilation)) over the time axis: x [B, T_in, Cin] (batch_first) or
+    [T_in, B, Cin], w [Cout, Cin, Kw] (torch's layout), b [Cout] or None -> y [B, T_out, Cout] / [T_out, B, Cout]."""
+    L = _lib.load()
+    _need(x, torch.float32, "x")
+    _need(w, torch.float32, "w")
+    B, T_in = _conv_dims(x, batch_first)
+    Cout, Cin, Kw, padding, dilation, T_out = _conv_geometry(w, padding, dilation, T_in)
+    if x.shape[2] != Cin:
+        raise ValueError("x has {} channels, w expects {}".format(x.shape[2], Cin))
+    if b is not None:
+        _need(b, torch.float32, "b")
+        if b.shape != (Cout,) or not b.is_contiguous():
+            raise ValueError("b must be contiguous [Cout]")
+    x, ldx = _conv_rows(x, "x")
+    shape = (B, T_out, Cout) if batch_first else (T_out, B, Cout)
+    if out is None:
+        out = _conv_out(x, batch_first, B, T_out, Cout)
+    elif tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError("out must be a contiguous {} tensor".format(shape))
+    _lib.check(L.itts_conv1d_fwd(_ptr(x), ldx, _ptr(w), _ptr(b), _ptr(out), Cout, B, T_in, Cin, Cout, Kw, padding,
+                                 dilation, 1 if batch_first else 0, act, _stream()), "itts_conv1d_fwd")
+    return out
+
+
+def conv1d_bwd_input(dz, w, T_in, padding, dilation, batch_first, yprev=None, act_prev=ACT_NONE, out=None):
+    """dx [B, T_in, Cin] (layout of dz) from dz [B, T_out, Cout]; with yprev (the previous layer's output, shaped
+    as dx) dx *= act_prev'(yprev)."""
+    L = _lib.load()
+    _need(dz, torch.float32, "dz")
+    _need(w, torch.float32, "w")
+    B, T_dz = _conv_dims(dz, batch_first)
+    Cout, Cin, Kw, padding, dilation, T_out = _conv_geometry(w, padding, dilation, int(T_in))
+    if T_dz != T_out or dz.shape[2] != Cout:
+        raise ValueError("dz must have {} steps and {} channels, got {}".format(T_out, Cout, tuple(dz.shape)))
+    shape = (B, T_in, Cin) if batch_first else (T_in, B, Cin)
+    dz, lddz = _conv_rows(dz, "dz")
+    ldyp = 0
+    if yprev is not None:
+        _need(yprev, torch.float32, "yprev")
+        if tuple(yprev.shape) != shape:
+            raise ValueError("yprev must be {}".format(shape))
+        yprev, ldyp = _conv_rows(yprev, "yprev")
+    if out is None:
+        out = _conv_out(dz, batch_first, B, T_in, Cin)
+    if tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError("out must be a contiguous {} tensor".format(shape))
+    _lib.check(L.itts_conv1d_bwd_input(_ptr(dz), lddz, _ptr(w), _ptr(out), Cin, _ptr(yprev), ldyp, act_prev, B,
+                                       int(T_in), Cin, Cout, Kw, padding, dilation, 1 if batch_first else 0,
+                                       _stream()), "itts_conv1d_bwd_input")
+    return out
+
+
+def conv1d_bwd_weight(dz, x, kernel_size, padding, dilation, batch_first, dw=None, db=None, accumulate=False,
+                      want_bias=True):
+    """(dw [Cout, Cin, Kw], db [Cout] or None) of conv1d_fwd from dz [B, T_out, Cout] and its input x; deterministic
+    (a fixed split of the B * T_out rows through a workspace); accumulate adds to dw / db."""
+    L = _lib.load()
+    _need(dz, torch.float32, "dz")
+    _need(x, torch.float32, "x")
+    B, T_in = _conv_dims(x, batch_first)
+    Cin, Cout, Kw = x.shape[2], dz.shape[2], int(kernel_size)
+    T_out = conv1d_out_len(T_in, Kw, int(padding), int(dilation))
+    if Kw < 1 or int(padding) < 0 or int(dilation) < 1 or T_out <= 0:
+        raise ValueError("Conv1d output length {} (T_in {}, kernel {}, padding {}, dilation {}) is not positive"
+                         .format(T_out, T_in, Kw, padding, dilation))
+    if _conv_dims(dz, batch_first) != (B, T_out):
+        raise ValueError("dz must have batch {} and {} steps, got {}".format(B, T_out, tuple(dz.shape)))
+    x, ldx = _conv_rows(x, "x")
+    dz, lddz = _conv_rows(dz, "dz")
+    if dw is None:
+        dw = (torch.zeros if accumulate else torch.empty)((Cout, Cin, Kw), dtype=torch.float32, device=dz.device)
+    if db is None and want_bias:
+        db = (torch.zeros if accumulate else torch.empty)((Cout,), dtype=torch.float32, device=dz.device)
+    if tuple(dw.shape) != (Cout, Cin, Kw) or not dw.is_contiguous():
+        raise ValueError("dw must be contiguous [{}, {}, {}]".format(Cout, Cin, Kw))
+    if db is not None and (tuple(db.shape) != (Cout,) or not db.is_contiguous()):
+        raise ValueError("db must be contiguous [{}]".format(Cout))
+    ws = _workspace(L.itts_conv1d_bwd_weight_workspace_bytes(B, T_in, Cin, Cout, Kw, int(padding), int(dilation)),
+                    dz.device)
+    _lib.check(L.itts_conv1d_bwd_weight(_ptr(dz), lddz, _ptr(x), ldx, _ptr(dw), _ptr(db), B, T_in, Cin, Cout, Kw,
+                                        int(padding), int(dilation), 1 if batch_first else 0, _ptr(ws),
+                                        1 if accumulate else 0, _stream()), "itts_conv1d_bwd_weight")
+    return dw, db
+
+
 def linear_bwd(dz, x, w, dw, db, dx, yprev=None, act_prev=ACT_NONE, accumulate=False):
     """dw [N, K] (+ db [N]) and dx [M, K] of a linear layer from dz [M, N], its input x [M, K] and its
     weight w [N, K] in one call (one launch when the buffers allow 16-byte rows); dx is multiplied by

@@ -1,6 +1,6 @@
 """rnn_dyn.Config / LayerConfig with the reference's fields
 (idiaptts/src/neural_networks/pytorch/models/rnn_dyn/Config.py:12-138), restricted to the layer
-types on the accelerated path: Linear (+Tanh/ReLU) groups and (Bi)LSTM groups."""
+types on the accelerated path: Linear (+Tanh/ReLU) groups, LSTM / GRU / RNN groups and Conv1d groups."""
 import copy
 import re
 from typing import List
@@ -84,7 +84,10 @@ def config_from_legacy_string(in_dim, name, batch_first=False, dropout=0.0):
     """'RNNDYN-2_TANH_512-3_BiLSTM_512-1_FC_187' -> Config (reference RNNDyn.py:150-357):
     groups '<n layers>_<type>_<out dim>' separated by '-'; TANH / RELU groups are Linear layers
     each followed by the non-linearity, FC / LIN are linear, a 'Bi' prefix makes an RNN group
-    bidirectional; dropout applies inside multi-layer RNN groups and after every FF layer."""
+    bidirectional; dropout applies inside multi-layer RNN groups and after every FF layer.
+    '<n>_Conv1d_<out>_<kernel>[_s<stride>][_p<padding>][_d<dilation>][_g<groups>]' is a Conv1d group without a
+    non-linearity (reference RNNDyn.py:282-320; sizes 'AxB' become tuples, padding defaults to (kernel - 1) // 2);
+    a 'BatchNorm1d' prefix (batch-normalised groups) is not implemented."""
     groups = re.split(r'-\s*(?![^()]*\))', name)[1:]
     if len(groups) == 0:
         raise ValueError("Empty RNNDYN configuration: {}".format(name))
@@ -93,6 +96,8 @@ def config_from_legacy_string(in_dim, name, batch_first=False, dropout=0.0):
     for group in groups:
         attr = group.split('_')
         n_layers, layer_type, out_dim = int(attr[0]), attr[1], int(attr[2])
+        if layer_type.startswith("BatchNorm"):
+            raise NotImplementedError("Layer type {}: BatchNorm groups are not implemented.".format(layer_type))
         bidirectional = layer_type[:2] == 'Bi'
         if bidirectional:
             layer_type = layer_type[2:]
@@ -109,7 +114,31 @@ def config_from_legacy_string(in_dim, name, batch_first=False, dropout=0.0):
                                                     num_layers=n_layers,
                                                     nonlin=nonlins.get(layer_type.upper()),
                                                     dropout=dropout))
+        elif layer_type == "Conv1d":
+            layer_configs.append(_legacy_conv1d_config(attr, n_layers, out_dim, name))
         else:
             raise NotImplementedError("Layer type {} is outside the accelerated path "
                                       "(SURVEY.md section 2).".format(layer_type))
     return Config(in_dim=int(in_dim), batch_first=batch_first, layer_configs=layer_configs)
+
+
+def _legacy_conv1d_config(attr, n_layers, out_dim, name):
+    """reference RNNDyn.py:282-320"""
+    if len(attr) < 4:
+        raise NotImplementedError("Kernel size has to be given in Conv1d as "
+                                  "<num layer>_<layer type>_<out dim>_<kernel size(s)>.")
+    kernel = tuple(map(int, attr[3].split('x')))
+    stride, padding, dilation, conv_groups = 1, int((kernel[0] - 1) / 2), 1, 1
+    for param in attr[4:]:
+        if param[0] == "s":
+            stride = tuple(map(int, param[1:].split('x')))
+        elif param[0] == "p":
+            padding = tuple(map(int, param[1:].split('x')))
+        elif param[0] == "d":
+            dilation = tuple(map(int, param[1:].split('x')))
+        elif param[0] == "g":
+            conv_groups = int(param[1:])
+        else:
+            raise NotImplementedError("Unknown param type {} in {}".format(param, name))
+    return Config.LayerConfig(layer_type="Conv1d", out_dim=out_dim, num_layers=n_layers, kernel_size=kernel,
+                              stride=stride, padding=padding, dilation=dilation, groups=conv_groups)

@@ -1,19 +1,20 @@
 """RNNDyn and its layer-group wrappers on the HIP kernels
-(reference: rnn_dyn/RNNDyn.py:26-147, FFWrapper.py:37-88, RNNWrapper.py:45-107).
+(reference: rnn_dyn/RNNDyn.py:26-147, FFWrapper.py:37-88, RNNWrapper.py:45-107, CNNWrapper.py,
+TransposingWrapper.py).
 
 state_dict() keys and shapes equal the reference's, so its checkpoints load unchanged:
 FF group `<i>.module.<k>.weight/bias` with k = index of the Linear inside the nn.Sequential
 (non-linearity / dropout modules keep their slots), RNN group `<i>.module.weight_ih_l0[_reverse]`,
-`<i>.h_0`, `<i>.c_0`; the group index starts at 1 because `emb_groups` takes slot 0 of the
-ModuleList.
+`<i>.h_0`, `<i>.c_0`, Conv1d group `<i>.module.<k>.weight/bias` as FF groups; the group index starts at 1
+because `emb_groups` takes slot 0 of the ModuleList.
 """
 import copy
 
 import torch
 from torch import nn
 
-from idiaptts_amd.nn.functional import LinearChainFunction, ValidRows, padding_is_identical
-from idiaptts_amd.nn.modules import GRU, LSTM, RNN, LinearAct
+from idiaptts_amd.nn.functional import LinearChainFunction, ValidRows, padding_is_identical, padding_rows_identical
+from idiaptts_amd.nn.modules import GRU, LSTM, RNN, Conv1dAct, LinearAct
 
 
 class FusedActivation(nn.Identity):
@@ -175,6 +176,64 @@ class RNNWrapper(nn.Module):
         return output, kwargs
 
 
+class CNNWrapper(nn.Module):
+    """A Conv1d layer group (reference CNNWrapper.py + TransposingWrapper.py): `num_layers` Conv1d layers, each
+    followed by the group's non-linearity, on the padded batch in the model's own layout -- the kernels take
+    channels-last rows, so nothing is transposed and the output comes back batch_first or time-major like the
+    input.  As in the reference: padding (kernel_size - 1) // 2 is filled in (and written back into
+    layer_config.kwargs) when neither padding nor a stride / dilation other than 1 is given, every weight is
+    re-initialised with xavier_uniform_(gain=calculate_gain('conv1d')), the non-linearity keeps its slot in the
+    nn.Sequential (state-dict keys `module.0.weight`, `module.2.weight`, ...), no dropout is appended, and
+    seq_lengths_input / max_length_inputs leave with the output's lengths.  Not an FFWrapper: a convolution
+    needs every position of the padded tensor, its padding included, never the valid-rows path."""
+
+    def __init__(self, in_dim, layer_config, batch_first=True):
+        super().__init__()
+        if layer_config.type != "Conv1d":
+            raise NotImplementedError("Layer type {} is outside the accelerated path: only Conv1d groups "
+                                      "are implemented.".format(layer_config.type))
+        nonlin = layer_config.nonlin
+        if nonlin is not None:
+            nonlin = {"relu": "ReLU", "tanh": "Tanh"}.get(nonlin.lower(), nonlin)
+        if nonlin not in (None, "Tanh", "ReLU"):
+            raise NotImplementedError("Conv1d group nonlin={}: only Tanh and ReLU are implemented."
+                                      .format(layer_config.nonlin))
+        self.batch_first = batch_first
+        kwargs = layer_config.kwargs
+        layers = []
+        for _ in range(layer_config.num_layers):
+            if 'padding' not in kwargs and kwargs.get('stride', 1) == 1 and kwargs.get('dilation', 1) == 1:
+                kernel = kwargs.get('kernel_size')
+                if isinstance(kernel, (tuple, list)):
+                    kernel = kernel[0]
+                kwargs['padding'] = int((kernel - 1) / 2)       # reference CNNWrapper.py:25-35
+            layer = Conv1dAct(in_dim, layer_config.out_dim, act=nonlin, batch_first=batch_first, **kwargs)
+            layers.append(layer)
+            in_dim = layer_config.out_dim
+            nn.init.xavier_uniform_(layer.weight, gain=nn.init.calculate_gain(layer_config.type.lower()))
+            if nonlin is not None:
+                layers.append(FusedActivation(nonlin))
+        self.module = nn.Sequential(*layers)
+        self.out_dim = in_dim
+
+    def init_hidden(self, batch_size=1):
+        pass
+
+    def get_output_length(self, seq_lengths_input):
+        """reference CNNWrapper.py:get_output_length (stride 1)"""
+        for layer in self.module:
+            if isinstance(layer, Conv1dAct):
+                seq_lengths_input = layer.output_length(seq_lengths_input)
+        return seq_lengths_input
+
+    def forward(self, input_, **kwargs):
+        output = self.module(input_)
+        for key in ("seq_lengths_input", "max_length_inputs"):
+            if kwargs.get(key) is not None:
+                kwargs[key] = self.get_output_length(kwargs[key])
+        return output, kwargs
+
+
 class RNNDyn(nn.ModuleList):
 
     def __init__(self, config):
@@ -193,8 +252,10 @@ class RNNDyn(nn.ModuleList):
             if layer_config.needs_packing:
                 layer = RNNWrapper(in_dim, layer_config, config.batch_first, enforce_sorted=False)
             elif layer_config.needs_transposing:
-                raise NotImplementedError("Conv / BatchNorm groups are outside the accelerated "
-                                          "path (SURVEY.md section 2).")
+                if layer_config.type != "Conv1d":
+                    raise NotImplementedError("{} groups are outside the accelerated path (SURVEY.md "
+                                              "section 2).".format(layer_config.type))
+                layer = CNNWrapper(in_dim, layer_config, config.batch_first)
             else:
                 layer = FFWrapper(in_dim, layer_config, config.batch_first)
             in_dim = layer.out_dim
@@ -227,9 +288,12 @@ class RNNDyn(nn.ModuleList):
             if chain:
                 rows, chain = (rows[0], run_linear_chain(rows[1], chain)), []
 
+        # After a Conv1d group the padding positions no longer hold one common row (those just past each length mix
+        # in valid frames), so no later group may stand one representative row in for them.
+        after_conv = False
         for group_idx, module in enumerate(self.layer_groups):
             affected = [emb for emb in self.emb_groups.values() if self._affects(emb, group_idx)]
-            if isinstance(module, FFWrapper) and not affected:
+            if isinstance(module, FFWrapper) and not affected and not after_conv:
                 if rows is None:
                     vr = module.valid_rows_for(input_, kwargs)
                     if vr is not None:
@@ -247,7 +311,12 @@ class RNNDyn(nn.ModuleList):
                 input_, rows = rows[0].unpack(rows[1]), None
             for emb in affected:
                 input_ = torch.cat((input_, embeddings[emb.name]), dim=2)
-            input_, kwargs = module(input_, **kwargs)
+            after_conv = after_conv or isinstance(module, CNNWrapper)
+            if after_conv and padding_is_identical():
+                with padding_rows_identical(False):
+                    input_, kwargs = module(input_, **kwargs)
+            else:
+                input_, kwargs = module(input_, **kwargs)
             # hidden states are not passed from one RNN group to the next (reference :118-121)
             last_hidden = kwargs.pop("hidden", last_hidden)
         if rows is not None:

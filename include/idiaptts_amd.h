@@ -356,6 +356,33 @@ int itts_linear_bwd(const float* d_dz, int64_t lddz, const float* d_x, int64_t l
                     int64_t ldyp, int act_prev, int64_t M, int N, int K, void* d_workspace,
                     int accumulate, void* stream);
 
+/* ---- acoustic model: Conv1d groups (rnn_dyn/CNNWrapper.py:28-61 -> torch.nn.Conv1d + act) ---
+ * 1-D convolution over the time axis of a zero-padded batch of B utterances, stride 1, groups 1,
+ * padding_mode 'zeros': T_out = T_in + 2 pad - dil (Kw - 1) (> 0, else ITTS_E_INVALID).  Activations
+ * are rows: row (b, t) is b * T + t (batch_first != 0) or t * B + b (time-major), T = T_in for x /
+ * dx / yprev and T_out for y / dz.  A time index outside [0, T_in) counts as zero (the edge of the
+ * padded tensor, not the valid length: nn.Conv1d on the padded batch).  w is torch's
+ * [Cout][Cin][Kw], contiguous.  fp32 MFMA implicit GEMM (the im2col matrix is never stored); the
+ * pitch rule of the dense layers above applies to x, dz and their 1-3 pad floats.
+ * y[(b,t), n] = act(b[n] + sum_k sum_c x[(b, t + k dil - pad), c] w[n][c][k])  (d_b may be NULL). */
+int itts_conv1d_fwd(const float* d_x, int64_t ldx, const float* d_w, const float* d_b, float* d_y,
+                    int64_t ldy, int B, int T_in, int Cin, int Cout, int Kw, int pad, int dil,
+                    int batch_first, int act, void* stream);
+/* Autograd's input gradient of nn.Conv1d (CNNWrapper.py:55-61 backward): dx [B*T_in, Cin] from dz
+ * [B*T_out, Cout]; if d_yprev != NULL the previous layer's act' (through its output yprev, rows as
+ * dx) is fused into the epilogue: dx *= act'(yprev). */
+int itts_conv1d_bwd_input(const float* d_dz, int64_t lddz, const float* d_w, float* d_dx, int64_t lddx,
+                          const float* d_yprev, int64_t ldyp, int act_prev, int B, int T_in, int Cin,
+                          int Cout, int Kw, int pad, int dil, int batch_first, void* stream);
+/* dw[n][c][k] = sum_(b,t) dz[(b,t), n] x[(b, t + k dil - pad), c], db[n] = colsum(dz) (d_db may be
+ * NULL): nn.Conv1d's weight / bias gradients.  Deterministic split over the B*T_out rows through
+ * d_workspace (>= itts_conv1d_bwd_weight_workspace_bytes); bit-identical run to run.  If
+ * accumulate != 0, adds. */
+int64_t itts_conv1d_bwd_weight_workspace_bytes(int B, int T_in, int Cin, int Cout, int Kw, int pad, int dil);
+int itts_conv1d_bwd_weight(const float* d_dz, int64_t lddz, const float* d_x, int64_t ldx, float* d_dw,
+                           float* d_db, int B, int T_in, int Cin, int Cout, int Kw, int pad, int dil,
+                           int batch_first, void* d_workspace, int accumulate, void* stream);
+
 /* ---- masked MSE, reduction 'mean_per_frame' (loss/NamedLoss.py:70-117) -------------------- */
 /*
  * loss = mean_d( sum_{valid frames} (pred-target)^2 / n_valid ), grad = dloss/dpred.
