@@ -42,6 +42,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #ifndef RING_DBG
 #define RING_DBG 0   // lab only: 1 no DMA, 2 no step barrier, 4 no MFMA, 8 no epilogue, 16 no fragment reads
 #endif
@@ -65,7 +67,15 @@ constexpr int PIECES = 6;                     // 1-KB DMA instructions per loade
 constexpr int THREADS = 512;         // 4 compute waves + 4 loader waves (workgroups of 5 or 6 waves do not share a CU)
 
 enum { EPI_STORE = 0, EPI_BIAS_ACT = 1, EPI_DACT = 2, EPI_MSE = 3 };
-enum { ACT_NONE = 0, ACT_TANH = 1, ACT_RELU = 2 };
+// the ITTS_ACT_* codes of include/idiaptts_amd.h
+enum {
+  ACT_NONE = 0, ACT_TANH = 1, ACT_RELU = 2, ACT_SIGMOID = 3, ACT_LOGSIGMOID = 4, ACT_SOFTPLUS = 5, ACT_SOFTSIGN = 6,
+  ACT_LEAKY_RELU = 7, ACT_ELU = 8, ACT_CELU = 9, ACT_SELU = 10, ACT_HARDTANH = 11, ACT_RELU6 = 12, ACT_HARDSIGMOID = 13
+};
+// Activation family of a kernel instantiation: AF_BASE picks NONE / TANH / RELU at run time (the headline FF step's
+// kernels, whose code the other activations must leave alone); AF_EXT picks among codes 3 .. 13.  The host
+// chooses the family from the code.
+enum { AF_BASE = 0, AF_EXT = 1 };
 
 struct Args {
   const float* A;
@@ -364,17 +374,69 @@ __device__ __forceinline__ void loader_wave(const Args& g, char* lds, uint32_t l
 // ------------------------------------------------------------------------------------------------
 // compute waves
 // ------------------------------------------------------------------------------------------------
+// torch.nn.SELU's constants
+constexpr float SELU_ALPHA = 1.6732632423543772848170429916717f;
+constexpr float SELU_SCALE = 1.0507009873554804934193349852946f;
+
+// y = f(z) with torch's default arguments (table in include/idiaptts_amd.h); accurate exp / expm1 / log1p, no
+// __expf.  The clamps compare rather than fminf / fmaxf so that a NaN passes through, as in torch.
 template <int ACT>
 __device__ __forceinline__ float act1(float z) {
   if (ACT == ACT_TANH) return fast_tanhf(z);
   if (ACT == ACT_RELU) return z > 0.f ? z : 0.f;
+  if (ACT == ACT_SIGMOID) return 1.f / (1.f + expf(-z));
+  if (ACT == ACT_LOGSIGMOID) return fminf(z, 0.f) - log1pf(expf(-fabsf(z)));
+  if (ACT == ACT_SOFTPLUS) return z > 20.f ? z : log1pf(expf(z));
+  if (ACT == ACT_SOFTSIGN) return z / (1.f + fabsf(z));
+  if (ACT == ACT_LEAKY_RELU) return z > 0.f ? z : 0.01f * z;
+  if (ACT == ACT_ELU || ACT == ACT_CELU) return z > 0.f ? z : expm1f(z);
+  if (ACT == ACT_SELU) return z > 0.f ? SELU_SCALE * z : (SELU_SCALE * SELU_ALPHA) * expm1f(z);
+  if (ACT == ACT_HARDTANH) return z < -1.f ? -1.f : (z > 1.f ? 1.f : z);
+  if (ACT == ACT_RELU6) return z < 0.f ? 0.f : (z > 6.f ? 6.f : z);
+  if (ACT == ACT_HARDSIGMOID) {
+    const float t = z + 3.f;
+    return (t < 0.f ? 0.f : (t > 6.f ? 6.f : t)) / 6.f;
+  }
   return z;
 }
+// f'(z) through y = f(z); at a branch point torch's value (LeakyReLU 0.01 and ELU 1 at z = 0, the clamps 0)
 template <int ACT>
 __device__ __forceinline__ float dact1(float y) {
   if (ACT == ACT_TANH) return 1.f - y * y;
   if (ACT == ACT_RELU) return y > 0.f ? 1.f : 0.f;
+  if (ACT == ACT_SIGMOID) return y * (1.f - y);
+  if (ACT == ACT_LOGSIGMOID) return -expm1f(y);
+  if (ACT == ACT_SOFTPLUS) return y > 20.f ? 1.f : -expm1f(-y);
+  if (ACT == ACT_SOFTSIGN) {
+    const float t = 1.f - fabsf(y);
+    return t * t;
+  }
+  if (ACT == ACT_LEAKY_RELU) return y > 0.f ? 1.f : 0.01f;
+  if (ACT == ACT_ELU || ACT == ACT_CELU) return y > 0.f ? 1.f : y + 1.f;
+  if (ACT == ACT_SELU) return y > 0.f ? SELU_SCALE : y + SELU_SCALE * SELU_ALPHA;
+  if (ACT == ACT_HARDTANH) return y > -1.f && y < 1.f ? 1.f : 0.f;
+  if (ACT == ACT_RELU6) return y > 0.f && y < 6.f ? 1.f : 0.f;
+  if (ACT == ACT_HARDSIGMOID) return y > 0.f && y < 1.f ? 1.f / 6.f : 0.f;
   return 1.f;
+}
+
+// run-time code -> compiled activation, for the codes of the AF_EXT family (ELU and CELU share one body);
+// f(std::integral_constant<int, ACT>()) is called once
+template <typename F>
+__device__ __forceinline__ void with_ext_act(int act, F&& f) {
+  switch (act) {
+    case ACT_SIGMOID: f(std::integral_constant<int, ACT_SIGMOID>()); break;
+    case ACT_LOGSIGMOID: f(std::integral_constant<int, ACT_LOGSIGMOID>()); break;
+    case ACT_SOFTPLUS: f(std::integral_constant<int, ACT_SOFTPLUS>()); break;
+    case ACT_SOFTSIGN: f(std::integral_constant<int, ACT_SOFTSIGN>()); break;
+    case ACT_LEAKY_RELU: f(std::integral_constant<int, ACT_LEAKY_RELU>()); break;
+    case ACT_ELU:
+    case ACT_CELU: f(std::integral_constant<int, ACT_ELU>()); break;
+    case ACT_SELU: f(std::integral_constant<int, ACT_SELU>()); break;
+    case ACT_HARDTANH: f(std::integral_constant<int, ACT_HARDTANH>()); break;
+    case ACT_RELU6: f(std::integral_constant<int, ACT_RELU6>()); break;
+    default: f(std::integral_constant<int, ACT_HARDSIGMOID>()); break;
+  }
 }
 
 template <int CTRL>
@@ -483,7 +545,7 @@ __device__ __forceinline__ void epilogue(const Args& g, const Tile& pc, const f3
   }
 }
 
-template <bool A_ROW, bool B_ROW, int EPI, int BMT, int BNT, bool GROUPED = false>
+template <bool A_ROW, bool B_ROW, int EPI, int BMT, int BNT, bool GROUPED = false, int AF = AF_BASE>
 __device__ __forceinline__ void compute_waves(const Args& g, char* lds, int wid, int lane) {
   constexpr int WN = BNT / 32;
   constexpr int A_BYTES = BMT * 128;
@@ -532,7 +594,11 @@ __device__ __forceinline__ void compute_waves(const Args& g, char* lds, int wid,
         if (t == 1.2345f) g.C[0] = t;
       } else {
         const float4 bv = load_bias<EPI>(g, pc.n0, wn, lane);
-        if (EPI == EPI_STORE || g.act == ACT_NONE) epilogue<EPI, ACT_NONE>(g, pc, acc0, acc1, wm, wn, lane, bv, lsum);
+        if (AF == AF_EXT && (EPI == EPI_BIAS_ACT || EPI == EPI_DACT)) {
+          with_ext_act(g.act, [&](auto act) {
+            epilogue<EPI, decltype(act)::value>(g, pc, acc0, acc1, wm, wn, lane, bv, lsum);
+          });
+        } else if (EPI == EPI_STORE || g.act == ACT_NONE) epilogue<EPI, ACT_NONE>(g, pc, acc0, acc1, wm, wn, lane, bv, lsum);
         else if (g.act == ACT_TANH) epilogue<EPI, ACT_TANH>(g, pc, acc0, acc1, wm, wn, lane, bv, lsum);
         else epilogue<EPI, ACT_RELU>(g, pc, acc0, acc1, wm, wn, lane, bv, lsum);
       }
@@ -617,7 +683,8 @@ __device__ __forceinline__ void compute_waves(const Args& g, char* lds, int wid,
 // WM = compute waves along the A (row) dimension: 2 -> 128 x 64 tile, 1 -> 64 x 128 tile.
 // GROUPED: the tile order in groups of g.gn column tiles (decode_tile); a kernel of its own so that the
 // plain order's code is untouched (as a run-time branch it cost the FF step 1 %, same box, same day).
-template <bool A_ROW, bool B_ROW, int EPI, int WM, bool GROUPED = false>
+// AF: activation family of the epilogue (AF_BASE / AF_EXT).
+template <bool A_ROW, bool B_ROW, int EPI, int WM, bool GROUPED = false, int AF = AF_BASE>
 __global__ __launch_bounds__(THREADS, (2 * THREADS + 255) / 256) void gemm_ring_kernel(Args g) {
   constexpr int BMT = 64 * WM, BNT = 32 * (4 / WM);
   __shared__ __attribute__((aligned(1024))) char lds[LDS_BYTES];
@@ -629,7 +696,7 @@ __global__ __launch_bounds__(THREADS, (2 * THREADS + 255) / 256) void gemm_ring_
   if (wid >= 4) {
     loader_wave<A_ROW, B_ROW, BMT, BNT, GROUPED>(g, lds, lds0, lane, EPI == EPI_MSE, wid - 4);
   } else {
-    compute_waves<A_ROW, B_ROW, EPI, BMT, BNT, GROUPED>(g, lds, wid, lane);
+    compute_waves<A_ROW, B_ROW, EPI, BMT, BNT, GROUPED, AF>(g, lds, wid, lane);
   }
   if (g.stamps && threadIdx.x == 0) {
     g.stamps[4 * blockIdx.x] = __builtin_amdgcn_s_memtime() - t0c;
@@ -642,8 +709,9 @@ __global__ __launch_bounds__(THREADS, (2 * THREADS + 255) / 256) void gemm_ring_
 // layer both start from dz): every persistent workgroup walks its tiles of the first problem, then
 // its tiles of the second.  One launch boundary less per layer (ramp, drain and the end-of-kernel
 // wait cost ~10 us each on this chip) and the workgroups that run out of tiles of the first
-// problem start the second right away instead of idling to the end of the launch.
-template <bool A1, bool B1, int E1, int W1, bool A2, bool B2, int E2, int W2>
+// problem start the second right away instead of idling to the end of the launch.  AF2: activation family of the
+// second problem's epilogue.
+template <bool A1, bool B1, int E1, int W1, bool A2, bool B2, int E2, int W2, int AF2 = AF_BASE>
 __global__ __launch_bounds__(THREADS, (2 * THREADS + 255) / 256) void gemm_ring_pair_kernel(Args g1, Args g2) {
   __shared__ __attribute__((aligned(1024))) char lds[LDS_BYTES];
   const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_char_p)lds;
@@ -654,7 +722,7 @@ __global__ __launch_bounds__(THREADS, (2 * THREADS + 255) / 256) void gemm_ring_
     loader_wave<A2, B2, 64 * W2, 32 * (4 / W2)>(g2, lds, lds0, lane, E2 == EPI_MSE, wid - 4);
   } else {
     compute_waves<A1, B1, E1, 64 * W1, 32 * (4 / W1)>(g1, lds, wid, lane);
-    compute_waves<A2, B2, E2, 64 * W2, 32 * (4 / W2)>(g2, lds, wid, lane);
+    compute_waves<A2, B2, E2, 64 * W2, 32 * (4 / W2), false, AF2>(g2, lds, wid, lane);
   }
 }
 

@@ -85,6 +85,22 @@ __device__ __forceinline__ float act_grad_from_out(float y, int act) {
   if (act == ITTS_ACT_RELU) return y > 0.f ? 1.f : 0.f;
   return 1.f;
 }
+// the activation family AF (ring::AF_BASE: the two above, ring::AF_EXT: codes 3 .. 13, gemm_ring.h's act1 / dact1)
+template <int AF>
+__device__ __forceinline__ float act_fwd_af(float z, int act) {
+  if (AF == ring::AF_BASE) return act_fwd(z, act);
+  float y = z;
+  ring::with_ext_act(act, [&](auto a) { y = ring::act1<decltype(a)::value>(z); });
+  return y;
+}
+template <int AF>
+__device__ __forceinline__ float act_grad_af(float y, int act) {
+  if (AF == ring::AF_BASE) return act_grad_from_out(y, act);
+  float d = 1.f;
+  ring::with_ext_act(act, [&](auto a) { d = ring::dact1<decltype(a)::value>(y); });
+  return d;
+}
+static inline int act_family(int act) { return act >= ITTS_ACT_SIGMOID ? ring::AF_EXT : ring::AF_BASE; }
 
 // Global -> registers for one 128(out) x 32(k) tile of an operand, 16 floats per thread.
 // Branch-free: out-of-range elements read a clamped (valid) address and are zeroed by a select,
@@ -159,8 +175,8 @@ __device__ __forceinline__ float4 read_frag(const float* __restrict__ S, int o, 
 }
 
 // TN = MFMA tiles per wave along N: output tile 128 x (64*TN). TN = 1 halves the tile so that
-// narrow outputs (N = 187) and awkward tile counts waste fewer workgroup slots.
-template <bool A_ROW, bool B_ROW, int EPI, bool VEC_A, bool VEC_B, int TN, int STAGES = 2>
+// narrow outputs (N = 187) and awkward tile counts waste fewer workgroup slots.  AF: activation family.
+template <bool A_ROW, bool B_ROW, int EPI, bool VEC_A, bool VEC_B, int TN, int STAGES = 2, int AF = ring::AF_BASE>
 __global__ __launch_bounds__(256, STAGES == 1 ? 4 : 2) void gemm_f32_kernel(GemmArgs g) {
   constexpr int BNT = 64 * TN;
   constexpr int B_FLOATS = STAGES == 1 ? (B_ROW ? BNT * LD_ROW : BK * (BNT + 4)) : TILE_FLOATS;
@@ -343,21 +359,21 @@ __global__ __launch_bounds__(256, STAGES == 1 ? 4 : 2) void gemm_f32_kernel(Gemm
         if (row >= g.M || col >= g.N) continue;
         if (full) {
           if (EPI == EPI_BIAS_ACT) {
-            v.x = act_fwd(v.x + bv.x, g.act); v.y = act_fwd(v.y + bv.y, g.act);
-            v.z = act_fwd(v.z + bv.z, g.act); v.w = act_fwd(v.w + bv.w, g.act);
+            v.x = act_fwd_af<AF>(v.x + bv.x, g.act); v.y = act_fwd_af<AF>(v.y + bv.y, g.act);
+            v.z = act_fwd_af<AF>(v.z + bv.z, g.act); v.w = act_fwd_af<AF>(v.w + bv.w, g.act);
           }
           if (EPI == EPI_DACT) {
             const float4 a = *reinterpret_cast<const float4*>(g.aux + row * g.ldaux + col);
-            v.x *= act_grad_from_out(a.x, g.act); v.y *= act_grad_from_out(a.y, g.act);
-            v.z *= act_grad_from_out(a.z, g.act); v.w *= act_grad_from_out(a.w, g.act);
+            v.x *= act_grad_af<AF>(a.x, g.act); v.y *= act_grad_af<AF>(a.y, g.act);
+            v.z *= act_grad_af<AF>(a.z, g.act); v.w *= act_grad_af<AF>(a.w, g.act);
           }
           *reinterpret_cast<float4*>(C + row * g.ldc + col) = v;
         } else {   // the float4 that straddles N: column by column
           const float vv[4] = {v.x, v.y, v.z, v.w};
           for (int e = 0; e < 4 && col + e < g.N; ++e) {
             float o = vv[e];
-            if (EPI == EPI_BIAS_ACT) o = act_fwd(o + (g.bias ? g.bias[col + e] : 0.f), g.act);
-            if (EPI == EPI_DACT) o *= act_grad_from_out(g.aux[row * g.ldaux + col + e], g.act);
+            if (EPI == EPI_BIAS_ACT) o = act_fwd_af<AF>(o + (g.bias ? g.bias[col + e] : 0.f), g.act);
+            if (EPI == EPI_DACT) o *= act_grad_af<AF>(g.aux[row * g.ldaux + col + e], g.act);
             C[row * g.ldc + col + e] = o;
           }
         }
@@ -378,26 +394,26 @@ __global__ __launch_bounds__(256, STAGES == 1 ? 4 : 2) void gemm_f32_kernel(Gemm
         const int64_t row = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * rh;
         if (row >= g.M) continue;
         float v = acc[i][j][r];
-        if (EPI == EPI_BIAS_ACT) v = act_fwd(v + bv, g.act);
-        if (EPI == EPI_DACT) v *= act_grad_from_out(g.aux[row * g.ldaux + col], g.act);
+        if (EPI == EPI_BIAS_ACT) v = act_fwd_af<AF>(v + bv, g.act);
+        if (EPI == EPI_DACT) v *= act_grad_af<AF>(g.aux[row * g.ldaux + col], g.act);
         C[row * g.ldc + col] = v;
       }
     }
 }
 
-template <bool A_ROW, bool B_ROW, int EPI, int TN, int STAGES>
+template <bool A_ROW, bool B_ROW, int EPI, int TN, int STAGES, int AF = ring::AF_BASE>
 static int launch_gemm_tn(const GemmArgs& g, int splitk, hipStream_t s) {
   const int64_t tiles = ((g.M + BM - 1) / BM) * ((g.N + 64 * TN - 1) / (64 * TN));
   dim3 grid((unsigned)tiles, 1, (unsigned)splitk);
   const bool va = g.vecA, vb = g.vecB;   // pitch and alignment allow 16-byte loads (see load_tile)
   if (va && vb)
-    hipLaunchKernelGGL((gemm_f32_kernel<A_ROW, B_ROW, EPI, true, true, TN, STAGES>), grid, dim3(256), 0, s, g);
+    hipLaunchKernelGGL((gemm_f32_kernel<A_ROW, B_ROW, EPI, true, true, TN, STAGES, AF>), grid, dim3(256), 0, s, g);
   else if (va)
-    hipLaunchKernelGGL((gemm_f32_kernel<A_ROW, B_ROW, EPI, true, false, TN, STAGES>), grid, dim3(256), 0, s, g);
+    hipLaunchKernelGGL((gemm_f32_kernel<A_ROW, B_ROW, EPI, true, false, TN, STAGES, AF>), grid, dim3(256), 0, s, g);
   else if (vb)
-    hipLaunchKernelGGL((gemm_f32_kernel<A_ROW, B_ROW, EPI, false, true, TN, STAGES>), grid, dim3(256), 0, s, g);
+    hipLaunchKernelGGL((gemm_f32_kernel<A_ROW, B_ROW, EPI, false, true, TN, STAGES, AF>), grid, dim3(256), 0, s, g);
   else
-    hipLaunchKernelGGL((gemm_f32_kernel<A_ROW, B_ROW, EPI, false, false, TN, STAGES>), grid, dim3(256), 0, s, g);
+    hipLaunchKernelGGL((gemm_f32_kernel<A_ROW, B_ROW, EPI, false, false, TN, STAGES, AF>), grid, dim3(256), 0, s, g);
   ITTS_LAUNCH_CHECK();
   return ITTS_OK;
 }
@@ -443,7 +459,7 @@ static bool ring_ok(const GemmArgs& g, int splitk, int epi) {
 
 static int ring_group(int tiles_n, int bnt, int64_t K, bool row_row);
 
-template <bool A_ROW, bool B_ROW, int EPI, int WM>
+template <bool A_ROW, bool B_ROW, int EPI, int WM, int AF = ring::AF_BASE>
 static int launch_ring_wm(const GemmArgs& g, int splitk, hipStream_t s) {
   constexpr int BMT = 64 * WM, BNT = 32 * (4 / WM);
   ring::Args r{};
@@ -460,10 +476,10 @@ static int launch_ring_wm(const GemmArgs& g, int splitk, hipStream_t s) {
   ITTS_REQUIRE(ntiles < ((int64_t)1 << 31), "too many tiles");
   const int grid = (int)std::min<int64_t>(kRingGrid, (ntiles + 7) / 8 * 8);
   if (A_ROW && B_ROW && EPI == ring::EPI_BIAS_ACT && r.gn < r.tiles_n)
-    hipLaunchKernelGGL((ring::gemm_ring_kernel<A_ROW, B_ROW, EPI, WM, A_ROW && B_ROW && EPI == ring::EPI_BIAS_ACT>),
+    hipLaunchKernelGGL((ring::gemm_ring_kernel<A_ROW, B_ROW, EPI, WM, A_ROW && B_ROW && EPI == ring::EPI_BIAS_ACT, AF>),
                        dim3(grid), dim3(ring::THREADS), 0, s, r);
   else
-    hipLaunchKernelGGL((ring::gemm_ring_kernel<A_ROW, B_ROW, EPI, WM>), dim3(grid), dim3(ring::THREADS), 0, s, r);
+    hipLaunchKernelGGL((ring::gemm_ring_kernel<A_ROW, B_ROW, EPI, WM, false, AF>), dim3(grid), dim3(ring::THREADS), 0, s, r);
   ITTS_LAUNCH_CHECK();
   return ITTS_OK;
 }
@@ -486,10 +502,10 @@ static int ring_wm(int64_t M, int N) {
   return w1 < w2 ? 1 : 2;
 }
 
-template <bool A_ROW, bool B_ROW, int EPI>
+template <bool A_ROW, bool B_ROW, int EPI, int AF>
 static int launch_ring(const GemmArgs& g, int splitk, hipStream_t s) {
-  if (ring_wm(g.M, g.N) == 1) return launch_ring_wm<A_ROW, B_ROW, EPI, 1>(g, splitk, s);
-  return launch_ring_wm<A_ROW, B_ROW, EPI, 2>(g, splitk, s);
+  if (ring_wm(g.M, g.N) == 1) return launch_ring_wm<A_ROW, B_ROW, EPI, 1, AF>(g, splitk, s);
+  return launch_ring_wm<A_ROW, B_ROW, EPI, 2, AF>(g, splitk, s);
 }
 
 template <int WM>
@@ -510,24 +526,24 @@ static ring::Args ring_args(const GemmArgs& g, int splitk) {
 
 // weight-gradient GEMM (col x col, split-K slabs) and input-gradient GEMM (row x col, activation
 // derivative in the epilogue) of one layer in ONE launch
-template <int WM_W, int EPI_X>
+template <int WM_W, int EPI_X, int AF_X = ring::AF_BASE>
 static int launch_ring_bwd_pair(const GemmArgs& gw, int splitk, const GemmArgs& gx, hipStream_t s) {
   const ring::Args rw = ring_args<WM_W>(gw, splitk), rx = ring_args<2>(gx, 1);
-  hipLaunchKernelGGL((ring::gemm_ring_pair_kernel<false, false, EPI_STORE, WM_W, true, false, EPI_X, 2>),
+  hipLaunchKernelGGL((ring::gemm_ring_pair_kernel<false, false, EPI_STORE, WM_W, true, false, EPI_X, 2, AF_X>),
                      dim3(kRingGrid), dim3(ring::THREADS), 0, s, rw, rx);
   ITTS_LAUNCH_CHECK();
   return ITTS_OK;
 }
 
-template <bool A_ROW, bool B_ROW, int EPI>
+template <bool A_ROW, bool B_ROW, int EPI, int AF = ring::AF_BASE>
 static int launch_gemm(GemmArgs g, int splitk, hipStream_t s) {
   if (g.M <= 0 || g.N <= 0) return ITTS_OK;
-  if (ring_ok<A_ROW, B_ROW>(g, splitk, EPI)) return launch_ring<A_ROW, B_ROW, EPI>(g, splitk, s);
-  if (A_ROW) return launch_gemm_tn<A_ROW, B_ROW, EPI, 1, 1>(g, splitk, s);
+  if (ring_ok<A_ROW, B_ROW>(g, splitk, EPI)) return launch_ring<A_ROW, B_ROW, EPI, AF>(g, splitk, s);
+  if (A_ROW) return launch_gemm_tn<A_ROW, B_ROW, EPI, 1, 1, AF>(g, splitk, s);
   const double e2 = tile_efficiency(g.M, g.N, splitk, 2, 1.0);
   const double e1 = tile_efficiency(g.M, g.N, splitk, 1, 0.90);
-  if (e1 > e2) return launch_gemm_tn<A_ROW, B_ROW, EPI, 1, 2>(g, splitk, s);
-  return launch_gemm_tn<A_ROW, B_ROW, EPI, 2, 2>(g, splitk, s);
+  if (e1 > e2) return launch_gemm_tn<A_ROW, B_ROW, EPI, 1, 2, AF>(g, splitk, s);
+  return launch_gemm_tn<A_ROW, B_ROW, EPI, 2, 2, AF>(g, splitk, s);
 }
 
 
@@ -705,11 +721,20 @@ extern "C" int itts_reduce_deferred(void* stream) {
   return flush_deferred(as_stream(stream));
 }
 
+template <int AF>
 __global__ void act_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y,
                                float* __restrict__ dz, int64_t n, int act) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    dz[i] = dy[i] * act_grad_from_out(y[i], act);
+  if (AF == ring::AF_BASE) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x)
+      dz[i] = dy[i] * act_grad_from_out(y[i], act);
+  } else {
+    ring::with_ext_act(act, [&](auto a) {
+      for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+           i += (int64_t)gridDim.x * blockDim.x)
+        dz[i] = dy[i] * ring::dact1<decltype(a)::value>(y[i]);
+    });
+  }
 }
 
 // ---- masked MSE -------------------------------------------------------------------------------
@@ -941,7 +966,7 @@ extern "C" int itts_linear_fwd(const float* d_x, int64_t ldx, const float* d_w, 
                                void* stream) {
   ITTS_REQUIRE(d_w && (M == 0 || (d_x && d_y)), "null pointer");
   ITTS_REQUIRE(M >= 0 && N > 0 && K > 0 && ldx >= K && ldy >= N, "bad sizes");
-  ITTS_REQUIRE(act >= 0 && act <= 2, "unknown activation");
+  ITTS_REQUIRE(act >= ITTS_ACT_NONE && act <= ITTS_ACT_HARDSIGMOID, "unknown activation");
   if (M == 0) return ITTS_OK;
   GemmArgs g{};
   g.A = d_x; g.lda = ldx; g.B = d_w; g.ldb = K; g.C = d_y; g.ldc = ldy;
@@ -950,6 +975,7 @@ extern "C" int itts_linear_fwd(const float* d_x, int64_t ldx, const float* d_w, 
   g.vecA = (ldx % 4 == 0) && aligned16(d_x);
   g.vecB = (K % 4 == 0) && aligned16(d_w);
   g.wide_out = (ldy % 4 == 0) && aligned16(d_y) && (!d_b || aligned16(d_b));
+  if (act_family(act) == ring::AF_EXT) return launch_gemm<true, true, EPI_BIAS_ACT, ring::AF_EXT>(g, 1, as_stream(stream));
   return launch_gemm<true, true, EPI_BIAS_ACT>(g, 1, as_stream(stream));
 }
 
@@ -1048,11 +1074,15 @@ extern "C" int itts_linear_fwd_mse(const float* d_x, int64_t ldx, const float* d
 extern "C" int itts_act_bwd(const float* d_dy, const float* d_y, float* d_dz, int64_t n_elem,
                             int act, void* stream) {
   ITTS_REQUIRE(d_dy && d_y && d_dz && n_elem >= 0, "bad arguments");
-  ITTS_REQUIRE(act >= 0 && act <= 2, "unknown activation");
+  ITTS_REQUIRE(act >= ITTS_ACT_NONE && act <= ITTS_ACT_HARDSIGMOID, "unknown activation");
   if (n_elem == 0) return ITTS_OK;
   const int blocks = (int)std::min<int64_t>((n_elem + 255) / 256, 4096);
-  hipLaunchKernelGGL(act_bwd_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), d_dy, d_y,
-                     d_dz, n_elem, act);
+  if (act_family(act) == ring::AF_EXT)
+    hipLaunchKernelGGL(act_bwd_kernel<ring::AF_EXT>, dim3(blocks), dim3(256), 0, as_stream(stream), d_dy, d_y,
+                       d_dz, n_elem, act);
+  else
+    hipLaunchKernelGGL(act_bwd_kernel<ring::AF_BASE>, dim3(blocks), dim3(256), 0, as_stream(stream), d_dy, d_y,
+                       d_dz, n_elem, act);
   ITTS_LAUNCH_CHECK();
   return ITTS_OK;
 }
@@ -1063,6 +1093,7 @@ extern "C" int itts_linear_bwd_input(const float* d_dz, int64_t lddz, const floa
                                      void* stream) {
   ITTS_REQUIRE(d_w && (M == 0 || (d_dz && d_dx)), "null pointer");
   ITTS_REQUIRE(M >= 0 && N > 0 && K > 0 && lddz >= N && lddx >= K, "bad sizes");
+  ITTS_REQUIRE(!d_yprev || (act_prev >= ITTS_ACT_NONE && act_prev <= ITTS_ACT_HARDSIGMOID), "unknown activation");
   if (M == 0) return ITTS_OK;
   // dx[M,K] = dz[M,N] (row form, reduction N) x w[N,K] (col form: [k=N][out=K])
   GemmArgs g{};
@@ -1074,6 +1105,7 @@ extern "C" int itts_linear_bwd_input(const float* d_dz, int64_t lddz, const floa
   g.wide_out = (lddx % 4 == 0) && aligned16(d_dx) && (!d_yprev || ((ldyp % 4 == 0) && aligned16(d_yprev)));
   if (d_yprev) {
     ITTS_REQUIRE(ldyp >= K, "ldyp too small");
+    if (act_family(act_prev) == ring::AF_EXT) return launch_gemm<true, false, EPI_DACT, ring::AF_EXT>(g, 1, as_stream(stream));
     return launch_gemm<true, false, EPI_DACT>(g, 1, as_stream(stream));
   }
   return launch_gemm<true, false, EPI_STORE>(g, 1, as_stream(stream));
@@ -1143,6 +1175,7 @@ extern "C" int itts_linear_bwd(const float* d_dz, int64_t lddz, const float* d_x
   ITTS_REQUIRE(d_w && d_dw && d_workspace && (M == 0 || (d_dz && d_x && d_dx)), "null pointer");
   ITTS_REQUIRE(M >= 0 && N > 0 && K > 0 && lddz >= N && ldx >= K && lddx >= K, "bad sizes");
   ITTS_REQUIRE(!d_yprev || ldyp >= K, "ldyp too small");
+  ITTS_REQUIRE(!d_yprev || (act_prev >= ITTS_ACT_NONE && act_prev <= ITTS_ACT_HARDSIGMOID), "unknown activation");
   hipStream_t s = as_stream(stream);
   const bool vec_ok = (lddz % 4 == 0) && aligned16(d_dz) && (ldx % 4 == 0) && aligned16(d_x) && (K % 4 == 0) &&
                       aligned16(d_w);
@@ -1176,7 +1209,10 @@ extern "C" int itts_linear_bwd(const float* d_dz, int64_t lddz, const float* d_x
   }
   int rc;
   const int wm = ring_wm(gw.M, gw.N);
-  if (d_yprev) rc = wm == 1 ? launch_ring_bwd_pair<1, EPI_DACT>(gw, S_eff, gx, s) : launch_ring_bwd_pair<2, EPI_DACT>(gw, S_eff, gx, s);
+  if (d_yprev && act_family(act_prev) == ring::AF_EXT)
+    rc = wm == 1 ? launch_ring_bwd_pair<1, EPI_DACT, ring::AF_EXT>(gw, S_eff, gx, s)
+                 : launch_ring_bwd_pair<2, EPI_DACT, ring::AF_EXT>(gw, S_eff, gx, s);
+  else if (d_yprev) rc = wm == 1 ? launch_ring_bwd_pair<1, EPI_DACT>(gw, S_eff, gx, s) : launch_ring_bwd_pair<2, EPI_DACT>(gw, S_eff, gx, s);
   else rc = wm == 1 ? launch_ring_bwd_pair<1, EPI_STORE>(gw, S_eff, gx, s) : launch_ring_bwd_pair<2, EPI_STORE>(gw, S_eff, gx, s);
   if (rc) return rc;
   float* slabs = reinterpret_cast<float*>(d_workspace);

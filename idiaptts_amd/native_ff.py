@@ -27,13 +27,14 @@ def _pad4(n):
 
 
 class FlatFFModel:
-    """Dense stack dims[0] -> dims[1] -> ... with activations `acts` (one per layer)."""
+    """Dense stack dims[0] -> dims[1] -> ... with activations `acts` (one per layer: a name of ops.ACT_BY_NAME in
+    any case, e.g. "tanh" / "Sigmoid", an ops.ACT_* code, or None)."""
 
     def __init__(self, dims=(425, 512, 512, 187), acts=("tanh", "tanh", None), device="cuda",
                  seed=0, state_dict=None):
         assert len(acts) == len(dims) - 1
         self.dims = tuple(int(d) for d in dims)
-        self.acts = [ops.ACT_BY_NAME[a] for a in acts]
+        self.acts = [ops.act_code(a) for a in acts]
         self.device = torch.device(device)
         # Row pitch of every weight matrix (and of the packed input) is padded to a multiple of
         # 4 floats so all GEMM operands take the 16-byte load path; pad columns stay exactly zero
@@ -86,7 +87,7 @@ class FlatFFModel:
             for m in seq:
                 if isinstance(m, LinearAct):
                     layers.append((m.weight.detach(), m.bias.detach()))
-                    acts.append({ops.ACT_NONE: None, ops.ACT_TANH: "tanh", ops.ACT_RELU: "relu"}[m.act])
+                    acts.append(ops.ACT_TORCH_NAME.get(m.act))
                 elif isinstance(m, (torch.nn.Dropout, torch.nn.Conv1d)):
                     return None
                 elif type(m).__name__ != "FusedActivation":
@@ -194,6 +195,9 @@ class FlatFFModel:
             hs = self.forward(x)
             loss, dz = ops.masked_mse(hs[-1], target, row_valid, n_valid_global,
                                       grad=self._rows_buffer("dz_out", M, self.dims[-1]))
+            if self.acts[-1] != ops.ACT_NONE:
+                # d loss / d output -> d loss / d pre-activation of the output layer (the loop below starts there)
+                dz = ops.act_bwd(dz, hs[-1], self.acts[-1])
         for i in range(n - 1, -1, -1):
             inp = hs[i - 1] if i > 0 else x
             dz_in = None

@@ -144,7 +144,7 @@ def _rows_padded(M, N, device):
 
 
 class LinearChainFunction(torch.autograd.Function):
-    """A run of Linear (+ Tanh / ReLU) layers on rows -- the layers of consecutive FFWrapper groups
+    """A run of Linear (+ activation) layers on rows -- the layers of consecutive FFWrapper groups
     (rnn_dyn/FFWrapper.py:63-73) -- as ONE autograd node: forward the same `itts_linear_fwd` launches as the layers
     one by one (the same bits), backward as the flat step runs it (native_ff.py): per layer ONE launch for weight
     gradient, bias gradient and input gradient (`itts_linear_bwd`), the previous layer's activation derivative in its

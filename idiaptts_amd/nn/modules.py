@@ -13,12 +13,13 @@ from .functional import (Conv1dActFunction, GRULayerFunction, LinearActFunction,
 
 
 class LinearAct(nn.Linear):
-    """torch.nn.Linear whose forward/backward run the fp32-MFMA kernels; `act` fuses the
-    following Tanh / ReLU of an FFWrapper group into the GEMM epilogue."""
+    """torch.nn.Linear whose forward/backward run the fp32-MFMA kernels; `act` (a name of ops.ACT_BY_NAME, any
+    case, or an ops.ACT_* code) fuses the following activation of an FFWrapper group into the GEMM epilogue."""
 
     def __init__(self, in_features, out_features, bias=True, act=None):
+        code = ops.act_code(act)
         super().__init__(in_features, out_features, bias=bias)
-        self.act = ops.ACT_BY_NAME[act.lower() if isinstance(act, str) else act]
+        self.act = code
 
     def forward(self, input_):
         return LinearActFunction.apply(input_, self.weight, self.bias, self.act)
@@ -45,9 +46,10 @@ class Conv1dAct(nn.Conv1d):
             raise NotImplementedError("Conv1d groups={}: only groups=1 is implemented".format(groups))
         if padding_mode != "zeros":
             raise NotImplementedError("Conv1d padding_mode={!r}: only 'zeros' is implemented".format(padding_mode))
+        code = ops.act_code(act, ops.CONV_ACTS, "Conv1d")
         super().__init__(in_channels, out_channels, kernel_size, stride=stride, padding=padding, dilation=dilation,
                          groups=groups, bias=bias, padding_mode=padding_mode)
-        self.act = ops.ACT_BY_NAME[act.lower() if isinstance(act, str) else act]
+        self.act = code
         self.batch_first = batch_first
 
     def forward(self, input_):

@@ -11,9 +11,28 @@ import torch
 
 from . import lib as _lib
 
+# activation codes of the dense layers (ITTS_ACT_* in include/idiaptts_amd.h)
 ACT_NONE, ACT_TANH, ACT_RELU = 0, 1, 2
-ACT_BY_NAME = {None: ACT_NONE, "none": ACT_NONE, "linear": ACT_NONE, "tanh": ACT_TANH,
-               "relu": ACT_RELU}
+(ACT_SIGMOID, ACT_LOGSIGMOID, ACT_SOFTPLUS, ACT_SOFTSIGN, ACT_LEAKY_RELU, ACT_ELU, ACT_CELU, ACT_SELU, ACT_HARDTANH,
+ ACT_RELU6, ACT_HARDSIGMOID) = range(3, 14)
+# the torch.nn module each code stands for (with its default arguments): FFWrapper's `nonlin` names
+ACT_TORCH_NAME = {ACT_TANH: "Tanh", ACT_RELU: "ReLU", ACT_SIGMOID: "Sigmoid", ACT_LOGSIGMOID: "LogSigmoid",
+                  ACT_SOFTPLUS: "Softplus", ACT_SOFTSIGN: "Softsign", ACT_LEAKY_RELU: "LeakyReLU", ACT_ELU: "ELU",
+                  ACT_CELU: "CELU", ACT_SELU: "SELU", ACT_HARDTANH: "Hardtanh", ACT_RELU6: "ReLU6",
+                  ACT_HARDSIGMOID: "Hardsigmoid"}
+# lower-case names (and None / "none" / "linear": no activation) -> code
+ACT_BY_NAME = {None: ACT_NONE, "none": ACT_NONE, "linear": ACT_NONE}
+ACT_BY_NAME.update({name.lower(): code for code, name in ACT_TORCH_NAME.items()})
+CONV_ACTS = (ACT_NONE, ACT_TANH, ACT_RELU)     # what the Conv1d kernels fuse
+
+
+def act_code(act, allowed=None, where="Linear"):
+    """ops.ACT_* of an activation name (any case) or code; NotImplementedError naming it when it is not one of
+    `allowed` (default: every code)"""
+    code = act if isinstance(act, int) else ACT_BY_NAME.get(act.lower() if isinstance(act, str) else act)
+    if code is None or code not in (allowed if allowed is not None else range(ACT_HARDSIGMOID + 1)):
+        raise NotImplementedError("{} activation {!r} is not implemented".format(where, act))
+    return code
 
 
 def _ptr(t):

@@ -310,9 +310,38 @@ int itts_batch_pad_colsum_f32(const float* d_x, int64_t ld_x, const int64_t* d_l
                               void* stream);
 
 /* ---- acoustic model: dense layers (rnn_dyn/FFWrapper.py:63-73 -> torch.nn.Linear + act) --- */
+/* Activation codes (act / act_prev): the torch.nn module of that name with its default arguments.
+ * The backward derives act' from the layer OUTPUT y (no pre-activation is stored); at a branch point
+ * it takes torch's value.  The Conv1d entry points below accept NONE, TANH and RELU only.
+ *   code  module        y = f(z)                            act'(y)
+ *   0     (none)        z                                   1
+ *   1     Tanh          tanh z                              1 - y^2
+ *   2     ReLU          max(z, 0)                           y > 0
+ *   3     Sigmoid       1 / (1 + e^-z)                      y (1 - y)
+ *   4     LogSigmoid    min(z, 0) - log1p(e^-|z|)           -expm1(y)
+ *   5     Softplus      z > 20 ? z : log1p(e^z)             y > 20 ? 1 : -expm1(-y)
+ *   6     Softsign      z / (1 + |z|)                       (1 - |y|)^2
+ *   7     LeakyReLU     z > 0 ? z : 0.01 z                  y > 0 ? 1 : 0.01
+ *   8     ELU           z > 0 ? z : expm1(z)                y > 0 ? 1 : y + 1
+ *   9     CELU          as ELU (alpha 1)                    as ELU
+ *   10    SELU          s (z > 0 ? z : a expm1(z))          y > 0 ? s : y + s a   (torch's a, s)
+ *   11    Hardtanh      clamp(z, -1, 1)                     -1 < y < 1
+ *   12    ReLU6         clamp(z, 0, 6)                      0 < y < 6
+ *   13    Hardsigmoid   clamp(z + 3, 0, 6) / 6              0 < y < 1 ? 1/6 : 0 */
 #define ITTS_ACT_NONE 0
 #define ITTS_ACT_TANH 1
 #define ITTS_ACT_RELU 2
+#define ITTS_ACT_SIGMOID 3
+#define ITTS_ACT_LOGSIGMOID 4
+#define ITTS_ACT_SOFTPLUS 5
+#define ITTS_ACT_SOFTSIGN 6
+#define ITTS_ACT_LEAKY_RELU 7
+#define ITTS_ACT_ELU 8
+#define ITTS_ACT_CELU 9
+#define ITTS_ACT_SELU 10
+#define ITTS_ACT_HARDTANH 11
+#define ITTS_ACT_RELU6 12
+#define ITTS_ACT_HARDSIGMOID 13
 /* Pitch rule for the row-major activations of the four entry points below (x, y, dz, dx, yprev):
  * a row pitch (ld*) that is a multiple of 4 floats on a 16-byte aligned base selects 16-byte loads.
  * If the logical width is not a multiple of 4, the 1-3 floats between the width and the next
