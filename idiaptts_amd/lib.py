@@ -77,6 +77,11 @@ _SIGNATURES = {
     "itts_mlpg_last_form": (c_int, []),
     "itts_sqrt_inplace_f64": (c_int, [_P, c_int64, _P]),
     "itts_square_inplace_f64": (c_int, [_P, c_int64, _P]),
+    "itts_stft": (c_int, [_P, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), c_int, c_int, c_int, c_int, _P,
+                          c_int, _P, c_int64, _P]),
+    "itts_stft_mel": (c_int, [_P, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), c_int, c_int, c_int, c_int,
+                              _P, _P, _P, c_int, _P, c_int64, _P]),
+    "itts_mel_project": (c_int, [_P, c_int64, c_int, c_int64, _P, _P, c_int, _P, c_int64, _P]),
     "itts_batch_pad_gather_f32": (c_int, [_P, c_int64, c_int64, _P, _P, c_int, c_int64, c_int, c_int, _P, c_int64, _P,
                                           _P, c_int64, _P, _P]),
     "itts_batch_pack_rows_f32": (c_int, [_P, c_int64, _P, _P, c_int, c_int64, c_int, c_int, _P, c_int64, c_int,

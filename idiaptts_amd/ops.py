@@ -197,6 +197,66 @@ def lf0_vuv(f0, offsets, f0_silence_threshold=30.0, lf0_zero=0.0):
     return lf0, vuv
 
 
+# ----------------------------------------------------------------------------------------- STFT
+STFT_PAD = {None: 0, "reflect": 1, "constant": 2}     # pad_mode of librosa.stft; None: center=False
+STFT_KIND = {"amp_sp": 0, "amp_sp_f64": 1, "log_amp_sp": 2}
+
+
+def _stft_offsets(x_off, f_off, first):
+    return _lib.offsets_array(x_off), _lib.offsets_array(f_off), _lib.offsets_array(first)
+
+
+def stft_amp(x, x_off, f_off, first, n_fft, hop, pad, window, kind="amp_sp", out=None):
+    """|librosa.stft| / sqrt(n_fft // 2 + 1) of the float64 samples x (utterances at x_off), one row per frame:
+    row f_off[u] + i is STFT frame first[u] + i of utterance u.  pad: None (center=False), "reflect" or
+    "constant"; window: float64 [n_fft] on the device.  kind "amp_sp" (float32), "amp_sp_f64" or "log_amp_sp"
+    (20 log10(max(1e-5, amplitude)), float32).  Returns [f_off[-1], n_fft // 2 + 1]."""
+    L = _lib.load()
+    _need(x, torch.float64, "x")
+    _need(window, torch.float64, "window")
+    K = n_fft // 2 + 1
+    if out is None:
+        out = torch.empty((int(f_off[-1]), K), device=x.device,
+                          dtype=torch.float64 if kind == "amp_sp_f64" else torch.float32)
+    _need(out, torch.float64 if kind == "amp_sp_f64" else torch.float32, "out")
+    xo, fo, fi = _stft_offsets(x_off, f_off, first)
+    _lib.check(L.itts_stft(_ptr(x), xo, fo, fi, len(x_off) - 1, int(n_fft), int(hop), STFT_PAD[pad], _ptr(window),
+                           STFT_KIND[kind], _ptr(out), _rows(out, "out"), _stream()), "itts_stft")
+    return out
+
+
+def mel_filterbank(x, x_off, f_off, first, n_fft, hop, pad, window, mel_tab, mel_w, n_mels, out=None):
+    """mel_basis @ stft_amp(...).T per frame, float32 [f_off[-1], n_mels], with the spectrum kept on the chip.
+    mel_tab int32 [3 n_mels] (first bin, bins, first weight per filter) and mel_w float32: world.mel_tables."""
+    L = _lib.load()
+    _need(x, torch.float64, "x")
+    _need(window, torch.float64, "window")
+    _need(mel_tab, torch.int32, "mel_tab")
+    _need(mel_w, torch.float32, "mel_w")
+    if out is None:
+        out = torch.empty((int(f_off[-1]), n_mels), device=x.device, dtype=torch.float32)
+    _need(out, torch.float32, "out")
+    xo, fo, fi = _stft_offsets(x_off, f_off, first)
+    _lib.check(L.itts_stft_mel(_ptr(x), xo, fo, fi, len(x_off) - 1, int(n_fft), int(hop), STFT_PAD[pad],
+                               _ptr(window), _ptr(mel_tab), _ptr(mel_w), int(n_mels), _ptr(out), _rows(out, "out"),
+                               _stream()), "itts_stft_mel")
+    return out
+
+
+def mel_project(amp, mel_tab, mel_w, n_mels, out=None):
+    """The mel projection of a given amplitude spectrum amp [T, K] float64 -> float32 [T, n_mels]."""
+    L = _lib.load()
+    _need(amp, torch.float64, "amp")
+    _need(mel_tab, torch.int32, "mel_tab")
+    _need(mel_w, torch.float32, "mel_w")
+    if out is None:
+        out = torch.empty((amp.shape[0], n_mels), device=amp.device, dtype=torch.float32)
+    _lib.check(L.itts_mel_project(_ptr(amp), amp.shape[0], amp.shape[1], _rows(amp, "amp"), _ptr(mel_tab),
+                                  _ptr(mel_w), int(n_mels), _ptr(out), _rows(out, "out"), _stream()),
+               "itts_mel_project")
+    return out
+
+
 def sqrt_inplace(x):
     """x <- sqrt(x) for a contiguous float64 tensor (IEEE square roots: numpy's bits)."""
     L = _lib.load()

@@ -1,7 +1,8 @@
 """AudioProcessing with the reference's interface for the WORLD hot path
 (idiaptts/src/data_preparation/audio/AudioProcessing.py); pysptk / pyworld calls are replaced
-by the HIP kernels behind libidiaptts_amd.so. librosa-based helpers (mel filter banks,
-Griffin-Lim) are out of scope."""
+by the HIP kernels behind libidiaptts_amd.so.  librosa's STFT features -- the amplitude spectrum and mel filter
+banks (librosa_extract_amp_sp, extract_mfbanks) -- run on the STFT kernel (csrc/stft.hip); the way back from
+mel filter banks (librosa's NNLS inversion) and Griffin-Lim are out of scope."""
 import logging
 import os
 
@@ -12,6 +13,7 @@ import torch
 
 from .... import lib as _lib
 from .... import ops
+from .... import world as _world
 
 
 def _dev():
@@ -196,6 +198,66 @@ class AudioProcessing:
             alpha = AudioProcessing.fs_to_mgc_alpha(fs)
         m = torch.from_numpy(np.ascontiguousarray(mcep, dtype=np.float64)).to(_dev())
         return ops.mgc2sp(m, alpha, AudioProcessing.fs_to_frame_length(fs)).cpu().numpy()
+
+    @staticmethod
+    def librosa_extract_amp_sp(raw: np.array, fs: int, n_fft: int = None, hop_size_ms: int = 5,
+                               win_length_ms: int = None, window: str = "hann", center: bool = True,
+                               pad_mode: str = "reflect") -> np.array:
+        """|librosa.stft(raw, ...)| / sqrt(n_fft // 2 + 1), transposed to [T, n_fft // 2 + 1], float64 (reference
+        :156-185), on the STFT kernel.  n_fft 1024 / 2048, the "hann" window, pad_mode "reflect" / "constant"."""
+        if n_fft is None:
+            assert fs is not None, "Either fs or n_fft has to be given."
+            n_fft = AudioProcessing.fs_to_frame_length(fs)
+        _world.check_stft_args(n_fft, window, pad_mode)
+        hop = _world.stft_hop(fs, hop_size_ms)
+        win_length = None if win_length_ms is None else int(win_length_ms / 1000. * fs)
+        raw = np.ascontiguousarray(raw, dtype=np.float64).reshape(-1)
+        T = _world.stft_num_frames(len(raw), n_fft, hop, center)
+        x = torch.from_numpy(raw).to(_dev())
+        amp = _world.stft_features(x, [0, len(raw)], [0, T], [0], fs, "amp_sp_f64", n_fft, hop,
+                                   win_length=win_length, center=center, pad_mode=pad_mode)
+        return amp.cpu().numpy()
+
+    @staticmethod
+    def extract_mfbanks(raw: np.array = None, fs: int = 22050, amp_sp: np.array = None, n_fft: int = None,
+                        hop_size_ms: int = 5, num_coded_sps: int = 80, win_length_ms: int = None) -> np.array:
+        """Mel filter banks, float32 [T, num_coded_sps] (reference :187-226): librosa.filters.mel(sr=fs,
+        n_fft=n_fft, n_mels=num_coded_sps) applied to the amplitude spectrum -- `amp_sp` [T, K] when given, else
+        librosa_extract_amp_sp(raw, ...), in which case the spectrum never leaves the device.  num_coded_sps=-1:
+        the amplitude spectrum itself."""
+        assert (n_fft is not None or amp_sp is not None), \
+            "Either FFT size has to be given or amplitude spectrogram."
+        if amp_sp is None:
+            assert raw is not None, "Either raw signal or amplitude spectrum must be given."
+            _world.check_stft_args(n_fft)
+            if num_coded_sps == -1:
+                return AudioProcessing.librosa_extract_amp_sp(raw, fs, n_fft, hop_size_ms, win_length_ms) \
+                    .astype(np.float32, copy=False)
+            hop = _world.stft_hop(fs, hop_size_ms)
+            win_length = None if win_length_ms is None else int(win_length_ms / 1000. * fs)
+            raw = np.ascontiguousarray(raw, dtype=np.float64).reshape(-1)
+            T = _world.stft_num_frames(len(raw), n_fft, hop)
+            x = torch.from_numpy(raw).to(_dev())
+            return _world.stft_features(x, [0, len(raw)], [0, T], [0], fs, "mfbanks", n_fft, hop,
+                                        n_mels=num_coded_sps, win_length=win_length).cpu().numpy()
+        if num_coded_sps == -1:
+            return np.asarray(amp_sp).astype(np.float32, copy=False)
+        amp_sp = np.ascontiguousarray(amp_sp, dtype=np.float64)
+        K = amp_sp.shape[1]
+        if n_fft is None or n_fft // 2 + 1 != K:       # librosa takes n_fft from the spectrum then
+            n_fft = 2 * (K - 1)
+        amp = torch.from_numpy(amp_sp).to(_dev())
+        return _world.mel_project(amp, fs, n_fft, num_coded_sps).cpu().numpy()
+
+    @staticmethod
+    def amp_to_db(amp_sp):
+        """reference :334-336"""
+        return 20 * np.log10(np.maximum(1e-5, amp_sp))
+
+    @staticmethod
+    def db_to_amp(log_amp_sp):
+        """reference :338-339"""
+        return np.power(10.0, log_amp_sp * 0.05)
 
     @staticmethod
     def decode_sp(coded_sp: np.array, sp_type: str = "mcep", fs: int = None, alpha: float = None,

@@ -155,7 +155,7 @@ class WorldFeatLabelGen(ReaderBase):
         self.mgc_alpha = mgc_alpha  # None: fs_to_mgc_alpha(fs) like the reference
         self.batch_utts = batch_utts
         self.dir_coded_sps = self.sp_type
-        if self.num_coded_sps is not None:
+        if self.num_coded_sps is not None and self.num_coded_sps != -1:      # (-1: the whole amplitude spectrum)
             self.dir_coded_sps += str(self.num_coded_sps)
         self.dir_deltas = WorldFeatLabelGen.dir_deltas + "_" + self.dir_coded_sps
         self.covs = [None] * 4
@@ -271,13 +271,56 @@ class WorldFeatLabelGen(ReaderBase):
         return res["sp"], res["lf0"], res["vuv"], res["bap"]
 
     @staticmethod
+    def check_sp_type(sp_type, num_coded_sps, n_fft=None):
+        """The sp_types gen_data / extract_features prepare (reference :848-874); raises before any device work."""
+        if sp_type not in ("mcep", "mgc") + _world.STFT_SP_TYPES:
+            raise NotImplementedError("sp_type {!r} is not implemented (mcep, mgc, {}).".format(
+                sp_type, ", ".join(_world.STFT_SP_TYPES)))
+        if sp_type in ("amp_sp", "log_amp_sp") and num_coded_sps != -1:
+            raise ValueError("Use num_coded_sps=-1 for the amplitude spectrum (sp_type {!r}, got {}).".format(
+                sp_type, num_coded_sps))
+        if sp_type in _world.STFT_SP_TYPES and n_fft is not None:
+            _world.check_stft_args(n_fft)
+
+    @staticmethod
+    def coded_sp_width(sp_type, num_coded_sps, fs, n_fft=None):
+        """Columns of the coded spectrum: num_coded_sps, or n_fft // 2 + 1 for the amplitude spectra (-1)."""
+        if sp_type in ("amp_sp", "log_amp_sp"):
+            return (n_fft or AudioProcessing.fs_to_frame_length(fs)) // 2 + 1
+        return num_coded_sps
+
+    @staticmethod
     def extract_features_batch(raws, fs, preemphasis_applied=True, n_fft=None, hop_size_ms=5,
                                sp_type="mcep", num_coded_sps=40, mgc_alpha=None,
-                               f0_silence_threshold=None, lf0_zero=None):
+                               f0_silence_threshold=None, lf0_zero=None, win_length_ms=None,
+                               load_lf0=True, load_vuv=True, load_bap=True):
         """MI355X-native batched form of extract_features: the spectral envelope never leaves
-        the GPU (CheapTrick -> mcep fused). Returns a list of (coded_sp, lf0, vuv, bap)."""
-        if sp_type not in ("mcep", "mgc"):
-            raise NotImplementedError("Only sp_type 'mcep' and 'mgc' are on the accelerated path.")
+        the GPU (CheapTrick -> mcep fused). Returns a list of (coded_sp, lf0, vuv, bap).
+        The STFT sp_types ("mfbanks", "amp_sp", "log_amp_sp") come from the STFT kernel, trimmed to the WORLD
+        frames like trim_to_shortest (:891-907) when a WORLD stream is loaded; with none loaded WORLD does not
+        run and lf0 / vuv / bap are None (reference :829)."""
+        WorldFeatLabelGen.check_sp_type(sp_type, num_coded_sps, n_fft)
+        if sp_type in _world.STFT_SP_TYPES:
+            world_streams = load_lf0 or load_vuv or load_bap
+            cmp_dev, f_off = _world.extract_cmp_batch(
+                raws, fs, hop_size_ms, n_fft, add_deltas=False, sp_type=sp_type, num_coded_sps=num_coded_sps,
+                win_length_ms=win_length_ms, world_streams=world_streams,
+                f0_silence_threshold=WorldFeatLabelGen.f0_silence_threshold if f0_silence_threshold is None
+                else f0_silence_threshold,
+                lf0_zero=WorldFeatLabelGen.lf0_zero if lf0_zero is None else lf0_zero,
+                f0_method=WorldFeatLabelGen.f0_estimator)
+            cmp_host = cmp_dev.cpu().numpy()
+            ncs = WorldFeatLabelGen.coded_sp_width(sp_type, num_coded_sps, fs, n_fft)
+            out = []
+            for u in range(len(raws) if not isinstance(raws, tuple) else len(raws[1]) - 1):
+                c = cmp_host[f_off[u]:f_off[u + 1]]
+                sp = np.ascontiguousarray(c[:, :ncs])
+                if world_streams:
+                    out.append((sp, np.ascontiguousarray(c[:, ncs:ncs + 1]),
+                                np.ascontiguousarray(c[:, ncs + 1:ncs + 2]), np.ascontiguousarray(c[:, ncs + 2:])))
+                else:
+                    out.append((sp, None, None, None))
+            return out
         if f0_silence_threshold is None:
             f0_silence_threshold = WorldFeatLabelGen.f0_silence_threshold
         if lf0_zero is None:
@@ -307,12 +350,19 @@ class WorldFeatLabelGen(ReaderBase):
                          f0_silence_threshold: int = None, lf0_zero: float = None,
                          mgc_alpha: float = None):
         """Extract acoustic features from a single audio file (reference :809-889)."""
+        WorldFeatLabelGen.check_sp_type(sp_type, num_coded_sps, n_fft)
         audio_name = os.path.join(dir_in, file_name + "." + file_ext)
         raw, fs = AudioProcessing.get_raw(audio_name, preemphasis)
         coded_sp, lf0, vuv, bap = WorldFeatLabelGen.extract_features_batch(
             [raw], fs, n_fft=n_fft, hop_size_ms=hop_size_ms, sp_type=sp_type,
             num_coded_sps=num_coded_sps, mgc_alpha=mgc_alpha,
-            f0_silence_threshold=f0_silence_threshold, lf0_zero=lf0_zero)[0]
+            f0_silence_threshold=f0_silence_threshold, lf0_zero=lf0_zero, win_length_ms=win_length_ms,
+            load_lf0=load_lf0, load_vuv=load_vuv, load_bap=load_bap)[0]
+        if sp_type in _world.STFT_SP_TYPES:
+            logging.info("Extracted ({}{}{}) features from {} at {} Hz with {} ms frame hop.".format(
+                coded_sp.shape[1], sp_type, "" if lf0 is None else ", WORLD lf0, vuv, {}bap".format(bap.shape[1]),
+                os.path.basename(file_name), fs, hop_size_ms))
+            return coded_sp if load_sp else None, lf0, vuv, bap
         if load_vuv:
             unvoiced_frames_percentage = vuv.sum() / len(vuv) * 100.0
             if unvoiced_frames_percentage < 5.0:
@@ -438,9 +488,10 @@ class WorldFeatLabelGen(ReaderBase):
         return output
 
     # stream layout of the feature matrix the device assembles (itts_assemble_cmp_f32)
-    def _cmp_columns(self, num_bap=None):
+    def _cmp_columns(self, num_bap=None, fs=None):
         f = 3 if self.add_deltas else 1
-        ncs, nb = self.num_coded_sps, self.num_bap if num_bap is None else num_bap
+        ncs = self.num_coded_sps if fs is None else self.coded_sp_width(self.sp_type, self.num_coded_sps, fs, self.n_fft)
+        nb = self.num_bap if num_bap is None else num_bap
         return {"sp": (0, f * ncs), "lf0": (f * ncs, f), "vuv": (f * (ncs + 1), 1),
                 "bap": (f * (ncs + 1) + 1, f * nb)}
 
@@ -505,6 +556,10 @@ class WorldFeatLabelGen(ReaderBase):
         import torch
         loaded = [k for k, load in zip(("sp", "lf0", "vuv", "bap"), self.load_flags) if load]
         cols = stats = None
+        stft_args = {}
+        if self.sp_type in _world.STFT_SP_TYPES:     # STFT features where the mel-cepstra go; WORLD only when needed
+            stft_args = dict(sp_type=self.sp_type, num_coded_sps=self.num_coded_sps, win_length_ms=self.win_length_ms,
+                             world_streams=self.load_lf0 or self.load_vuv or self.load_bap)
         batches = self._batch_schedule(id_list)
 
         n_io = max(2, min(16, (os.cpu_count() or 2) // 2))
@@ -596,7 +651,7 @@ class WorldFeatLabelGen(ReaderBase):
                 pending_reads[bi] = None
                 assert len(set(fss)) == 1, "All files of a batch need the same sampling rate."
                 fs = fss[0]
-                alpha = self.mgc_alpha if self.mgc_alpha is not None \
+                alpha = None if stft_args else self.mgc_alpha if self.mgc_alpha is not None \
                     else AudioProcessing.fs_to_mgc_alpha(fs)
                 st = analysis_streams[bi % n_flight]
                 with torch.cuda.stream(st):
@@ -608,7 +663,7 @@ class WorldFeatLabelGen(ReaderBase):
                         alpha, WorldFeatLabelGen.f0_silence_threshold, WorldFeatLabelGen.lf0_zero,
                         self.add_deltas,
                         mgc_gamma=AudioProcessing.mgc_gamma if self.sp_type == "mgc" else None,
-                        f0_method=self.f0_estimator)
+                        f0_method=self.f0_estimator, **stft_args)
                     ready = st.record_event()
                 mark("analysis queued (host side done)", bi)
                 return cmp_dev, f_off, ready, fs
@@ -642,7 +697,7 @@ class WorldFeatLabelGen(ReaderBase):
                     main.wait_event(ready)
                     cmp_dev.record_stream(main)
                     if cols is None:      # WORLD fixes the number of bap bands by the sampling rate
-                        cols = self._cmp_columns(AudioProcessing.fs_to_num_bap(fs))
+                        cols = self._cmp_columns(AudioProcessing.fs_to_num_bap(fs), fs)
                         stats = _world.StreamStats({k: cols[k] for k in loaded if k != "vuv"},
                                                    self.add_deltas)
                     stats.add(cmp_dev)
@@ -682,6 +737,7 @@ class WorldFeatLabelGen(ReaderBase):
         ranks, length balanced by file size, every rank writes the features of its own utterances
         and the additive normalisation statistics are merged with one sum all-reduce per stream
         (SURVEY.md section 8e); all ranks return the same parameters, rank 0 writes them."""
+        self.check_sp_type(self.sp_type, self.num_coded_sps, self.n_fft)
         if id_list is None:
             id_list = [os.path.splitext(os.path.basename(f))[0]
                        for f in glob.glob(os.path.join(dir_in, "*" + file_ext))]
@@ -702,8 +758,6 @@ class WorldFeatLabelGen(ReaderBase):
         if world > 1:
             sizes = [os.path.getsize(os.path.join(dir_in, n + "." + file_ext)) for n in all_ids]
             id_list = [all_ids[i] for i in _parallel.shard_by_length(sizes, world)[rank]]
-        if self.sp_type not in ("mcep", "mgc"):
-            raise NotImplementedError("Only sp_type 'mcep' and 'mgc' are on the accelerated path.")
         self._gen_data_pipeline(dir_in, dir_out, file_ext, id_list, label_dict if return_dict
                                 else None)
         if world > 1:

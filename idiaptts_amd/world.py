@@ -1,10 +1,13 @@
 """Batched, GPU-resident WORLD feature path (the MI355X-native fast path behind the drop-in shims).
 
 analysis : wav(s) -> DIO -> StoneMask -> CheapTrick (+ fused SPTK mcep) / D4C (+ coded bap)
+STFT     : wav(s) -> amplitude spectrum / its dB form / mel filter banks (librosa's STFT features, stft.hip)
 synthesis: (f0, sp, ap) -> WORLD synthesis -> float32 (+ de-pre-emphasis)
 Utterances are concatenated and processed by single launches; only the small per-frame features
 (f0, mcep, bap) travel back to the host unless the spectral envelope is asked for.
 """
+import functools
+
 import numpy as np
 import torch
 
@@ -117,6 +120,177 @@ def analyse_batch(raws, fs, hop_ms=5.0, n_fft=None, want_sp=True, want_ap=False,
     return out
 
 
+# ------------------------------------------------------------------------------------------ STFT features
+STFT_SP_TYPES = ("mfbanks", "amp_sp", "log_amp_sp")
+
+
+def fs_to_frame_length(fs):
+    return int(_lib.load().itts_cheaptrick_fft_size(int(fs), 71.0))
+
+
+def stft_hop(fs, hop_ms):
+    """hop_length of the reference's librosa calls: int(hop_size_ms / 1000. * fs) (AudioProcessing.py:180)."""
+    return int(hop_ms / 1000. * fs)
+
+
+def check_stft_args(n_fft, window="hann", pad_mode="reflect"):
+    """What the STFT kernel covers; anything else raises before any device work."""
+    if n_fft not in (1024, 2048):
+        raise NotImplementedError("STFT n_fft={} is not implemented (1024, 2048).".format(n_fft))
+    if window != "hann":
+        raise NotImplementedError("STFT window {!r} is not implemented ('hann').".format(window))
+    if pad_mode not in ("reflect", "constant"):
+        raise NotImplementedError("STFT pad_mode {!r} is not implemented ('reflect', 'constant').".format(pad_mode))
+
+
+def stft_num_frames(n, n_fft, hop, center=True):
+    """Frames of librosa.stft: 1 + n // hop with the centre padding, 1 + (n - n_fft) // hop without."""
+    if center:
+        return 1 + int(n) // hop
+    if n < n_fft:
+        raise ValueError("center=False needs at least n_fft={} samples, got {}.".format(n_fft, n))
+    return 1 + (int(n) - n_fft) // hop
+
+
+@functools.lru_cache(maxsize=None)
+def stft_window(n_fft, win_length=None, window="hann"):
+    """librosa.stft's window: scipy.signal.get_window(window, win_length, fftbins=True), zero-padded to n_fft
+    and centred (librosa.util.pad_center).  float64 [n_fft], read-only."""
+    import scipy.signal
+    win_length = n_fft if win_length is None else int(win_length)
+    if not 0 < win_length <= n_fft:
+        raise ValueError("win_length={} must be in (0, n_fft={}].".format(win_length, n_fft))
+    w = np.asarray(scipy.signal.get_window(window, win_length, fftbins=True), dtype=np.float64)
+    lpad = (n_fft - win_length) // 2
+    out = np.zeros(n_fft)
+    out[lpad:lpad + win_length] = w
+    out.setflags(write=False)
+    return out
+
+
+def hz_to_mel(f):
+    """Slaney mel scale (librosa.hz_to_mel, htk=False): linear below 1 kHz at 200/3 Hz per mel, logarithmic
+    above with step log(6.4) / 27."""
+    f = np.asarray(f, dtype=np.float64)
+    f_sp, min_log_hz = 200.0 / 3, 1000.0
+    min_log_mel, logstep = min_log_hz / f_sp, np.log(6.4) / 27.0
+    return np.where(f >= min_log_hz, min_log_mel + np.log(np.maximum(f, min_log_hz) / min_log_hz) / logstep,
+                    f / f_sp)
+
+
+def mel_to_hz(m):
+    m = np.asarray(m, dtype=np.float64)
+    f_sp, min_log_hz = 200.0 / 3, 1000.0
+    min_log_mel, logstep = min_log_hz / f_sp, np.log(6.4) / 27.0
+    return np.where(m >= min_log_mel, min_log_hz * np.exp(logstep * (np.maximum(m, min_log_mel) - min_log_mel)),
+                    f_sp * m)
+
+
+@functools.lru_cache(maxsize=None)
+def mel_basis(fs, n_fft, n_mels):
+    """librosa.filters.mel(sr=fs, n_fft=n_fft, n_mels=n_mels) with its defaults (fmin 0, fmax fs / 2, Slaney
+    scale, norm="slaney"): triangles computed in float64 and stored into float32, then scaled in place by the
+    float64 Slaney factors 2 / (f[i+2] - f[i]) -- float32 [n_mels, n_fft // 2 + 1], rounded twice like librosa's."""
+    n_mels = int(n_mels)
+    fftfreqs = np.fft.rfftfreq(n=n_fft, d=1.0 / fs)
+    mel_f = mel_to_hz(np.linspace(hz_to_mel(0.0), hz_to_mel(float(fs) / 2), n_mels + 2))
+    fdiff = np.diff(mel_f)
+    ramps = np.subtract.outer(mel_f, fftfreqs)
+    weights = np.zeros((n_mels, n_fft // 2 + 1), dtype=np.float32)
+    for i in range(n_mels):
+        weights[i] = np.maximum(0, np.minimum(-ramps[i] / fdiff[i], ramps[i + 2] / fdiff[i + 1]))
+    weights *= (2.0 / (mel_f[2:n_mels + 2] - mel_f[:n_mels]))[:, np.newaxis]
+    weights.setflags(write=False)
+    return weights
+
+
+@functools.lru_cache(maxsize=None)
+def mel_tables(fs, n_fft, n_mels):
+    """The kernel's form of mel_basis: per filter (first bin, bins, first weight) of its contiguous support,
+    int32 [3 n_mels], and the weights of all supports back to back, float32."""
+    basis = mel_basis(fs, n_fft, n_mels)
+    tab, ws = [], []
+    pos = 0
+    for row in basis:
+        nz = np.flatnonzero(row)
+        k0, n = (int(nz[0]), int(nz[-1] - nz[0] + 1)) if len(nz) else (0, 0)
+        tab += [k0, n, pos]
+        ws.append(row[k0:k0 + n])
+        pos += n
+    return np.asarray(tab, dtype=np.int32), np.concatenate(ws).astype(np.float32)
+
+
+_stft_device_tables = {}
+
+
+def _stft_table(key, build, dev):
+    k = key + (dev.index if dev.index is not None else torch.cuda.current_device(),)
+    t = _stft_device_tables.get(k)
+    if t is None:
+        t = _stft_device_tables[k] = tuple(torch.from_numpy(np.array(a, order="C")).to(dev) for a in build())
+    return t
+
+
+def stft_features(x, x_off, f_off, first, fs, sp_type, n_fft, hop, n_mels=None, win_length=None,
+                  center=True, pad_mode="reflect", out=None):
+    """The STFT feature rows of utterances stored back to back in the float64 device tensor x: row f_off[u] + i is
+    frame first[u] + i of utterance u.  sp_type "amp_sp" (float32; "amp_sp_f64": float64), "log_amp_sp" or
+    "mfbanks" (n_mels bands)."""
+    check_stft_args(n_fft, "hann", pad_mode)
+    dev = x.device
+    (window,) = _stft_table(("window", n_fft, win_length), lambda: (stft_window(n_fft, win_length),), dev)
+    pad = pad_mode if center else None
+    if sp_type == "mfbanks":
+        tab, w = _stft_table(("mel", fs, n_fft, n_mels), lambda: mel_tables(fs, n_fft, n_mels), dev)
+        return ops.mel_filterbank(x, x_off, f_off, first, n_fft, hop, pad, window, tab, w, n_mels, out=out)
+    return ops.stft_amp(x, x_off, f_off, first, n_fft, hop, pad, window, kind=sp_type, out=out)
+
+
+def mel_project(amp_sp, fs, n_fft, n_mels):
+    """mel_basis @ amp_sp.T, transposed, float32, for a given amplitude spectrum [T, n_fft // 2 + 1] on the device."""
+    tab, w = _stft_table(("mel", fs, n_fft, n_mels), lambda: mel_tables(fs, n_fft, n_mels), amp_sp.device)
+    return ops.mel_project(amp_sp, tab, w, n_mels)
+
+
+def _extract_cmp_stft(x, x_off, fs, hop_ms, n_fft, sp_type, n_mels, win_length_ms, world_streams,
+                      f0_silence_threshold, lf0_zero, add_deltas, f0_method):
+    """extract_cmp_batch for the STFT sp_types (x already on the device)."""
+    dev = x.device
+    hop = stft_hop(fs, hop_ms)
+    win_length = None if win_length_ms is None else int(win_length_ms / 1000. * fs)
+    lens = [b - a for a, b in zip(x_off[:-1], x_off[1:])]
+    t_stft = [stft_num_frames(n, n_fft, hop) for n in lens]
+    if world_streams:
+        t_world = [num_frames(n, fs, hop_ms) for n in lens]
+        if any(a < b for a, b in zip(t_stft, t_world)):
+            raise NotImplementedError("STFT hop {} gives fewer frames than WORLD's {} ms grid.".format(hop, hop_ms))
+        first = [(a - b) // 2 for a, b in zip(t_stft, t_world)]      # trim_to_shortest: diff // 2 in front
+        f_off = offsets(t_world)
+    else:
+        first = [0] * len(lens)
+        f_off = offsets(t_stft)
+    main = torch.cuda.current_stream(dev)
+    if world_streams:
+        f0 = estimate_f0(x, x_off, f_off, fs, hop_ms, f0_method)
+        side = _side_stream(dev)
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            _, bap = ops.d4c(x, x_off, f0, f_off, fs, hop_ms, n_fft, want_ap=False, want_bap=torch.float32)
+            lf0, vuv = ops.lf0_vuv(f0, f_off, f0_silence_threshold, lf0_zero)
+    sp = stft_features(x, x_off, f_off, first, fs, sp_type, n_fft, hop, n_mels, win_length)
+    if world_streams:
+        main.wait_stream(side)
+        for t in (x, f0, bap, lf0, vuv):
+            t.record_stream(side)
+            t.record_stream(main)
+    else:       # WORLD does not run: the columns of its streams are left at zero (gen_data writes none of them)
+        n_rows = f_off[-1]
+        lf0 = torch.zeros(n_rows, dtype=torch.float32, device=dev)
+        vuv = torch.zeros(n_rows, dtype=torch.float32, device=dev)
+        bap = torch.zeros((n_rows, _lib.load().itts_num_aperiodicities(int(fs))), dtype=torch.float32, device=dev)
+    return ops.assemble_cmp(sp, lf0, vuv, bap, f_off, add_deltas=add_deltas), f_off
+
+
 class StreamStats(object):
     """Normalisation sums of the continuous streams (coded sp, lf0, bap) of a feature matrix,
     accumulated on the device over the batches of a gen_data run (fp64, fixed summation order):
@@ -150,11 +324,19 @@ class StreamStats(object):
 
 def extract_cmp_batch(raws, fs, hop_ms=5.0, n_fft=None, mcep_order=59, mcep_alpha=None,
                       f0_silence_threshold=30, lf0_zero=0, add_deltas=True, device=None,
-                      mgc_gamma=None, f0_method="dio"):
+                      mgc_gamma=None, f0_method="dio", sp_type=None, num_coded_sps=None, win_length_ms=None,
+                      world_streams=True):
     """wav(s) -> the `[T, 3*(ncs+1+nb)+1]` feature matrix of the reference's gen_data in one go,
     everything on the device: DIO + StoneMask, D4C -> coded bap, CheapTrick -> mcep, lf0 / V-UV
     with interpolate_lin, deltas and the stream layout (WorldFeatLabelGen.py:778-807, 809-889,
-    1121-1172).  Returns (cmp [Ttot, W] f32 on the device, frame offsets [U+1])."""
+    1121-1172).  Returns (cmp [Ttot, W] f32 on the device, frame offsets [U+1]).
+    sp_type "mfbanks" (num_coded_sps bands), "amp_sp" or "log_amp_sp" put librosa's STFT features where the
+    mel-cepstra go (WorldFeatLabelGen.py:865-874; CheapTrick and mcep do not run): with `world_streams` trimmed
+    to the WORLD frame count like trim_to_shortest (:891-907), without them WORLD does not run at all and the
+    lf0 / vuv / bap columns are zeros."""
+    if sp_type in STFT_SP_TYPES:
+        n_fft = n_fft or fs_to_frame_length(fs)
+        check_stft_args(n_fft)
     dev = _device(device)
     L = _lib.load()
     n_fft = n_fft or L.itts_cheaptrick_fft_size(int(fs), 71.0)
@@ -164,11 +346,14 @@ def extract_cmp_batch(raws, fs, hop_ms=5.0, n_fft=None, mcep_order=59, mcep_alph
     else:
         x_off = offsets([len(r) for r in raws])
         samples = np.concatenate(raws) if len(raws) else np.empty(0)
-    f_off = offsets([num_frames(b - a, fs, hop_ms) for a, b in zip(x_off[:-1], x_off[1:])])
     if isinstance(samples, torch.Tensor):     # float64 samples of gen_data's readers: page-locked (fetched asynchronously)
         x = samples if samples.is_cuda else samples.to(dev, non_blocking=True)     # or uploaded by the reader already
     else:
         x = torch.from_numpy(np.ascontiguousarray(samples, dtype=np.float64)).to(dev)
+    if sp_type in STFT_SP_TYPES:
+        return _extract_cmp_stft(x, x_off, fs, hop_ms, n_fft, sp_type, num_coded_sps, win_length_ms,
+                                 world_streams, f0_silence_threshold, lf0_zero, add_deltas, f0_method)
+    f_off = offsets([num_frames(b - a, fs, hop_ms) for a, b in zip(x_off[:-1], x_off[1:])])
     f0 = estimate_f0(x, x_off, f_off, fs, hop_ms, f0_method)
     main = torch.cuda.current_stream(dev)
     side = _side_stream(dev)

@@ -241,6 +241,27 @@ int itts_sqrt_inplace_f64(double* d_x, int64_t n, void* stream);
  * of WorldFeatLabelGen.world_features_to_raw (world/WorldFeatLabelGen.py:925, np.square), after the upload. */
 int itts_square_inplace_f64(double* d_x, int64_t n, void* stream);
 
+/* Short-time Fourier transform features (AudioProcessing.librosa_extract_amp_sp / extract_mfbanks,
+ * AudioProcessing.py:156-226): librosa.stft of the float64 samples d_x (utterances back to back at
+ * h_x_off [U+1]) with the window table d_window [n_fft] (scipy's window, zero-padded to n_fft and
+ * centred), n_fft 1024 or 2048, hop > 0; pad_mode 0 = center=False, 1 = centre padding by np.pad
+ * "reflect", 2 = "constant".  Output row g (h_f_off [U+1], h_f_off[0] = 0) of utterance u is STFT
+ * frame g - h_f_off[u] + h_first[u] of that utterance (h_first drops frames in front: trim_to_shortest).
+ * itts_stft writes |X| / sqrt(n_fft/2+1) to d_out [T, ld_out] as float32 (out_kind 0), float64 (1) or
+ * 20 log10(max(1e-5, float32 value)) float32 (2).  itts_stft_mel writes the mel projection float32
+ * [T, ld_out >= n_mels]: filter m sums d_mel_w[tab[3m+2] + j] * |X|[tab[3m] + j] / sqrt(K), j < tab[3m+1],
+ * in ascending order (float64).  itts_mel_project applies the same tables to a given amplitude
+ * spectrum d_amp [T, ld_amp] f64 with K bins.  Bit-identical from run to run. */
+int itts_stft(const double* d_x, const int64_t* h_x_off, const int64_t* h_f_off, const int64_t* h_first,
+              int n_utts, int n_fft, int hop, int pad_mode, const double* d_window, int out_kind,
+              void* d_out, int64_t ld_out, void* stream);
+int itts_stft_mel(const double* d_x, const int64_t* h_x_off, const int64_t* h_f_off, const int64_t* h_first,
+                  int n_utts, int n_fft, int hop, int pad_mode, const double* d_window,
+                  const int* d_mel_tab, const float* d_mel_w, int n_mels, float* d_out, int64_t ld_out,
+                  void* stream);
+int itts_mel_project(const double* d_amp, int64_t T, int K, int64_t ld_amp, const int* d_mel_tab,
+                     const float* d_mel_w, int n_mels, float* d_out, int64_t ld_out, void* stream);
+
 /* interpolate_lin (misc/utils.py:40-86) on float32 contours stored back to back: frames <= 0 are
  * gaps; bit-exact including the reference's quirks (target reached one frame early; a gap whose
  * next voiced frame is the last frame is filled, with that frame, by the last voiced value).
