@@ -5,6 +5,12 @@ Metric (BASELINE.json): acoustic valid frames/sec in training, FF 425->512->512-
 32 utterances per GPU per step, fp32, synthetic data.  One "step" = forward +
 masked-MSE + backward + (all-reduce) + Adam on one mini-batch already resident in HBM.
 Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: set-up, clock ramp, warm-up, the timed steps, the
+--dump-outputs arrays and the line (with the roofline of the timed steps).  --full adds everything
+else: the GEMM-only replay and the shader clock behind the timed steps, the BiLSTM / BiGRU, WORLD,
+MLPG, duration, resident-epoch, trainer-epoch, single-call and gen_data sections, the CPU baselines
+and the exchange plan.
 """
 import argparse
 import gc
@@ -1165,6 +1171,41 @@ def ff_step_outputs(model, loss):
     return {k: np.ascontiguousarray(v.detach().cpu().numpy()) for k, v in arrays.items()}
 
 
+def gemm_replay_ms(model, batches, steps, stream, passes=3):
+    """GEMM-only replay of the six GEMM launches of a step, RIGHT BEHIND the timed region (same clocks, same
+    batches in the same order, events on the launch stream): how much of a step its dominant kernel is; ms per
+    step of each of `passes` passes over `steps` steps.  (Round 4 ran this replay after the RNN sections, on
+    batch 0 only: its 1.022 ms per step exceeded the 1.0095 ms step it was supposed to be a part of.)"""
+    from idiaptts_amd import ops
+    dims = model.dims
+
+    def gemms(i):
+        x = batches[i % len(batches)][0]
+        M = x.shape[0]
+        buf = model._rows_buffer       # the step's own padded-pitch activation buffers
+        W, G = model.weight_padded, model.grads
+        h1 = ops.linear_fwd(x, W(0), model.bias(0), 1, out=buf("h0", M, dims[1]))
+        h2 = ops.linear_fwd(h1, W(1), model.bias(1), 1, out=buf("h1", M, dims[2]))
+        ops.linear_fwd(h2, W(2), model.bias(2), 0, out=buf("h2", M, dims[3]))
+        # the backward launches of the step (native_ff.loss_and_backward): weight, bias and input
+        # gradient of a layer share one launch; dz_out holds the last timed step's loss gradient
+        dz3, dz2, dz1 = buf("dz_out", M, dims[3]), buf("dz0", M, dims[2]), buf("dz1", M, dims[1])
+        ops.linear_bwd(dz3, h2, W(2), W(2, G), model.bias(2, G), dz2, yprev=h2, act_prev=1)
+        ops.linear_bwd(dz2, h1, W(1), W(1, G), model.bias(1, G), dz1, yprev=h1, act_prev=1)
+        ops.linear_bwd_weight(dz1, x, dw=W(0, G), db=model.bias(0, G))
+
+    replay_ms = []
+    for _ in range(passes):
+        r0, r1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        r0.record(stream)
+        for i in range(steps):
+            gemms(i)
+        r1.record(stream)
+        r1.synchronize()
+        replay_ms.append(r0.elapsed_time(r1) / steps)
+    return replay_ms
+
+
 def write_outputs(out_dir, arrays):
     """--dump-outputs: one <name>.npy per array."""
     os.makedirs(out_dir, exist_ok=True)
@@ -1245,6 +1286,10 @@ def main():
     ap.add_argument("--ramp-steps", type=int, default=80,
                     help="untimed steps run before the --warmup steps so that the shader clock has "
                          "settled (about 1 ms each; 0 = none); reported as clock_ramp in the JSON line")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: GEMM replay and shader clock behind the timed "
+                         "steps, the other sections, the CPU baselines and the exchange plan (the options below "
+                         "that size or skip those apply only with --full)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget-s", type=float, default=100.0,
                     help="wall-time budget of ALL host baselines together (FF stack, BiLSTM stack, "
@@ -1283,7 +1328,7 @@ def main():
         os.environ["ITTS_BENCH_SHARE_GPU"] = "1"
 
     cpu_extra = {}
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
 
     from idiaptts_amd import lib
     lib.require_gpu()
@@ -1370,48 +1415,21 @@ def main():
     t_launched = time.perf_counter() - t0
     barrier()
     dt = time.perf_counter() - t0
-    # taken before the GEMM replay and the clock sampling below overwrite the gradients and parameters
+    # taken before the GEMM replay and the clock sampling of --full overwrite the gradients and parameters
     outputs = ff_step_outputs(model, loss) if args.dump_outputs and rank == 0 else None
-    # GEMM-only replay of the six GEMM launches of a step, RIGHT BEHIND the timed region (same clocks, same
-    # batches in the same order, events on the launch stream): how much of a step its dominant kernel is.
-    # (Round 4 ran this replay after the RNN sections, on batch 0 only: its 1.022 ms per step exceeded the
-    # 1.0095 ms step it was supposed to be a part of.)
-    from idiaptts_amd import ops
-
-    def gemms(i):
-        x, y, valid, nloc = batches[i % n_batches]
-        M = x.shape[0]
-        buf = model._rows_buffer       # the step's own padded-pitch activation buffers
-        W, G = model.weight_padded, model.grads
-        h1 = ops.linear_fwd(x, W(0), model.bias(0), 1, out=buf("h0", M, dims[1]))
-        h2 = ops.linear_fwd(h1, W(1), model.bias(1), 1, out=buf("h1", M, dims[2]))
-        ops.linear_fwd(h2, W(2), model.bias(2), 0, out=buf("h2", M, dims[3]))
-        # the backward launches of the step (native_ff.loss_and_backward): weight, bias and input
-        # gradient of a layer share one launch; dz_out holds the last timed step's loss gradient
-        dz3, dz2, dz1 = buf("dz_out", M, dims[3]), buf("dz0", M, dims[2]), buf("dz1", M, dims[1])
-        ops.linear_bwd(dz3, h2, W(2), W(2, G), model.bias(2, G), dz2, yprev=h2, act_prev=1)
-        ops.linear_bwd(dz2, h1, W(1), W(1, G), model.bias(1, G), dz1, yprev=h1, act_prev=1)
-        ops.linear_bwd_weight(dz1, x, dw=W(0, G), db=model.bias(0, G))
-
-    replay_ms = []
-    for _ in range(3):
-        r0, r1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        r0.record(stream)
-        for i in range(args.steps):
-            gemms(i)
-        r1.record(stream)
-        r1.synchronize()
-        replay_ms.append(r0.elapsed_time(r1) / args.steps)
-    # The shader clock is sampled AFTER the timed region, over 60 more steps of the same load.  Rounds 2
-    # and 3 sampled it (sysfs pp_dpm_sclk, from a thread) DURING the timed steps, and that was the "fixed
-    # 2 ms" of the driver's 20-step protocol: the first ~20 ms of such reads slow every step by 10-40 %
-    # (per-step events, profiles/r4m_step_traces.txt: 1.13 ms per step with the sampler, 1.007 without,
-    # same box, same binary) -- the instrument was perturbing the measurement.
-    clock = SclkSampler(local_rank, period_s=0.002)
-    with clock:
-        for i in range(60):
-            step(i)
-        torch.cuda.synchronize()
+    replay_ms, clock = None, None
+    if args.full:
+        replay_ms = gemm_replay_ms(model, batches, args.steps, stream)
+        # The shader clock is sampled AFTER the timed region, over 60 more steps of the same load.  Rounds 2
+        # and 3 sampled it (sysfs pp_dpm_sclk, from a thread) DURING the timed steps, and that was the "fixed
+        # 2 ms" of the driver's 20-step protocol: the first ~20 ms of such reads slow every step by 10-40 %
+        # (per-step events, profiles/r4m_step_traces.txt: 1.13 ms per step with the sampler, 1.007 without,
+        # same box, same binary) -- the instrument was perturbing the measurement.
+        clock = SclkSampler(local_rank, period_s=0.002)
+        with clock:
+            for i in range(60):
+                step(i)
+            torch.cuda.synchronize()
     dt_events = evs[0].elapsed_time(evs[-1]) * 1e-3
     step_ms = [evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps)]
     if dist_on:
@@ -1423,7 +1441,7 @@ def main():
 
     # config 3 (and its GRU variant): every rank takes part, rank 0 reports
     rnn_extra = {}
-    if args.bilstm_utts > 0:
+    if args.full and args.bilstm_utts > 0:
         for cell in ("LSTM", "GRU"):
             rnn_extra.update(bilstm_section(dev, args.bilstm_utts, cell=cell, rank=rank,
                                             world=world))
@@ -1441,7 +1459,7 @@ def main():
 
     # config 5 (WORLD analysis / synthesis real-time factors, MLPG): every rank takes part
     world_extra = {}
-    if args.world_utts > 0:
+    if args.full and args.world_utts > 0:
         with_cpu = not args.no_cpu_baseline and world == 1    # CPU baseline: rank 0 at N = 1 only
         world_extra = world_section(dev, args.world_utts, args.world_fs, with_cpu=with_cpu,
                                     cpu_seconds=min(25.0, args.cpu_budget_s / 6),
@@ -1456,13 +1474,12 @@ def main():
         # dominant kernel roofline FROM THE TIMED STEPS: algorithmic flops of the K timed batches (this rank's
         # frames) over the event time of the K timed steps on the launch stream -- the six GEMM launches plus
         # everything else a step holds (loss reduction, split-K slab sums, Adam), so `achieved` is a lower
-        # bound of the rate the GEMM launches run at; `gemm_replay` is the GEMM-only replay of the same
-        # batches queued right behind the timed region.
+        # bound of the rate the GEMM launches run at; `gemm_replay` (--full) is the GEMM-only replay of the
+        # same batches queued right behind the timed region.
         local_frames = sum(batches[i % n_batches][3] for i in range(args.steps))
         flops = flops_per_frame(dims) * local_frames
         ms_step_events = dt_events / args.steps * 1e3
         achieved = flops / dt_events / 1e12
-        gemm_ms = float(np.median(replay_ms))
         # HBM bytes per GEMM launch from the committed PMC passes (FETCH_SIZE x2 + WRITE_SIZE,
         # see profiles/r4_gemm_traffic.json); not re-measured inside bench.py.
         traffic = None
@@ -1481,17 +1498,19 @@ def main():
                             "(HIP events on the launch stream around the timed region)".format(
                                 args.steps, flops / args.steps / 1e9, ms_step_events),
                     "algorithmic_flops_per_launch": flops / args.steps / n_launch,
-                    "avg_launch_us": ms_step_events * 1e3 / n_launch,
-                    "gemm_replay": {
-                        "what": "the six GEMM launches alone, same batches and order, queued right behind the "
-                                "timed region; median of 3 passes of {} steps".format(args.steps),
-                        "gemm_ms_per_step": gemm_ms, "passes_ms_per_step": [round(v, 4) for v in replay_ms],
-                        "achieved": flops / args.steps / (gemm_ms * 1e-3) / 1e12,
-                        "frac": flops / args.steps / (gemm_ms * 1e-3) / 1e12 / PEAK_MFMA_F32_TFLOPS,
-                        "avg_launch_us": gemm_ms * 1e3 / n_launch,
-                        "share_of_step": gemm_ms / ms_step_events,
-                        "consistent": bool(gemm_ms <= ms_step_events)},
-                    "shader_clock_under_the_same_load_after_the_timed_steps": clock.summary()}
+                    "avg_launch_us": ms_step_events * 1e3 / n_launch}
+        if args.full:
+            gemm_ms = float(np.median(replay_ms))
+            roofline["gemm_replay"] = {
+                "what": "the six GEMM launches alone, same batches and order, queued right behind the "
+                        "timed region; median of 3 passes of {} steps".format(args.steps),
+                "gemm_ms_per_step": gemm_ms, "passes_ms_per_step": [round(v, 4) for v in replay_ms],
+                "achieved": flops / args.steps / (gemm_ms * 1e-3) / 1e12,
+                "frac": flops / args.steps / (gemm_ms * 1e-3) / 1e12 / PEAK_MFMA_F32_TFLOPS,
+                "avg_launch_us": gemm_ms * 1e3 / n_launch,
+                "share_of_step": gemm_ms / ms_step_events,
+                "consistent": bool(gemm_ms <= ms_step_events)}
+            roofline["shader_clock_under_the_same_load_after_the_timed_steps"] = clock.summary()
         cpu = None
         if want_cpu:   # CPU baseline: rank 0 at N = 1 only
             cpu = cpu_baseline_ff(args.utts_per_gpu, max_seconds=min(20.0, args.cpu_budget_s / 4))
@@ -1512,7 +1531,7 @@ def main():
             lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
             if res.returncode == 0 and lines:
                 extra["world"]["cpu_baseline_pool"] = json.loads(lines[-1])
-        if world == 1 and args.world_utts > 0:
+        if args.full and world == 1 and args.world_utts > 0:
             extra.update(resident_epoch_section(dev))
             if args.trainer_utts > 0:
                 extra.update(trainer_epoch_section(dev, args.trainer_utts, with_bilstm=args.bilstm_utts > 0))
@@ -1556,15 +1575,17 @@ def main():
                                    "(every rank its own {} utterances; config 3 likewise: 64 per GPU)".format(
                                        args.utts_per_gpu, args.utts_per_gpu),
                        "utts_per_gpu": args.utts_per_gpu, "parallelism": "dp{}".format(world)},
-            "roofline": roofline, "cpu_baseline": cpu,
+            "roofline": roofline, "cpu_baseline": cpu, "full": args.full,
         }
-        rnn_params = 2 * (4 * 512 * (428 + 512) + 8 * 512) + 2 * 2 * (4 * 512 * (1024 + 512) + 8 * 512) + 1024 * 187 + 187
-        out["exchange_plan"] = exchange_plan(
-            world if world > 1 else 8, model.numel, rnn_params, dt / args.steps * 1e3,
-            rnn_extra.get("bilstm", {}).get("ms_per_step"),
-            rnn_extra.get("bilstm_global_batch", rnn_extra.get("bilstm_eighth_batch", {})).get("ms_per_step"))
-        if world == 1:
-            out["exchange_plan"]["note"] = "prediction for 8 GPUs from this run's single-GPU step times (nothing here has run on more than one GPU)"
+        if args.full:
+            rnn_params = 2 * (4 * 512 * (428 + 512) + 8 * 512) + 2 * 2 * (4 * 512 * (1024 + 512) + 8 * 512) + 1024 * 187 + 187
+            out["exchange_plan"] = exchange_plan(
+                world if world > 1 else 8, model.numel, rnn_params, dt / args.steps * 1e3,
+                rnn_extra.get("bilstm", {}).get("ms_per_step"),
+                rnn_extra.get("bilstm_global_batch", rnn_extra.get("bilstm_eighth_batch", {})).get("ms_per_step"))
+            if world == 1:
+                out["exchange_plan"]["note"] = ("prediction for 8 GPUs from this run's single-GPU step times (nothing "
+                                                "here has run on more than one GPU)")
         if share_gpu:
             out["shared_gpu"] = ("functional check only: {} ranks on ONE device, collectives over "
                                  "gloo -- not a measurement".format(world))

@@ -7,7 +7,7 @@
 # decode_tile it cost the FF step 1 % (1.0184 against 1.0087 ms, three alternating pairs); as a kernel of its own, nothing
 # (1.0041 / 1.0043 / 1.0081 against 1.0047 / 1.0085 / 1.0088).
 R=$GRAFT_REPO_ROOT; L=$R/idiaptts_amd/_lib; cd /tmp
-FF="--steps 20 --warmup 5 --world-utts 0 --bilstm-utts 0 --no-cpu-baseline"
+FF="--steps 20 --warmup 5 --full --world-utts 0 --bilstm-utts 0 --no-cpu-baseline"
 line() { python3 $R/bench.py $FF 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('$1', round(d['ms_per_step'],4), round(d['roofline']['frac'],4), round(d['roofline']['gemm_ms_per_step'],4))"; }
 cp $L/libidiaptts_amd.so /tmp/lib_new.so
 OBJS=$(ls $L/*.o | grep -v "/nn.o")

@@ -2,7 +2,7 @@
 set -x
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$1; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
-FF="--world-utts 0 --bilstm-utts 0 --no-cpu-baseline"
+FF="--full --world-utts 0 --bilstm-utts 0 --no-cpu-baseline"
 python3 $R/bench.py $FF 2> $O/ff_stderr.txt | tail -1 > $O/ff_bench_line.json
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ff_raw -- python3 $R/bench.py $FF > /dev/null 2>&1
 cp $(ls $O/ff_raw/*/*kernel_stats.csv | head -1) $O/ff_kernel_stats.csv
@@ -16,8 +16,8 @@ python3 $R/scripts/pmc_summary.py $O/pmc_m gemm_ring > $O/gemm_mfma_busy.txt 2>&
 find $O -name "*counter_collection.csv" -size +20M -delete
 ls -la $O
 # the whole default bench: line + per-kernel statistics of every section
-python3 $R/bench.py 2> $O/full_stderr.txt | tail -1 > $O/full_bench_line.json
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/full_raw -- python3 $R/bench.py --no-cpu-baseline > /dev/null 2>&1
+python3 $R/bench.py --full 2> $O/full_stderr.txt | tail -1 > $O/full_bench_line.json
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/full_raw -- python3 $R/bench.py --full --no-cpu-baseline > /dev/null 2>&1
 cp $(ls $O/full_raw/*/*kernel_stats.csv | head -1) $O/bench_kernel_stats.csv
 rm -rf $O/full_raw
 # MLPG: HBM traffic of the solves

@@ -1,14 +1,14 @@
 # Round-4 evidence (run on the GPU box): bash scripts/prof_round4.sh <tag>   -> gpurun_out/<tag>/
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$1; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
-FF="--world-utts 0 --bilstm-utts 0 --no-cpu-baseline"
+FF="--full --world-utts 0 --bilstm-utts 0 --no-cpu-baseline"
 # 1. the driver's protocol, three times (the line the round is judged on), and the long form
 for i in 1 2 3; do python3 $R/bench.py --steps 20 --warmup 5 $FF 2>> $O/ff_stderr.txt | tail -1 > $O/ff_bench_line_20_5_run$i.json; done
 python3 $R/bench.py $FF 2>> $O/ff_stderr.txt | tail -1 > $O/ff_bench_line_200_20.json
 # 2. per-kernel statistics of the FF step and of the whole default bench
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ff_raw -- python3 $R/bench.py $FF > /dev/null 2>&1
 cp $(ls $O/ff_raw/*/*kernel_stats.csv | head -1) $O/ff_kernel_stats.csv; rm -rf $O/ff_raw
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/full_raw -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/full_raw -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > /dev/null 2>&1
 cp $(ls $O/full_raw/*/*kernel_stats.csv | head -1) $O/bench_kernel_stats.csv; rm -rf $O/full_raw
 # 3. HBM traffic: the GEMM launches of the FF step, then every secondary section
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_f -- python3 $R/bench.py --steps 20 --warmup 3 $FF > /dev/null 2>&1

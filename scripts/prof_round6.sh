@@ -1,7 +1,7 @@
 # Round-6 evidence (run on the GPU box): bash scripts/prof_round6.sh <tag>   -> gpurun_out/<tag>/
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$1; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
-FF="--world-utts 0 --bilstm-utts 0 --no-cpu-baseline --trainer-utts 0"
+FF="--full --world-utts 0 --bilstm-utts 0 --no-cpu-baseline --trainer-utts 0"
 # 1. the driver's protocol, three times (the line the round is judged on)
 for i in 1 2 3; do python3 $R/bench.py --steps 20 --warmup 5 $FF 2>> $O/ff_stderr.txt | tail -1 > $O/ff_bench_line_20_5_run$i.json; done
 # 2. per-kernel statistics of the FF step (the same command under the profiler)
@@ -42,7 +42,7 @@ for what in analysis synthesis mlpg; do
   python3 $R/scripts/trace_tail.py /tmp/tr > $O/single_call_${what}_timeline.txt 2>&1
 done
 # 6. the whole default bench (what the driver runs), its line and its kernel statistics
-python3 $R/bench.py --steps 20 --warmup 5 2>> $O/bench_stderr.txt | tail -1 > $O/bench_line_20_5.json
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/full_raw -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline > /dev/null 2>&1
+python3 $R/bench.py --full --steps 20 --warmup 5 2>> $O/bench_stderr.txt | tail -1 > $O/bench_line_20_5.json
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/full_raw -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > /dev/null 2>&1
 cp $(ls $O/full_raw/*/*kernel_stats.csv | head -1) $O/bench_kernel_stats.csv; rm -rf $O/full_raw
 ls -la $O

@@ -1,8 +1,8 @@
 """Writes profiles/<tag>_{bench_line.json, ff_kernel_stats.csv, bench_kernel_stats.csv, summary.md}
 from a gpurun_out/<tag>/ directory holding
-    bench_line.json             python3 bench.py
-    ff/ff_kernel_stats.csv      rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --world-utts 0 --bilstm-utts 0 --no-cpu-baseline
-    full/full_kernel_stats.csv  rocprofv3 ... -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline
+    bench_line.json             python3 bench.py --full
+    ff/ff_kernel_stats.csv      rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --world-utts 0 --bilstm-utts 0 --no-cpu-baseline
+    full/full_kernel_stats.csv  rocprofv3 ... -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline
 usage: python3 scripts/profile_summary.py <tag> [title]"""
 import csv
 import json
@@ -25,11 +25,11 @@ gt, gc = sum(float(r["TotalDurationNs"]) for r in g), sum(int(r["Calls"]) for r 
 w, w48, ml, bl, bg, re_ = d["world"], d["world_48k"], d["mlpg"], d["bilstm"], d["bigru"], d["resident_epoch"]
 rf = d["roofline"]
 o = ["# Profile set {}: {}\n".format(tag, title),
-     "`python3 bench.py` (defaults: 1 GPU, 200 steps, 20 warm-up) on an MI355X, line in `{}_bench_line.json`:\n".format(tag),
+     "`python3 bench.py --full` (defaults: 1 GPU, 200 steps, 20 warm-up) on an MI355X, line in `{}_bench_line.json`:\n".format(tag),
      "| item | value |\n|---|---|",
      "| FF 425-512-512-187 train step, 32 utterances / step | %.3f ms -> %.1f M valid frames/s |" % (d["ms_per_step"], d["value"] / 1e6),
      "| fp32-MFMA GEMMs of one step (8 launches, events on the launch stream, live in bench.py) | %.3f ms, avg %.1f us per launch, %.1f TFLOP/s = %.1f %% of 157.3 |" % (rf["gemm_ms_per_step"], rf["avg_launch_us"], rf["achieved"], 100 * rf["frac"]),
-     "| the same launches in `rocprofv3 --kernel-trace --stats` (`%s_ff_kernel_stats.csv`: `python3 bench.py --world-utts 0 --bilstm-utts 0 --no-cpu-baseline`) | %d GEMM launches, avg %.1f us (kernel time only; the live figure includes the gaps between the launches) |" % (tag, gc, gt / gc / 1e3),
+     "| the same launches in `rocprofv3 --kernel-trace --stats` (`%s_ff_kernel_stats.csv`: `python3 bench.py --full --world-utts 0 --bilstm-utts 0 --no-cpu-baseline`) | %d GEMM launches, avg %.1f us (kernel time only; the live figure includes the gaps between the launches) |" % (tag, gc, gt / gc / 1e3),
      "| HBM bytes per GEMM launch (PMC FETCH_SIZE x 2 + WRITE_SIZE, `%s_gemm_traffic.json`) | %.0f MB |" % (tag, rf["traffic"] / 1e6),
      "| CPU baseline (torch reference stack, %d threads) | %.0f valid frames/s |" % (d["cpu_baseline"]["cores"], d["cpu_baseline"]["value"]),
      "| WORLD analysis, %d utterances = %.0f s of 16 kHz audio | %.2f ms, RTF %.2e (C oracle, 1 core: %.3f) |" % (w["utterances"], w["audio_seconds"], w["analysis_ms"], w["analysis_rtf"], w["cpu_baseline"]["analysis_rtf"]),
@@ -47,7 +47,7 @@ o = ["# Profile set {}: {}\n".format(tag, title),
      "\nFF-only run, top kernels (`%s_ff_kernel_stats.csv`):\n\n| kernel | calls | total ms | avg us | %% |\n|---|---|---|---|---|" % tag]
 for r in ff[:9]:
     o.append("| `%s` | %s | %.2f | %.2f | %s |" % (r["Name"].split("(")[0][:70], r["Calls"], float(r["TotalDurationNs"]) / 1e6, float(r["AverageNs"]) / 1e3, r["Percentage"]))
-o.append("\n`rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline` (`%s_bench_kernel_stats.csv`; all sections of the bench in one process: FF loop, 16 kHz and 48 kHz WORLD passes, MLPG, BiLSTM / BiGRU steps, resident epoch):\n\n| kernel | calls | total ms | avg us | %% |\n|---|---|---|---|---|" % tag)
+o.append("\n`rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline` (`%s_bench_kernel_stats.csv`; all sections of the bench in one process: FF loop, 16 kHz and 48 kHz WORLD passes, MLPG, BiLSTM / BiGRU steps, resident epoch):\n\n| kernel | calls | total ms | avg us | %% |\n|---|---|---|---|---|" % tag)
 for r in full[:32]:
     o.append("| `%s` | %s | %.2f | %.2f | %s |" % (r["Name"].split("(")[0][:70], r["Calls"], float(r["TotalDurationNs"]) / 1e6, float(r["AverageNs"]) / 1e3, r["Percentage"]))
 open(os.path.join(dst, tag + "_summary.md"), "w").write("\n".join(o) + "\n")

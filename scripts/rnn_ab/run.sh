@@ -10,7 +10,7 @@ FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -ffp-cont
 hipcc $FLAGS -c /tmp/old_tree/idiaptts_amd/csrc/lstm.hip -o /tmp/lstm_old.o || exit 1
 hipcc $FLAGS -c /tmp/old_tree/idiaptts_amd/csrc/gru.hip -o /tmp/gru_old.o || exit 1
 OBJS=$(ls $L/*.o | grep -v "/lstm.o\|/gru.o")
-run() { python3 $R/bench.py --steps 5 --warmup 2 --world-utts 0 --no-cpu-baseline 2>/dev/null | python3 -c "
+run() { python3 $R/bench.py --steps 5 --warmup 2 --full --world-utts 0 --no-cpu-baseline 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$1', 'bilstm %.2f ms  bigru %.2f ms  ff %.4f ms' % (d['bilstm']['ms_per_step'], d['bigru']['ms_per_step'], d['ms_per_step']))"; }

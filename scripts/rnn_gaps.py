@@ -1,4 +1,4 @@
-"""GPU busy time inside the BiLSTM steps of a rocprofv3 kernel trace of `bench.py --world-utts 0`: span from
+"""GPU busy time inside the BiLSTM steps of a rocprofv3 kernel trace of `bench.py --full --world-utts 0`: span from
 the first to the last LSTM recurrence kernel, time with at least one kernel running, the largest idle gaps.
 usage: python3 scripts/rnn_gaps.py <dir with *kernel_trace.csv>"""
 import csv

@@ -1,8 +1,9 @@
 # Per-kernel time of one WORLD analysis + synthesis pass at the bench size (run on the GPU box):
 # bash scripts/world_prof.sh [fs] [utts]
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-rm -rf /tmp/wp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/wp -- python3 $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 2 --bilstm-utts 0 --no-cpu-baseline --world-utts ${2:-256} --world-fs ${1:-16000} > /tmp/wp.log 2>&1
-python3 $GRAFT_REPO_ROOT/scripts/world_timeline.py /tmp/wp; python3 - <<'PY'
+rm -rf /tmp/wp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/wp -- python3 $R/bench.py --steps 5 --warmup 2 --full --bilstm-utts 0 --no-cpu-baseline --world-utts ${2:-256} --world-fs ${1:-16000} > /tmp/wp.log 2>&1
+python3 $R/scripts/world_timeline.py /tmp/wp; python3 - <<'PY'
 import csv, glob, collections
 f = glob.glob('/tmp/wp/**/*kernel_trace.csv', recursive=True)[0]
 rows = list(csv.DictReader(open(f)))

@@ -173,7 +173,7 @@ def test_bench_starts_its_own_ranks(gpu):
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2",
-                          "--share-gpu", "--steps", "3", "--warmup", "1", "--world-utts", "4",
+                          "--share-gpu", "--steps", "3", "--warmup", "1", "--full", "--world-utts", "4",
                           "--bilstm-utts", "4", "--no-cpu-baseline"], env=env,
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
@@ -196,7 +196,7 @@ def test_bench_with_four_ranks_on_one_device(gpu):
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--share-gpu",
-                          "--steps", "2", "--warmup", "1", "--ramp-steps", "0", "--utts-per-gpu", "2",
+                          "--steps", "2", "--warmup", "1", "--ramp-steps", "0", "--utts-per-gpu", "2", "--full",
                           "--world-utts", "0", "--bilstm-utts", "8", "--trainer-utts", "0", "--no-cpu-baseline"],
                          env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1500)
     assert res.returncode == 0, res.stderr[-3000:]
