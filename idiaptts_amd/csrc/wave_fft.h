@@ -456,7 +456,10 @@ __device__ __forceinline__ void irfft(double2 (&z)[R], const double2 xh, const P
       const double orr = dr * w.x - di * w.y, oi = dr * w.y + di * w.x;
       const double2 zk = make_double2(er - oi, ei + orr);
       const double2 zj = make_double2(er + oi, -ei + orr);
-      z[q] = (lo || (q == R / 2 && l == 0)) ? zk : zj;      // m = 32 R pairs with itself: the "k" form
+      // m = 32 R pairs with itself: the "k" form (selected per component: a select of the whole pair can go
+      // through scratch memory)
+      const bool use_k = lo || (q == R / 2 && l == 0);
+      z[q] = make_double2(use_k ? zk.x : zj.x, use_k ? zk.y : zj.y);
     }
     __builtin_amdgcn_sched_barrier(0);
   }

@@ -82,6 +82,9 @@ _SIGNATURES = {
     "itts_stft_mel": (c_int, [_P, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), c_int, c_int, c_int, c_int,
                               _P, _P, _P, c_int, _P, c_int64, _P]),
     "itts_mel_project": (c_int, [_P, c_int64, c_int, c_int64, _P, _P, c_int, _P, c_int64, _P]),
+    "itts_griffinlim": (c_int, [_P, _P, _P, _P, POINTER(c_int64), c_int, c_int, c_int, c_int, _P, c_int, c_double,
+                                c_int, _P, _P]),
+    "itts_griffinlim_tile_frames": (c_int, [c_int, c_int]),
     "itts_batch_pad_gather_f32": (c_int, [_P, c_int64, c_int64, _P, _P, c_int, c_int64, c_int, c_int, _P, c_int64, _P,
                                           _P, c_int64, _P, _P]),
     "itts_batch_pack_rows_f32": (c_int, [_P, c_int64, _P, _P, c_int, c_int64, c_int, c_int, _P, c_int64, c_int,

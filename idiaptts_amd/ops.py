@@ -243,6 +243,31 @@ def mel_filterbank(x, x_off, f_off, first, n_fft, hop, pad, window, mel_tab, mel
     return out
 
 
+def griffinlim(S, angles, f_off, n_fft, hop, pad, window, n_iter, momentum):
+    """librosa.griffinlim on the amplitude spectra S [f_off[-1], n_fft // 2 + 1] (float32 or float64) of utterances
+    stored back to back, from the initial phases `angles` (complex64 / complex128 of S's precision, same shape;
+    overwritten).  pad: "reflect" or "constant"; window: float64 [n_fft] on the device.  Returns the waveforms
+    back to back, hop (T_u - 1) samples each, in S's dtype."""
+    L = _lib.load()
+    f64 = S.dtype == torch.float64
+    _need(S, torch.float64 if f64 else torch.float32, "S")
+    _need(angles, torch.complex128 if f64 else torch.complex64, "angles")
+    _need(window, torch.float64, "window")
+    K = n_fft // 2 + 1
+    rows = int(f_off[-1])
+    if tuple(S.shape) != (rows, K) or tuple(angles.shape) != (rows, K) or not (S.is_contiguous()
+                                                                              and angles.is_contiguous()):
+        raise ValueError("S and angles must be contiguous [{}, {}]".format(rows, K))
+    ang_b = torch.empty_like(angles)
+    tprev = torch.empty_like(angles)
+    y = torch.empty(sum((b - a - 1) * int(hop) for a, b in zip(f_off[:-1], f_off[1:])), dtype=S.dtype,
+                    device=S.device)
+    _lib.check(L.itts_griffinlim(_ptr(S), _ptr(angles), _ptr(ang_b), _ptr(tprev), _lib.offsets_array(f_off),
+                                 len(f_off) - 1, int(n_fft), int(hop), STFT_PAD[pad], _ptr(window), int(n_iter),
+                                 float(momentum), int(f64), _ptr(y), _stream()), "itts_griffinlim")
+    return y
+
+
 def mel_project(amp, mel_tab, mel_w, n_mels, out=None):
     """The mel projection of a given amplitude spectrum amp [T, K] float64 -> float32 [T, n_mels]."""
     L = _lib.load()

@@ -1,4 +1,5 @@
-"""Synthesiser.run_world_synth with the reference's interface (idiaptts/src/Synthesiser.py:38-106).
+"""Synthesiser.run_world_synth and run_griffin_lim with the reference's interface (idiaptts/src/Synthesiser.py:38-106,
+:320-351).
 
 The reference walks the utterances one by one (decode_sp -> world_features_to_raw -> write);
 here all utterances of the call are decoded (mgc2sp), aperiodicity-decoded and synthesised by
@@ -6,12 +7,14 @@ single batched GPU launches, then written. `synth_world_features` is the name BA
 north-star uses for this entry point; it is provided as an alias.
 """
 import logging
+import math
 import os
 from typing import Dict
 
 import numpy as np
 import scipy.io.wavfile
 
+from .. import world as _world
 from .data_preparation.audio.AudioProcessing import AudioProcessing
 from .data_preparation.world.WorldFeatLabelGen import WorldFeatLabelGen
 
@@ -20,6 +23,10 @@ def _has(hparams, name):
     if hasattr(hparams, "has_value"):
         return hparams.has_value(name)
     return getattr(hparams, name, None) is not None
+
+
+def _get(hparams, name, default):
+    return getattr(hparams, name) if _has(hparams, name) else default
 
 
 class Synthesiser(object):
@@ -67,6 +74,53 @@ class Synthesiser(object):
             return dict(zip(ids, waveforms))
 
     synth_world_features = run_world_synth
+
+    @staticmethod
+    def run_griffin_lim_on_log(synth_output: Dict[str, np.ndarray], *args, **kwargs):
+        """reference :320-322: Griffin-Lim of dB amplitude spectra (db_to_amp first)."""
+        synth_output = {k: AudioProcessing.db_to_amp(v) for k, v in synth_output.items()}
+        return Synthesiser.run_griffin_lim(synth_output, *args, **kwargs)
+
+    @staticmethod
+    def run_griffin_lim(synth_output: Dict[str, np.ndarray], hparams, epoch: int = None, step: int = None,
+                        use_model_name: bool = True, return_waveforms: bool = False):
+        """Griffin-Lim of every amplitude spectrum [T, K] in synth_output (id -> spectrum), written to
+        <basename>[_<model_name>]<synth_file_suffix>.<synth_ext> (reference :324-351).  The reference runs
+        librosa.griffinlim(output.T ** griffin_lim_power, n_iter=griffin_lim_iters, hop_length, win_length) per
+        utterance; here all utterances of the call run as one batch on the Griffin-Lim kernel (the random initial
+        phases are drawn from np.random in the same order).  Samples are written as raw_to_file does -- times
+        2 ** (bit_depth - 1), truncated to int16 -- but clipped to the int16 range first, where the reference's
+        cast is undefined.  Only wav output is supported."""
+        if getattr(hparams, "synth_ext", "wav").lower() != "wav":
+            raise NotImplementedError("Only wav output is supported (pydub is out of scope).")
+        fs = hparams.synth_fs
+        hop_length = int(hparams.hop_size_ms / 1000. * fs)
+        win_length_ms = getattr(hparams, "win_length_ms", None)
+        win_length = None if win_length_ms is None else int(win_length_ms / 1000. * fs)
+        power = _get(hparams, "griffin_lim_power", 1.2)
+        ids = list(synth_output.keys())
+        spectra = [np.asarray(synth_output[i]) ** power for i in ids]
+        waveforms = _world.griffinlim_batch(spectra, n_iter=_get(hparams, "griffin_lim_iters", 60),
+                                            hop_length=hop_length, win_length=win_length)
+        preemphasis = _get(hparams, "preemphasis", 0.0)
+        if preemphasis != 0:
+            waveforms = [AudioProcessing.depreemphasis(raw, preemphasis) for raw in waveforms]
+        save_dir = Synthesiser._get_synth_dir(hparams, use_model_name, epoch=epoch, step=step)
+        bit_depth = _get(hparams, "bit_depth", 16)
+        for id_name, raw in zip(ids, waveforms):
+            file_name = "{}{}{}.{}".format(os.path.basename(id_name).rsplit('.', 1)[0],
+                                           "_" + hparams.model_name if use_model_name else "",
+                                           getattr(hparams, "synth_file_suffix", ""), hparams.synth_ext)
+            Synthesiser.raw_to_file(os.path.join(save_dir, file_name), raw, fs, bit_depth)
+        if return_waveforms:
+            return dict(zip(ids, waveforms))
+
+    @staticmethod
+    def raw_to_file(file_path, raw, fs, bit_depth=16):
+        """reference :181-201 for wav: raw * 2 ** (bit_depth - 1) truncated to int16 (clipped to its range first)."""
+        logging.info("Save {} from raw waveform.".format(file_path))
+        pcm = np.clip(np.asarray(raw) * math.pow(2, bit_depth - 1), -32768, 32767).astype(np.int16)
+        scipy.io.wavfile.write(file_path, fs, pcm)
 
     @staticmethod
     def _get_synth_dir(hparams, use_model_name: bool = True, epoch: int = None, step: int = None):

@@ -2,7 +2,8 @@
 (idiaptts/src/data_preparation/audio/AudioProcessing.py); pysptk / pyworld calls are replaced
 by the HIP kernels behind libidiaptts_amd.so.  librosa's STFT features -- the amplitude spectrum and mel filter
 banks (librosa_extract_amp_sp, extract_mfbanks) -- run on the STFT kernel (csrc/stft.hip); the way back from
-mel filter banks (librosa's NNLS inversion) and Griffin-Lim are out of scope."""
+mel filter banks (librosa's NNLS inversion) is out of scope.  Griffin-Lim (amp_sp_to_raw, librosa.griffinlim) runs
+on the Griffin-Lim kernel (csrc/griffinlim.hip), one launch per iteration."""
 import logging
 import os
 
@@ -258,6 +259,16 @@ class AudioProcessing:
     def db_to_amp(log_amp_sp):
         """reference :338-339"""
         return np.power(10.0, log_amp_sp * 0.05)
+
+    @staticmethod
+    def amp_sp_to_raw(amp_sp: np.array, fs: int, hop_size_ms: int = 5, preemphasis: float = 0.0) -> np.array:
+        """Griffin-Lim of the amplitude spectrum [T, K] (reference :279-289): librosa.griffinlim(amp_sp.T * sqrt(K),
+        hop_length=int(fs * hop_size_ms / 1000.)) with librosa's defaults (32 iterations, momentum 0.99, random
+        initial phases from np.random), then depreemphasis.  The amplitude spectrum has to carry the pitch: one
+        extracted with pitch-aligned windows (as WORLD does) does not work."""
+        amp_sp = np.asarray(amp_sp)
+        raw = _world.griffinlim(amp_sp.T * np.sqrt(amp_sp.shape[1]), hop_length=int(fs * hop_size_ms / 1000.))
+        return AudioProcessing.depreemphasis(raw, preemphasis)
 
     @staticmethod
     def decode_sp(coded_sp: np.array, sp_type: str = "mcep", fs: int = None, alpha: float = None,

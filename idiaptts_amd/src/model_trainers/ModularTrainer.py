@@ -558,7 +558,8 @@ class ModularTrainer(object):
 
     # ------------------------------------------------------------------------------ waveforms
     def gen_waveform(self, id_list, data, hparams, use_model_name=True, has_deltas=False):
-        """reference :1014-1085; only the WORLD vocoder is on the accelerated path."""
+        """reference :1014-1085; the WORLD and Griffin-Lim ("GL", "GL_on_log") vocoders are on the accelerated
+        path."""
         if type(next(iter(data.values()))) is dict:
             if hparams.has_value("synth_feature_names"):
                 feature_names = hparams.synth_feature_names
@@ -568,6 +569,12 @@ class ModularTrainer(object):
                 feature_names = list(next(iter(data.values())).keys())
             data = {id_name: np.concatenate([features[n] for n in feature_names], axis=1)
                     for id_name, features in data.items()}
+        if hparams.synth_vocoder == "GL_on_log":
+            Synthesiser.run_griffin_lim_on_log(data, hparams, epoch=self.total_epoch, step=self.total_steps)
+            return
+        if hparams.synth_vocoder == "GL":
+            Synthesiser.run_griffin_lim(data, hparams, epoch=self.total_epoch, step=self.total_steps)
+            return
         if hparams.synth_vocoder != "WORLD":
             raise NotImplementedError("Unknown vocoder type {}.".format(hparams.synth_vocoder))
         return Synthesiser.run_world_synth(data, hparams, use_model_name=use_model_name,

@@ -2,6 +2,7 @@
 
 analysis : wav(s) -> DIO -> StoneMask -> CheapTrick (+ fused SPTK mcep) / D4C (+ coded bap)
 STFT     : wav(s) -> amplitude spectrum / its dB form / mel filter banks (librosa's STFT features, stft.hip)
+Griffin-Lim: amplitude spectra -> waveforms (librosa.griffinlim, griffinlim.hip)
 synthesis: (f0, sp, ap) -> WORLD synthesis -> float32 (+ de-pre-emphasis)
 Utterances are concatenated and processed by single launches; only the small per-frame features
 (f0, mcep, bap) travel back to the host unless the spectral envelope is asked for.
@@ -250,6 +251,103 @@ def mel_project(amp_sp, fs, n_fft, n_mels):
     """mel_basis @ amp_sp.T, transposed, float32, for a given amplitude spectrum [T, n_fft // 2 + 1] on the device."""
     tab, w = _stft_table(("mel", fs, n_fft, n_mels), lambda: mel_tables(fs, n_fft, n_mels), amp_sp.device)
     return ops.mel_project(amp_sp, tab, w, n_mels)
+
+
+# ------------------------------------------------------------------------------------------ Griffin-Lim
+def griffinlim_args(n_bins, n_frames, hop_length=None, win_length=None, window="hann", center=True, length=None,
+                    pad_mode="reflect", momentum=0.99, init="random", random_state=None):
+    """librosa.griffinlim's argument handling for spectra of n_bins bins and the given frame counts, restricted to
+    what griffinlim.hip covers; raises before any device work.  Returns (n_fft, hop_length, win_length, rng)."""
+    n_fft = 2 * (int(n_bins) - 1)
+    if n_fft not in (1024, 2048):
+        raise NotImplementedError("Griffin-Lim n_fft={} is not implemented (1024, 2048).".format(n_fft))
+    if window != "hann":
+        raise NotImplementedError("Griffin-Lim window {!r} is not implemented ('hann').".format(window))
+    if not center:
+        raise NotImplementedError("Griffin-Lim center=False is not implemented.")
+    if length is not None:
+        raise NotImplementedError("Griffin-Lim length={} is not implemented (None).".format(length))
+    check_stft_args(n_fft, window, pad_mode)
+    win_length = n_fft if win_length is None else int(win_length)
+    hop_length = win_length // 4 if hop_length is None else int(hop_length)
+    if not 0 < win_length <= n_fft:
+        raise ValueError("win_length={} must be in (0, n_fft={}].".format(win_length, n_fft))
+    if not 0 < hop_length <= n_fft // 2:
+        raise NotImplementedError("Griffin-Lim hop_length={} is not implemented (1 .. n_fft / 2 = {})."
+                                  .format(hop_length, n_fft // 2))
+    if momentum > 1:
+        import warnings
+        warnings.warn("Momentum {} > 1 can be unstable. Proceed with caution.".format(momentum))
+    elif momentum < 0:
+        raise ValueError("griffinlim() called with momentum={} < 0".format(momentum))
+    if init not in ("random", None):
+        raise ValueError("init={} must either None or 'random'".format(init))
+    for t in n_frames:
+        if t < 2:
+            raise ValueError("Griffin-Lim needs at least 2 frames, got {} (the signal would be empty).".format(t))
+    if random_state is None:
+        rng = np.random
+    elif isinstance(random_state, (int, np.integer)) and not isinstance(random_state, bool):
+        rng = np.random.RandomState(seed=int(random_state))
+    elif isinstance(random_state, np.random.RandomState):
+        rng = random_state
+    else:
+        raise ValueError("Unsupported random_state={!r}".format(random_state))
+    return n_fft, hop_length, win_length, rng
+
+
+def griffinlim_init_phases(shapes, init, rng, dtype=np.complex128):
+    """The initial phases of librosa.griffinlim, [T, K] per spectrum of shape (T, K): exp(2j pi rng.rand(K, T)),
+    drawn in librosa's [K, T] order, one spectrum after the other from the same rng, stored as `dtype`; all ones
+    for init=None."""
+    out = []
+    for T, K in shapes:
+        if init is None:
+            out.append(np.ones((T, K), dtype=dtype))
+        else:
+            out.append(np.exp(2j * np.pi * rng.rand(K, T)).astype(dtype).T)
+    return out
+
+
+def griffinlim_batch(spectra, n_iter=32, hop_length=None, win_length=None, window="hann", center=True, length=None,
+                     pad_mode="reflect", momentum=0.99, init="random", random_state=None, device=None):
+    """librosa.griffinlim of every amplitude spectrum in `spectra` (list of [T_u, K] arrays: librosa's S
+    transposed) in one batched run of griffinlim.hip, one launch per iteration.  float32 spectra keep a complex64
+    phase state and give float32 waveforms, anything else float64.  The random initial phases are drawn utterance
+    by utterance in the given order from one rng (the reference's per-utterance loop with the same seed).
+    Returns one waveform of hop (T_u - 1) samples per spectrum."""
+    spectra = [np.asarray(sp) for sp in spectra]
+    if not spectra:
+        return []
+    if any(sp.ndim != 2 or sp.shape[1] != spectra[0].shape[1] for sp in spectra):
+        raise ValueError("spectra must be [T, K] arrays with the same K")
+    n_fft, hop, win_length, rng = griffinlim_args(spectra[0].shape[1], [sp.shape[0] for sp in spectra],
+                                                  hop_length, win_length, window, center, length, pad_mode,
+                                                  momentum, init, random_state)
+    n_iter = int(n_iter)
+    if n_iter < 0:
+        raise ValueError("n_iter={} must not be negative".format(n_iter))
+    f32 = all(sp.dtype in (np.float16, np.float32) for sp in spectra)
+    real, cplx = (np.float32, np.complex64) if f32 else (np.float64, np.complex128)
+    phases = griffinlim_init_phases([sp.shape for sp in spectra], init, rng, cplx)
+    dev = _device(device)
+    f_off = offsets([sp.shape[0] for sp in spectra])
+    S = torch.from_numpy(np.ascontiguousarray(np.concatenate(spectra), dtype=real)).to(dev)
+    angles = torch.from_numpy(np.ascontiguousarray(np.concatenate(phases))).to(dev)
+    (win,) = _stft_table(("window", n_fft, win_length), lambda: (stft_window(n_fft, win_length),), dev)
+    y = ops.griffinlim(S, angles, f_off, n_fft, hop, pad_mode, win, n_iter, momentum).cpu().numpy()
+    y_off = offsets([hop * (sp.shape[0] - 1) for sp in spectra])
+    return [y[y_off[u]:y_off[u + 1]] for u in range(len(spectra))]
+
+
+def griffinlim(S, n_iter=32, hop_length=None, win_length=None, window="hann", center=True, length=None,
+               pad_mode="reflect", momentum=0.99, init="random", random_state=None, device=None):
+    """librosa.griffinlim(S, ...) for one amplitude spectrum S [K, T] (librosa's orientation), on the GPU."""
+    S = np.asarray(S)
+    if S.ndim != 2:
+        raise ValueError("S must be [n_fft // 2 + 1, T]")
+    return griffinlim_batch([S.T], n_iter, hop_length, win_length, window, center, length, pad_mode, momentum,
+                            init, random_state, device)[0]
 
 
 def _extract_cmp_stft(x, x_off, fs, hop_ms, n_fft, sp_type, n_mels, win_length_ms, world_streams,

@@ -262,6 +262,21 @@ int itts_stft_mel(const double* d_x, const int64_t* h_x_off, const int64_t* h_f_
 int itts_mel_project(const double* d_amp, int64_t T, int K, int64_t ld_amp, const int* d_mel_tab,
                      const float* d_mel_w, int n_mels, float* d_out, int64_t ld_out, void* stream);
 
+/* Griffin-Lim (librosa.griffinlim as AudioProcessing.amp_sp_to_raw, AudioProcessing.py:279-289, and
+ * Synthesiser.run_griffin_lim / run_griffin_lim_on_log, Synthesiser.py:320-351, call it): n_iter iterations of
+ * angles <- phase(stft(istft(S * angles)) - momentum / (1 + momentum) * previous stft) on the amplitude spectra
+ * d_S [T, n_fft/2+1] of utterances stored back to back (rows h_f_off [U+1], h_f_off[0] = 0, >= 2 frames each),
+ * then d_y = istft(S * angles), hop (T_u - 1) samples per utterance, back to back.  is_f64 = 0: d_S float32,
+ * the phase state complex64 and d_y float32; 1: double / complex128 / double.  d_ang_a holds the initial
+ * phases (overwritten); d_ang_b and d_tprev are workspaces of the same size.  d_window [n_fft]: the window
+ * table (as for itts_stft); n_fft 1024 or 2048, 1 <= hop <= n_fft/2, pad_mode 1 (reflect) or 2 (constant) of
+ * the centre padding.  One launch per iteration; bit-identical from run to run and whatever else is in the
+ * batch.  itts_griffinlim_tile_frames: the frames per workgroup tile for (n_fft, hop), 0 when not covered. */
+int itts_griffinlim(const void* d_S, void* d_ang_a, void* d_ang_b, void* d_tprev, const int64_t* h_f_off,
+                    int n_utts, int n_fft, int hop, int pad_mode, const double* d_window, int n_iter,
+                    double momentum, int is_f64, void* d_y, void* stream);
+int itts_griffinlim_tile_frames(int n_fft, int hop);
+
 /* interpolate_lin (misc/utils.py:40-86) on float32 contours stored back to back: frames <= 0 are
  * gaps; bit-exact including the reference's quirks (target reached one frame early; a gap whose
  * next voiced frame is the last frame is filled, with that frame, by the last voiced value).
