@@ -25,8 +25,6 @@
 
 namespace itts {
 
-static inline int aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // padded position r -> (b, t); the entry points keep n_utts * t_max below 2^31, so 32-bit division does
 __device__ __forceinline__ void split_row(int64_t r, int64_t t_max, int n_utts, int batch_first, int& b, int64_t& t) {
   const uint32_t r32 = (uint32_t)r;

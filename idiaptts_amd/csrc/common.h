@@ -108,4 +108,7 @@ class ScratchScope {
 
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// 16-byte aligned: with a pitch that is a multiple of 4 floats, rows may be read as float4
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 }  // namespace itts

@@ -1,7 +1,8 @@
 // Conv1d groups of RNNDyn (rnn_dyn/CNNWrapper.py -> torch.nn.Conv1d + act) on gfx950: a 1-D
-// convolution over the time axis of a padded batch, computed as an implicit GEMM on
-// v_mfma_f32_32x32x2_f32 (exact fp32, like the dense layers of nn.hip).  The im2col matrix is never
-// written: every K step reads one row shift of the activations straight from global memory.
+// convolution over the time axis of a padded batch, computed as an implicit GEMM on the
+// register-staged fp32-MFMA GEMM of the dense layers (gemm_staged.h).  The im2col matrix is never
+// written: every K step reads one row shift of the activations straight from global memory (the
+// operand loads of Im2colLoader; everything else is the shared body).
 //
 // Notation: activations are rows; row (b, t) of a tensor with T time steps sits at b * sb + t * st
 // (batch_first: sb = T, st = 1; time-major: sb = 1, st = B).  Stride 1, T_out = T_in + 2 pad -
@@ -19,26 +20,18 @@
 //                 chunks of whole K steps, one slab each; a fixed-order reduction sums the slabs and
 //                 writes dw back in [Cout][Cin][Kw] (bit-identical run to run).
 //
-// Tile: 128 x (64 * TN) output per 256-thread workgroup, 4 waves as 2 x 2, each wave 2 x TN MFMA
-// tiles of 32 x 32; K step 32, LDS double buffered (73.7 KB -> 2 workgroups per CU), global loads
-// of tile k+1 in flight during the MFMAs of tile k.  LDS layouts and the K permutation are those of
-// nn.hip's gemm_f32_kernel (row form [out][36], col form [k][out + 4], one ds_read_b128 per lane
-// feeds four MFMAs).
+// Tile: 128 x (64 * TN) output per 256-thread workgroup, LDS double buffered (73.7 KB -> 2
+// workgroups per CU); forward and input gradient take both operands in row form, the weight
+// gradient both in col form.
 #include <algorithm>
 
 #include "common.h"
+#include "gemm_staged.h"
 
 namespace itts {
 namespace conv {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int BM = 128, BK = 32;
-constexpr int LD_ROW = BK + 4;
-constexpr int TILE_FLOATS = 128 * LD_ROW;  // 4608 >= 32 * 132
-
 enum { MODE_FWD = 0, MODE_WGRAD = 1 };
-enum { EPI_STORE = 0, EPI_BIAS_ACT = 1, EPI_DACT = 2 };
 
 // Unsigned division by a runtime constant for n < 2^31: q = (umulhi(n, mul) + n) >> shr.
 struct FastDiv {
@@ -62,45 +55,11 @@ struct Geo {
   FastDiv div_T, div_Cp;                  // by T_out, by Cp
 };
 
-struct ConvArgs {
-  const float* A;   // FWD: x (implicit im2col rows); WGRAD: dz (col form [k = m][out = n])
-  int64_t lda;
-  const float* Bm;  // FWD: packed weights [N][K] (row form); WGRAD: x (implicit im2col, col form)
-  int64_t ldb;
-  float* C;
-  int64_t ldc;
-  int64_t M;        // output rows (FWD: B * T_out; WGRAD: Cout)
-  int N;            // output cols (FWD: Cout; WGRAD: Kw * Cp)
-  int64_t K;        // reduction (FWD: Kw * Cp; WGRAD: B * T_out)
-  const float* bias;
-  const float* aux;
-  int64_t ldaux;
-  int act;
-  int64_t kchunk;
-  int64_t slab_stride;
-  float* bias_part;   // WGRAD: [slab][Cout] column sums of dz, or NULL
+// FWD: A = x (implicit im2col rows), B = packed weights [N][K] (row form).
+// WGRAD: A = dz (col form [k = m][out = n]), B = x (implicit im2col, col form [k = m][out = kk]).
+struct ConvArgs : GemmArgs {
   Geo geo;
 };
-
-__device__ __forceinline__ float fast_tanhf(float z) {   // nn.hip's epilogue tanh, same arithmetic
-  const float a = fabsf(z);
-  const float z2 = z * z;
-  const float poly = z * (1.f + z2 * (-0.33333334f + z2 * (0.13333334f + z2 * (-0.053968254f +
-                                                                              z2 * 0.021869488f))));
-  const float e = __expf(2.f * a);
-  const float big = copysignf(1.f - 2.f * __builtin_amdgcn_rcpf(e + 1.f), z);
-  return a < 0.25f ? poly : big;
-}
-__device__ __forceinline__ float act_fwd(float z, int act) {
-  if (act == ITTS_ACT_TANH) return fast_tanhf(z);
-  if (act == ITTS_ACT_RELU) return z > 0.f ? z : 0.f;
-  return z;
-}
-__device__ __forceinline__ float act_grad_from_out(float y, int act) {
-  if (act == ITTS_ACT_TANH) return 1.f - y * y;
-  if (act == ITTS_ACT_RELU) return y > 0.f ? 1.f : 0.f;
-  return 1.f;
-}
 
 // 4 consecutive floats at p (valid address), lanes e with ok[e] false read as zero.
 template <bool VEC>
@@ -118,10 +77,9 @@ __device__ __forceinline__ float4 load4(const float* __restrict__ p, bool ok, in
 }
 
 // Physical row of logical output row m = b * T_out + t of a tensor with row strides (sb, st).
-__device__ __forceinline__ int64_t phys_row(uint32_t m, const Geo& g, int64_t sb, int64_t st, int* t_out) {
+__device__ __forceinline__ int64_t phys_row(uint32_t m, const Geo& g, int64_t sb, int64_t st) {
   const uint32_t b = fdiv(m, g.div_T);
   const int t = (int)(m - b * (uint32_t)g.T_out);
-  *t_out = t;
   return (int64_t)b * sb + (int64_t)t * st;
 }
 
@@ -138,210 +96,82 @@ __device__ __forceinline__ float4 im2col4(const float* __restrict__ x, int64_t l
   return load4<VEC>(x + row * ldx + (ok ? c : 0), ok, g.C - c);
 }
 
-template <int MODE, bool VEC, int NROWS>
-__device__ __forceinline__ void load_A(const ConvArgs& a, int64_t out0, int64_t k0, int64_t k_end,
-                                       float4 (&r)[NROWS / 32]) {
-  const int tid = threadIdx.x;
-  if (MODE == MODE_FWD) {   // row form: rows m (output rows), 4 reduction elements kk per thread
-    const int64_t kk = k0 + ((tid & 7) << 2);
-    const bool kk_ok = kk < k_end;
-    const uint32_t kq = kk_ok ? (uint32_t)kk : 0u;
-    const int tap = (int)fdiv(kq, a.geo.div_Cp);
-    const int c = (int)(kq - (uint32_t)tap * (uint32_t)a.geo.Cp);
-#pragma unroll
-    for (int i = 0; i < NROWS / 32; ++i) {
-      const int64_t m = out0 + ((tid + 256 * i) >> 3);
-      const bool m_ok = m < a.M;
-      r[i] = im2col4<VEC>(a.A, a.lda, a.geo, m_ok ? (uint32_t)m : 0u, m_ok, tap, c, kk_ok);
-    }
-  } else {                  // col form: dz rows m (reduction), 4 output channels n per thread
-#pragma unroll
-    for (int i = 0; i < NROWS / 32; ++i) {
-      const int idx = tid + 256 * i;
-      const int64_t m = k0 + idx / (NROWS / 4);
-      const int64_t n = out0 + ((idx % (NROWS / 4)) << 2);
-      const bool ok = m < k_end && n < a.M;
-      int t;
-      const int64_t row = ok ? phys_row((uint32_t)m, a.geo, a.geo.out_sb, a.geo.out_st, &t) : 0;
-      r[i] = load4<VEC>(a.A + row * a.lda + (ok ? n : 0), ok, (int)(a.M - n));
-    }
-  }
-}
+// The operand loads of the shared GEMM body (gemm_staged.h).
+template <int MODE, bool VEC>
+struct Im2colLoader {
+  const ConvArgs& a;
 
-template <int MODE, bool VEC, int NROWS>
-__device__ __forceinline__ void load_B(const ConvArgs& a, int64_t out0, int64_t k0, int64_t k_end,
-                                       float4 (&r)[NROWS / 32]) {
-  const int tid = threadIdx.x;
-  if (MODE == MODE_FWD) {   // packed weights, row form [N][K], K % 4 == 0, 16-byte aligned
-#pragma unroll
-    for (int i = 0; i < NROWS / 32; ++i) {
-      const int idx = tid + 256 * i;
-      const int64_t o = out0 + (idx >> 3), k = k0 + ((idx & 7) << 2);
-      const bool ok = o < a.N && k < k_end;
-      r[i] = load4<true>(a.Bm + (ok ? o * a.ldb + k : 0), ok, 4);
-    }
-  } else {                  // implicit im2col, col form [k = m][out = kk]
-#pragma unroll
-    for (int i = 0; i < NROWS / 32; ++i) {
-      const int idx = tid + 256 * i;
-      const int64_t m = k0 + idx / (NROWS / 4);
-      const int64_t kk = out0 + ((idx % (NROWS / 4)) << 2);
-      const bool kk_ok = kk < a.N;
+  template <int NROWS>
+  __device__ __forceinline__ void load_a(int64_t out0, int64_t k0, int64_t k_end, float4 (&r)[NROWS / 32]) const {
+    const int tid = threadIdx.x;
+    if (MODE == MODE_FWD) {   // row form: rows m (output rows), 4 reduction elements kk per thread
+      const int64_t kk = k0 + ((tid & 7) << 2);
+      const bool kk_ok = kk < k_end;
       const uint32_t kq = kk_ok ? (uint32_t)kk : 0u;
       const int tap = (int)fdiv(kq, a.geo.div_Cp);
       const int c = (int)(kq - (uint32_t)tap * (uint32_t)a.geo.Cp);
-      const bool m_ok = m < k_end;
-      r[i] = im2col4<VEC>(a.Bm, a.ldb, a.geo, m_ok ? (uint32_t)m : 0u, m_ok, tap, c, kk_ok);
+#pragma unroll
+      for (int i = 0; i < NROWS / 32; ++i) {
+        const int64_t m = out0 + ((tid + 256 * i) >> 3);
+        const bool m_ok = m < a.M;
+        r[i] = im2col4<VEC>(a.A, a.lda, a.geo, m_ok ? (uint32_t)m : 0u, m_ok, tap, c, kk_ok);
+      }
+    } else {                  // col form: dz rows m (reduction), 4 output channels n per thread
+#pragma unroll
+      for (int i = 0; i < NROWS / 32; ++i) {
+        const int idx = tid + 256 * i;
+        const int64_t m = k0 + idx / (NROWS / 4);
+        const int64_t n = out0 + ((idx % (NROWS / 4)) << 2);
+        const bool ok = m < k_end && n < a.M;
+        const int64_t row = ok ? phys_row((uint32_t)m, a.geo, a.geo.out_sb, a.geo.out_st) : 0;
+        r[i] = load4<VEC>(a.A + row * a.lda + (ok ? n : 0), ok, (int)(a.M - n));
+      }
     }
   }
-}
 
-template <bool ROWFORM, int NROWS>
-__device__ __forceinline__ void store_tile(float* __restrict__ S, const float4 (&r)[NROWS / 32]) {
-  const int tid = threadIdx.x;
+  template <int NROWS>
+  __device__ __forceinline__ void load_b(int64_t out0, int64_t k0, int64_t k_end, float4 (&r)[NROWS / 32]) const {
+    const int tid = threadIdx.x;
+    if (MODE == MODE_FWD) {   // packed weights, row form [N][K], K % 4 == 0, 16-byte aligned
 #pragma unroll
-  for (int i = 0; i < NROWS / 32; ++i) {
-    const int idx = tid + 256 * i;
-    int off;
-    if (ROWFORM)
-      off = (idx >> 3) * LD_ROW + ((idx & 7) << 2);
-    else
-      off = (idx / (NROWS / 4)) * (NROWS + 4) + ((idx % (NROWS / 4)) << 2);
-    *reinterpret_cast<float4*>(S + off) = r[i];
+      for (int i = 0; i < NROWS / 32; ++i) {
+        const int idx = tid + 256 * i;
+        const int64_t o = out0 + (idx >> 3), k = k0 + ((idx & 7) << 2);
+        const bool ok = o < a.N && k < k_end;
+        r[i] = load4<true>(a.B + (ok ? o * a.ldb + k : 0), ok, 4);
+      }
+    } else {                  // implicit im2col, col form [k = m][out = kk]
+#pragma unroll
+      for (int i = 0; i < NROWS / 32; ++i) {
+        const int idx = tid + 256 * i;
+        const int64_t m = k0 + idx / (NROWS / 4);
+        const int64_t kk = out0 + ((idx % (NROWS / 4)) << 2);
+        const bool kk_ok = kk < a.N;
+        const uint32_t kq = kk_ok ? (uint32_t)kk : 0u;
+        const int tap = (int)fdiv(kq, a.geo.div_Cp);
+        const int c = (int)(kq - (uint32_t)tap * (uint32_t)a.geo.Cp);
+        const bool m_ok = m < k_end;
+        r[i] = im2col4<VEC>(a.B, a.ldb, a.geo, m_ok ? (uint32_t)m : 0u, m_ok, tap, c, kk_ok);
+      }
+    }
   }
-}
+};
 
-template <bool ROWFORM, int NROWS>
-__device__ __forceinline__ float4 read_frag(const float* __restrict__ S, int o, int g, int lane) {
-  const int r = lane & 31, h = lane >> 5;
-  if (ROWFORM) {
-    return *reinterpret_cast<const float4*>(S + (o + r) * LD_ROW + g * 8 + 4 * h);
-  } else {
-    constexpr int LDC = NROWS + 4;
-    const float* p = S + (g * 8 + 4 * h) * LDC + o + r;
-    return make_float4(p[0], p[LDC], p[2 * LDC], p[3 * LDC]);
-  }
-}
-
+// The forward's output rows are those of the padded batch (geo.out_*); the weight gradient's are Cout.
 template <int MODE, int EPI, bool VEC, int TN>
 __global__ __launch_bounds__(256, 2) void conv1d_gemm_kernel(ConvArgs a) {
   constexpr bool ROW = MODE == MODE_FWD;   // both operands row form (FWD) or both col form (WGRAD)
-  constexpr int BNT = 64 * TN;
-  __shared__ __attribute__((aligned(16))) float lds[4 * TILE_FLOATS];
-
-  // XCD-aware tile order (as gemm_f32_kernel): blocks b and b + 8 share an XCD.
-  const int tiles_n = (a.N + BNT - 1) / BNT;
-  const int64_t tiles_m = (a.M + BM - 1) / BM;
-  const int64_t ntiles = tiles_m * tiles_n;
-  int64_t bid = blockIdx.x;
-  {
-    const int64_t q = ntiles / 8, r = ntiles % 8;
-    const int64_t xcd = bid % 8, pos = bid / 8;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-  }
-  const int64_t tm = bid / tiles_n;
-  const int tn = (int)(bid % tiles_n);
-  const int64_t m0 = tm * BM;
-  const int n0 = tn * BNT;
-
-  const int64_t kbeg = (int64_t)blockIdx.z * a.kchunk;
-  const int64_t kend = std::min<int64_t>(a.K, kbeg + a.kchunk);
-  const int64_t nkt = (kend - kbeg + BK - 1) / BK;
-
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int wm = wid >> 1, wn = wid & 1;
-
+  __shared__ __attribute__((aligned(16))) float lds[staged_lds_floats<ROW, TN, 2>()];
   f32x16 acc[2][TN];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  const bool do_bias = MODE == MODE_WGRAD && a.bias_part != nullptr && tn == 0;
-  float bsum = 0.f;
-  float4 ra[BM / 32], rb[BNT / 32];
-  if (nkt > 0) {
-    load_A<MODE, VEC, BM>(a, m0, kbeg, kend, ra);
-    load_B<MODE, VEC, BNT>(a, n0, kbeg, kend, rb);
-    store_tile<ROW, BM>(lds, ra);
-    store_tile<ROW, BNT>(lds + TILE_FLOATS, rb);
-  }
-  __syncthreads();
-
-  for (int64_t kt = 0; kt < nkt; ++kt) {
-    const int cur = (int)(kt & 1);
-    const bool more = kt + 1 < nkt;
-    if (more) {
-      load_A<MODE, VEC, BM>(a, m0, kbeg + (kt + 1) * BK, kend, ra);
-      load_B<MODE, VEC, BNT>(a, n0, kbeg + (kt + 1) * BK, kend, rb);
-    }
-    const float* cA = lds + (2 * cur) * TILE_FLOATS;
-    const float* cB = lds + (2 * cur + 1) * TILE_FLOATS;
-#pragma unroll
-    for (int kg = 0; kg < BK / 8; ++kg) {
-      float4 fa[2], fb[TN];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) fa[i] = read_frag<ROW, BM>(cA, wm * 64 + i * 32, kg, lane);
-#pragma unroll
-      for (int j = 0; j < TN; ++j) fb[j] = read_frag<ROW, BNT>(cB, wn * 32 * TN + j * 32, kg, lane);
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].x, fb[j].x, acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].y, fb[j].y, acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].z, fb[j].z, acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].w, fb[j].w, acc[i][j], 0, 0, 0);
-        }
-    }
-    if (MODE == MODE_WGRAD && do_bias) {   // column sums of the resident dz tile ([k][out], pitch BM + 4)
-      const int o = threadIdx.x & 127, kh = threadIdx.x >> 7;
-      const float* ct = cA + (kh * (BK / 2)) * (BM + 4) + o;
-#pragma unroll
-      for (int kk = 0; kk < BK / 2; ++kk) bsum += ct[kk * (BM + 4)];
-    }
-    if (more) {
-      store_tile<ROW, BM>(lds + (2 * (cur ^ 1)) * TILE_FLOATS, ra);
-      store_tile<ROW, BNT>(lds + (2 * (cur ^ 1) + 1) * TILE_FLOATS, rb);
-    }
-    __syncthreads();
-  }
-
-  if (MODE == MODE_WGRAD && do_bias) {   // the two k halves meet in LDS (tile reads retired by the last barrier)
-    const int o = threadIdx.x & 127, kh = threadIdx.x >> 7;
-    if (kh == 1) lds[o] = bsum;
-    __syncthreads();
-    if (kh == 0 && m0 + o < a.M) a.bias_part[(int64_t)blockIdx.z * a.M + m0 + o] = bsum + lds[o];
-  }
-
-  // epilogue: C/D map of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-  float* C = a.C + (int64_t)blockIdx.z * a.slab_stride;
-  const int cl = lane & 31, rh = lane >> 5;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int col = n0 + wn * 32 * TN + j * 32 + cl;
-      if (col >= a.N) continue;
-      float bv = 0.f;
-      if (EPI == EPI_BIAS_ACT && a.bias) bv = a.bias[col];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int64_t m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * rh;
-        if (m >= a.M) continue;
-        int64_t row = m;
-        if (MODE == MODE_FWD) {
-          int t;
-          row = phys_row((uint32_t)m, a.geo, a.geo.out_sb, a.geo.out_st, &t);
-        }
-        float v = acc[i][j][r];
-        if (EPI == EPI_BIAS_ACT) v = act_fwd(v + bv, a.act);
-        if (EPI == EPI_DACT) v *= act_grad_from_out(a.aux[row * a.ldaux + col], a.act);
-        C[row * a.ldc + col] = v;
-      }
-    }
+  const StagedTile t = staged_gemm_tile<ROW, ROW, TN, 2>(a, Im2colLoader<MODE, VEC>{a}, lds, acc);
+  // geo by value: captured by reference, hipcc no longer folds ldc into the row strides and spends a
+  // 64-bit multiply per stored element (+0.5 % on the forward at the bench shapes)
+  if (MODE == MODE_FWD)
+    staged_epilogue<EPI, TN, AF_BASE>(a, t, acc, [geo = a.geo](int64_t m) {
+      return phys_row((uint32_t)m, geo, geo.out_sb, geo.out_st);
+    });
+  else
+    staged_epilogue<EPI, TN, AF_BASE>(a, t, acc, [](int64_t m) { return m; });
 }
 
 // Weights [Cout][Cin][Kw] -> packed [O][Kw * Ip]: forward (O = Cout, I = Cin) w_t[n][k Ip + c] =
@@ -386,8 +216,6 @@ __global__ __launch_bounds__(256) void reduce_wgrad_kernel(const float* __restri
     }
   }
 }
-
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 template <int MODE, int EPI, int TN>
 static int launch_tn(const ConvArgs& a, bool vec, int splitk, hipStream_t s) {
@@ -473,7 +301,7 @@ extern "C" int itts_conv1d_fwd(const float* d_x, int64_t ldx, const float* d_w, 
   int rc = launch_pack(d_w, wt, Cout, Cin, Kw, 0, s);
   if (rc) return rc;
   ConvArgs a{};
-  a.A = d_x; a.lda = ldx; a.Bm = wt; a.ldb = Kp; a.C = d_y; a.ldc = ldy;
+  a.A = d_x; a.lda = ldx; a.B = wt; a.ldb = Kp; a.C = d_y; a.ldc = ldy;
   a.M = (int64_t)B * T_out; a.N = Cout; a.K = Kp; a.bias = d_b; a.act = act;
   a.kchunk = ((Kp + BK - 1) / BK) * BK;
   a.geo = make_geo(B, T_in, T_out, Cin, pad, dil, batch_first);
@@ -502,7 +330,7 @@ extern "C" int itts_conv1d_bwd_input(const float* d_dz, int64_t lddz, const floa
   int rc = launch_pack(d_w, wf, Cout, Cin, Kw, 1, s);
   if (rc) return rc;
   ConvArgs a{};
-  a.A = d_dz; a.lda = lddz; a.Bm = wf; a.ldb = Kp; a.C = d_dx; a.ldc = lddx;
+  a.A = d_dz; a.lda = lddz; a.B = wf; a.ldb = Kp; a.C = d_dx; a.ldc = lddx;
   a.M = (int64_t)B * T_in; a.N = Cin; a.K = Kp; a.aux = d_yprev; a.ldaux = ldyp; a.act = act_prev;
   a.kchunk = ((Kp + BK - 1) / BK) * BK;
   a.geo = make_geo(B, T_out, T_in, Cout, dil * (Kw - 1) - pad, dil, batch_first);
@@ -541,9 +369,10 @@ extern "C" int itts_conv1d_bwd_weight(const float* d_dz, int64_t lddz, const flo
   // C[Cout][Kp] = dz^T x_col: A = dz as col form [k = m][out = n]; B = the implicit im2col as col
   // form [k = m][out = kk]
   ConvArgs a{};
-  a.A = d_dz; a.lda = lddz; a.Bm = d_x; a.ldb = ldx; a.C = slabs; a.ldc = Kp;
+  a.A = d_dz; a.lda = lddz; a.B = d_x; a.ldb = ldx; a.C = slabs; a.ldc = Kp;
   a.M = Cout; a.N = Kp; a.K = rows; a.kchunk = kchunk; a.slab_stride = (int64_t)Cout * Kp;
   a.bias_part = d_db ? slabs + (int64_t)S_eff * Cout * Kp : nullptr;
+  a.bias_part_stride = Cout;
   a.geo = make_geo(B, T_in, T_out, Cin, pad, dil, batch_first);
   const bool vec = lddz % 4 == 0 && aligned16(d_dz) && ldx % 4 == 0 && aligned16(d_x);
   int rc = launch<MODE_WGRAD, EPI_STORE>(a, vec, S_eff, s);

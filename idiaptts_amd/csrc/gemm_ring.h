@@ -36,13 +36,13 @@
 //   * the clock follows the previous kernel for milliseconds: time a kernel after it has run for a
 //     few hundred launches, never right behind another one.
 //
-// K order inside the MFMA chain equals the register-staged kernel's (nn.hip), so results are
+// K order inside the MFMA chain equals the register-staged kernel's (gemm_staged.h), so results are
 // bit-identical to it for the same split-K chunking.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <type_traits>
+#include "activations.h"
 
 #ifndef RING_DBG
 #define RING_DBG 0   // lab only: 1 no DMA, 2 no step barrier, 4 no MFMA, 8 no epilogue, 16 no fragment reads
@@ -67,15 +67,6 @@ constexpr int PIECES = 6;                     // 1-KB DMA instructions per loade
 constexpr int THREADS = 512;         // 4 compute waves + 4 loader waves (workgroups of 5 or 6 waves do not share a CU)
 
 enum { EPI_STORE = 0, EPI_BIAS_ACT = 1, EPI_DACT = 2, EPI_MSE = 3 };
-// the ITTS_ACT_* codes of include/idiaptts_amd.h
-enum {
-  ACT_NONE = 0, ACT_TANH = 1, ACT_RELU = 2, ACT_SIGMOID = 3, ACT_LOGSIGMOID = 4, ACT_SOFTPLUS = 5, ACT_SOFTSIGN = 6,
-  ACT_LEAKY_RELU = 7, ACT_ELU = 8, ACT_CELU = 9, ACT_SELU = 10, ACT_HARDTANH = 11, ACT_RELU6 = 12, ACT_HARDSIGMOID = 13
-};
-// Activation family of a kernel instantiation: AF_BASE picks NONE / TANH / RELU at run time (the headline FF step's
-// kernels, whose code the other activations must leave alone); AF_EXT picks among codes 3 .. 13.  The host
-// chooses the family from the code.
-enum { AF_BASE = 0, AF_EXT = 1 };
 
 struct Args {
   const float* A;
@@ -100,16 +91,6 @@ struct Args {
   int act;
   float gscale;               // EPI_MSE
 };
-
-__device__ __forceinline__ float fast_tanhf(float z) {
-  const float a = fabsf(z);
-  const float z2 = z * z;
-  const float poly = z * (1.f + z2 * (-0.33333334f + z2 * (0.13333334f + z2 * (-0.053968254f +
-                                                                              z2 * 0.021869488f))));
-  const float e = __expf(2.f * a);
-  const float big = copysignf(1.f - 2.f * __builtin_amdgcn_rcpf(e + 1.f), z);
-  return a < 0.25f ? poly : big;
-}
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, uint32_t bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
@@ -374,71 +355,6 @@ __device__ __forceinline__ void loader_wave(const Args& g, char* lds, uint32_t l
 // ------------------------------------------------------------------------------------------------
 // compute waves
 // ------------------------------------------------------------------------------------------------
-// torch.nn.SELU's constants
-constexpr float SELU_ALPHA = 1.6732632423543772848170429916717f;
-constexpr float SELU_SCALE = 1.0507009873554804934193349852946f;
-
-// y = f(z) with torch's default arguments (table in include/idiaptts_amd.h); accurate exp / expm1 / log1p, no
-// __expf.  The clamps compare rather than fminf / fmaxf so that a NaN passes through, as in torch.
-template <int ACT>
-__device__ __forceinline__ float act1(float z) {
-  if (ACT == ACT_TANH) return fast_tanhf(z);
-  if (ACT == ACT_RELU) return z > 0.f ? z : 0.f;
-  if (ACT == ACT_SIGMOID) return 1.f / (1.f + expf(-z));
-  if (ACT == ACT_LOGSIGMOID) return fminf(z, 0.f) - log1pf(expf(-fabsf(z)));
-  if (ACT == ACT_SOFTPLUS) return z > 20.f ? z : log1pf(expf(z));
-  if (ACT == ACT_SOFTSIGN) return z / (1.f + fabsf(z));
-  if (ACT == ACT_LEAKY_RELU) return z > 0.f ? z : 0.01f * z;
-  if (ACT == ACT_ELU || ACT == ACT_CELU) return z > 0.f ? z : expm1f(z);
-  if (ACT == ACT_SELU) return z > 0.f ? SELU_SCALE * z : (SELU_SCALE * SELU_ALPHA) * expm1f(z);
-  if (ACT == ACT_HARDTANH) return z < -1.f ? -1.f : (z > 1.f ? 1.f : z);
-  if (ACT == ACT_RELU6) return z < 0.f ? 0.f : (z > 6.f ? 6.f : z);
-  if (ACT == ACT_HARDSIGMOID) {
-    const float t = z + 3.f;
-    return (t < 0.f ? 0.f : (t > 6.f ? 6.f : t)) / 6.f;
-  }
-  return z;
-}
-// f'(z) through y = f(z); at a branch point torch's value (LeakyReLU 0.01 and ELU 1 at z = 0, the clamps 0)
-template <int ACT>
-__device__ __forceinline__ float dact1(float y) {
-  if (ACT == ACT_TANH) return 1.f - y * y;
-  if (ACT == ACT_RELU) return y > 0.f ? 1.f : 0.f;
-  if (ACT == ACT_SIGMOID) return y * (1.f - y);
-  if (ACT == ACT_LOGSIGMOID) return -expm1f(y);
-  if (ACT == ACT_SOFTPLUS) return y > 20.f ? 1.f : -expm1f(-y);
-  if (ACT == ACT_SOFTSIGN) {
-    const float t = 1.f - fabsf(y);
-    return t * t;
-  }
-  if (ACT == ACT_LEAKY_RELU) return y > 0.f ? 1.f : 0.01f;
-  if (ACT == ACT_ELU || ACT == ACT_CELU) return y > 0.f ? 1.f : y + 1.f;
-  if (ACT == ACT_SELU) return y > 0.f ? SELU_SCALE : y + SELU_SCALE * SELU_ALPHA;
-  if (ACT == ACT_HARDTANH) return y > -1.f && y < 1.f ? 1.f : 0.f;
-  if (ACT == ACT_RELU6) return y > 0.f && y < 6.f ? 1.f : 0.f;
-  if (ACT == ACT_HARDSIGMOID) return y > 0.f && y < 1.f ? 1.f / 6.f : 0.f;
-  return 1.f;
-}
-
-// run-time code -> compiled activation, for the codes of the AF_EXT family (ELU and CELU share one body);
-// f(std::integral_constant<int, ACT>()) is called once
-template <typename F>
-__device__ __forceinline__ void with_ext_act(int act, F&& f) {
-  switch (act) {
-    case ACT_SIGMOID: f(std::integral_constant<int, ACT_SIGMOID>()); break;
-    case ACT_LOGSIGMOID: f(std::integral_constant<int, ACT_LOGSIGMOID>()); break;
-    case ACT_SOFTPLUS: f(std::integral_constant<int, ACT_SOFTPLUS>()); break;
-    case ACT_SOFTSIGN: f(std::integral_constant<int, ACT_SOFTSIGN>()); break;
-    case ACT_LEAKY_RELU: f(std::integral_constant<int, ACT_LEAKY_RELU>()); break;
-    case ACT_ELU:
-    case ACT_CELU: f(std::integral_constant<int, ACT_ELU>()); break;
-    case ACT_SELU: f(std::integral_constant<int, ACT_SELU>()); break;
-    case ACT_HARDTANH: f(std::integral_constant<int, ACT_HARDTANH>()); break;
-    case ACT_RELU6: f(std::integral_constant<int, ACT_RELU6>()); break;
-    default: f(std::integral_constant<int, ACT_HARDSIGMOID>()); break;
-  }
-}
-
 template <int CTRL>
 __device__ __forceinline__ float quad_swap(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
@@ -598,9 +514,9 @@ __device__ __forceinline__ void compute_waves(const Args& g, char* lds, int wid,
           with_ext_act(g.act, [&](auto act) {
             epilogue<EPI, decltype(act)::value>(g, pc, acc0, acc1, wm, wn, lane, bv, lsum);
           });
-        } else if (EPI == EPI_STORE || g.act == ACT_NONE) epilogue<EPI, ACT_NONE>(g, pc, acc0, acc1, wm, wn, lane, bv, lsum);
-        else if (g.act == ACT_TANH) epilogue<EPI, ACT_TANH>(g, pc, acc0, acc1, wm, wn, lane, bv, lsum);
-        else epilogue<EPI, ACT_RELU>(g, pc, acc0, acc1, wm, wn, lane, bv, lsum);
+        } else if (EPI == EPI_STORE || g.act == ITTS_ACT_NONE) epilogue<EPI, ITTS_ACT_NONE>(g, pc, acc0, acc1, wm, wn, lane, bv, lsum);
+        else if (g.act == ITTS_ACT_TANH) epilogue<EPI, ITTS_ACT_TANH>(g, pc, acc0, acc1, wm, wn, lane, bv, lsum);
+        else epilogue<EPI, ITTS_ACT_RELU>(g, pc, acc0, acc1, wm, wn, lane, bv, lsum);
       }
       pending = false;
     }

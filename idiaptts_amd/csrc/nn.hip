@@ -3,18 +3,11 @@
 // makes per mini-batch (rnn_dyn/FFWrapper.py:63-73, loss/NamedLoss.py:70-117,
 // ModularModelHandlerPyTorch.py:769-820).
 //
-// GEMM design (exact fp32: v_mfma_f32_32x32x2_f32, 64 FLOP/clk/SIMD = 157 TFLOP/s chip peak):
-//   * 128x128 output tile per 256-thread workgroup, 4 waves as 2x2, each wave 64x64 =
-//     2x2 MFMA tiles of 32x32 (64 accumulator VGPRs), K step 32, LDS double buffered
-//     (73.7 KB -> 2 workgroups per CU); or a 128x64 tile with a single LDS stage (36.9 KB,
-//     106 VGPRs -> 4 workgroups per CU) -- see launch_gemm for which shape runs when.
-//   * an operand is either "row form" [out][k] (k contiguous, e.g. x[M,K], w[N,K]) or "col
-//     form" [k][out] (e.g. dz[M,N] as the reduction-major operand of dW).  Row-form tiles are
-//     copied to LDS unchanged with a 4-float pad (144-B rows: conflict-free ds_read_b128);
-//     col-form tiles are [k][128+4] and read with ds_read_b32 (lanes = consecutive floats).
-//   * K permutation instead of an LDS transpose: the MFMA takes k = lane>>5 from each lane;
-//     lane half h feeds k = 8g + 4h + j on step j of k-group g, for A and B alike, so one
-//     ds_read_b128 per lane supplies four MFMAs.
+// GEMMs (exact fp32: v_mfma_f32_32x32x2_f32, 64 FLOP/clk/SIMD = 157 TFLOP/s chip peak): the LDS-DMA
+// ring kernel (gemm_ring.h) takes every call whose operands allow 16-byte rows; the register-staged
+// kernel gemm_f32_kernel (its body in gemm_staged.h, shared with conv1d.hip) takes the rest, as a
+// 128x128 double-buffered tile or a 128x64 tile with a single LDS stage (36.9 KB, 106 VGPRs -> 4
+// workgroups per CU) -- see launch_gemm for which runs when.
 //   * roofline: MFMA fp32.  FLOPs per valid frame of the 425-512-512-187 model: fwd 1.15 M,
 //     fwd+bwd 3.45 M (first-layer input gradient skipped: 3.01 M) -- SURVEY.md section 8d.
 #include <algorithm>
@@ -22,85 +15,11 @@
 
 #include "common.h"
 #include "gemm_ring.h"
+#include "gemm_staged.h"
 
 namespace itts {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int BM = 128, BN = 128, BK = 32;  // BN: widest tile (TN = 2)
-constexpr int LD_ROW = BK + 4;    // row-form tile [128][36]
-constexpr int TILE_FLOATS = 128 * LD_ROW;  // 4608 >= 32*132 = 4224
-
-enum { EPI_STORE = 0, EPI_BIAS_ACT = 1, EPI_DACT = 2, EPI_MSE = 3 };
-
-struct GemmArgs {
-  const float* A;
-  int64_t lda;
-  const float* B;
-  int64_t ldb;
-  float* C;
-  int64_t ldc;
-  int64_t M;  // output rows
-  int N;      // output cols
-  int64_t K;  // reduction length
-  const float* bias;
-  const float* aux;
-  int64_t ldaux;
-  int act;
-  int64_t kchunk;       // reduction elements per blockIdx.z (multiple of BK)
-  int64_t slab_stride;  // floats between split-K slabs of C
-  int vecA, vecB;       // 16-B vector loads allowed
-  int wide_out;         // C (and bias, aux) allow 16-B accesses: float4 epilogue of the row-form kernel
-  // EPI_MSE (last layer of a training step): C receives d loss / d output instead of the output
-  const uint8_t* row_valid;   // [M]
-  float gscale;               // 2 * loss_weight / (n_valid * D)
-  double* loss_partial;       // [grid] sums of squared masked differences, one per workgroup
-  // col-form A (weight gradients): column sums of A over this launch's K chunk, i.e. the bias
-  // gradient, as a by-product of the workgroups of the first column tile
-  float* bias_part;           // [slab][M] or NULL
-  int64_t bias_part_stride;
-};
-
-// tanh in ~12 VALU ops (ocml tanhf costs ~40 and showed up as ~15 % of the fused-epilogue GEMMs):
-// |z| < 0.25: odd Taylor polynomial up to z^9 (truncation < 9e-9 relative);
-// else 1 - 2/(exp(2|z|)+1) with the hardware exp2/rcp (abs. error <= ~1.5e-7, i.e. ~2 ulp of
-// the result in [0.24, 1]).  Max deviation from torch.tanh (fp32) observed: 2.4e-7.
-__device__ __forceinline__ float fast_tanhf(float z) {
-  const float a = fabsf(z);
-  const float z2 = z * z;
-  const float poly = z * (1.f + z2 * (-0.33333334f + z2 * (0.13333334f + z2 * (-0.053968254f +
-                                                                              z2 * 0.021869488f))));
-  const float e = __expf(2.f * a);
-  const float big = copysignf(1.f - 2.f * __builtin_amdgcn_rcpf(e + 1.f), z);
-  return a < 0.25f ? poly : big;
-}
-
-__device__ __forceinline__ float act_fwd(float z, int act) {
-  if (act == ITTS_ACT_TANH) return fast_tanhf(z);
-  if (act == ITTS_ACT_RELU) return z > 0.f ? z : 0.f;
-  return z;
-}
-__device__ __forceinline__ float act_grad_from_out(float y, int act) {
-  if (act == ITTS_ACT_TANH) return 1.f - y * y;
-  if (act == ITTS_ACT_RELU) return y > 0.f ? 1.f : 0.f;
-  return 1.f;
-}
-// the activation family AF (ring::AF_BASE: the two above, ring::AF_EXT: codes 3 .. 13, gemm_ring.h's act1 / dact1)
-template <int AF>
-__device__ __forceinline__ float act_fwd_af(float z, int act) {
-  if (AF == ring::AF_BASE) return act_fwd(z, act);
-  float y = z;
-  ring::with_ext_act(act, [&](auto a) { y = ring::act1<decltype(a)::value>(z); });
-  return y;
-}
-template <int AF>
-__device__ __forceinline__ float act_grad_af(float y, int act) {
-  if (AF == ring::AF_BASE) return act_grad_from_out(y, act);
-  float d = 1.f;
-  ring::with_ext_act(act, [&](auto a) { d = ring::dact1<decltype(a)::value>(y); });
-  return d;
-}
-static inline int act_family(int act) { return act >= ITTS_ACT_SIGMOID ? ring::AF_EXT : ring::AF_BASE; }
+constexpr int BN = 128;  // widest tile of the register-staged kernel (TN = 2)
 
 // Global -> registers for one 128(out) x 32(k) tile of an operand, 16 floats per thread.
 // Branch-free: out-of-range elements read a clamped (valid) address and are zeroed by a select,
@@ -146,136 +65,32 @@ __device__ __forceinline__ void load_tile(const float* __restrict__ P, int64_t l
   }
 }
 
-template <bool ROWFORM, int NROWS>
-__device__ __forceinline__ void store_tile(float* __restrict__ S, const float4 (&r)[NROWS / 32]) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int i = 0; i < NROWS / 32; ++i) {
-    const int idx = tid + 256 * i;
-    int off;
-    if (ROWFORM)
-      off = (idx >> 3) * LD_ROW + ((idx & 7) << 2);
-    else
-      off = (idx / (NROWS / 4)) * (NROWS + 4) + ((idx % (NROWS / 4)) << 2);
-    *reinterpret_cast<float4*>(S + off) = r[i];
+template <bool A_ROW, bool B_ROW, bool VEC_A, bool VEC_B>
+struct DenseLoader {
+  const GemmArgs& g;
+  template <int NROWS>
+  __device__ __forceinline__ void load_a(int64_t out0, int64_t k0, int64_t k_end, float4 (&r)[NROWS / 32]) const {
+    load_tile<A_ROW, VEC_A, NROWS>(g.A, g.lda, out0, g.M, k0, k_end, r);
   }
-}
-
-// Fragment of k-group g for the 32 rows starting at `o` (tile-local): 4 k values per lane.
-template <bool ROWFORM, int NROWS>
-__device__ __forceinline__ float4 read_frag(const float* __restrict__ S, int o, int g, int lane) {
-  const int r = lane & 31, h = lane >> 5;
-  if (ROWFORM) {
-    return *reinterpret_cast<const float4*>(S + (o + r) * LD_ROW + g * 8 + 4 * h);
-  } else {
-    constexpr int LDC = NROWS + 4;
-    const float* p = S + (g * 8 + 4 * h) * LDC + o + r;
-    return make_float4(p[0], p[LDC], p[2 * LDC], p[3 * LDC]);
+  template <int NROWS>
+  __device__ __forceinline__ void load_b(int64_t out0, int64_t k0, int64_t k_end, float4 (&r)[NROWS / 32]) const {
+    load_tile<B_ROW, VEC_B, NROWS>(g.B, g.ldb, out0, g.N, k0, k_end, r);
   }
-}
+};
 
 // TN = MFMA tiles per wave along N: output tile 128 x (64*TN). TN = 1 halves the tile so that
 // narrow outputs (N = 187) and awkward tile counts waste fewer workgroup slots.  AF: activation family.
-template <bool A_ROW, bool B_ROW, int EPI, bool VEC_A, bool VEC_B, int TN, int STAGES = 2, int AF = ring::AF_BASE>
+template <bool A_ROW, bool B_ROW, int EPI, bool VEC_A, bool VEC_B, int TN, int STAGES = 2, int AF = AF_BASE>
 __global__ __launch_bounds__(256, STAGES == 1 ? 4 : 2) void gemm_f32_kernel(GemmArgs g) {
-  constexpr int BNT = 64 * TN;
-  constexpr int B_FLOATS = STAGES == 1 ? (B_ROW ? BNT * LD_ROW : BK * (BNT + 4)) : TILE_FLOATS;
-  __shared__ __attribute__((aligned(16))) float lds[STAGES * 2 * TILE_FLOATS - (STAGES == 1 ? TILE_FLOATS - B_FLOATS : 0)];
-  // buffer b: A tile at lds + 2b*TILE, B tile at lds + (2b+1)*TILE.  STAGES == 1: one LDS buffer
-  // (36.9 KB -> 4 workgroups per CU), the next tile waits in registers and two barriers per K
-  // tile separate its store from the reads of the current one.
-
-  // XCD-aware tile order: blocks b and b+8 share an XCD (round-robin dispatch), so give each
-  // XCD a contiguous run of tiles that share the same B panel (weights) where possible.
-  const int tiles_n = (g.N + BNT - 1) / BNT;
-  const int64_t tiles_m = (g.M + BM - 1) / BM;
-  const int64_t ntiles = tiles_m * tiles_n;
-  int64_t bid = blockIdx.x;
-  {
-    const int64_t q = ntiles / 8, r = ntiles % 8;
-    const int64_t xcd = bid % 8, pos = bid / 8;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-  }
-  const int64_t tm = bid / tiles_n;
-  const int tn = (int)(bid % tiles_n);
-  const int64_t m0 = tm * BM;
-  const int n0 = tn * BNT;
-
-  const int64_t kbeg = (int64_t)blockIdx.z * g.kchunk;
-  const int64_t kend = std::min<int64_t>(g.K, kbeg + g.kchunk);
-  const int64_t nkt = (kend - kbeg + BK - 1) / BK;
-
+  __shared__ __attribute__((aligned(16))) float lds[staged_lds_floats<B_ROW, TN, STAGES>()];
+  f32x16 acc[2][TN];
+  const StagedTile t =
+      staged_gemm_tile<A_ROW, B_ROW, TN, STAGES>(g, DenseLoader<A_ROW, B_ROW, VEC_A, VEC_B>{g}, lds, acc);
+  const int64_t m0 = t.m0;
+  const int n0 = t.n0;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int wm = wid >> 1, wn = wid & 1;
-
-  f32x16 acc[2][TN];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  const bool do_bias = !A_ROW && g.bias_part != nullptr && tn == 0;
-  float bsum = 0.f;
-  float4 ra[4], rb[BNT / 32];
-  if (nkt > 0) {
-    load_tile<A_ROW, VEC_A, BM>(g.A, g.lda, m0, g.M, kbeg, kend, ra);
-    load_tile<B_ROW, VEC_B, BNT>(g.B, g.ldb, n0, g.N, kbeg, kend, rb);
-    store_tile<A_ROW, BM>(lds, ra);
-    store_tile<B_ROW, BNT>(lds + TILE_FLOATS, rb);
-  }
-  __syncthreads();
-
-  for (int64_t kt = 0; kt < nkt; ++kt) {
-    const int cur = STAGES == 1 ? 0 : (int)(kt & 1);
-    const bool more = kt + 1 < nkt;
-    if (more) {
-      load_tile<A_ROW, VEC_A, BM>(g.A, g.lda, m0, g.M, kbeg + (kt + 1) * BK, kend, ra);
-      load_tile<B_ROW, VEC_B, BNT>(g.B, g.ldb, n0, g.N, kbeg + (kt + 1) * BK, kend, rb);
-    }
-    const float* cA = lds + (2 * cur) * TILE_FLOATS;
-    const float* cB = lds + (2 * cur + 1) * TILE_FLOATS;
-#pragma unroll
-    for (int kg = 0; kg < BK / 8; ++kg) {
-      float4 fa[2], fb[TN];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) fa[i] = read_frag<A_ROW, BM>(cA, wm * 64 + i * 32, kg, lane);
-#pragma unroll
-      for (int j = 0; j < TN; ++j) fb[j] = read_frag<B_ROW, BNT>(cB, wn * 32 * TN + j * 32, kg, lane);
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].x, fb[j].x, acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].y, fb[j].y, acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].z, fb[j].z, acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].w, fb[j].w, acc[i][j], 0, 0, 0);
-        }
-    }
-    if (!A_ROW && do_bias) {   // column sums of the A tile ([k][out], pitch BM + 4) while it is resident
-      const int o = threadIdx.x & 127, kh = threadIdx.x >> 7;
-      const float* ct = cA + (kh * (BK / 2)) * (BM + 4) + o;
-#pragma unroll
-      for (int kk = 0; kk < BK / 2; ++kk) bsum += ct[kk * (BM + 4)];
-    }
-    if (STAGES == 1) __syncthreads();   // everyone has read the current tile
-    if (more) {
-      constexpr int nb = STAGES == 1 ? 0 : 1;
-      store_tile<A_ROW, BM>(lds + (2 * (cur ^ nb)) * TILE_FLOATS, ra);
-      store_tile<B_ROW, BNT>(lds + (2 * (cur ^ nb) + 1) * TILE_FLOATS, rb);
-    }
-    __syncthreads();
-  }
-
-  if (!A_ROW && do_bias) {   // the two k halves meet in LDS (all tile reads are behind the loop's last barrier)
-    const int o = threadIdx.x & 127, kh = threadIdx.x >> 7;
-    if (kh == 1) lds[o] = bsum;
-    __syncthreads();
-    if (kh == 0 && m0 + o < g.M)
-      g.bias_part[(int64_t)blockIdx.z * g.bias_part_stride + m0 + o] = bsum + lds[o];
-  }
-  // epilogue: C/D map of 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
+  // C/D map of 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
   float* C = g.C + (int64_t)blockIdx.z * g.slab_stride;
   const int cl = lane & 31, rh = lane >> 5;
   if (EPI == EPI_MSE) {
@@ -381,27 +196,10 @@ __global__ __launch_bounds__(256, STAGES == 1 ? 4 : 2) void gemm_f32_kernel(Gemm
     }
     return;
   }
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int col = n0 + wn * 32 * TN + j * 32 + cl;
-      if (col >= g.N) continue;
-      float bv = 0.f;
-      if (EPI == EPI_BIAS_ACT && g.bias) bv = g.bias[col];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int64_t row = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * rh;
-        if (row >= g.M) continue;
-        float v = acc[i][j][r];
-        if (EPI == EPI_BIAS_ACT) v = act_fwd_af<AF>(v + bv, g.act);
-        if (EPI == EPI_DACT) v *= act_grad_af<AF>(g.aux[row * g.ldaux + col], g.act);
-        C[row * g.ldc + col] = v;
-      }
-    }
+  staged_epilogue<EPI, TN, AF>(g, t, acc, [](int64_t m) { return m; });
 }
 
-template <bool A_ROW, bool B_ROW, int EPI, int TN, int STAGES, int AF = ring::AF_BASE>
+template <bool A_ROW, bool B_ROW, int EPI, int TN, int STAGES, int AF = AF_BASE>
 static int launch_gemm_tn(const GemmArgs& g, int splitk, hipStream_t s) {
   const int64_t tiles = ((g.M + BM - 1) / BM) * ((g.N + 64 * TN - 1) / (64 * TN));
   dim3 grid((unsigned)tiles, 1, (unsigned)splitk);
@@ -435,8 +233,6 @@ static double tile_efficiency(int64_t M, int N, int splitk, int tn, double loop_
   return loop_eff * useful * (double)tiles / (double)(rounds * 512);
 }
 
-static inline int aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // ---- the LDS-DMA ring kernel (gemm_ring.h) -----------------------------------------------------
 // Takes every call whose operands allow 16-byte row accesses (the trainer's buffers all do); the
 // register-staged kernel above stays the general path (odd pitches, unaligned bases).
@@ -459,8 +255,8 @@ static bool ring_ok(const GemmArgs& g, int splitk, int epi) {
 
 static int ring_group(int tiles_n, int bnt, int64_t K, bool row_row);
 
-template <bool A_ROW, bool B_ROW, int EPI, int WM, int AF = ring::AF_BASE>
-static int launch_ring_wm(const GemmArgs& g, int splitk, hipStream_t s) {
+template <int WM>
+static ring::Args ring_args(const GemmArgs& g, int splitk) {
   constexpr int BMT = 64 * WM, BNT = 32 * (4 / WM);
   ring::Args r{};
   r.A = g.A; r.B = g.B; r.C = g.C; r.bias = g.bias; r.aux = g.aux;
@@ -470,8 +266,16 @@ static int launch_ring_wm(const GemmArgs& g, int splitk, hipStream_t s) {
   r.M = (int)g.M; r.N = g.N; r.K = (int)g.K; r.kchunk = (int)g.kchunk; r.splitk = splitk;
   r.tiles_m = (int)((g.M + BMT - 1) / BMT);
   r.tiles_n = (g.N + BNT - 1) / BNT;
-  r.gn = ring_group(r.tiles_n, BNT, g.K, A_ROW && B_ROW);
+  r.gn = r.tiles_n;
   r.act = g.act; r.gscale = g.gscale;
+  return r;
+}
+
+template <bool A_ROW, bool B_ROW, int EPI, int WM, int AF = AF_BASE>
+static int launch_ring_wm(const GemmArgs& g, int splitk, hipStream_t s) {
+  constexpr int BNT = 32 * (4 / WM);
+  ring::Args r = ring_args<WM>(g, splitk);
+  r.gn = ring_group(r.tiles_n, BNT, g.K, A_ROW && B_ROW);
   const int64_t ntiles = (int64_t)r.tiles_m * r.tiles_n * splitk;
   ITTS_REQUIRE(ntiles < ((int64_t)1 << 31), "too many tiles");
   const int grid = (int)std::min<int64_t>(kRingGrid, (ntiles + 7) / 8 * 8);
@@ -508,25 +312,9 @@ static int launch_ring(const GemmArgs& g, int splitk, hipStream_t s) {
   return launch_ring_wm<A_ROW, B_ROW, EPI, 2, AF>(g, splitk, s);
 }
 
-template <int WM>
-static ring::Args ring_args(const GemmArgs& g, int splitk) {
-  constexpr int BMT = 64 * WM, BNT = 32 * (4 / WM);
-  ring::Args r{};
-  r.A = g.A; r.B = g.B; r.C = g.C; r.bias = g.bias; r.aux = g.aux;
-  r.row_valid = g.row_valid; r.loss_partial = g.loss_partial; r.bias_part = g.bias_part;
-  r.slab_stride = g.slab_stride; r.bias_part_stride = g.bias_part_stride;
-  r.lda = (int)g.lda; r.ldb = (int)g.ldb; r.ldc = (int)g.ldc; r.ldaux = (int)g.ldaux;
-  r.M = (int)g.M; r.N = g.N; r.K = (int)g.K; r.kchunk = (int)g.kchunk; r.splitk = splitk;
-  r.tiles_m = (int)((g.M + BMT - 1) / BMT);
-  r.tiles_n = (g.N + BNT - 1) / BNT;
-  r.gn = r.tiles_n;
-  r.act = g.act; r.gscale = g.gscale;
-  return r;
-}
-
 // weight-gradient GEMM (col x col, split-K slabs) and input-gradient GEMM (row x col, activation
 // derivative in the epilogue) of one layer in ONE launch
-template <int WM_W, int EPI_X, int AF_X = ring::AF_BASE>
+template <int WM_W, int EPI_X, int AF_X = AF_BASE>
 static int launch_ring_bwd_pair(const GemmArgs& gw, int splitk, const GemmArgs& gx, hipStream_t s) {
   const ring::Args rw = ring_args<WM_W>(gw, splitk), rx = ring_args<2>(gx, 1);
   hipLaunchKernelGGL((ring::gemm_ring_pair_kernel<false, false, EPI_STORE, WM_W, true, false, EPI_X, 2, AF_X>),
@@ -535,7 +323,7 @@ static int launch_ring_bwd_pair(const GemmArgs& gw, int splitk, const GemmArgs& 
   return ITTS_OK;
 }
 
-template <bool A_ROW, bool B_ROW, int EPI, int AF = ring::AF_BASE>
+template <bool A_ROW, bool B_ROW, int EPI, int AF = AF_BASE>
 static int launch_gemm(GemmArgs g, int splitk, hipStream_t s) {
   if (g.M <= 0 || g.N <= 0) return ITTS_OK;
   if (ring_ok<A_ROW, B_ROW>(g, splitk, EPI)) return launch_ring<A_ROW, B_ROW, EPI, AF>(g, splitk, s);
@@ -724,15 +512,15 @@ extern "C" int itts_reduce_deferred(void* stream) {
 template <int AF>
 __global__ void act_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y,
                                float* __restrict__ dz, int64_t n, int act) {
-  if (AF == ring::AF_BASE) {
+  if (AF == AF_BASE) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * blockDim.x)
       dz[i] = dy[i] * act_grad_from_out(y[i], act);
   } else {
-    ring::with_ext_act(act, [&](auto a) {
+    with_ext_act(act, [&](auto a) {
       for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
            i += (int64_t)gridDim.x * blockDim.x)
-        dz[i] = dy[i] * ring::dact1<decltype(a)::value>(y[i]);
+        dz[i] = dy[i] * dact1<decltype(a)::value>(y[i]);
     });
   }
 }
@@ -975,7 +763,7 @@ extern "C" int itts_linear_fwd(const float* d_x, int64_t ldx, const float* d_w, 
   g.vecA = (ldx % 4 == 0) && aligned16(d_x);
   g.vecB = (K % 4 == 0) && aligned16(d_w);
   g.wide_out = (ldy % 4 == 0) && aligned16(d_y) && (!d_b || aligned16(d_b));
-  if (act_family(act) == ring::AF_EXT) return launch_gemm<true, true, EPI_BIAS_ACT, ring::AF_EXT>(g, 1, as_stream(stream));
+  if (act_family(act) == AF_EXT) return launch_gemm<true, true, EPI_BIAS_ACT, AF_EXT>(g, 1, as_stream(stream));
   return launch_gemm<true, true, EPI_BIAS_ACT>(g, 1, as_stream(stream));
 }
 
@@ -1077,11 +865,11 @@ extern "C" int itts_act_bwd(const float* d_dy, const float* d_y, float* d_dz, in
   ITTS_REQUIRE(act >= ITTS_ACT_NONE && act <= ITTS_ACT_HARDSIGMOID, "unknown activation");
   if (n_elem == 0) return ITTS_OK;
   const int blocks = (int)std::min<int64_t>((n_elem + 255) / 256, 4096);
-  if (act_family(act) == ring::AF_EXT)
-    hipLaunchKernelGGL(act_bwd_kernel<ring::AF_EXT>, dim3(blocks), dim3(256), 0, as_stream(stream), d_dy, d_y,
+  if (act_family(act) == AF_EXT)
+    hipLaunchKernelGGL(act_bwd_kernel<AF_EXT>, dim3(blocks), dim3(256), 0, as_stream(stream), d_dy, d_y,
                        d_dz, n_elem, act);
   else
-    hipLaunchKernelGGL(act_bwd_kernel<ring::AF_BASE>, dim3(blocks), dim3(256), 0, as_stream(stream), d_dy, d_y,
+    hipLaunchKernelGGL(act_bwd_kernel<AF_BASE>, dim3(blocks), dim3(256), 0, as_stream(stream), d_dy, d_y,
                        d_dz, n_elem, act);
   ITTS_LAUNCH_CHECK();
   return ITTS_OK;
@@ -1105,7 +893,7 @@ extern "C" int itts_linear_bwd_input(const float* d_dz, int64_t lddz, const floa
   g.wide_out = (lddx % 4 == 0) && aligned16(d_dx) && (!d_yprev || ((ldyp % 4 == 0) && aligned16(d_yprev)));
   if (d_yprev) {
     ITTS_REQUIRE(ldyp >= K, "ldyp too small");
-    if (act_family(act_prev) == ring::AF_EXT) return launch_gemm<true, false, EPI_DACT, ring::AF_EXT>(g, 1, as_stream(stream));
+    if (act_family(act_prev) == AF_EXT) return launch_gemm<true, false, EPI_DACT, AF_EXT>(g, 1, as_stream(stream));
     return launch_gemm<true, false, EPI_DACT>(g, 1, as_stream(stream));
   }
   return launch_gemm<true, false, EPI_STORE>(g, 1, as_stream(stream));
@@ -1209,9 +997,9 @@ extern "C" int itts_linear_bwd(const float* d_dz, int64_t lddz, const float* d_x
   }
   int rc;
   const int wm = ring_wm(gw.M, gw.N);
-  if (d_yprev && act_family(act_prev) == ring::AF_EXT)
-    rc = wm == 1 ? launch_ring_bwd_pair<1, EPI_DACT, ring::AF_EXT>(gw, S_eff, gx, s)
-                 : launch_ring_bwd_pair<2, EPI_DACT, ring::AF_EXT>(gw, S_eff, gx, s);
+  if (d_yprev && act_family(act_prev) == AF_EXT)
+    rc = wm == 1 ? launch_ring_bwd_pair<1, EPI_DACT, AF_EXT>(gw, S_eff, gx, s)
+                 : launch_ring_bwd_pair<2, EPI_DACT, AF_EXT>(gw, S_eff, gx, s);
   else if (d_yprev) rc = wm == 1 ? launch_ring_bwd_pair<1, EPI_DACT>(gw, S_eff, gx, s) : launch_ring_bwd_pair<2, EPI_DACT>(gw, S_eff, gx, s);
   else rc = wm == 1 ? launch_ring_bwd_pair<1, EPI_STORE>(gw, S_eff, gx, s) : launch_ring_bwd_pair<2, EPI_STORE>(gw, S_eff, gx, s);
   if (rc) return rc;

@@ -259,15 +259,15 @@ int main(int argc, char** argv) {
     rows.push_back({name, t_old, t_new, 2.0 * M * N * (double)K, 0.0, bd});
   };
 
-  run_rowA("fwd1 425->512", x, 428, w1, 428, true, 512, 428, EPI_BIAS_ACT, b1, nullptr, 0, ACT_TANH, 512,
+  run_rowA("fwd1 425->512", x, 428, w1, 428, true, 512, 428, EPI_BIAS_ACT, b1, nullptr, 0, ITTS_ACT_TANH, 512,
            [&]() { itts_linear_fwd(x, 428, w1, b1, o_old, 512, M, 512, 428, 1, nullptr); });
-  run_rowA("fwd2 512->512", h1, 512, w2, 512, true, 512, 512, EPI_BIAS_ACT, b1, nullptr, 0, ACT_TANH, 512,
+  run_rowA("fwd2 512->512", h1, 512, w2, 512, true, 512, 512, EPI_BIAS_ACT, b1, nullptr, 0, ITTS_ACT_TANH, 512,
            [&]() { itts_linear_fwd(h1, 512, w2, b1, o_old, 512, M, 512, 512, 1, nullptr); });
-  run_rowA("fwd3 512->187", h2, 512, w3, 512, true, 187, 512, EPI_BIAS_ACT, b3, nullptr, 0, ACT_NONE, 188,
+  run_rowA("fwd3 512->187", h2, 512, w3, 512, true, 187, 512, EPI_BIAS_ACT, b3, nullptr, 0, ITTS_ACT_NONE, 188,
            [&]() { itts_linear_fwd(h2, 512, w3, b3, o_old, 188, M, 187, 512, 0, nullptr); });
-  run_rowA("dX2 187->512", dz3, 188, w3, 512, false, 512, 187, EPI_DACT, nullptr, h2, 512, ACT_TANH, 512,
+  run_rowA("dX2 187->512", dz3, 188, w3, 512, false, 512, 187, EPI_DACT, nullptr, h2, 512, ITTS_ACT_TANH, 512,
            [&]() { itts_linear_bwd_input(dz3, 188, w3, o_old, 512, h2, 512, 1, M, 187, 512, nullptr); });
-  run_rowA("dX1 512->512", dz2, 512, w2, 512, false, 512, 512, EPI_DACT, nullptr, h1, 512, ACT_TANH, 512,
+  run_rowA("dX1 512->512", dz2, 512, w2, 512, false, 512, 512, EPI_DACT, nullptr, h1, 512, ITTS_ACT_TANH, 512,
            [&]() { itts_linear_bwd_input(dz2, 512, w2, o_old, 512, h1, 512, 1, M, 512, 512, nullptr); });
 
   // weight gradients: dw[N][K] = dz^T x

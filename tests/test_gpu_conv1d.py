@@ -179,3 +179,22 @@ def test_autograd_module_matches_torch(gpu):
     _check(x.grad, xr.grad, 90, "module input gradient")
     _check(mod.weight.grad, wr.grad, 4 * 23, "module weight gradient", rel=3e-6)
     _check(mod.bias.grad, br.grad, 4 * 23, "module bias gradient", rel=3e-6)
+
+
+@pytest.mark.parametrize("act", ["none", "tanh"])
+@pytest.mark.parametrize("Cin,Cout", [(64, 128), (67, 45)])
+def test_kernel_size_one_is_the_dense_layer(gpu, Cin, Cout, act):
+    """Kw = 1, padding 0: the forward and the input gradient are the dense layer's GEMMs with the same K order
+    (padded channels add zeros), so they equal itts_linear_fwd / itts_linear_bwd_input bit for bit; 64 channels
+    take the dense ring kernel, 67 its register-staged kernel"""
+    B, T = 3, 70
+    x, w, b = _make(gpu, B, T, Cin, Cout, 1, True, seed=Cin)
+    w2 = w[:, :, 0].contiguous()
+    y = ops.conv1d_fwd(x, w, b, 0, 1, True, ACTS[act])
+    assert torch.equal(y.reshape(B * T, Cout), ops.linear_fwd(x.reshape(B * T, Cin), w2, b, ACTS[act]))
+    dz = torch.randn(B, T, Cout, device=gpu)
+    yprev = torch.tanh(x) if act == "tanh" else None
+    dx = ops.conv1d_bwd_input(dz, w, T, 0, 1, True, yprev=yprev, act_prev=ACTS[act])
+    dx2 = ops.linear_bwd_input(dz.reshape(B * T, Cout), w2, None if yprev is None else yprev.reshape(B * T, Cin),
+                               ACTS[act])
+    assert torch.equal(dx.reshape(B * T, Cin), dx2)
