@@ -85,6 +85,8 @@ _SIGNATURES = {
     "itts_griffinlim": (c_int, [_P, _P, _P, _P, POINTER(c_int64), c_int, c_int, c_int, c_int, _P, c_int, c_double,
                                 c_int, _P, _P]),
     "itts_griffinlim_tile_frames": (c_int, [c_int, c_int]),
+    "itts_mel_inverse": (c_int, [_P, c_int64, c_int, c_int64, c_int, c_int, _P, _P, _P, _P, c_double, c_double, c_int,
+                                 c_int, _P, c_int64, c_int, _P, _P]),
     "itts_batch_pad_gather_f32": (c_int, [_P, c_int64, c_int64, _P, _P, c_int, c_int64, c_int, c_int, _P, c_int64, _P,
                                           _P, c_int64, _P, _P]),
     "itts_batch_pack_rows_f32": (c_int, [_P, c_int64, _P, _P, c_int, c_int64, c_int, c_int, _P, c_int64, c_int,

@@ -268,6 +268,34 @@ def griffinlim(S, angles, f_off, n_fft, hop, pad, window, n_iter, momentum):
     return y
 
 
+def mel_inverse(mel, n_fft, bin_j, bin_w, filt, pinv_t, inv_lipschitz, tol, max_iter, check_every, out_dtype,
+                iters=None):
+    """NNLS inversion of the mel filter banks mel [F, n_mels] (float32 or float64 rows) on the tables of
+    world.mel_inverse_tables -> K x [F, n_fft // 2 + 1] in out_dtype (float32 / float64).  iters: an int32 [F]
+    tensor that receives the iterations each frame took, or None."""
+    L = _lib.load()
+    if mel.dtype not in (torch.float32, torch.float64):
+        raise TypeError("mel must be float32 or float64, got {}".format(mel.dtype))
+    _need(mel, mel.dtype, "mel")
+    _need(bin_j, torch.int32, "bin_j")
+    _need(bin_w, torch.float64, "bin_w")
+    _need(filt, torch.int32, "filt")
+    _need(pinv_t, torch.float64, "pinv_t")
+    ld = _rows(mel, "mel")
+    F, n_mels = mel.shape
+    K = n_fft // 2 + 1
+    out = torch.empty((F, K), dtype=out_dtype, device=mel.device)
+    if iters is not None:
+        _need(iters, torch.int32, "iters")
+        if iters.numel() != F or not iters.is_contiguous():
+            raise ValueError("iters must be a contiguous int32 tensor of {} elements".format(F))
+    _lib.check(L.itts_mel_inverse(_ptr(mel), F, n_mels, ld, int(mel.dtype == torch.float64), int(n_fft), _ptr(bin_j),
+                                  _ptr(bin_w), _ptr(filt), _ptr(pinv_t), float(inv_lipschitz), float(tol),
+                                  int(max_iter), int(check_every), _ptr(out), K, int(out_dtype == torch.float64),
+                                  _ptr(iters), _stream()), "itts_mel_inverse")
+    return out
+
+
 def mel_project(amp, mel_tab, mel_w, n_mels, out=None):
     """The mel projection of a given amplitude spectrum amp [T, K] float64 -> float32 [T, n_mels]."""
     L = _lib.load()

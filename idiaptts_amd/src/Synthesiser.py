@@ -2,8 +2,8 @@
 :320-351).
 
 The reference walks the utterances one by one (decode_sp -> world_features_to_raw -> write);
-here all utterances of the call are decoded (mgc2sp), aperiodicity-decoded and synthesised by
-single batched GPU launches, then written. `synth_world_features` is the name BASELINE.json's
+here all utterances of the call are decoded (mgc2sp, or the mel inversion kernel for sp_type "mfbanks"),
+aperiodicity-decoded and synthesised by single batched GPU launches, then written. `synth_world_features` is the name BASELINE.json's
 north-star uses for this entry point; it is provided as an alias.
 """
 import logging
@@ -31,29 +31,45 @@ def _get(hparams, name, default):
 
 class Synthesiser(object):
     SYNTH_SUB_DIR = "synth"
+    # Amplitude floor of spectra decoded from mel filter banks before WORLD synthesis: the NNLS inversion leaves
+    # bins at exactly 0, where WORLD's aperiodic response takes log(0) and the waveform turns NaN (the reference
+    # passes them on unchanged).  1e-6 is WORLD's own safe-guard minimum of the power spectrum, 1e-12, as an
+    # amplitude.
+    MFBANKS_AMP_FLOOR = 1e-6
 
     @staticmethod
     def run_world_synth(synth_output: Dict[str, np.ndarray], hparams, epoch: int = None,
                         step: int = None, use_model_name: bool = True,
                         has_deltas: bool = False, return_waveforms: bool = False):
-        """Run the WORLD synthesize method on every entry of synth_output (id -> features)."""
+        """Run the WORLD synthesize method on every entry of synth_output (id -> features).  sp_type "mfbanks":
+        the mel filter banks of all utterances are inverted in one launch (AudioProcessing.mfbanks_to_amp_sp_batch)
+        and floored at MFBANKS_AMP_FLOOR, a departure from the reference that keeps the waveforms finite."""
         fs = hparams.synth_fs
         fft_size = AudioProcessing.fs_to_frame_length(fs)
         save_dir = Synthesiser._get_synth_dir(hparams, use_model_name, epoch=epoch, step=step)
         ids, amp_sps, lf0s, vuvs, baps = [], [], [], [], []
+        post_filtering = getattr(hparams, "do_post_filtering", False)
+        mfbanks = []
         for id_name, output in synth_output.items():
             coded_sp, lf0, vuv, bap = WorldFeatLabelGen.convert_to_world_features(
                 output, contains_deltas=has_deltas, num_coded_sps=hparams.num_coded_sps,
                 num_bap=hparams.num_bap)
-            amp_sp = AudioProcessing.decode_sp(
-                coded_sp, hparams.sp_type, fs,
-                post_filtering=getattr(hparams, "do_post_filtering", False)
-            ).astype(np.double, copy=False)
+            if hparams.sp_type == "mfbanks":
+                mfbanks.append(coded_sp)    # decoded below, all utterances in one launch
+                amp_sp = None
+            else:
+                amp_sp = AudioProcessing.decode_sp(coded_sp, hparams.sp_type, fs,
+                                                   post_filtering=post_filtering).astype(np.double, copy=False)
             ids.append(id_name)
             amp_sps.append(amp_sp)
             lf0s.append(lf0)
             vuvs.append(vuv)
             baps.append(bap)
+        if mfbanks:
+            if post_filtering:
+                logging.warning("Post-filtering only implemented for cepstrum features.")
+            amp_sps = [np.maximum(a.astype(np.double, copy=False), Synthesiser.MFBANKS_AMP_FLOOR)
+                       for a in AudioProcessing.mfbanks_to_amp_sp_batch(mfbanks, fs)]
         args = dict()
         for attr in "preemphasis", "f0_silence_threshold", "lf0_zero":
             if hasattr(hparams, attr):

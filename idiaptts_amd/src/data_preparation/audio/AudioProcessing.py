@@ -2,8 +2,9 @@
 (idiaptts/src/data_preparation/audio/AudioProcessing.py); pysptk / pyworld calls are replaced
 by the HIP kernels behind libidiaptts_amd.so.  librosa's STFT features -- the amplitude spectrum and mel filter
 banks (librosa_extract_amp_sp, extract_mfbanks) -- run on the STFT kernel (csrc/stft.hip); the way back from
-mel filter banks (librosa's NNLS inversion) is out of scope.  Griffin-Lim (amp_sp_to_raw, librosa.griffinlim) runs
-on the Griffin-Lim kernel (csrc/griffinlim.hip), one launch per iteration."""
+mel filter banks (mfbanks_to_amp_sp, librosa's NNLS inversion) runs on csrc/mel_inverse.hip.  Griffin-Lim
+(amp_sp_to_raw, librosa.griffinlim) runs on the Griffin-Lim kernel (csrc/griffinlim.hip), one launch per
+iteration."""
 import logging
 import os
 
@@ -271,6 +272,48 @@ class AudioProcessing:
         return AudioProcessing.depreemphasis(raw, preemphasis)
 
     @staticmethod
+    def mfbanks_to_amp_sp(coded_sp: np.array, fs: int, n_fft: int = None) -> np.array:
+        """Mel filter banks [T, n_mels] back to the amplitude spectrum [T, K] (reference :291-301):
+        librosa.feature.inverse.mel_to_stft(coded_sp.T, sr=fs, n_fft=n_fft, power=1.0, norm=None).T * K, the
+        non-negative least-squares solution for the basis without the Slaney factors, on the mel inversion kernel
+        (world.mel_inverse; the reference's `* K` and norm=None are kept).  float32 in, float32 out; anything else
+        is computed and returned as float64.  n_fft defaults to fs_to_frame_length(fs)."""
+        if n_fft is None:
+            n_fft = AudioProcessing.fs_to_frame_length(fs)
+        coded_sp = np.asarray(coded_sp)
+        if coded_sp.ndim != 2:
+            raise ValueError("coded_sp must be [T, n_mels]")
+        _world.check_mel_inverse_args(n_fft, coded_sp.shape[1])
+        dtype = np.float32 if coded_sp.dtype == np.float32 else np.float64
+        mel = torch.from_numpy(np.ascontiguousarray(coded_sp, dtype=dtype)).to(_dev())
+        return _world.mel_inverse(mel, fs, n_fft).cpu().numpy()
+
+    @staticmethod
+    def mfbanks_to_amp_sp_batch(coded_sps, fs: int, n_fft: int = None):
+        """mfbanks_to_amp_sp of every [T_u, n_mels] array in coded_sps, the frames of all utterances of one dtype
+        in one launch; each result equals the single call's."""
+        if n_fft is None:
+            n_fft = AudioProcessing.fs_to_frame_length(fs)
+        coded_sps = [np.asarray(c) for c in coded_sps]
+        if any(c.ndim != 2 or c.shape[1] != coded_sps[0].shape[1] for c in coded_sps):
+            raise ValueError("coded_sps must be [T, n_mels] arrays with the same n_mels")
+        if not coded_sps:
+            return []
+        _world.check_mel_inverse_args(n_fft, coded_sps[0].shape[1])
+        out = [None] * len(coded_sps)
+        for dtype in (np.float32, np.float64):
+            group = [u for u, c in enumerate(coded_sps) if (c.dtype == np.float32) == (dtype == np.float32)]
+            if not group:
+                continue
+            rows = np.concatenate([coded_sps[u] for u in group]).astype(dtype, copy=False)
+            amp = _world.mel_inverse(torch.from_numpy(np.ascontiguousarray(rows)).to(_dev()), fs, n_fft)
+            amp = amp.cpu().numpy()
+            off = _world.offsets([coded_sps[u].shape[0] for u in group])
+            for i, u in enumerate(group):
+                out[u] = amp[off[i]:off[i + 1]]
+        return out
+
+    @staticmethod
     def decode_sp(coded_sp: np.array, sp_type: str = "mcep", fs: int = None, alpha: float = None,
                   mgc_gamma: float = None, n_fft: int = None, post_filtering: bool = False):
         """reference :303-327"""
@@ -286,7 +329,7 @@ class AudioProcessing:
         elif sp_type == "amp_sp":
             return coded_sp
         elif sp_type == "mfbanks":
-            raise NotImplementedError("sp_type {} is outside the accelerated path.".format(sp_type))
+            return AudioProcessing.mfbanks_to_amp_sp(coded_sp, fs, n_fft)
         else:
             raise NotImplementedError("Unknown feature type {}. No decoding method available."
                                       .format(sp_type))

@@ -3,6 +3,7 @@
 analysis : wav(s) -> DIO -> StoneMask -> CheapTrick (+ fused SPTK mcep) / D4C (+ coded bap)
 STFT     : wav(s) -> amplitude spectrum / its dB form / mel filter banks (librosa's STFT features, stft.hip)
 Griffin-Lim: amplitude spectra -> waveforms (librosa.griffinlim, griffinlim.hip)
+mel inverse: mel filter banks -> amplitude spectra (librosa's NNLS mel_to_stft, mel_inverse.hip)
 synthesis: (f0, sp, ap) -> WORLD synthesis -> float32 (+ de-pre-emphasis)
 Utterances are concatenated and processed by single launches; only the small per-frame features
 (f0, mcep, bap) travel back to the host unless the spectral envelope is asked for.
@@ -251,6 +252,111 @@ def mel_project(amp_sp, fs, n_fft, n_mels):
     """mel_basis @ amp_sp.T, transposed, float32, for a given amplitude spectrum [T, n_fft // 2 + 1] on the device."""
     tab, w = _stft_table(("mel", fs, n_fft, n_mels), lambda: mel_tables(fs, n_fft, n_mels), amp_sp.device)
     return ops.mel_project(amp_sp, tab, w, n_mels)
+
+
+# ------------------------------------------------------------------------------------------ mel inverse
+MEL_INVERSE_TOL = 1e-6      # KKT stopping threshold, relative to max |A^T b| (DESIGN.md section 12)
+MEL_INVERSE_CAP = 1024      # iteration cap
+MEL_INVERSE_CHECK = 16      # iterations between stopping tests
+MEL_INVERSE_MAX_MELS = 256
+
+
+def mel_basis_plain(fs, n_fft, n_mels, dtype=np.float32):
+    """librosa.filters.mel(sr=fs, n_fft=n_fft, n_mels=n_mels, norm=None, dtype=dtype): the Slaney-scale triangles
+    computed in float64 and stored as `dtype`, without the Slaney factors of mel_basis.  [n_mels, n_fft // 2 + 1]"""
+    n_mels = int(n_mels)
+    fftfreqs = np.fft.rfftfreq(n=n_fft, d=1.0 / fs)
+    mel_f = mel_to_hz(np.linspace(hz_to_mel(0.0), hz_to_mel(float(fs) / 2), n_mels + 2))
+    fdiff = np.diff(mel_f)
+    ramps = np.subtract.outer(mel_f, fftfreqs)
+    weights = np.zeros((n_mels, n_fft // 2 + 1), dtype=dtype)
+    for i in range(n_mels):
+        weights[i] = np.maximum(0, np.minimum(-ramps[i] / fdiff[i], ramps[i + 2] / fdiff[i + 1]))
+    return weights
+
+
+def check_mel_inverse_args(n_fft, n_mels):
+    """What mel_inverse.hip covers; anything else raises before any device work."""
+    if n_fft not in (1024, 2048):
+        raise NotImplementedError("mel inversion n_fft={} is not implemented (1024, 2048).".format(n_fft))
+    if not 1 <= int(n_mels) <= MEL_INVERSE_MAX_MELS:
+        raise NotImplementedError("mel inversion n_mels={} is not implemented (1 .. {}).".format(
+            n_mels, MEL_INVERSE_MAX_MELS))
+
+
+@functools.lru_cache(maxsize=None)
+def mel_inverse_tables(fs, n_fft, n_mels, dtype=np.float32):
+    """The kernel's form of the norm=None basis A (mel_basis_plain, values rounded to `dtype` -- float32 or
+    float64 -- then used in float64), over KP = 64 ceil(K / 64) bins, zero beyond K:
+      bin_j  int32 [KP]       m1 + 1, where m1, m1 + 1 are the filters the bin lies in (m1 = -1: only filter 0;
+                              bins in no filter carry the previous bin's m1 with zero weights, so m1 never falls)
+      bin_w  float64 [KP, 2]  A[m1, k], A[m1 + 1, k] (0 outside the basis)
+      filt   int32 [n_mels, 3]  sb, eb, ea: filter m's bins are [sb, eb) (m1 = m - 1) and [eb, ea) (m1 = m)
+      pinv_t float64 [n_mels, KP]  np.linalg.pinv(A)^T (librosa's start)
+    and 1 / lambda_max(A A^T).  Raises NotImplementedError when a bin lies in more than two filters or in two
+    that are not adjacent."""
+    check_mel_inverse_args(n_fft, n_mels)
+    dtype = np.dtype(dtype)
+    A = mel_basis_plain(fs, n_fft, n_mels, dtype).astype(np.float64)
+    n_mels, K = A.shape
+    KP = 64 * ((K + 63) // 64)
+    bin_j = np.zeros(KP, dtype=np.int32)
+    bin_w = np.zeros((KP, 2), dtype=np.float64)
+    m1 = -1
+    for k in range(K):
+        nz = np.flatnonzero(A[:, k])
+        if len(nz) > 2 or (len(nz) == 2 and nz[1] != nz[0] + 1):
+            raise NotImplementedError("mel inversion: bin {} lies in filters {} (at most two adjacent ones are "
+                                      "implemented).".format(k, list(nz)))
+        if len(nz) == 2:
+            m = int(nz[0])
+        elif len(nz) == 1:          # as the lower filter after a bin of the same pair, else as the upper one
+            m = int(nz[0]) if m1 >= nz[0] else int(nz[0]) - 1
+        else:
+            m = m1
+        if m < m1:
+            raise NotImplementedError("mel inversion: the filters of bin {} fall below those of bin {}."
+                                      .format(k, k - 1))
+        m1 = m
+        bin_w[k] = (A[m1, k] if m1 >= 0 else 0.0, A[m1 + 1, k] if m1 + 1 < n_mels else 0.0)
+        bin_j[k] = m1 + 1
+    j = bin_j[:K] - 1
+    filt = np.zeros((n_mels, 3), dtype=np.int32)
+    for m in range(n_mels):
+        filt[m] = (np.searchsorted(j, m - 1, "left"), np.searchsorted(j, m, "left"), np.searchsorted(j, m, "right"))
+    pinv_t = np.zeros((n_mels, KP))
+    pinv_t[:, :K] = np.linalg.pinv(A).T
+    inv_l = 1.0 / float(np.linalg.eigvalsh(A @ A.T)[-1])
+    return bin_j, bin_w, filt, pinv_t, inv_l
+
+
+def mel_inverse(mel, fs, n_fft, tol=MEL_INVERSE_TOL, max_iter=MEL_INVERSE_CAP, return_iters=False):
+    """NNLS inversion of the mel filter banks mel [F, n_mels] (float32 or float64 rows on the device; the frames
+    of any number of utterances) -> K x [F, n_fft // 2 + 1] on the device, float32 for float32 input, else float64:
+    librosa.feature.inverse.mel_to_stft(mel.T, sr=fs, n_fft=n_fft, power=1.0, norm=None).T * K as the reference's
+    mfbanks_to_amp_sp computes it, on mel_inverse.hip's FISTA iteration (tests/mel_inverse_spec.py).  With
+    return_iters also the int32 [F] iterations each frame took."""
+    if mel.dim() != 2:
+        raise ValueError("mel must be [frames, n_mels]")
+    check_mel_inverse_args(n_fft, mel.shape[1])
+    max_iter = int(max_iter)
+    if max_iter < 0:
+        raise ValueError("max_iter={} must not be negative".format(max_iter))
+    if not tol >= 0:
+        raise ValueError("tol={} must not be negative".format(tol))
+    if mel.dtype not in (torch.float32, torch.float64):
+        mel = mel.to(torch.float64)
+    dtype = np.float32 if mel.dtype == torch.float32 else np.float64
+    n_mels = int(mel.shape[1])
+    bin_j, bin_w, filt, pinv_t, inv_l = mel_inverse_tables(fs, n_fft, n_mels, dtype)
+    dev = mel.device
+    tabs = _stft_table(("mel_inverse", fs, n_fft, n_mels, np.dtype(dtype).name),
+                       lambda: (bin_j, bin_w, filt, pinv_t), dev)
+    if mel.shape[0] > 0 and mel.stride(1) != 1:
+        mel = mel.contiguous()
+    iters = torch.empty(mel.shape[0], dtype=torch.int32, device=dev) if return_iters else None
+    out = ops.mel_inverse(mel, n_fft, *tabs, inv_l, tol, max_iter, MEL_INVERSE_CHECK, mel.dtype, iters)
+    return (out, iters) if return_iters else out
 
 
 # ------------------------------------------------------------------------------------------ Griffin-Lim

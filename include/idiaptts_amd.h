@@ -277,6 +277,23 @@ int itts_griffinlim(const void* d_S, void* d_ang_a, void* d_ang_b, void* d_tprev
                     double momentum, int is_f64, void* d_y, void* stream);
 int itts_griffinlim_tile_frames(int n_fft, int hop);
 
+/* Mel filter-bank inversion (librosa.feature.inverse.mel_to_stft(M, sr, n_fft, power=1.0, norm=None) times K, as
+ * AudioProcessing.mfbanks_to_amp_sp, AudioProcessing.py:291-301, and decode_sp(sp_type="mfbanks"), :321-322,
+ * call it): per frame b = row f of d_mel [n_frames, ld_mel] (float32, or double with mel_f64 = 1) the NNLS
+ * problem min ||A x - b||^2, x >= 0, for the norm=None mel basis A [n_mels, K], K = n_fft / 2 + 1, solved by
+ * FISTA with step inv_lipschitz = 1 / lambda_max(A A^T) from x = clip(pinv(A) b, 0), stopped every check_every
+ * iterations once max |min(x, A^T (A x - b))| <= tol max |A^T b|, after max_iter iterations at the latest;
+ * d_out row f [ld_out >= K] (float32, or double with out_f64 = 1) = K x.  The state is fp64.  Tables (built by
+ * world.mel_inverse_tables), over KP = 64 ceil(K / 64) bins, zero beyond K: d_bin_j [KP] int32 m1 + 1 for the
+ * two filters m1, m1 + 1 a bin lies in (0 .. n_mels), d_bin_w [KP][2] their weights, d_filt [n_mels][3] the bin
+ * ranges [sb, eb) with m1 = m - 1 and [eb, ea) with m1 = m of filter m, d_pinv_t [n_mels, KP] pinv(A)^T.
+ * d_iters [n_frames] (may be null): the iterations each frame took.  n_fft 1024 or 2048, 1 <= n_mels <= 256.
+ * One wave per frame, one launch; bit-identical from run to run and whatever else is in the batch. */
+int itts_mel_inverse(const void* d_mel, int64_t n_frames, int n_mels, int64_t ld_mel, int mel_f64, int n_fft,
+                     const int* d_bin_j, const double* d_bin_w, const int* d_filt, const double* d_pinv_t,
+                     double inv_lipschitz, double tol, int max_iter, int check_every, void* d_out, int64_t ld_out,
+                     int out_f64, int* d_iters, void* stream);
+
 /* interpolate_lin (misc/utils.py:40-86) on float32 contours stored back to back: frames <= 0 are
  * gaps; bit-exact including the reference's quirks (target reached one frame early; a gap whose
  * next voiced frame is the last frame is filled, with that frame, by the last voiced value).
