@@ -229,13 +229,17 @@ static int launch_tn(const ConvArgs& a, bool vec, int splitk, hipStream_t s) {
   return ITTS_OK;
 }
 
-// The 64-wide tile where the output is narrow (N <= 64) or where 128-wide tiles would leave most of
-// the 256 CUs idle.
+// What a call runs: the tile width (64 * tn columns), the slabs of the reduction (grid z) and the
+// reduction elements per slab.  make_plan below is the only place that decides it.
+struct Plan {
+  int tn, slabs;
+  int64_t kchunk;
+};
+
 template <int MODE, int EPI>
-static int launch(const ConvArgs& a, bool vec, int splitk, hipStream_t s) {
-  const int64_t tiles128 = ((a.M + BM - 1) / BM) * ((a.N + 127) / 128) * splitk;
-  if (a.N <= 64 || tiles128 < 256) return launch_tn<MODE, EPI, 1>(a, vec, splitk, s);
-  return launch_tn<MODE, EPI, 2>(a, vec, splitk, s);
+static int launch(const ConvArgs& a, const Plan& p, bool vec, hipStream_t s) {
+  if (p.tn == 1) return launch_tn<MODE, EPI, 1>(a, vec, p.slabs, s);
+  return launch_tn<MODE, EPI, 2>(a, vec, p.slabs, s);
 }
 
 static int launch_pack(const float* w, float* out, int Cout, int Cin, int Kw, int flip, hipStream_t s) {
@@ -271,6 +275,52 @@ static int wgrad_splitk(int64_t M_rows, int Cout, int Kp) {
   return (int)std::min<int64_t>(s, 128);
 }
 
+static bool sizes_positive(int B, int T_in, int Cin, int Cout, int Kw, int pad, int dil) {
+  return B > 0 && T_in > 0 && Cin > 0 && Cout > 0 && Kw > 0 && dil > 0 && pad >= 0;
+}
+static bool within_2_31(int B, int T_in, int Cin, int Cout, int Kw, int pad, int dil) {
+  return (int64_t)B * T_in < ((int64_t)1 << 31) && (int64_t)B * out_len(T_in, Kw, pad, dil) < ((int64_t)1 << 31) &&
+         (int64_t)Kw * (std::max(Cin, Cout) + 3) < ((int64_t)1 << 31);
+}
+// What CONV_CHECK_GEOMETRY asks of the entry points, for the plan query.
+static bool geometry_ok(int B, int T_in, int Cin, int Cout, int Kw, int pad, int dil) {
+  return sizes_positive(B, T_in, Cin, Cout, Kw, pad, dil) && out_len(T_in, Kw, pad, dil) > 0 &&
+         within_2_31(B, T_in, Cin, Cout, Kw, pad, dil);
+}
+
+// 16-byte loads from rows of this pitch at this base (the VEC instantiations).
+static bool rows16(const float* p, int64_t ld) { return ld % 4 == 0 && aligned16(p); }
+
+// The plan of product 0 (forward), 1 (input gradient) or 2 (weight gradient) for a valid geometry.
+// The GEMM is M x N over K: forward B*T_out x Cout over Kw * Cinp, input gradient B*T_in x Cin over
+// Kw * Coutp, weight gradient Cout x Kw * Cinp over the B*T_out rows in slabs of whole K steps (the
+// last slab may be shorter; rounding kchunk up to a K step can leave fewer slabs than wgrad_splitk
+// sized the workspace for).  The 64-wide tile where the output is narrow (N <= 64) or where 128-wide
+// tiles would leave most of the 256 CUs idle.  (vec, the 16-byte operand loads, selects the kernel
+// instantiation but no tile or split today.)
+static Plan make_plan(int product, int B, int T_in, int Cin, int Cout, int Kw, int pad, int dil, int vec) {
+  (void)vec;
+  const int64_t T_out = out_len(T_in, Kw, pad, dil);
+  int64_t M, N;
+  Plan p{1, 1, 0};
+  if (product == 2) {
+    const int Kp = Kw * ((Cin + 3) & ~3);
+    const int64_t rows = (int64_t)B * T_out;
+    const int S = wgrad_splitk(rows, Cout, Kp);
+    p.kchunk = (((rows + S - 1) / S + BK - 1) / BK) * BK;
+    p.slabs = (int)((rows + p.kchunk - 1) / p.kchunk);
+    M = Cout; N = Kp;
+  } else {
+    const int64_t Kp = (int64_t)Kw * (((product == 0 ? Cin : Cout) + 3) & ~3);
+    p.kchunk = ((Kp + BK - 1) / BK) * BK;
+    M = (int64_t)B * (product == 0 ? T_out : T_in);
+    N = product == 0 ? Cout : Cin;
+  }
+  const int64_t tiles128 = ((M + BM - 1) / BM) * ((N + 127) / 128) * p.slabs;
+  p.tn = (N <= 64 || tiles128 < 256) ? 1 : 2;
+  return p;
+}
+
 }  // namespace conv
 }  // namespace itts
 
@@ -278,12 +328,19 @@ using namespace itts;
 using namespace itts::conv;
 
 #define CONV_CHECK_GEOMETRY()                                                                              \
-  ITTS_REQUIRE(B > 0 && T_in > 0 && Cin > 0 && Cout > 0 && Kw > 0 && dil > 0 && pad >= 0, "bad sizes");    \
+  ITTS_REQUIRE(sizes_positive(B, T_in, Cin, Cout, Kw, pad, dil), "bad sizes");                             \
   ITTS_REQUIRE(out_len(T_in, Kw, pad, dil) > 0, "T_out = T_in + 2 pad - dil (Kw - 1) must be positive");   \
-  ITTS_REQUIRE((int64_t)B * T_in < ((int64_t)1 << 31) &&                                                    \
-                   (int64_t)B * out_len(T_in, Kw, pad, dil) < ((int64_t)1 << 31) &&                          \
-                   (int64_t)Kw * (std::max(Cin, Cout) + 3) < ((int64_t)1 << 31),                            \
-               "sizes beyond 2^31 rows / reduction elements")
+  ITTS_REQUIRE(within_2_31(B, T_in, Cin, Cout, Kw, pad, dil), "sizes beyond 2^31 rows / reduction elements")
+
+extern "C" int itts_conv1d_plan(int product, int B, int T_in, int Cin, int Cout, int Kw, int pad, int dil, int vec,
+                                int* tile_cols, int* slabs, int64_t* kchunk) {
+  if (product < 0 || product > 2 || !geometry_ok(B, T_in, Cin, Cout, Kw, pad, dil)) return -1;
+  const Plan p = make_plan(product, B, T_in, Cin, Cout, Kw, pad, dil, vec);
+  if (tile_cols) *tile_cols = 64 * p.tn;
+  if (slabs) *slabs = p.slabs;
+  if (kchunk) *kchunk = p.kchunk;
+  return 0;
+}
 
 extern "C" int itts_conv1d_fwd(const float* d_x, int64_t ldx, const float* d_w, const float* d_b, float* d_y,
                                int64_t ldy, int B, int T_in, int Cin, int Cout, int Kw, int pad, int dil,
@@ -303,10 +360,11 @@ extern "C" int itts_conv1d_fwd(const float* d_x, int64_t ldx, const float* d_w, 
   ConvArgs a{};
   a.A = d_x; a.lda = ldx; a.B = wt; a.ldb = Kp; a.C = d_y; a.ldc = ldy;
   a.M = (int64_t)B * T_out; a.N = Cout; a.K = Kp; a.bias = d_b; a.act = act;
-  a.kchunk = ((Kp + BK - 1) / BK) * BK;
   a.geo = make_geo(B, T_in, T_out, Cin, pad, dil, batch_first);
-  const bool vec = ldx % 4 == 0 && aligned16(d_x);
-  rc = launch<MODE_FWD, EPI_BIAS_ACT>(a, vec, 1, s);
+  const bool vec = rows16(d_x, ldx);
+  const Plan p = make_plan(0, B, T_in, Cin, Cout, Kw, pad, dil, vec);
+  a.kchunk = p.kchunk;
+  rc = launch<MODE_FWD, EPI_BIAS_ACT>(a, p, vec, s);
   if (rc) return rc;
   ITTS_HIP_CHECK(scratch_free(wt, s));
   return ITTS_OK;
@@ -332,10 +390,11 @@ extern "C" int itts_conv1d_bwd_input(const float* d_dz, int64_t lddz, const floa
   ConvArgs a{};
   a.A = d_dz; a.lda = lddz; a.B = wf; a.ldb = Kp; a.C = d_dx; a.ldc = lddx;
   a.M = (int64_t)B * T_in; a.N = Cin; a.K = Kp; a.aux = d_yprev; a.ldaux = ldyp; a.act = act_prev;
-  a.kchunk = ((Kp + BK - 1) / BK) * BK;
   a.geo = make_geo(B, T_out, T_in, Cout, dil * (Kw - 1) - pad, dil, batch_first);
-  const bool vec = lddz % 4 == 0 && aligned16(d_dz);
-  rc = d_yprev ? launch<MODE_FWD, EPI_DACT>(a, vec, 1, s) : launch<MODE_FWD, EPI_STORE>(a, vec, 1, s);
+  const bool vec = rows16(d_dz, lddz);
+  const Plan p = make_plan(1, B, T_in, Cin, Cout, Kw, pad, dil, vec);
+  a.kchunk = p.kchunk;
+  rc = d_yprev ? launch<MODE_FWD, EPI_DACT>(a, p, vec, s) : launch<MODE_FWD, EPI_STORE>(a, p, vec, s);
   if (rc) return rc;
   ITTS_HIP_CHECK(scratch_free(wf, s));
   return ITTS_OK;
@@ -361,21 +420,19 @@ extern "C" int itts_conv1d_bwd_weight(const float* d_dz, int64_t lddz, const flo
   const int T_out = (int)out_len(T_in, Kw, pad, dil);
   const int Cp = (Cin + 3) & ~3, Kp = Kw * Cp;
   const int64_t rows = (int64_t)B * T_out;
-  const int S = wgrad_splitk(rows, Cout, Kp);
-  int64_t kchunk = (rows + S - 1) / S;
-  kchunk = ((kchunk + BK - 1) / BK) * BK;
-  const int S_eff = (int)((rows + kchunk - 1) / kchunk);
+  const bool vec = rows16(d_dz, lddz) && rows16(d_x, ldx);
+  const Plan p = make_plan(2, B, T_in, Cin, Cout, Kw, pad, dil, vec);
+  const int S_eff = p.slabs;
   float* slabs = reinterpret_cast<float*>(d_workspace);
   // C[Cout][Kp] = dz^T x_col: A = dz as col form [k = m][out = n]; B = the implicit im2col as col
   // form [k = m][out = kk]
   ConvArgs a{};
   a.A = d_dz; a.lda = lddz; a.B = d_x; a.ldb = ldx; a.C = slabs; a.ldc = Kp;
-  a.M = Cout; a.N = Kp; a.K = rows; a.kchunk = kchunk; a.slab_stride = (int64_t)Cout * Kp;
+  a.M = Cout; a.N = Kp; a.K = rows; a.kchunk = p.kchunk; a.slab_stride = (int64_t)Cout * Kp;
   a.bias_part = d_db ? slabs + (int64_t)S_eff * Cout * Kp : nullptr;
   a.bias_part_stride = Cout;
   a.geo = make_geo(B, T_in, T_out, Cin, pad, dil, batch_first);
-  const bool vec = lddz % 4 == 0 && aligned16(d_dz) && ldx % 4 == 0 && aligned16(d_x);
-  int rc = launch<MODE_WGRAD, EPI_STORE>(a, vec, S_eff, s);
+  int rc = launch<MODE_WGRAD, EPI_STORE>(a, p, vec, s);
   if (rc) return rc;
   const int64_t n = (int64_t)Cout * Kp + Cout;
   const int blocks = (int)std::min<int64_t>((n + 255) / 256, 8192);

@@ -696,6 +696,36 @@ def _conv_out(like, batch_first, B, T, C):
     return torch.empty(shape, dtype=torch.float32, device=like.device)
 
 
+def _conv_out_rows(out, shape, name="out"):
+    """The row pitch of a caller's output: a contiguous `shape` tensor or a column slice of a wider one (only its own
+    columns are written)."""
+    C = shape[2]
+    if tuple(out.shape) == tuple(shape) and out.dtype == torch.float32:
+        ld = out.stride(1) if shape[1] > 1 else (out.stride(0) if shape[0] > 1 else C)
+        if (out.stride(2) == 1 or C == 1) and ld >= C and (shape[0] == 1 or out.stride(0) == shape[1] * ld):
+            return ld
+    raise ValueError("{} must be a float32 {} tensor with contiguous rows of one pitch".format(name, tuple(shape)))
+
+
+CONV_FWD, CONV_BWD_INPUT, CONV_BWD_WEIGHT = 0, 1, 2
+
+
+def conv1d_plan(product, B, T_in, Cin, Cout, kernel_size, padding, dilation, vec=True):
+    """(tile_cols, slabs, kchunk) of conv1d_fwd (product CONV_FWD), conv1d_bwd_input (CONV_BWD_INPUT) or
+    conv1d_bwd_weight (CONV_BWD_WEIGHT) for such a call: the workgroup tile's 64 or 128 output columns, the number of
+    slabs the reduction is split into and the reduction elements per slab (itts_conv1d_plan, the function the kernels'
+    launches read; no device work).  vec: whether the operands allow 16-byte loads (it selects the kernel
+    instantiation; no tile or split depends on it today).  ValueError for a geometry the products reject."""
+    tile, slabs, kchunk = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
+    rc = _lib.load().itts_conv1d_plan(int(product), int(B), int(T_in), int(Cin), int(Cout), int(kernel_size),
+                                      int(padding), int(dilation), 1 if vec else 0, ctypes.byref(tile),
+                                      ctypes.byref(slabs), ctypes.byref(kchunk))
+    if rc != 0:
+        raise ValueError("no Conv1d plan for product {} B {} T_in {} Cin {} Cout {} kernel {} padding {} dilation {}"
+                         .format(product, B, T_in, Cin, Cout, kernel_size, padding, dilation))
+    return tile.value, slabs.value, kchunk.value
+
+
 def conv1d_fwd(x, w, b, padding, dilation, batch_first, act=ACT_NONE, out=None):
     """y = act(conv1d(x, w, b, padding, dilation)) over the time axis: x [B, T_in, Cin] (batch_first) or
     [T_in, B, Cin], w [Cout, Cin, Kw] (torch's layout), b [Cout] or None -> y [B, T_out, Cout] / [T_out, B, Cout]."""
@@ -714,9 +744,8 @@ def conv1d_fwd(x, w, b, padding, dilation, batch_first, act=ACT_NONE, out=None):
     shape = (B, T_out, Cout) if batch_first else (T_out, B, Cout)
     if out is None:
         out = _conv_out(x, batch_first, B, T_out, Cout)
-    elif tuple(out.shape) != shape or not out.is_contiguous():
-        raise ValueError("out must be a contiguous {} tensor".format(shape))
-    _lib.check(L.itts_conv1d_fwd(_ptr(x), ldx, _ptr(w), _ptr(b), _ptr(out), Cout, B, T_in, Cin, Cout, Kw, padding,
+    ldy = _conv_out_rows(out, shape)
+    _lib.check(L.itts_conv1d_fwd(_ptr(x), ldx, _ptr(w), _ptr(b), _ptr(out), ldy, B, T_in, Cin, Cout, Kw, padding,
                                  dilation, 1 if batch_first else 0, act, _stream()), "itts_conv1d_fwd")
     return out
 
@@ -741,9 +770,8 @@ def conv1d_bwd_input(dz, w, T_in, padding, dilation, batch_first, yprev=None, ac
         yprev, ldyp = _conv_rows(yprev, "yprev")
     if out is None:
         out = _conv_out(dz, batch_first, B, T_in, Cin)
-    if tuple(out.shape) != shape or not out.is_contiguous():
-        raise ValueError("out must be a contiguous {} tensor".format(shape))
-    _lib.check(L.itts_conv1d_bwd_input(_ptr(dz), lddz, _ptr(w), _ptr(out), Cin, _ptr(yprev), ldyp, act_prev, B,
+    lddx = _conv_out_rows(out, shape)
+    _lib.check(L.itts_conv1d_bwd_input(_ptr(dz), lddz, _ptr(w), _ptr(out), lddx, _ptr(yprev), ldyp, act_prev, B,
                                        int(T_in), Cin, Cout, Kw, padding, dilation, 1 if batch_first else 0,
                                        _stream()), "itts_conv1d_bwd_input")
     return out

@@ -464,6 +464,15 @@ int64_t itts_conv1d_bwd_weight_workspace_bytes(int B, int T_in, int Cin, int Cou
 int itts_conv1d_bwd_weight(const float* d_dz, int64_t lddz, const float* d_x, int64_t ldx, float* d_dw,
                            float* d_db, int B, int T_in, int Cin, int Cout, int Kw, int pad, int dil,
                            int batch_first, void* d_workspace, int accumulate, void* stream);
+/* What such a call runs, without device work (the function the three entry points take their choice
+ * from): product 0 = itts_conv1d_fwd, 1 = _bwd_input, 2 = _bwd_weight; vec != 0 when the operands
+ * allow 16-byte loads (pitch % 4 == 0 and a 16-byte aligned base, of x for 0, dz for 1, both for 2).
+ * *tile_cols: 64 or 128 output columns per workgroup tile; *slabs: parts of the reduction summed in
+ * a fixed order (1 except for the weight gradient); *kchunk: reduction elements per slab (a multiple
+ * of 32; the last slab may hold fewer).  Any of the three may be NULL.  Returns 0, or -1 for an
+ * unknown product or a geometry the entry points reject. */
+int itts_conv1d_plan(int product, int B, int T_in, int Cin, int Cout, int Kw, int pad, int dil, int vec,
+                     int* tile_cols, int* slabs, int64_t* kchunk);
 
 /* ---- masked MSE, reduction 'mean_per_frame' (loss/NamedLoss.py:70-117) -------------------- */
 /*

@@ -1,11 +1,22 @@
 """itts_conv1d_fwd / _bwd_input / _bwd_weight (csrc/conv1d.hip) against torch's conv1d in float64 on the CPU: the
 Conv1d groups of rnn_dyn/CNNWrapper.py.  Tolerances of the dense-layer tests (test_gpu_nn.py): relative error
 ||got - ref|| / ||ref|| < 2e-6 (3e-6 for the weight and bias gradients, sums over B * T_out rows), and on every
-element |got - ref| <= 2e-5 * max(1, max|ref|)."""
+element |got - ref| <= 2e-5 * max(1, max|ref|).
+
+The small shapes below (SHAPES, the strided / module / activation cases) all take the 64-wide tile with one slab.
+The code that runs at production sizes -- the 128-wide tile, weight gradients summed over many slabs, a short last
+slab, fewer slabs than the workspace was sized for, the non-vector loads at such sizes -- is compared under CASES
+(tests/conv_harness.py) against tests/conv_ref.py (float64 im2col + matrix products on the GPU, pinned to torch on
+the CPU by test_conv_ref.py) with the same bounds; every case asserts the plan ops.conv1d_plan names for it, so a change of the
+dispatch rule fails here instead of quietly testing other code."""
+import collections
+
 import numpy as np
 import pytest
 import torch
 
+from conv_harness import CASES, expected_vec, run_case
+from conv_ref import SHAPES, conv_ref, same_pad
 from idiaptts_amd import ops
 
 pytestmark = pytest.mark.gpu
@@ -26,12 +37,20 @@ def _ref_fwd(x, w, b, pad, dil, bf, act):
     return y.permute(0, 2, 1) if bf else y.permute(2, 0, 1)
 
 
-def _check(got, ref, K, what, rel=2e-6):
-    got = got.double().cpu()
+WORST = collections.defaultdict(float)   # product -> worst error of the CASES as a fraction of its tolerance
+
+
+def _check(got, ref, K, what, rel=2e-6, key=None):
+    got = got.double().to(ref.device)
     err = float((got - ref).norm()) / (float(ref.norm()) + 1e-30)
-    assert err < rel, "{}: relative error {:.3g}".format(what, err)
     amax = float((got - ref).abs().max())
-    assert amax <= 2e-5 * max(1.0, float(ref.abs().max())), "{}: max abs error {:.3g}".format(what, amax)
+    tol = 2e-5 * max(1.0, float(ref.abs().max()))
+    if key is not None:
+        WORST[key] = max(WORST[key], err / rel, amax / tol)
+        print("{}: relative error {:.3g} (bound {:g}), max abs error {:.3g} (bound {:.3g})".format(what, err, rel, amax,
+                                                                                                 tol))
+    assert err < rel, "{}: relative error {:.3g}".format(what, err)
+    assert amax <= tol, "{}: max abs error {:.3g}".format(what, amax)
 
 
 def _make(gpu, B, T, Cin, Cout, Kw, bf, seed, bias=True):
@@ -51,21 +70,7 @@ def _grads_ref(x, w, b, pad, dil, bf, dy):
     return xr.grad, wr.grad, (None if br is None else br.grad)
 
 
-SHAPES = [   # B, T, Cin, Cout, Kw, dil, pad ("same" = dil * (Kw - 1) // 2)
-    (3, 37, 409, 16, 3, 1, "same"),
-    (2, 29, 67, 67, 5, 2, "same"),
-    (1, 50, 1, 5, 1, 1, 0),
-    (2, 64, 512, 512, 5, 1, "same"),
-    (3, 45, 13, 7, 31, 1, "same"),
-    (2, 20, 6, 9, 3, 4, 0),
-    (2, 9, 10, 11, 5, 2, 12),          # padding wider than the kernel span
-    (1, 3, 5, 6, 5, 1, 2),             # T shorter than the kernel span
-    (4, 17, 33, 65, 3, 4, "same"),
-]
-
-
-def _pad(p, Kw, dil):
-    return dil * (Kw - 1) // 2 if p == "same" else p
+_pad = same_pad
 
 
 @pytest.mark.parametrize("bf", [True, False])
@@ -124,8 +129,11 @@ def test_nonpositive_output_length_raises(gpu):
 
 
 def test_repeated_calls_are_bit_identical(gpu):
+    """(8 x 300, 512 -> 512, k5: the weight gradient sums 6 slabs on the 128-wide tile) three runs agree bit for bit,
+    and the values are those of the float64 restatement"""
     x, w, b = _make(gpu, 8, 300, 512, 512, 5, True, seed=3)
     dy = torch.randn(8, 300, 512, device=gpu)
+    assert ops.conv1d_plan(ops.CONV_BWD_WEIGHT, 8, 300, 512, 512, 5, 2, 1) == (128, 6, 416)
     outs = []
     for _ in range(3):
         y = ops.conv1d_fwd(x, w, b, 2, 1, True, ops.ACT_TANH)
@@ -135,6 +143,11 @@ def test_repeated_calls_are_bit_identical(gpu):
     for o in outs[1:]:
         for a, r in zip(o, outs[0]):
             assert np.array_equal(a, r)
+    ry, rdx, rdw, rdb = conv_ref(x, w, b, 2, 1, True, act="tanh", dz=dy)
+    _check(y, ry, 5 * 512, "forward")
+    _check(dx, rdx, 5 * 512, "input gradient")
+    _check(dw, rdw, 8 * 300, "weight gradient", rel=3e-6)
+    _check(db, rdb, 8 * 300, "bias gradient", rel=3e-6)
 
 
 @pytest.mark.parametrize("bf", [True, False])
@@ -198,3 +211,32 @@ def test_kernel_size_one_is_the_dense_layer(gpu, Cin, Cout, act):
     dx2 = ops.linear_bwd_input(dz.reshape(B * T, Cout), w2, None if yprev is None else yprev.reshape(B * T, Cin),
                                ACTS[act])
     assert torch.equal(dx.reshape(B * T, Cin), dx2)
+
+
+# ------------------------------------------------------------------ the code that runs at production sizes
+@pytest.fixture(scope="module", autouse=True)
+def _report_worst():
+    yield
+    if WORST:
+        print("\nConv1d CASES, worst error as a fraction of its tolerance:",
+              {k: round(v, 3) for k, v in sorted(WORST.items())})
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c.name for c in CASES])
+def test_production_size_paths(gpu, case):
+    """All three products of one CASES entry (tests/conv_harness.py) against conv_ref with the bounds of _check: the
+    plan asserted first; outputs written into column slices of sentinel-filled buffers (the columns around them stay
+    bit-unchanged); in the pad4 cases whose channels are no multiple of 4 (425, 409, 130, 70: the rows that 16-byte
+    loads read beyond their width) 1e30 in the pad floats of x / dz changes no bit of any result; and where the entry
+    says so the dense kernels on an explicit im2col pass the same bounds on the same data."""
+    g = case.geo
+    vec = expected_vec(g)
+    for product in range(3):
+        assert ops.conv1d_plan(product, g.B, g.T, g.Cin, g.Cout, g.Kw, g.pad, g.dil, vec[product]) \
+            == case.plan[product], product
+    res = run_case(gpu, g, torch.Generator(device=gpu).manual_seed(CASES.index(case)), case.name)
+    for key, got, ref, rel in res.items():
+        _check(got, ref, None, key, rel=rel, key=key)
+    if case.yardstick:
+        for key, got, ref, rel in res.items():
+            _check(res.yardstick(key), ref, None, "yardstick " + key, rel=rel, key="yardstick " + key)

@@ -1,6 +1,7 @@
 """Random-shape sweeps as tests: MLPG (the library's choice of solve and each form forced) against the C
 oracle utterance by utterance, the fp32 GEMM entry points against torch in float64
-(scripts/gemm_fuzz.py, a child process)."""
+(scripts/gemm_fuzz.py, a child process), the Conv1d products against a float64 im2col restatement
+(scripts/conv_fuzz.py, a child process)."""
 import os
 import subprocess
 import sys
@@ -82,6 +83,25 @@ def test_gemm_random_shapes(gpu):
                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
     assert res.returncode == 0, res.stdout[-3000:]
     assert "cases 60" in res.stdout
+
+
+def test_conv1d_random_shapes(gpu):
+    """120 random Conv1d geometries (scripts/conv_fuzz.py, seed 8): all three products against tests/conv_ref.py in
+    float64 with the bounds of test_gpu_conv1d.py asserted for every result, sentinels around the output slices, 1e30
+    in the pad floats, ValueError for T_out <= 0; the script exits non-zero unless every (product, tile width, one
+    slab / many, 16-byte loads or not) cell that ops.conv1d_plan can name was hit at least twice.  One result is held
+    to a bound of its own (the script's PINNED, DESIGN.md: 4.61e-6 relative for an input gradient over 17 329 terms
+    whose yardstick misses 2e-6 too): exactly that one, at no more than that figure.
+    Run time on an MI355X: 3.5 s."""
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "conv_fuzz.py"), "120", "8"],
+                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
+    print(res.stdout[-3000:])
+    assert res.returncode == 0, res.stdout[-3000:]
+    assert "cases 120" in res.stdout and "coverage too thin" not in res.stdout
+    held = [line for line in res.stdout.splitlines() if line.startswith("held to the pinned bound")]
+    assert len(held) == 1 and "case 26 bwd_input" in held[0], held
+    bounds = [float(tok.rstrip("),")) for prev, tok in zip(held[0].split(), held[0].split()[1:]) if prev.lstrip("(") == "bound"]
+    assert len(bounds) == 2 and bounds[0] <= 4.61e-6, held
 
 
 def test_grouped_tile_order_random_shapes(gpu):
