@@ -185,8 +185,10 @@ __global__ __launch_bounds__(768) void gru_step_bwd_kernel(GruArgs a) {
 
   const int row = b0 + lr;
   const bool has_next = row < a.nact_next;
-  const int kiter = a.kiter;                     // 3H rows / waves / 16 per step
-  const int kb0 = wv * 4 * kiter + kg;
+  // 3H rows / waves / 16 per step; a workgroup has at least the four waves the cell update needs (16 rows x 16
+  // units), so with ksplit = 3 the fourth takes no part in the product
+  const int kiter = wv < a.ksplit ? a.kiter : 0;
+  const int kb0 = (kiter ? wv * 4 * kiter : 0) + kg;
   const int KB = 3 * H / 4;
   const float4* ap = reinterpret_cast<const float4*>(dgb_in) + (size_t)kb0 * B + (row < B ? row : 0);
   const float4* wp = reinterpret_cast<const float4*>(a.wp) +
@@ -204,7 +206,7 @@ __global__ __launch_bounds__(768) void gru_step_bwd_kernel(GruArgs a) {
   f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
   f32x4 acc2 = {0.f, 0.f, 0.f, 0.f}, acc3 = {0.f, 0.f, 0.f, 0.f};   // four independent chains
 #pragma unroll 1
-  for (int c = 0; c < kiter; c += 8) {
+  for (int c = 0; c < kiter || c == 0; c += 8) {
     float4 av[8], bv[8];
 #pragma unroll
     for (int s = 0; s < 8; ++s) {

@@ -418,3 +418,16 @@ extern "C" int itts_lstm_layer_bwd(const float* d_dy, const float* d_whh, const 
     ITTS_HIP_CHECK(hipMemcpyAsync(d_dc0, a.cs, (size_t)ndir * B * H * 4, hipMemcpyDeviceToDevice, s));
   return ITTS_OK;
 }
+
+// Forward ran / declined / gave_up, backward ran / declined / gave_up of the persistent recurrences (rnn_persist.h),
+// LSTM and GRU layer calls of this process together.  No device is touched.
+extern "C" int itts_rnn_path_counts(int64_t out[6]) {
+  ITTS_REQUIRE(out != nullptr, "null pointer");
+  const PersistPathCounts* both[2] = {&g_persist_fwd_counts, &g_persist_bwd_counts};
+  for (int i = 0; i < 2; ++i) {
+    out[3 * i + 0] = both[i]->ran.load(std::memory_order_relaxed);
+    out[3 * i + 1] = both[i]->declined.load(std::memory_order_relaxed);
+    out[3 * i + 2] = both[i]->gave_up.load(std::memory_order_relaxed);
+  }
+  return ITTS_OK;
+}

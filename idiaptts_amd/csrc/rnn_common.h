@@ -141,7 +141,8 @@ static void rnn_fwd_steps(void (*const kernels[4])(Args), Args& a, const int* h_
 }
 
 // Backward recurrence on the step kernels, steps T - 1 .. 0: workgroups of `units` hidden units x one
-// 16-row batch tile, 64 * a.ksplit threads each.
+// 16-row batch tile, 64 * a.ksplit threads each -- and never fewer than the 256 the cell update of a tile takes (the
+// GRU's ksplit = 3: with 192 threads rows 12 .. 15 of every tile were left out).
 template <class Args>
 static void rnn_bwd_steps(void (*kernel)(Args), int units, Args& a, const int* h_lengths, hipStream_t s) {
   const std::vector<int> row_off = rnn_row_offsets(h_lengths, a.T, a.B);
@@ -153,6 +154,7 @@ static void rnn_bwd_steps(void (*kernel)(Args), int units, Args& a, const int* h
     nact_next = a.nact;
     a.row_base = row_off[step];
     a.row_base_prev = step > 0 ? row_off[step - 1] : 0;
-    hipLaunchKernelGGL(kernel, dim3((a.H / units) * ((a.nact + 15) / 16), a.ndir), dim3(64 * a.ksplit), 0, s, a);
+    hipLaunchKernelGGL(kernel, dim3((a.H / units) * ((a.nact + 15) / 16), a.ndir), dim3(std::max(64 * a.ksplit, 256)),
+                       0, s, a);
   }
 }

@@ -389,20 +389,29 @@ static void persist_ran(PersistDevices& table, int dev) {
   d.give_ups = 0;
 }
 
+// Which way the layer calls of this process went (itts_rnn_path_counts, lstm.hip): `ran` = persist_run returned 1,
+// `declined` = it returned 0 without launching (switched off, H != 512, device not ready, cooling down), `gave_up` =
+// the abort flag came back set or a launch failed.  One pair for the whole library: lstm.hip and gru.hip share it.
+struct PersistPathCounts {
+  std::atomic<int64_t> ran{0}, declined{0}, gave_up{0};
+};
+inline PersistPathCounts g_persist_fwd_counts, g_persist_bwd_counts;
+
 // The host half of both persistent recurrences: 1 = done, 0 = run the step kernels, -1 = HIP error.  The scratch
 // block holds the exchange buffer (`xbytes`, cleared), the abort flag and -- when h_lengths is given (the backward
 // kernel reads them) -- a device copy of the lengths.
 template <class Args>
 static int persist_run(void (*kernel)(Args), int lds_bytes, size_t xbytes, Args p, const int* h_lengths, int H,
-                       PersistDevices& devices, const char* what, hipStream_t s) {
+                       PersistDevices& devices, const char* what, PersistPathCounts& counts, hipStream_t s) {
+  const auto declined = [&counts]() { counts.declined.fetch_add(1, std::memory_order_relaxed); return 0; };
   const char* pe = getenv("ITTS_RNN_PERSISTENT");       // read per call: tests switch it
-  if (pe && pe[0] == '0') return 0;
+  if (pe && pe[0] == '0') return declined();
   p.ntiles = (p.B + 15) / 16;
-  if (H != PH) return 0;
+  if (H != PH) return declined();
   int dev = 0;
-  if (!persist_device_ready(reinterpret_cast<const void*>(kernel), lds_bytes, devices, &dev)) return 0;
+  if (!persist_device_ready(reinterpret_cast<const void*>(kernel), lds_bytes, devices, &dev)) return declined();
   DeviceContext* ctx = get_context();
-  if (!ctx) return 0;
+  if (!ctx) return declined();
   const size_t lbytes = h_lengths ? ((size_t)p.B * sizeof(int) + 63) / 64 * 64 : 0;
   char* blk = nullptr;
   itts::ScratchScope scope(s);
@@ -426,13 +435,19 @@ static int persist_run(void (*kernel)(Args), int lds_bytes, size_t xbytes, Args 
     hipLaunchKernelGGL(kernel, dim3(256), dim3(256), lds_bytes, s, p);
     if (hipGetLastError() != hipSuccess) {          // nothing of this round ran: the step kernels redo the layer
       persist_cool_down(devices, dev);
+      counts.gave_up.fetch_add(1, std::memory_order_relaxed);
       return 0;
     }
   }
   const int gave_up = persist_read_flag(pinned_slot(ctx), p.abort_flag, s);
   if (gave_up < 0) return -1;
   if (itts::scratch_free(blk, s) != hipSuccess) return -1;
-  if (gave_up == 0) { persist_ran(devices, dev); return 1; }
+  if (gave_up == 0) {
+    persist_ran(devices, dev);
+    counts.ran.fetch_add(1, std::memory_order_relaxed);
+    return 1;
+  }
+  counts.gave_up.fetch_add(1, std::memory_order_relaxed);
   const int calls = persist_cool_down(devices, dev);
   if (calls > 0)
     fprintf(stderr, "libidiaptts_amd: the persistent %srecurrence gave up waiting (are all 256 CUs available to "
@@ -444,7 +459,7 @@ template <int G>
 static int rnn_persist_forward(RnnPersistArgs p, int H, hipStream_t s) {
   static PersistDevices devices;
   return persist_run(rnn_persist_fwd_kernel<G>, persist_lds_bytes(G), (size_t)8 * 4 * 32 * 64 * sizeof(uint4), p,
-                     nullptr, H, devices, "", s);
+                     nullptr, H, devices, "", g_persist_fwd_counts, s);
 }
 
 // ---- persistent backward recurrence, same placement (G = 4: LSTM, G = 3: GRU) ---------------------
@@ -715,7 +730,7 @@ template <int G>
 static int rnn_persist_backward(RnnPersistBwdArgs p, const int* h_lengths, int H, hipStream_t s) {
   static PersistDevices devices;
   return persist_run(rnn_persist_bwd_kernel<G>, persist_bwd_lds_bytes(G), (size_t)8 * 2 * 32 * 32 * PT * sizeof(uint4),
-                     p, h_lengths, H, devices, "backward ", s);
+                     p, h_lengths, H, devices, "backward ", g_persist_bwd_counts, s);
 }
 
 }  // namespace itts

@@ -3,6 +3,7 @@
 Every function takes CUDA(HIP) tensors, passes raw device pointers + the current HIP stream to
 libidiaptts_amd.so and raises on any failure.  Nothing here computes on the CPU.
 """
+import collections
 import contextlib
 import ctypes
 import threading
@@ -943,6 +944,19 @@ def ema_update(shadow, param, decay):
             raise ValueError(n + " must be contiguous")
     _lib.check(L.itts_ema_update(_ptr(shadow), _ptr(param), shadow.numel(), float(decay),
                                  _stream()), "itts_ema_update")
+
+
+RnnPathCounts = collections.namedtuple("RnnPathCounts", "fwd_ran fwd_declined fwd_gave_up bwd_ran bwd_declined bwd_gave_up")
+
+
+def rnn_path_counts():
+    """Which way the LSTM / GRU layer calls of this process went so far (itts_rnn_path_counts; no device call): per
+    recurrence, `ran` = the persistent kernel did the layer, `declined` = it was not launched and the per-step
+    kernels did it, `gave_up` = a persistent launch failed or gave up waiting and the per-step kernels redid it."""
+    out = (ctypes.c_int64 * 6)()
+    _lib.check(_lib.load().itts_rnn_path_counts(out), "itts_rnn_path_counts")
+    return RnnPathCounts(*[int(v) for v in out])
+
 
 
 # ------------------------------------------------------------------------- WORLD frame kernels

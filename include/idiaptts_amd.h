@@ -715,6 +715,13 @@ int itts_gru_layer_bwd(const float* d_dy, const float* d_whh, const float* d_gat
                        const int* d_row_off, const int* d_rev_row, int T, int B, int H, int ndir,
                        float* d_dgi, float* d_dgh, float* d_dh0, void* d_state, void* stream);
 
+/* Which way the LSTM / GRU layer calls of this process went (process-wide atomic counts, no device call):
+ * out = forward ran, declined, gave_up, backward ran, declined, gave_up.  `ran`: the persistent recurrence did
+ * the layer; `declined`: it was not launched (ITTS_RNN_PERSISTENT=0, H != 512, device not ready, cooling down)
+ * and the per-step kernels did the layer; `gave_up`: a launch failed or came back with its abort flag set, and
+ * the per-step kernels redid the layer. */
+int itts_rnn_path_counts(int64_t out[6]);
+
 #ifdef __cplusplus
 }
 #endif

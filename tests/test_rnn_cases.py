@@ -1,0 +1,138 @@
+"""The case table of tests/rnn_cases.py reaches what it claims -- worked out from the lengths and widths alone, no
+GPU -- and the path counter of the recurrent layers (ops.rnn_path_counts) is callable without a device."""
+import os
+import subprocess
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import rnn_cases as rc  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _case(name):
+    return rc.ALL_CASES[name]
+
+
+def test_case_names_are_unique_and_sequences_short():
+    table = rc.CASES_512 + rc.CASES_WIDTHS + [rc.CASE_PADDED, rc.CASE_RNN]
+    assert len(rc.ALL_CASES) == len(table)
+    for c in table:
+        assert 1 <= min(c.lengths) and max(c.lengths) <= 21, c.name
+        assert sorted(rc.case_lengths(c)) == sorted(c.lengths), c.name
+        if len(set(c.lengths)) > 1:
+            assert rc.case_lengths(c) != sorted(c.lengths, reverse=True), c.name      # the sort has work to do
+    assert all(c.H == 512 for c in rc.CASES_512)
+
+
+def test_tile_lengths_cover_every_wrap_and_flip_of_the_exchanges():
+    seen = set()
+    for c in rc.CASES_512:
+        seen.update(rc.tiles(c)[0])
+    assert {1, 2, 3, 4, 5, 8, 9} <= seen
+    assert max(seen) >= 11
+
+
+def test_short_tiles():
+    c = _case("short_tiles")
+    t_tiles, last_rows, rounds = rc.tiles(c)
+    assert (c.ndir, len(c.lengths)) == (2, 133)
+    assert t_tiles == [11, 4, 3, 2, 1, 1, 1, 1, 1] and last_rows == 5
+    assert len(rounds) == 3
+    # a whole round that is one step long and is not the last: what the clearing between rounds exists for
+    assert rounds[1] == [1, 1, 1, 1] and len(rounds[2]) == 1
+    assert any(max(r) == 1 for r in rounds[:-1])
+
+
+def test_mid_tiles():
+    c = _case("mid_tiles")
+    t_tiles, last_rows, rounds = rc.tiles(c)
+    assert (c.ndir, len(c.lengths)) == (2, 51)
+    assert t_tiles == [9, 8, 5, 4] and last_rows == 3 and len(rounds) == 1
+
+
+def test_unidir_two_rounds():
+    c = _case("unidir_two_rounds")
+    t_tiles, last_rows, rounds = rc.tiles(c)
+    assert (c.ndir, len(c.lengths)) == (1, 129)
+    assert len(t_tiles) == 9 and last_rows == 1
+    assert [len(r) for r in rounds] == [8, 1] and rounds[1] == [1]
+    assert t_tiles[0] == 21
+
+
+def test_rounds_without_a_partial_tile():
+    for name, ndir, rows in (("unidir_full", 1, 128), ("full_round", 2, 64), ("exact_tile", 2, 16)):
+        c = _case(name)
+        t_tiles, last_rows, rounds = rc.tiles(c)
+        assert (c.ndir, len(c.lengths)) == (ndir, rows), name
+        assert last_rows == 16 and len(rounds) == 1, name
+    assert len(rc.tiles(_case("unidir_full"))[0]) == 8 and len(rc.tiles(_case("full_round"))[0]) == 4
+    full = _case("full_round")
+    assert full.lengths_none and full.batch_first and set(full.lengths) == {6}
+    assert sorted(set(_case("unidir_full").lengths)) == [1, 2, 3, 4, 5, 6, 7]
+    assert list(_case("exact_tile").lengths) == [10, 9, 8, 7, 6, 5, 4, 3, 2, 1, 10, 9, 8, 7, 6, 5]
+
+
+def test_one_step_and_one_row_cases():
+    c = _case("one_frame")
+    assert (c.ndir, len(c.lengths), set(c.lengths)) == (2, 70, {1})
+    assert [len(r) for r in rc.tiles(c)[2]] == [4, 1]                      # two one-step rounds
+    c = _case("one_frame_one_row")
+    assert (c.ndir, c.lengths) == (1, (1,))
+    assert [(_case(n).ndir, _case(n).lengths) for n in ("single_row_1dir", "single_row_2dir")] == [(1, (13,)), (2, (13,))]
+    c = _case("two_layers_states")
+    assert (c.ndir, c.layers, len(c.lengths), max(c.lengths)) == (2, 2, 20, 12) and len(set(c.lengths)) > 6
+    c = rc.CASE_PADDED
+    assert (c.ndir, c.H, len(c.lengths), max(c.lengths), dict(c.env)) == (2, 256, 20, 12, {"ITTS_RNN_PAD_HIDDEN": "1"})
+    c = rc.CASE_RNN
+    assert (c.ndir, c.H, c.layers, len(c.lengths)) == (2, 40, 2, 19) and len(set(c.lengths)) > 6
+
+
+# the launch geometry of the step kernels, as lstm.hip / gru.hip (itts_*_layer_fwd / _bwd) work it out
+def _fwd_split(H):
+    ksplit = 4 if H % 64 == 0 else (2 if H % 32 == 0 else 1)
+    return ksplit, H // (16 * ksplit)
+
+
+def _lstm_bwd_split(H):
+    ksplit = 16 if H % 64 == 0 else (8 if H % 32 == 0 else 4)
+    return ksplit, H // (4 * ksplit)
+
+
+def _gru_bwd_split(H):
+    ksplit = 12 if H % 64 == 0 else (6 if H % 32 == 0 else 3)
+    return ksplit, (3 * H // 16) // ksplit
+
+
+def test_step_kernel_widths_reach_the_recorded_splits():
+    widths = sorted({c.H for c in rc.CASES_WIDTHS})
+    assert widths == sorted(rc.STEP_SPLITS) == [48, 96, 288, 576]
+    for H in widths:
+        assert H % 16 == 0 and H != 512, H                               # the recurrence kernels' own unit, not 512
+        assert rc.STEP_SPLITS[H]["LSTM"] == (_fwd_split(H), _lstm_bwd_split(H)), H
+        assert rc.STEP_SPLITS[H]["GRU"] == (_fwd_split(H), _gru_bwd_split(H)), H
+    for cell, bwd_splits in (("LSTM", {4, 8, 16}), ("GRU", {3, 6, 12})):
+        fwd = {rc.STEP_SPLITS[H][cell][0] for H in widths}
+        assert {(1, 3), (2, 3), (2, 9), (4, 9)} <= fwd, cell            # a partly empty chunk at every ksplit
+        assert {rc.STEP_SPLITS[H][cell][1][0] for H in widths} == bwd_splits, cell
+        for H in widths:
+            assert rc.STEP_SPLITS[H][cell][1][1] in (3, 9), (cell, H)   # backward chunks of 8 too
+    for c in rc.CASES_WIDTHS:
+        assert dict(c.env) == {"ITTS_RNN_PAD_HIDDEN": "0"}, c.name
+    assert list(_case("width_48").lengths) == [13, 13, 9, 4, 1, 1, 2] * 3 and _case("width_48").ndir == 2
+    five = _case("width_576_five_tiles")
+    assert (five.ndir, five.H, len(five.lengths), len(rc.tiles(five)[0])) == (1, 576, 70, 5)
+
+
+def test_path_counts_are_zero_in_a_fresh_process_without_a_gpu():
+    code = ("import sys; sys.path.insert(0, %r)\n"
+            "from idiaptts_amd import ops\n"
+            "c = ops.rnn_path_counts()\n"
+            "assert c._fields == ('fwd_ran', 'fwd_declined', 'fwd_gave_up', 'bwd_ran', 'bwd_declined', 'bwd_gave_up')\n"
+            "assert tuple(c) == (0, 0, 0, 0, 0, 0), c\n"
+            "print('counts', tuple(c))\n" % ROOT)
+    res = subprocess.run([sys.executable, "-c", code], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                         timeout=300)
+    assert res.returncode == 0, res.stdout + res.stderr
+    assert "counts (0, 0, 0, 0, 0, 0)" in res.stdout
