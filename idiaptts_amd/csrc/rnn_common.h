@@ -1,4 +1,5 @@
-// Shared pieces of the LSTM / GRU recurrence kernels (lstm.hip, gru.hip).
+// Shared pieces of the LSTM / GRU recurrence kernels (rnn_step.h, rnn_persist.h): the scratch layouts, the cell
+// arithmetic -- written here once, called by the step kernels and by the persistent kernels -- and the host helpers.
 //
 // Memory layouts that make every operand load of a step a fully coalesced 1 KB wave access.
 // v_mfma_f32_16x16x4_f32 wants lane (lr = lane & 15, kg = lane >> 4) to hold row lr, k = kg; with
@@ -36,6 +37,64 @@ __device__ __forceinline__ float sigmoid_acc(float x) {
 }
 __device__ __forceinline__ float tanh_cell(float x) {
   return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(x * 2.88539008177792681f));
+}
+
+// ---- cell arithmetic (one thread = one (batch row, hidden unit)) --------------------------------------------------
+// torch.nn.LSTM, gate order i, f, g, o.  p* = the unit's four rows of h_{t-1} W_hh^T, x* = its input projections
+// (both biases included); c, h: previous state in, new state out; (ig, fg, gg, og) is what backward needs.
+__device__ __forceinline__ void lstm_cell_fwd(float p0, float p1, float p2, float p3, float x0, float x1, float x2,
+                                              float x3, float& c, float& h, float& ig, float& fg, float& gg,
+                                              float& og) {
+  ig = sigmoid_acc(p0 + x0);
+  fg = sigmoid_acc(p1 + x1);
+  gg = tanh_cell(p2 + x2);
+  og = sigmoid_acc(p3 + x3);
+  c = fg * c + ig * gg;
+  h = og * tanh_cell(c);
+}
+
+// torch.nn.GRU, gate order r, z, n:
+//   r = sigmoid(gin_r + W_hr h + b_hr)      z = sigmoid(gin_z + W_hz h + b_hz)
+//   n = tanh(gin_n + r * (W_hn h + b_hn))   h' = (1 - z) * n + z * h
+// p* = h_{t-1} W_hh^T, x* = input projections (b_ih included), b* = b_hh; saved for backward: (r, z, n, W_hn h + b_hn)
+__device__ __forceinline__ void gru_cell_fwd(float p0, float p1, float p2, float x0, float x1, float x2, float b0,
+                                             float b1, float b2, float& h, float& rg, float& zg, float& ng,
+                                             float& hnp) {
+  rg = sigmoid_acc(x0 + p0 + b0);
+  zg = sigmoid_acc(x1 + p1 + b1);
+  hnp = p2 + b2;
+  ng = tanh_cell(x2 + rg * hnp);
+  h = (1.f - zg) * ng + zg * h;
+}
+
+// LSTM gate gradients of one step: the saved gates, c_t and c_{t-1}, dh = dy + dG(s + 1) W_hh; carry: the dc that
+// step s + 1 left (dc * f there) in, this step's out; d0 .. d3: gradient wrt the pre-activations of i, f, g, o.
+__device__ __forceinline__ void lstm_cell_bwd(float ig, float fg, float gg, float og, float ct, float cp, float dh,
+                                              float& carry, float& d0, float& d1, float& d2, float& d3) {
+  const float tc = tanh_cell(ct);
+  const float dcv = dh * og * (1.f - tc * tc) + carry;
+  d0 = dcv * gg * ig * (1.f - ig);
+  d1 = dcv * cp * fg * (1.f - fg);
+  d2 = dcv * ig * (1.f - gg * gg);
+  d3 = dh * tc * og * (1.f - og);
+  carry = dcv * fg;
+}
+
+// GRU gate gradients of one step: the saved (r, z, n, W_hn h + b_hn), h_{t-1}, dydh = dy + dGh(s + 1) W_hh; carry:
+// dh * z of step s + 1 in, of this step out.
+//   dh   = dydh + carry       dn = dh (1 - z)      dz = dh (h_prev - n)
+//   da_n = dn (1 - n^2)       da_r = da_n * hn_pre * r (1 - r)      da_z = dz * z (1 - z)
+// dGi = (da_r, da_z, da_n) is the gradient wrt gin, dGh = (da_r, da_z, da_n * r) wrt the hidden projections.
+__device__ __forceinline__ void gru_cell_bwd(float rg, float zg, float ng, float hnp, float hp, float dydh,
+                                             float& carry, float& dar, float& daz, float& dan, float& danr) {
+  const float dh = dydh + carry;
+  const float dn = dh * (1.f - zg);
+  const float dz = dh * (hp - ng);
+  dan = dn * (1.f - ng * ng);
+  dar = dan * hnp * rg * (1.f - rg);
+  daz = dz * zg * (1.f - zg);
+  danr = dan * rg;
+  carry = dh * zg;
 }
 
 // Forward tiling of W_hh [ndir][G*H][H] (G = 3 or 4 gates) for workgroups of 4 hidden units:
@@ -123,38 +182,4 @@ static inline std::vector<int> rnn_row_offsets(const int* h_lengths, int T, int 
   int q = B;
   for (int t = 0; t < T; ++t) row_off[t + 1] = row_off[t] + rnn_active_rows(h_lengths, B, t, &q);
   return row_off;
-}
-
-// Forward recurrence on the step kernels: one launch per step, kernels[n - 1] taking n batch tiles of 16
-// rows per pass (the cell's step kernel for NT = 1 .. 4).
-template <class Args>
-static void rnn_fwd_steps(void (*const kernels[4])(Args), Args& a, const int* h_lengths, dim3 grid, hipStream_t s) {
-  int p = a.B;
-  int row_base = 0;
-  for (int step = 0; step < a.T; ++step) {
-    a.step = step;
-    a.nact = rnn_active_rows(h_lengths, a.B, step, &p);
-    a.row_base = row_base;          // row_off[step] = rows active in all earlier steps
-    row_base += a.nact;
-    hipLaunchKernelGGL(kernels[std::min((a.nact + 15) / 16, 4) - 1], grid, dim3(256), 0, s, a);
-  }
-}
-
-// Backward recurrence on the step kernels, steps T - 1 .. 0: workgroups of `units` hidden units x one
-// 16-row batch tile, 64 * a.ksplit threads each -- and never fewer than the 256 the cell update of a tile takes (the
-// GRU's ksplit = 3: with 192 threads rows 12 .. 15 of every tile were left out).
-template <class Args>
-static void rnn_bwd_steps(void (*kernel)(Args), int units, Args& a, const int* h_lengths, hipStream_t s) {
-  const std::vector<int> row_off = rnn_row_offsets(h_lengths, a.T, a.B);
-  int p = 0, nact_next = 0;
-  for (int step = a.T - 1; step >= 0; --step) {
-    a.step = step;
-    a.nact = rnn_active_rows(h_lengths, a.B, step, &p);
-    a.nact_next = nact_next;
-    nact_next = a.nact;
-    a.row_base = row_off[step];
-    a.row_base_prev = step > 0 ? row_off[step - 1] : 0;
-    hipLaunchKernelGGL(kernel, dim3((a.H / units) * ((a.nact + 15) / 16), a.ndir), dim3(std::max(64 * a.ksplit, 256)),
-                       0, s, a);
-  }
 }

@@ -1,7 +1,7 @@
-// Persistent recurrences of the LSTM / GRU layers (included by lstm.hip and gru.hip): what
+// Persistent recurrences of the LSTM / GRU layers (included by rnn.hip): what
 // torch.nn.LSTM / GRU do between pack_padded_sequence and pad_packed_sequence in
 // rnn_dyn/RNNWrapper.py:89-102 and what autograd does on the way back -- one launch per layer for
-// the forward recurrence, one for the backward recurrence (the step kernels of lstm.hip / gru.hip
+// the forward recurrence, one for the backward recurrence (the step kernels of rnn_step.h
 // remain for other sizes and as the fallback).
 #pragma once
 #include <atomic>
@@ -268,18 +268,16 @@ __global__ __launch_bounds__(256) void rnn_persist_fwd_kernel(RnnPersistArgs a) 
                (Pp[((2 * 4 + gg) * 16 + r) * 17 + u] + Pp[((3 * 4 + gg) * 16 + r) * 17 + u]);
       };
       if (G == 4) {
-        const float ig = sigmoid_acc(pre(0) + g0), fg = sigmoid_acc(pre(1) + g1), gg_ = tanh_cell(pre(2) + g2),
-                    og = sigmoid_acc(pre(3) + g3);
-        c = fg * c + ig * gg_;
-        h = og * tanh_cell(c);
+        float ig, fg, gg_, og;
+        lstm_cell_fwd(pre(0), pre(1), pre(2), pre(3), g0, g1, g2, g3, c, h, ig, fg, gg_, og);
         a.y[row * ldh + (size_t)dir * H + j] = h;
         if (a.gates) {
           reinterpret_cast<float4*>(a.gates)[(row * a.ndir + dir) * H + j] = make_float4(ig, fg, gg_, og);
           a.csave[row * ldh + (size_t)dir * H + j] = c;
         }
       } else {
-        // torch.nn.GRU: r, z from both projections, n = tanh(gin_n + r (W_hn h + b_hn)); saved for
-        // backward as (r, z, n, W_hn h + b_hn)
+        // gru_cell_fwd of rnn_common.h, written out: called from here, the compiler orders this kernel's
+        // instructions differently (and the gate gradients of the backward kernel below likewise)
         const float rg = sigmoid_acc(g0 + pre(0) + bh0), zg = sigmoid_acc(g1 + pre(1) + bh1);
         const float hnp = pre(2) + bh2;
         const float ng = tanh_cell(g2 + rg * hnp);
@@ -389,9 +387,9 @@ static void persist_ran(PersistDevices& table, int dev) {
   d.give_ups = 0;
 }
 
-// Which way the layer calls of this process went (itts_rnn_path_counts, lstm.hip): `ran` = persist_run returned 1,
+// Which way the layer calls of this process went (itts_rnn_path_counts, rnn.hip): `ran` = persist_run returned 1,
 // `declined` = it returned 0 without launching (switched off, H != 512, device not ready, cooling down), `gave_up` =
-// the abort flag came back set or a launch failed.  One pair for the whole library: lstm.hip and gru.hip share it.
+// the abort flag came back set or a launch failed.  One pair for both cells.
 struct PersistPathCounts {
   std::atomic<int64_t> ran{0}, declined{0}, gave_up{0};
 };
@@ -464,7 +462,7 @@ static int rnn_persist_forward(RnnPersistArgs p, int H, hipStream_t s) {
 
 // ---- persistent backward recurrence, same placement (G = 4: LSTM, G = 3: GRU) ---------------------
 // Step s (T_tile - 1 ... 0) of row b:  dh = dy + dG(s + 1) W_hh (+ the GRU's dh z carry),  then the
-// cell gradients (lstm.hip, lstm_step_bwd_kernel; gru.hip, gru_step_bwd_kernel).  dG is G gates
+// cell gradients (lstm_cell_bwd / gru_cell_bwd of rnn_common.h, written out below).  dG is G gates
 // wide, so handing it around as the forward kernel hands h around would multiply the exchange by G;
 // instead the product is split along K: workgroup c multiplies ITS OWN 16 G gate values per row (kept
 // in LDS, never exchanged) with its 16 G rows of W_hh (a G x 32 KB LDS image: [column tile 32][gate]

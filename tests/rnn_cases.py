@@ -59,7 +59,7 @@ CASES_WIDTHS = [_case("width_%d" % H, 2, WIDTH_LENGTHS, H=H, env=_NO_PAD) for H 
     # five tiles in one direction: the NT = 4 instantiation of the forward step kernel makes a second pass
     _case("width_576_five_tiles", 1, [6, 5, 4, 3, 2, 1, 1] * 10, H=576, env=_NO_PAD)]
 
-# (ksplit, kiter) of the forward and of the backward step kernel these widths are meant to reach (lstm.hip / gru.hip:
+# (ksplit, kiter) of the forward and of the backward step kernel these widths are meant to reach (rnn_step.h:
 # the forward K loop runs kiter steps in chunks of 8 with `c + s < kiter` guards, so 3 and 9 leave a chunk partly empty)
 STEP_SPLITS = {
     48: {"LSTM": ((1, 3), (4, 3)), "GRU": ((1, 3), (3, 3))},

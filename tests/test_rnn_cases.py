@@ -89,7 +89,7 @@ def test_one_step_and_one_row_cases():
     assert (c.ndir, c.H, c.layers, len(c.lengths)) == (2, 40, 2, 19) and len(set(c.lengths)) > 6
 
 
-# the launch geometry of the step kernels, as lstm.hip / gru.hip (itts_*_layer_fwd / _bwd) work it out
+# the launch geometry of the step kernels, as rnn_step.h (rnn_step_forward / rnn_step_backward) works it out
 def _fwd_split(H):
     ksplit = 4 if H % 64 == 0 else (2 if H % 32 == 0 else 1)
     return ksplit, H // (16 * ksplit)
