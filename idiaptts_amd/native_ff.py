@@ -76,7 +76,7 @@ class FlatFFModel:
     def from_module(model, device=None):
         """Mirror of a drop-in module stack (NamedForwardWrapper / RNNDyn) that consists of Linear
         groups only: same weights, flat buffers.  Returns None when the model has anything else
-        (recurrent groups, Conv1d groups, dropout) -- those train through the module path."""
+        (recurrent groups, Conv1d groups, LayerNorm groups, dropout) -- those train through the module path."""
         from .nn.modules import LinearAct
         inner = getattr(model, "model", model)
         layers, acts = [], []

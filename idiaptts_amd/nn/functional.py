@@ -134,6 +134,59 @@ class Conv1dActFunction(torch.autograd.Function):
         return dx, dw, (db if ctx.has_bias else None), None, None, None, None
 
 
+class LayerNormActFunction(torch.autograd.Function):
+    """y = act(layer_norm(x) * weight + bias) over the last extent (any leading shape); rnn_dyn/FFWrapper.py: a
+    LayerNorm group, torch.nn.LayerNorm + the group's non-linearity.  Saves x, mean and rstd, and y only under an
+    activation (its derivative goes through y).  2-D rows stay rows with a 16-byte pitch, like the outputs inside
+    a LinearChainFunction: an input of D rounded up to a multiple of four columns (and not D itself: what
+    ValidRows.pack hands out, pad columns zero) is taken as rows of D columns, and the [N, D] result is a view of
+    rows of that pitch, so the GEMMs of a following Linear group take their 16-byte loads."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, D, eps, act):
+        shape = x.shape
+        ctx.col_pad = 0
+        if x.dim() == 2:
+            x2 = x
+            if shape[1] != D and shape[1] == (D + 3) // 4 * 4:
+                ctx.col_pad = shape[1] - D
+                x2 = x[:, :D]
+        else:
+            x2 = x.reshape(-1, shape[-1])
+        if x2.shape[1] != D:
+            raise RuntimeError("LayerNorm over {} features got an input of {} (shape {})"
+                               .format(D, x2.shape[1], tuple(shape)))
+        if x2.stride(-1) != 1:
+            x2 = x2.contiguous()
+        y, mean, rstd = ops.layer_norm_fwd(x2, weight, bias, eps, act, out=_rows_padded(x2.shape[0], D, x2.device))
+        ctx.save_for_backward(x2, mean, rstd, weight if weight is not None else x2.new_empty(0),
+                              y if act != ops.ACT_NONE else x2.new_empty(0))
+        ctx.act, ctx.in_shape = act, shape
+        ctx.has = (weight is not None, bias is not None)
+        return y if x.dim() == 2 else y.contiguous().reshape(shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, mean, rstd, weight, y = ctx.saved_tensors
+        has_weight, has_bias = ctx.has
+        M, D = x2.shape
+        dy2 = dy if dy.dim() == 2 else dy.reshape(-1, D)
+        if dy2.stride(-1) != 1 or (M > 1 and dy2.stride(0) < D):     # (an expanded gradient: rows of stride 0)
+            dy2 = dy2.contiguous()
+        full = torch.empty((M, (D + 3) // 4 * 4), dtype=torch.float32, device=x2.device)
+        if full.shape[1] != D:
+            full[:, D:] = 0
+        dx, dw, db = ops.layer_norm_bwd(dy2, x2, mean, rstd, weight if has_weight else None,
+                                        y=y if ctx.act != ops.ACT_NONE else None, act=ctx.act,
+                                        want_gamma=has_weight and ctx.needs_input_grad[1],
+                                        want_beta=has_bias and ctx.needs_input_grad[2], dx=full[:, :D])
+        if len(ctx.in_shape) != 2:
+            dx = dx.contiguous().reshape(ctx.in_shape)
+        elif ctx.col_pad:
+            dx = full
+        return (dx if ctx.needs_input_grad[0] else None), dw, db, None, None, None
+
+
 def _rows_padded(M, N, device):
     """[M, N] view of a fresh buffer whose row pitch is N rounded up to four floats, pad columns zero"""
     Np = (N + 3) // 4 * 4

@@ -8,8 +8,8 @@ import torch
 from torch import nn
 
 from .. import ops
-from .functional import (Conv1dActFunction, GRULayerFunction, LinearActFunction, LSTMLayerFunction, PackedBatch,
-                         StatesToCallerOrder)
+from .functional import (Conv1dActFunction, GRULayerFunction, LayerNormActFunction, LinearActFunction,
+                         LSTMLayerFunction, PackedBatch, StatesToCallerOrder)
 
 
 class LinearAct(nn.Linear):
@@ -61,8 +61,35 @@ class Conv1dAct(nn.Conv1d):
         return lengths + 2 * self.padding[0] - self.dilation[0] * (self.kernel_size[0] - 1)
 
 
+class LayerNormAct(nn.LayerNorm):
+    """torch.nn.LayerNorm over the last extent (same parameters `weight` / `bias`, ones and zeros) whose
+    forward/backward run the row kernels of csrc/layernorm.hip; `act` (as LinearAct's) fuses the following
+    activation of an FFWrapper group.  `normalized_shape` is an int or a one-element list / tuple of at most
+    ops.LAYER_NORM_MAX_WIDTH; the input is [N, D] rows or a padded batch [B, T, D] / [T, B, D] (any leading shape).
+    CPU tensors go through torch.nn.functional.layer_norm and the torch activation."""
+
+    def __init__(self, normalized_shape, eps=1e-5, elementwise_affine=True, bias=True, act=None, **kwargs):
+        code = ops.act_code(act, where="LayerNorm")
+        if isinstance(normalized_shape, (tuple, list, torch.Size)) and len(normalized_shape) != 1:
+            raise NotImplementedError("LayerNorm normalized_shape={}: only the last dimension is normalised"
+                                      .format(tuple(normalized_shape)))
+        width = int(_first(normalized_shape))
+        if not 1 <= width <= ops.LAYER_NORM_MAX_WIDTH:
+            raise NotImplementedError("LayerNorm over {} features: the kernel takes 1 .. {}"
+                                      .format(width, ops.LAYER_NORM_MAX_WIDTH))
+        super().__init__(normalized_shape, eps=eps, elementwise_affine=elementwise_affine, bias=bias, **kwargs)
+        self.act = code
+
+    def forward(self, input_):
+        if not input_.is_cuda:
+            y = torch.nn.functional.layer_norm(input_, self.normalized_shape, self.weight, self.bias, self.eps)
+            return y if self.act == ops.ACT_NONE else getattr(nn, ops.ACT_TORCH_NAME[self.act])()(y)
+        return LayerNormActFunction.apply(input_, self.weight, self.bias, self.normalized_shape[0], self.eps,
+                                          self.act)
+
+
 def _first(v):
-    return v[0] if isinstance(v, (tuple, list)) else v
+    return v[0] if isinstance(v, (tuple, list, torch.Size)) else v
 
 
 _cu_count = {}

@@ -852,6 +852,56 @@ def masked_mse(pred, target, row_valid, n_valid, loss_weight=1.0, want_grad=True
     return loss, (grad if want_grad else None)
 
 
+LAYER_NORM_MAX_WIDTH = 4096      # LN_MAX_D of csrc/layernorm.hip
+
+
+def layer_norm_fwd(x, gamma, beta, eps=1e-5, act=ACT_NONE, out=None):
+    """torch.nn.LayerNorm over the last extent of [N, D] rows (+ the activation `act`): (y, mean [N], rstd [N]);
+    gamma / beta [D] or None (rnn_dyn/FFWrapper.py: a LayerNorm group)."""
+    L = _lib.load()
+    _need(x, torch.float32, "x")
+    ldx = _rows(x, "x")
+    N, D = x.shape
+    for name, t in (("gamma", gamma), ("beta", beta)):
+        if t is not None:
+            _need(t, torch.float32, name)
+            if t.shape != (D,) or not t.is_contiguous():
+                raise ValueError("{} must be a contiguous [{}] vector".format(name, D))
+    if out is None:
+        out = torch.empty((N, D), dtype=torch.float32, device=x.device)
+    stats = torch.empty((2, N), dtype=torch.float32, device=x.device)
+    _lib.check(L.itts_layernorm_fwd(_ptr(x), ldx, _ptr(gamma), _ptr(beta), _ptr(out), _rows(out, "out"),
+                                    _ptr(stats[0]), _ptr(stats[1]), N, D, float(eps), int(act), _stream()),
+               "itts_layernorm_fwd")
+    return out, stats[0], stats[1]
+
+
+def layer_norm_bwd(dy, x, mean, rstd, gamma, y=None, act=ACT_NONE, want_gamma=True, want_beta=True, dx=None):
+    """(dx, dgamma or None, dbeta or None) of layer_norm_fwd; `y` (the forward's output) is needed under an
+    activation only.  The column sums go through per-workgroup slabs reduced in a fixed order."""
+    L = _lib.load()
+    _need(dy, torch.float32, "dy")
+    _need(x, torch.float32, "x")
+    N, D = x.shape
+    if dy.shape != x.shape:
+        raise ValueError("dy must have the shape of x")
+    if act != ACT_NONE and y is None:
+        raise ValueError("layer_norm_bwd under an activation needs the forward's output y")
+    if dx is None:
+        dx = torch.empty((N, D), dtype=torch.float32, device=x.device)
+    dgamma = torch.empty((D,), dtype=torch.float32, device=x.device) if want_gamma else None
+    dbeta = torch.empty((D,), dtype=torch.float32, device=x.device) if want_beta else None
+    ws = None
+    if want_gamma or want_beta:
+        ws = _workspace(max(L.itts_layernorm_workspace_bytes(N, D), 8), x.device)
+    _lib.check(L.itts_layernorm_bwd(_ptr(dy), _rows(dy, "dy"), _ptr(x), _rows(x, "x"),
+                                    _ptr(y) if act != ACT_NONE else None,
+                                    _rows(y, "y") if act != ACT_NONE else 0, _ptr(mean), _ptr(rstd), _ptr(gamma),
+                                    _ptr(dx), _rows(dx, "dx"), _ptr(dgamma), _ptr(dbeta), N, D, int(act), _ptr(ws),
+                                    _stream()), "itts_layernorm_bwd")
+    return dx, dgamma, dbeta
+
+
 def weighted_loss(pred, target, row_weight, kind, want_grad=True, want_elem=False):
     """sum_r w[r] sum_c e(pred - target) on [M, D] rows, e squared (kind 0) / absolute (kind 1)
     error: (loss [1], grad or None, elementwise values or None)."""

@@ -1,6 +1,7 @@
 """rnn_dyn.Config / LayerConfig with the reference's fields
 (idiaptts/src/neural_networks/pytorch/models/rnn_dyn/Config.py:12-138), restricted to the layer
-types on the accelerated path: Linear (+ activation, RNNDyn.LINEAR_NONLINS) groups, LSTM / GRU / RNN groups and Conv1d groups."""
+types on the accelerated path: Linear (+ activation, RNNDyn.LINEAR_NONLINS) groups, LSTM / GRU / RNN groups, Conv1d
+groups and LayerNorm (+ activation) groups; LayerNorm takes no in_dim and has no spelling in the legacy model string."""
 import copy
 import re
 from typing import List

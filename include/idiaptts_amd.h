@@ -474,6 +474,31 @@ int itts_conv1d_bwd_weight(const float* d_dz, int64_t lddz, const float* d_x, in
 int itts_conv1d_plan(int product, int B, int T_in, int Cin, int Cout, int Kw, int pad, int dil, int vec,
                      int* tile_cols, int* slabs, int64_t* kchunk);
 
+/* ---- LayerNorm layer groups (rnn_dyn/FFWrapper.py: torch.nn.LayerNorm(normalized_shape=D) + the group's
+ *      non-linearity; csrc/layernorm.hip) --------------------------------------------------------
+ * y[N,D] = act((x - mean) * rstd * gamma + beta) per row: mean and the biased variance over the row's D
+ * columns (two passes, on the centred values), rstd = 1 / sqrt(var + eps); d_mean / d_rstd [N] receive
+ * them for the backward.  d_gamma / d_beta [D] may each be NULL (elementwise_affine=False, bias=False);
+ * act is any ITTS_ACT_* code.  1 <= D <= 4096, anything wider is refused before any device work.
+ * Row pitches ld* >= D; pitches that are multiples of 4 floats on 16-byte aligned bases select 16-byte
+ * loads and stores (whatever lies between D and the pitch is read and dropped, never written).  A row's
+ * result depends on nothing but the row: the same bits for any N, any position and either load form. */
+int itts_layernorm_fwd(const float* d_x, int64_t ldx, const float* d_gamma, const float* d_beta,
+                       float* d_y, int64_t ldy, float* d_mean, float* d_rstd, int64_t N, int D,
+                       double eps, int act, void* stream);
+/* With dy' = dy * act'(y) (through the forward's output y; d_y may be NULL for ITTS_ACT_NONE),
+ * g = dy' * gamma and xhat = (x - mean) * rstd:
+ *   dx = rstd * (g - mean_D(g) - xhat * mean_D(g * xhat)),  dgamma = sum_rows dy' * xhat,  dbeta = sum_rows dy'.
+ * d_dgamma / d_dbeta [D] may each be NULL; when either is given, d_workspace holds
+ * itts_layernorm_workspace_bytes(N, D) bytes: one slab of 2 * D floats per workgroup of
+ * 32 * ceil(N / 32768) rows, summed in a fixed order by a second launch (no atomics: repeated calls give
+ * identical bits). */
+int64_t itts_layernorm_workspace_bytes(int64_t N, int D);
+int itts_layernorm_bwd(const float* d_dy, int64_t lddy, const float* d_x, int64_t ldx,
+                       const float* d_y, int64_t ldy, const float* d_mean, const float* d_rstd,
+                       const float* d_gamma, float* d_dx, int64_t lddx, float* d_dgamma,
+                       float* d_dbeta, int64_t N, int D, int act, void* d_workspace, void* stream);
+
 /* ---- masked MSE, reduction 'mean_per_frame' (loss/NamedLoss.py:70-117) -------------------- */
 /*
  * loss = mean_d( sum_{valid frames} (pred-target)^2 / n_valid ), grad = dloss/dpred.
