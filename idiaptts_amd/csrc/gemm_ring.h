@@ -11,9 +11,13 @@
 //     of three 24-KB slots, two K-steps ahead of the compute waves and straight across tile
 //     boundaries, so neither the first loads of a tile nor its epilogue expose memory latency; its
 //     counted `s_waitcnt vmcnt(6)` is the only wait on that traffic.  (The DMA is inline asm: hipcc
-//     would otherwise drain it with vmcnt(0) in front of every ds_read of the ring.)  The compute
-//     waves issue no memory instruction inside the K loop except ds_read, and their epilogue
-//     stores are never waited for;
+//     would otherwise drain it with vmcnt(0) in front of every ds_read of the ring.)  Inside the
+//     K loop the compute waves issue ds_reads and, with the EPI_DACT and EPI_MSE epilogues, at a
+//     tile's first K-step the global loads of what its epilogue will combine with the accumulators
+//     (the previous layer's output; the target, row_valid and the bias -- EpiOperands below): the
+//     epilogue of a tile of 6 or 16 K-steps would otherwise wait a whole memory latency for them
+//     on all four compute waves.  They are waited for with counted vmcnts behind the next tile
+//     boundary; the epilogue's stores are never waited for;
 //   * one workgroup barrier per K-step (everybody has left step s-1, whose slot the loaders refill
 //     next; the loaders have seen step s land);
 //   * row-form tiles [out][32 k] are stored unpadded (the DMA writes lane-linear) with the 16-byte
@@ -45,8 +49,8 @@
 #include "activations.h"
 
 #ifndef RING_DBG
-#define RING_DBG 0   // lab only: 1 no DMA, 2 no step barrier, 4 no MFMA, 8 no epilogue, 16 no fragment reads
-#endif
+#define RING_DBG 0   // lab only: 1 no DMA, 2 no step barrier, 4 no MFMA, 8 no epilogue, 16 no fragment reads,
+#endif               //           32 constants for the epilogue's early operands (no global loads), 64 no stores
 
 namespace itts {
 namespace ring {
@@ -387,9 +391,76 @@ __device__ __forceinline__ float4 load_bias(const Args& g, int n0, int wn, int l
   return bv;
 }
 
+// Operands of a tile's epilogue that do not depend on its accumulators, fetched at the tile's FIRST
+// K-step into registers that live across the tile boundary (fetch_epilogue_operands) and consumed
+// behind the first barrier of the next tile.  A compile-time property of the epilogue kind: the
+// other kinds carry nothing and compile to the code they had without it.
+// EPI_MSE: all eight target segments early would take the K loop beyond the 128 registers of a wave
+// (two workgroups per CU): six are fetched early, the last two at the head of the epilogue, which
+// uses them last, behind the arithmetic and the stores of the other six.  With six the kernel takes
+// 124 of the 128 registers: there is no room for more state in that epilogue or its K loop.
+constexpr int kMseEarly = 6;
+template <int EPI>
+struct EpiOperands {};
+template <>
+struct EpiOperands<EPI_DACT> {
+  f32x4 y[8];        // the previous layer's output at the lane's eight float4 row segments
+};
+template <>
+struct EpiOperands<EPI_MSE> {
+  float t[4 * kMseEarly];   // the target, dword-wise (any pitch), of the first kMseEarly row segments
+  uint8_t rv;        // row_valid of row wm * 64 + lane of the tile (row 0's for rows >= M): one register,
+                     // the epilogue spreads it over the wave's rows with a ballot
+  float4 bv;
+};
+template <int EPI>
+constexpr bool kEarlyOperands = EPI == EPI_DACT || EPI == EPI_MSE;
+
+template <int EPI>
+__device__ __forceinline__ void fetch_epilogue_operands(const Args& g, const Tile& c, int wm, int wn, int lane,
+                                                        EpiOperands<EPI>& e) {
+  if constexpr (kEarlyOperands<EPI>) {
+    const int quad = (lane & 31) >> 2, j = lane & 3, h = lane >> 5;
+    const int col = c.n0 + wn * 32 + 4 * quad;
+    const int rloc = wm * 64 + 4 * h + j;          // + 32 i + 8 rg
+    int rows_valid = g.M - c.m0;
+    rows_valid = rows_valid < 0 ? 0 : rows_valid;
+    // the descriptor and the offsets are the epilogue's own: rows >= M arrive as zeros
+    const __amdgpu_buffer_rsrc_t rx =
+        make_rsrc(g.aux + (int64_t)c.m0 * g.ldaux, (uint32_t)((int64_t)rows_valid * g.ldaux * 4));
+    if constexpr (EPI == EPI_MSE) {
+      e.bv = load_bias<EPI>(g, c.n0, wn, lane);
+      const int row = c.m0 + wm * 64 + lane;
+      e.rv = (RING_DBG & 32) ? 1 : g.row_valid[row < g.M ? row : 0];
+    }
+#pragma unroll
+    for (int s = 0; s < (EPI == EPI_MSE ? kMseEarly : 8); ++s) {
+      const int rl = (s >> 2) * 32 + 8 * (s & 3);   // uniform part of the row
+      const uint32_t so = (uint32_t)(rl * g.ldaux * 4);
+      if constexpr (EPI == EPI_DACT) {
+        const uint32_t xofs = col < g.ldaux ? (uint32_t)((rloc * g.ldaux + col) * 4) : 0xfffffff0u;
+        if (RING_DBG & 32) e.y[s] = f32x4{0.5f, 0.25f, -0.5f, 0.125f};
+        else e.y[s] = __builtin_amdgcn_raw_buffer_load_b128(rx, xofs, so, 0);
+      } else {
+        // the target may have any pitch (e.g. 187 floats): four dword loads, not one 16-byte load
+        const uint32_t tofs = (uint32_t)((rloc * g.ldaux + col) * 4);
+        if (RING_DBG & 32) {
+          e.t[4 * s] = 0.5f; e.t[4 * s + 1] = 0.25f; e.t[4 * s + 2] = -0.5f; e.t[4 * s + 3] = 0.125f;
+        } else {
+          e.t[4 * s] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, tofs, so, 0));
+          e.t[4 * s + 1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, tofs + 4, so, 0));
+          e.t[4 * s + 2] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, tofs + 8, so, 0));
+          e.t[4 * s + 3] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, tofs + 12, so, 0));
+        }
+      }
+    }
+  }
+}
+
 template <int EPI, int ACT>
 __device__ __forceinline__ void epilogue(const Args& g, const Tile& pc, const f32x16& acc0, const f32x16& acc1,
-                                         int wm, int wn, int lane, const float4& bv, double& lsum) {
+                                         int wm, int wn, int lane, const float4& bv, double& lsum,
+                                         const EpiOperands<EPI>& eo) {
   const int quad = (lane & 31) >> 2, j = lane & 3, h = lane >> 5;
   const int col = pc.n0 + wn * 32 + 4 * quad;
   const int rloc = wm * 64 + 4 * h + j;          // + 32 i + 8 rg
@@ -400,13 +471,28 @@ __device__ __forceinline__ void epilogue(const Args& g, const Tile& pc, const f3
   float* Cb = g.C + (int64_t)pc.z * g.slab_stride + (int64_t)pc.m0 * g.ldc;
   const __amdgpu_buffer_rsrc_t rc = make_rsrc(Cb, (uint32_t)((int64_t)rows_valid * g.ldc * 4));
   const uint32_t cofs = col < g.ldc ? (uint32_t)((rloc * g.ldc + col) * 4) : 0xfffffff0u;
-  __amdgpu_buffer_rsrc_t rx = rc;
-  uint32_t xofs = 0;
-  if (EPI == EPI_DACT || EPI == EPI_MSE) {
-    rx = make_rsrc(g.aux + (int64_t)pc.m0 * g.ldaux, (uint32_t)((int64_t)rows_valid * g.ldaux * 4));
-    xofs = col < g.ldaux ? (uint32_t)((rloc * g.ldaux + col) * 4) : 0xfffffff0u;
-  }
   const bool k0 = col < g.N, k1 = col + 1 < g.N, k2 = col + 2 < g.N, k3 = col + 3 < g.N;
+  uint64_t okrows = 0;   // EPI_MSE: bit r = row wm * 64 + r of the tile is inside M and valid
+  float tl[4 * (8 - kMseEarly)] = {};   // EPI_MSE: the target segments that were not fetched early
+  if constexpr (EPI == EPI_MSE) {
+    const __amdgpu_buffer_rsrc_t rx =
+        make_rsrc(g.aux + (int64_t)pc.m0 * g.ldaux, (uint32_t)((int64_t)rows_valid * g.ldaux * 4));
+    const uint32_t tofs = (uint32_t)((rloc * g.ldaux + col) * 4);
+#pragma unroll
+    for (int s = kMseEarly; s < 8; ++s) {
+      const uint32_t so = (uint32_t)(((s >> 2) * 32 + 8 * (s & 3)) * g.ldaux * 4);
+      float* t = tl + 4 * (s - kMseEarly);
+      if (RING_DBG & 32) {
+        t[0] = 0.5f; t[1] = 0.25f; t[2] = -0.5f; t[3] = 0.125f;
+      } else {
+        t[0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, tofs, so, 0));
+        t[1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, tofs + 4, so, 0));
+        t[2] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, tofs + 8, so, 0));
+        t[3] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, tofs + 12, so, 0));
+      }
+    }
+    okrows = __ballot(pc.m0 + wm * 64 + lane < g.M && eo.rv != 0);
+  }
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const f32x16& a = i == 0 ? acc0 : acc1;
@@ -418,24 +504,15 @@ __device__ __forceinline__ void epilogue(const Args& g, const Tile& pc, const f3
         v.x = act1<ACT>(v.x + bv.x); v.y = act1<ACT>(v.y + bv.y);
         v.z = act1<ACT>(v.z + bv.z); v.w = act1<ACT>(v.w + bv.w);
       }
-      if (EPI == EPI_DACT) {
-        const f32x4 y = __builtin_amdgcn_raw_buffer_load_b128(rx, xofs, rl * g.ldaux * 4, 0);
+      if constexpr (EPI == EPI_DACT) {
+        const f32x4 y = eo.y[4 * i + rg];   // fetched at the tile's first K-step
         v.x *= dact1<ACT>(y[0]); v.y *= dact1<ACT>(y[1]);
         v.z *= dact1<ACT>(y[2]); v.w *= dact1<ACT>(y[3]);
       }
-      if (EPI == EPI_MSE) {
-        // the target may have any pitch (e.g. 187 floats): four dword loads, not one 16-byte load
-        f32x4 t;
-        {
-          const uint32_t so = (uint32_t)(rl * g.ldaux * 4);
-          const uint32_t tofs = (uint32_t)((rloc * g.ldaux + col) * 4);
-          t[0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, tofs, so, 0));
-          t[1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, tofs + 4, so, 0));
-          t[2] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, tofs + 8, so, 0));
-          t[3] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, tofs + 12, so, 0));
-        }
-        const int row = pc.m0 + rloc + rl;
-        const bool ok = row < g.M && g.row_valid[row < g.M ? row : 0] != 0;
+      if constexpr (EPI == EPI_MSE) {
+        // target and row_valid (and bv) were fetched at the tile's first K-step
+        const float* t = 4 * i + rg < kMseEarly ? eo.t + 4 * (4 * i + rg) : tl + 4 * (4 * i + rg - kMseEarly);
+        const bool ok = ((uint32_t)(okrows >> (32 * i)) >> (4 * h + j + 8 * rg)) & 1u;
         const float d0 = ok && k0 ? (v.x + bv.x) - t[0] : 0.f;
         const float d1 = ok && k1 ? (v.y + bv.y) - t[1] : 0.f;
         const float d2 = ok && k2 ? (v.z + bv.z) - t[2] : 0.f;
@@ -483,11 +560,13 @@ __device__ __forceinline__ void compute_waves(const Args& g, char* lds, int wid,
 #pragma unroll
   for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
   float bsum = 0.f;
+  EpiOperands<EPI> eo{};     // of the tile whose K loop runs, then of the pending tile
 
   int ct = w.first;
   bool have = ct < w.end;
   Tile c{};
   if (have) c = decode_tile<GROUPED>(g, ct, BMT, BNT);
+  if (kEarlyOperands<EPI> && have) fetch_epilogue_operands<EPI>(g, c, wm, wn, lane, eo);   // the first tile's
   int kt = 0;
   while (have || pending) {
     // step entry: behind the barrier the slot of this step is complete and everybody has left the
@@ -509,16 +588,25 @@ __device__ __forceinline__ void compute_waves(const Args& g, char* lds, int wid,
         for (int r = 0; r < 16; ++r) t += acc0[r] + acc1[r];
         if (t == 1.2345f) g.C[0] = t;
       } else {
-        const float4 bv = load_bias<EPI>(g, pc.n0, wn, lane);
+        float4 bv;
+        if constexpr (EPI == EPI_MSE) bv = eo.bv;
+        else bv = load_bias<EPI>(g, pc.n0, wn, lane);
         if (AF == AF_EXT && (EPI == EPI_BIAS_ACT || EPI == EPI_DACT)) {
           with_ext_act(g.act, [&](auto act) {
-            epilogue<EPI, decltype(act)::value>(g, pc, acc0, acc1, wm, wn, lane, bv, lsum);
+            epilogue<EPI, decltype(act)::value>(g, pc, acc0, acc1, wm, wn, lane, bv, lsum, eo);
           });
-        } else if (EPI == EPI_STORE || g.act == ITTS_ACT_NONE) epilogue<EPI, ITTS_ACT_NONE>(g, pc, acc0, acc1, wm, wn, lane, bv, lsum);
-        else if (g.act == ITTS_ACT_TANH) epilogue<EPI, ITTS_ACT_TANH>(g, pc, acc0, acc1, wm, wn, lane, bv, lsum);
-        else epilogue<EPI, ITTS_ACT_RELU>(g, pc, acc0, acc1, wm, wn, lane, bv, lsum);
+          // (EPI_MSE has no activation: one copy of its epilogue whatever g.act holds, not three identical ones)
+        } else if (EPI == EPI_STORE || EPI == EPI_MSE || g.act == ITTS_ACT_NONE) epilogue<EPI, ITTS_ACT_NONE>(g, pc, acc0, acc1, wm, wn, lane, bv, lsum, eo);
+        else if (g.act == ITTS_ACT_TANH) epilogue<EPI, ITTS_ACT_TANH>(g, pc, acc0, acc1, wm, wn, lane, bv, lsum, eo);
+        else epilogue<EPI, ITTS_ACT_RELU>(g, pc, acc0, acc1, wm, wn, lane, bv, lsum, eo);
       }
       pending = false;
+      // the operands of the epilogue of the tile that starts now, a whole K loop ahead of their use:
+      // the registers are free again (the pending tile's epilogue has just read them -- issued right
+      // here, not under a test of kt, so that hipcc sees that and waits for nothing before it
+      // overwrites them); the epilogue behind the next tile boundary waits for them with counted
+      // vmcnts that leave its own stores in flight
+      if (kEarlyOperands<EPI> && have) fetch_epilogue_operands<EPI>(g, c, wm, wn, lane, eo);
     }
     if (!have) break;   // only the last epilogue was left
 

@@ -11,6 +11,7 @@
 //   * roofline: MFMA fp32.  FLOPs per valid frame of the 425-512-512-187 model: fwd 1.15 M,
 //     fwd+bwd 3.45 M (first-layer input gradient skipped: 3.01 M) -- SURVEY.md section 8d.
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 
 #include "common.h"
@@ -199,8 +200,13 @@ __global__ __launch_bounds__(256, STAGES == 1 ? 4 : 2) void gemm_f32_kernel(Gemm
   staged_epilogue<EPI, TN, AF>(g, t, acc, [](int64_t m) { return m; });
 }
 
+// Which kernel the dense-layer products of this process ran on, per epilogue kind (itts_gemm_path_counts): [0][epi] the
+// LDS-DMA ring kernel (a pair launch counts its two products), [1][epi] the register-staged kernel.
+static std::atomic<int64_t> g_gemm_path[2][4];
+
 template <bool A_ROW, bool B_ROW, int EPI, int TN, int STAGES, int AF = AF_BASE>
 static int launch_gemm_tn(const GemmArgs& g, int splitk, hipStream_t s) {
+  g_gemm_path[1][EPI].fetch_add(1, std::memory_order_relaxed);
   const int64_t tiles = ((g.M + BM - 1) / BM) * ((g.N + 64 * TN - 1) / (64 * TN));
   dim3 grid((unsigned)tiles, 1, (unsigned)splitk);
   const bool va = g.vecA, vb = g.vecB;   // pitch and alignment allow 16-byte loads (see load_tile)
@@ -274,6 +280,7 @@ static ring::Args ring_args(const GemmArgs& g, int splitk) {
 template <bool A_ROW, bool B_ROW, int EPI, int WM, int AF = AF_BASE>
 static int launch_ring_wm(const GemmArgs& g, int splitk, hipStream_t s) {
   constexpr int BNT = 32 * (4 / WM);
+  g_gemm_path[0][EPI].fetch_add(1, std::memory_order_relaxed);
   ring::Args r = ring_args<WM>(g, splitk);
   r.gn = ring_group(r.tiles_n, BNT, g.K, A_ROW && B_ROW);
   const int64_t ntiles = (int64_t)r.tiles_m * r.tiles_n * splitk;
@@ -316,6 +323,8 @@ static int launch_ring(const GemmArgs& g, int splitk, hipStream_t s) {
 // derivative in the epilogue) of one layer in ONE launch
 template <int WM_W, int EPI_X, int AF_X = AF_BASE>
 static int launch_ring_bwd_pair(const GemmArgs& gw, int splitk, const GemmArgs& gx, hipStream_t s) {
+  g_gemm_path[0][EPI_STORE].fetch_add(1, std::memory_order_relaxed);
+  g_gemm_path[0][EPI_X].fetch_add(1, std::memory_order_relaxed);
   const ring::Args rw = ring_args<WM_W>(gw, splitk), rx = ring_args<2>(gx, 1);
   hipLaunchKernelGGL((ring::gemm_ring_pair_kernel<false, false, EPI_STORE, WM_W, true, false, EPI_X, 2, AF_X>),
                      dim3(kRingGrid), dim3(ring::THREADS), 0, s, rw, rx);
@@ -809,6 +818,13 @@ extern "C" int itts_rows_gather_f32(const float* d_src, int64_t ld_src, int64_t 
   hipLaunchKernelGGL(rows_gather_kernel, dim3(grid), dim3(256), 0, as_stream(stream), d_src, ld_src, n_src, d_idx, n_out,
                      width, d_fill_row, d_dst, ld_dst, dst_width, vec);
   ITTS_LAUNCH_CHECK();
+  return ITTS_OK;
+}
+
+extern "C" int itts_gemm_path_counts(int64_t out[8]) {
+  ITTS_REQUIRE(out != nullptr, "null pointer");
+  for (int k = 0; k < 2; ++k)
+    for (int e = 0; e < 4; ++e) out[4 * k + e] = g_gemm_path[k][e].load(std::memory_order_relaxed);
   return ITTS_OK;
 }
 

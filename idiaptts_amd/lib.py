@@ -163,6 +163,7 @@ _SIGNATURES = {
     "itts_gru_layer_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P,
                                    _P, _P, _P, _P]),
     "itts_rnn_path_counts": (c_int, [POINTER(c_int64)]),
+    "itts_gemm_path_counts": (c_int, [POINTER(c_int64)]),
     "itts_adam_step": (c_int, [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float,
                                c_float, c_int64, c_float, _P]),
     "itts_grad_norm_accum": (c_int, [_P, c_int64, c_int, _P, c_int, _P, _P]),

@@ -996,6 +996,19 @@ def ema_update(shadow, param, decay):
                                  _stream()), "itts_ema_update")
 
 
+GemmPathCounts = collections.namedtuple("GemmPathCounts", "ring staged")
+
+
+def gemm_path_counts():
+    """Which kernel the dense-layer products of this process ran on so far (itts_gemm_path_counts; no device call):
+    `ring` and `staged` are 4-tuples indexed by the epilogue kind (0 store, 1 bias + activation, 2 activation
+    derivative, 3 masked MSE)."""
+    out = (ctypes.c_int64 * 8)()
+    _lib.check(_lib.load().itts_gemm_path_counts(out), "itts_gemm_path_counts")
+    v = [int(x) for x in out]
+    return GemmPathCounts(tuple(v[:4]), tuple(v[4:]))
+
+
 RnnPathCounts = collections.namedtuple("RnnPathCounts", "fwd_ran fwd_declined fwd_gave_up bwd_ran bwd_declined bwd_gave_up")
 
 

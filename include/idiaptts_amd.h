@@ -740,6 +740,13 @@ int itts_gru_layer_bwd(const float* d_dy, const float* d_whh, const float* d_gat
                        const int* d_row_off, const int* d_rev_row, int T, int B, int H, int ndir,
                        float* d_dgi, float* d_dgh, float* d_dh0, void* d_state, void* stream);
 
+/* Which kernel the dense-layer products (itts_linear_*) of this process ran on (process-wide atomic counts, no device
+ * call): out[e] = products on the LDS-DMA ring kernel, out[4 + e] = on the register-staged kernel, e = the epilogue
+ * kind: 0 plain store (weight gradients, input gradients without an activation), 1 bias + activation (forward),
+ * 2 activation derivative (input gradients), 3 masked MSE (itts_linear_fwd_mse).  The two products of a fused
+ * itts_linear_bwd launch count one each. */
+int itts_gemm_path_counts(int64_t out[8]);
+
 /* Which way the LSTM / GRU layer calls of this process went (process-wide atomic counts, no device call):
  * out = forward ran, declined, gave_up, backward ran, declined, gave_up.  `ran`: the persistent recurrence did
  * the layer; `declined`: it was not launched (ITTS_RNN_PERSISTENT=0, H != 512, device not ready, cooling down)
