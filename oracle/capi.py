@@ -70,14 +70,16 @@ def cheaptrick_fft_size(fs, f0_floor=71.0):
     return 2 ** (1 + int(math.log2(3.0 * fs / f0_floor + 1)))
 
 
-def dio(x, fs, frame_period=5.0):
+def dio(x, fs, frame_period=5.0, f0_floor=71.0, f0_ceil=800.0, channels_in_octave=2.0,
+        allowed_range=0.1):
     x = np.ascontiguousarray(x, dtype=np.float64)
     T = num_frames(len(x), fs, frame_period)
     f0 = np.zeros(T)
     tp = np.zeros(T)
     fn = _fn("orc_dio", c_int, [c_void_p, c_int, c_int, c_double, c_double, c_double, c_double,
                                 c_double, c_void_p, c_void_p])
-    rc = fn(_p(x), len(x), fs, frame_period, 71.0, 800.0, 2.0, 0.1, _p(f0), _p(tp))
+    rc = fn(_p(x), len(x), fs, frame_period, f0_floor, f0_ceil, channels_in_octave, allowed_range,
+            _p(f0), _p(tp))
     assert rc == 0
     return f0, tp
 
