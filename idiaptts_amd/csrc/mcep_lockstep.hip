@@ -241,7 +241,6 @@ __global__ __launch_bounds__(256, MGC2SP ? 3 : 2) void gemm_f64_kernel(const dou
 // 0.86 / 1.5 ms.  What holds it now is the request pattern of A (a lane fetches 2 x 16 bytes of its
 // own row: every 128-byte line is asked for by two instructions, four lanes each); loading whole
 // lines and transposing through LDS is the next step.
-template <bool VEC_A>
 __global__ __launch_bounds__(256) void gemm_f64_staged_kernel(const double* __restrict__ A, int64_t lda,
                                                               const double* __restrict__ Bm, int64_t ldb,
                                                               double* __restrict__ C, int64_t ldc, int64_t T,
@@ -276,14 +275,9 @@ __global__ __launch_bounds__(256) void gemm_f64_staged_kernel(const double* __re
       const int k0 = ks + 16 * c + 4 * kg;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        if (VEC_A) {
-          const double2* p2 = reinterpret_cast<const double2*>(ap[h] + (k0 < K ? k0 : 0));
-          const double2 v0 = p2[0], v1 = p2[1];
-          o.av[c][h][0] = v0.x; o.av[c][h][1] = v0.y; o.av[c][h][2] = v1.x; o.av[c][h][3] = v1.y;
-        } else {
+        // scalar loads: rows that allow 16-byte loads go to gemm_f64_lds_kernel (launch_gemm_f64)
 #pragma unroll
-          for (int jj = 0; jj < 4; ++jj) o.av[c][h][jj] = ap[h][k0 + jj < K ? k0 + jj : 0];
-        }
+        for (int jj = 0; jj < 4; ++jj) o.av[c][h][jj] = ap[h][k0 + jj < K ? k0 + jj : 0];
       }
     }
   };
@@ -1164,9 +1158,7 @@ int launch_gemm_f64(const double* A, int64_t lda, const double* B, int64_t ldb, 
   if (K > 64 && T >= 1024) {      // long K, enough rows to fill the chip: the staged kernel
     static bool attr_set = false;
     if (!attr_set) {
-      ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_f64_staged_kernel<true>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
-      ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_f64_staged_kernel<false>,
+      ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_f64_staged_kernel,
                                          hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
       attr_set = true;
     }
@@ -1178,10 +1170,8 @@ int launch_gemm_f64(const double* A, int64_t lda, const double* B, int64_t ldb, 
         attr2 = true;
       }
       hipLaunchKernelGGL(gemm_f64_lds_kernel, dim3(grid.x * grid.y), dim3(256), GEMM_LDS_BYTES, s, A, lda, B, ldb, C, ldc, T, N, K, rows);
-    } else if (vec)
-      hipLaunchKernelGGL(gemm_f64_staged_kernel<true>, grid, dim3(256), 65536, s, A, lda, B, ldb, C, ldc, T, N, K, rows);
-    else
-      hipLaunchKernelGGL(gemm_f64_staged_kernel<false>, grid, dim3(256), 65536, s, A, lda, B, ldb, C, ldc, T, N, K, rows);
+    } else
+      hipLaunchKernelGGL(gemm_f64_staged_kernel, grid, dim3(256), 65536, s, A, lda, B, ldb, C, ldc, T, N, K, rows);
   } else if (vec)
     hipLaunchKernelGGL(gemm_f64_kernel<true>, dim3(gemm_f64_grid(T, N)), dim3(256), 0, s, A, lda, B, ldb, C, ldc, T, N, K, rows);
   else

@@ -2,7 +2,9 @@
 against the C oracle (oracle/c/sptk.c: orc_mgcep, orc_mgc2sp_gamma) and the bound the reference's
 own test applies (test_WorldFeatLabelGen.py:827-836).  PARITY UNPINNED for gamma != 0 (pysptk is
 not installable, the reference holds no MGC vector); see tests/test_oracle_golden.py for what pins
-the oracle."""
+the oracle, and tests/test_cepstral_cases.py / tests/test_gpu_cepstral.py for the closed-form model
+spectrum that pins decoding and in-model recovery of the oracle and of these kernels, and for the
+other sizes, orders, frame counts and stopping rules."""
 import os
 
 import numpy as np
