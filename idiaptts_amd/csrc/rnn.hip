@@ -1,15 +1,15 @@
-// (Bi)LSTM and (Bi)GRU recurrences for padded batches of frame sequences -- the recurrent half of the
-// acoustic model of BASELINE config 3 (3 x 512 BiLSTM) and the GRU flavour of the recurrent groups
-// (`..._BiGRU_...`).  Replaces what torch.nn.LSTM / GRU do between
+// (Bi)LSTM, (Bi)GRU and vanilla (Bi)RNN recurrences for padded batches of frame sequences -- the recurrent half of
+// the acoustic model of BASELINE config 3 (3 x 512 BiLSTM) and the GRU / RNNTANH / RNNRELU flavours of the recurrent
+// groups (`..._BiGRU_...`, `..._BiRNNTANH_...`).  Replaces what torch.nn.LSTM / GRU / RNN do between
 // pack_padded_sequence(enforce_sorted=False) and pad_packed_sequence in
 // rnn_dyn/RNNWrapper.py:45-107 (cuDNN / MIOpen RNN in the reference).
 //
 // Split of the work (per layer):
-//   * gin = X W_ih^T + bias (LSTM: b_ih + b_hh, GRU: b_ih) for ALL time steps and both directions is ONE
+//   * gin = X W_ih^T + bias (LSTM and RNN: b_ih + b_hh, GRU: b_ih) for ALL time steps and both directions is ONE
 //     fp32-MFMA GEMM (nn.hip), so are dX, dW_ih, dW_hh and the bias gradients in the backward pass;
 //   * only the true recurrence h_{t-1} W_hh^T runs per time step.  Forward and backward: one
 //     persistent launch per layer each where it applies (rnn_persist.h: H = 512, every recurrence
-//     inside one XCD).  Otherwise (rnn_step.h): one launch per step, both directions in it: the kernel
+//     inside one XCD; LSTM and GRU only).  Otherwise (rnn_step.h): one launch per step, both directions in it: the kernel
 //     boundary is the grid-wide dependency (an in-kernel grid barrier ACROSS XCDs costs 2.3-2.5 us
 //     on this chip, scripts/handoff_lab).  A workgroup owns a slice of hidden units and
 //     streams its W_hh rows and h_{t-1} [B, H] from L2 through v_mfma_f32_16x16x4_f32
@@ -31,8 +31,8 @@
 //     wave access thanks to the K-blocked state / re-tiled W_hh layouts of rnn_common.h.
 // Gate order (LSTM i, f, g, o; GRU r, z, n), the bias vectors and the cell formulas (rnn_common.h) follow torch.nn.
 //
-// Every entry point: argument checks, the arguments of both kernel families, the persistent attempt, then the
-// step driver of rnn_step.h.
+// Every LSTM / GRU entry point: argument checks, the arguments of both kernel families, the persistent attempt, then
+// the step driver of rnn_step.h.  The vanilla RNN's: argument checks, then the step driver.
 
 #include "rnn_persist.h"
 #include "rnn_step.h"
@@ -142,6 +142,50 @@ extern "C" int itts_gru_layer_bwd(const float* d_dy, const float* d_whh, const f
   RnnStepArgs a = step_args(d_rev_row, T, B, H, ndir);
   a.gates = const_cast<float*>(d_gates); a.aux = const_cast<float*>(d_hprev); a.dy = d_dy; a.dg = d_dgi; a.dg2 = d_dgh;
   return rnn_step_backward<3>(a, d_whh, h_lengths, d_dh0, d_state, s);
+}
+
+// The same for one (bi)directional vanilla RNN layer, h_t = act(gin_t + W_hh h_{t-1}): one gate, no cell state, and
+// nothing saved but d_y -- backward takes act' from it.  Step kernels only.
+static std::atomic<int64_t> g_rnn_layer_fwd_calls{0}, g_rnn_layer_bwd_calls{0};
+
+extern "C" int64_t itts_rnn_layer_state_bytes(int B, int H, int ndir) { return rnn_state_bytes(1, B, H, ndir); }
+
+extern "C" int itts_rnn_layer_fwd(const float* d_gin, const float* d_whh, const float* d_h0, const int* d_lengths,
+                                  const int* h_lengths, const int* d_row_off, const int* d_rev_row, int T, int B,
+                                  int H, int ndir, int act, float* d_y, float* d_hn, void* d_state, void* stream) {
+  ITTS_REQUIRE(d_gin && d_whh && d_lengths && d_row_off && d_y && d_state, "null pointer");
+  ITTS_REQUIRE(ndir == 1 || d_rev_row, "the reverse direction needs its row table");
+  ITTS_REQUIRE(act == ITTS_ACT_TANH || act == ITTS_ACT_RELU, "the activation must be ITTS_ACT_TANH or ITTS_ACT_RELU");
+  int rc = rnn_check(h_lengths, T, B, H, ndir);
+  if (rc) return rc;
+  g_rnn_layer_fwd_calls.fetch_add(1, std::memory_order_relaxed);
+  RnnStepArgs a = step_args(d_rev_row, T, B, H, ndir);
+  a.gin = d_gin; a.y = d_y; a.act = act;
+  return rnn_step_forward<1>(a, d_whh, d_h0, nullptr, d_lengths, h_lengths, d_hn, nullptr, d_state, as_stream(stream));
+}
+
+// Backward recurrence: fills d_dg [N, ndir*H] (gradient wrt gin, which is also the one wrt the hidden projection)
+// from d_dy and the forward's output d_y.
+extern "C" int itts_rnn_layer_bwd(const float* d_dy, const float* d_whh, const float* d_y, const int* h_lengths,
+                                  const int* d_row_off, const int* d_rev_row, int T, int B, int H, int ndir, int act,
+                                  float* d_dg, void* d_state, void* stream) {
+  ITTS_REQUIRE(d_dy && d_whh && d_y && d_row_off && d_dg && d_state, "null pointer");
+  ITTS_REQUIRE(ndir == 1 || d_rev_row, "the reverse direction needs its row table");
+  ITTS_REQUIRE(act == ITTS_ACT_TANH || act == ITTS_ACT_RELU, "the activation must be ITTS_ACT_TANH or ITTS_ACT_RELU");
+  int rc = rnn_check(h_lengths, T, B, H, ndir);
+  if (rc) return rc;
+  g_rnn_layer_bwd_calls.fetch_add(1, std::memory_order_relaxed);
+  RnnStepArgs a = step_args(d_rev_row, T, B, H, ndir);
+  a.y = const_cast<float*>(d_y); a.dy = d_dy; a.dg = d_dg; a.act = act;
+  return rnn_step_backward<1>(a, d_whh, h_lengths, nullptr, d_state, as_stream(stream));
+}
+
+// Forward and backward vanilla RNN layer calls of this process that passed their argument checks.  No device is touched.
+extern "C" int itts_rnn_layer_counts(int64_t out[2]) {
+  ITTS_REQUIRE(out != nullptr, "null pointer");
+  out[0] = g_rnn_layer_fwd_calls.load(std::memory_order_relaxed);
+  out[1] = g_rnn_layer_bwd_calls.load(std::memory_order_relaxed);
+  return ITTS_OK;
 }
 
 // Forward ran / declined / gave_up, backward ran / declined / gave_up of the persistent recurrences (rnn_persist.h),

@@ -1,5 +1,5 @@
-// Shared pieces of the LSTM / GRU recurrence kernels (rnn_step.h, rnn_persist.h): the scratch layouts, the cell
-// arithmetic -- written here once, called by the step kernels and by the persistent kernels -- and the host helpers.
+// Shared pieces of the LSTM / GRU / vanilla RNN recurrence kernels (rnn_step.h, rnn_persist.h): the scratch layouts, the
+// cell arithmetic -- written here once, called by the step kernels and by the persistent kernels -- and the host helpers.
 //
 // Memory layouts that make every operand load of a step a fully coalesced 1 KB wave access.
 // v_mfma_f32_16x16x4_f32 wants lane (lr = lane & 15, kg = lane >> 4) to hold row lr, k = kg; with
@@ -97,20 +97,35 @@ __device__ __forceinline__ void gru_cell_bwd(float rg, float zg, float ng, float
   carry = dh * zg;
 }
 
-// Forward tiling of W_hh [ndir][G*H][H] (G = 3 or 4 gates) for workgroups of 4 hidden units:
-//   out[dir][jg = H/4][kb = H/4][lr = gate*4 + unit][4] = W[dir][gate*H + jg*4 + unit][kb*4 ..]
+// torch.nn.RNN: h' = act(gin + W_hh h), act = ITTS_ACT_TANH or ITTS_ACT_RELU.  p = the unit's row of h_{t-1} W_hh^T,
+// x = its input projection (both biases included).  Nothing is saved: backward takes the derivative from h' itself.
+__device__ __forceinline__ float rnn_cell_fwd(float p, float x, int act) {
+  const float z = p + x;
+  return act == ITTS_ACT_RELU ? (z < 0.f ? 0.f : z) : tanh_cell(z);
+}
+
+// Its gradient wrt the pre-activation from the stored output y = h' and dh = dy + dG(s + 1) W_hh: 1 - y^2, or y > 0
+// (torch's rule at 0).
+__device__ __forceinline__ float rnn_cell_bwd(float y, float dh, int act) {
+  return act == ITTS_ACT_RELU ? (y > 0.f ? dh : 0.f) : dh * (1.f - y * y);
+}
+
+// Forward tiling of W_hh [ndir][G*H][H] for workgroups of U hidden units, U = 4 with G = 3 or 4 gates, U = 16 with the
+// vanilla RNN's one:
+//   out[dir][jg = H/U][kb = H/4][lr = gate*U + unit][4] = W[dir][gate*H + jg*U + unit][kb*4 ..]
 // tile rows of a missing 4th gate are zero.
 static __global__ void rnn_pack_w_fwd_kernel(const float* __restrict__ w, float* __restrict__ out, int ndir,
                                       int G, int H) {
-  const int64_t n = (int64_t)ndir * (H / 4) * (H / 4) * 16;
+  const int U = G == 1 ? 16 : 4;
+  const int64_t n = (int64_t)ndir * (H / U) * (H / 4) * 16;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const int lr = (int)(i & 15);
     const int kb = (int)((i >> 4) % (H / 4));
-    const int jg = (int)(((i >> 4) / (H / 4)) % (H / 4));
-    const int d = (int)((i >> 4) / ((int64_t)(H / 4) * (H / 4)));
-    const int g = lr >> 2, u = lr & 3;
+    const int jg = (int)(((i >> 4) / (H / 4)) % (H / U));
+    const int d = (int)((i >> 4) / ((int64_t)(H / 4) * (H / U)));
+    const int g = lr / U, u = lr % U;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (g < G) v = *reinterpret_cast<const float4*>(w + ((size_t)d * G * H + (size_t)g * H + jg * 4 + u) * H + kb * 4);
+    if (g < G) v = *reinterpret_cast<const float4*>(w + ((size_t)d * G * H + (size_t)g * H + jg * U + u) * H + kb * 4);
     reinterpret_cast<float4*>(out)[i] = v;
   }
 }

@@ -1,13 +1,14 @@
-// Per-step recurrence kernels of the LSTM (G = 4 gates) and GRU (G = 3) layers and their host driver (included by
-// rnn.hip): one launch per time step, both directions in it.  They run every case the persistent kernels of
-// rnn_persist.h do not take (other hidden sizes, devices with fewer than 256 CUs) and every layer call a persistent
-// launch gave up on.  Packed layout, load ordering and the split of the work: rnn.hip.
+// Per-step recurrence kernels of the LSTM (G = 4 gates), GRU (G = 3) and vanilla RNN (G = 1) layers and their host
+// driver (included by rnn.hip): one launch per time step, both directions in it.  They run every case the persistent
+// kernels of rnn_persist.h do not take (other hidden sizes, devices with fewer than 256 CUs, every vanilla RNN layer)
+// and every layer call a persistent launch gave up on.  Packed layout, load ordering and the split of the work: rnn.hip.
 #pragma once
 #include "rnn_common.h"
 
 namespace itts {
 
 constexpr int FW_UNITS = 4;    // hidden units per workgroup in the forward step (G of the 16 tile rows x 4 used)
+constexpr int FW_UNITS_1 = 16; // ... of the vanilla RNN: one gate, so every tile row is a unit
 constexpr int BW_UNITS = 16;   // hidden units per workgroup in the backward step
 
 struct RnnStepArgs {
@@ -22,7 +23,7 @@ struct RnnStepArgs {
   float* hs;              // [2 parity][ndir] K-blocked running hidden state; GRU backward: the dh * z carry
   float* cs;              // LSTM: [2 parity][ndir] K-blocked running cell state; backward: the dc * f carry
   float* dgb;             // [2 parity][ndir] K-blocked dG (GRU: dGh) of the step just processed (backward)
-  float* y;               // [N, ndir*H] layer output
+  float* y;               // [N, ndir*H] layer output (vanilla RNN backward: input, all it saved)
   float* gates;           // [N, ndir, H, 4] saved for backward, one 16-byte store / load per (frame, unit):
                           //       LSTM (i, f, g, o) after activation, GRU (r, z, n, W_hn h + b_hn)
   float* aux;             // [N, ndir*H]  LSTM: c_t (written forward, read backward); GRU: the h_{t-1} that
@@ -36,6 +37,7 @@ struct RnnStepArgs {
   int nact, nact_next;    // rows active at this step / at step + 1 (a prefix: rows are sorted)
   int row_base;           // row_off[step], from the host's copy of the lengths (no table read)
   int row_base_prev;      // row_off[step - 1] (LSTM backward: c_{t-1} of the forward direction)
+  int act;                // vanilla RNN: ITTS_ACT_TANH or ITTS_ACT_RELU
 };
 
 // packed row that row b visits at the step being processed / the one before it (the caller knows that it is
@@ -199,11 +201,107 @@ __global__ __launch_bounds__(256) void rnn_step_fwd_kernel(RnnStepArgs a) {
   }
 }
 
+// The vanilla RNN's forward step.  One gate: workgroup = 16 hidden units (tile row = unit) x every active batch tile,
+// grid (H/16, ndir) -- no tile row is padding (laid out like the GRU, 4 units x 4 gate slots, three quarters of the W_hh
+// stream and of the MFMAs would be zeros).  K split, operand loads and their order, tile-outermost MFMAs with four
+// chains and the reduction through LDS are those of rnn_step_fwd_kernel; thread (batch row bl, unit n) then applies the
+// cell to its element of each of the NT tiles.  A row of a launched tile that is no longer active only has its state
+// copied to the other parity.
+template <int NT>
+__global__ __launch_bounds__(256) void rnn1_step_fwd_kernel(RnnStepArgs a) {
+  __shared__ float P[NT][4][16][17];
+  const int H = a.H, B = a.B;
+  const int dir = blockIdx.y;
+  const int par = a.step & 1;
+  const size_t dsz = (size_t)B * H;
+  const float* hprev = a.hs + ((size_t)par * a.ndir + dir) * dsz;
+  float* hnext = a.hs + ((size_t)(par ^ 1) * a.ndir + dir) * dsz;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int lr = lane & 15, kg = lane >> 4;
+  const int ntiles = (a.nact + 15) >> 4;
+
+  const int kiter = wv < a.ksplit ? a.kiter : 0;
+  const int kb0 = wv * 4 * a.kiter + kg;                       // this lane's first k-block
+  const float4* wp = reinterpret_cast<const float4*>(a.wp) +
+                     (((size_t)dir * (H / FW_UNITS_1) + blockIdx.x) * (H / 4) + (kiter ? kb0 : 0)) * 16 + lr;
+  const float4* hp4 = reinterpret_cast<const float4*>(hprev);
+  const int bl = threadIdx.x >> 4, j = blockIdx.x * FW_UNITS_1 + (threadIdx.x & 15);
+
+  for (int tb = 0; tb < ntiles; tb += NT) {
+    f32x4 acc[NT][4];
+    int ridx[NT];
+    float hp_v[NT], x[NT];
+#pragma unroll
+    for (int tt = 0; tt < NT; ++tt) {
+#pragma unroll
+      for (int n = 0; n < 4; ++n) acc[tt][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+      // the packed-row index heads the only dependent load chain of a step: requested before the operand loads
+      const int b = (tb + tt) * 16 + bl;
+      ridx[tt] = b < a.nact ? row_now(a, dir, b) : 0;
+      hp_v[tt] = 0.f; x[tt] = 0.f;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll 1
+    for (int c = 0; c < kiter || c == 0; c += 8) {
+      float4 bv[8], av[NT][8];
+#pragma unroll
+      for (int s = 0; s < 8; ++s) bv[s] = wp[(size_t)(c + s < kiter ? 4 * (c + s) : 0) * 16];
+#pragma unroll
+      for (int tt = 0; tt < NT; ++tt) {
+        const int row = (tb + tt) * 16 + lr;
+        const float4* hp = hp4 + (size_t)(kiter ? kb0 : 0) * B + (row < B ? row : 0);
+#pragma unroll
+        for (int s = 0; s < 8; ++s) av[tt][s] = hp[(size_t)(c + s < kiter ? 4 * (c + s) : 0) * B];
+      }
+      if (c == 0) {
+#pragma unroll
+        for (int tt = 0; tt < NT; ++tt) {
+          const int b = (tb + tt) * 16 + bl;
+          if (b < a.nact) x[tt] = a.gin[(size_t)ridx[tt] * (a.ndir * H) + (size_t)dir * H + j];
+          else if (b < B && tb + tt < ntiles) hp_v[tt] = hprev[blocked(b, j, B)];
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);   // all loads above are in flight before the first MFMA
+#pragma unroll
+      for (int tt = 0; tt < NT; ++tt) {
+        const bool rok = (tb + tt) * 16 + lr < B;
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+          float4 v = av[tt][s];
+          if (!rok || c + s >= kiter) v = make_float4(0.f, 0.f, 0.f, 0.f);
+          acc[tt][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(v.x, bv[s].x, acc[tt][0], 0, 0, 0);
+          acc[tt][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(v.y, bv[s].y, acc[tt][1], 0, 0, 0);
+          acc[tt][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(v.z, bv[s].z, acc[tt][2], 0, 0, 0);
+          acc[tt][3] = __builtin_amdgcn_mfma_f32_16x16x4f32(v.w, bv[s].w, acc[tt][3], 0, 0, 0);
+        }
+      }
+    }
+    if (tb > 0) __syncthreads();   // P of the previous group has been consumed
+#pragma unroll
+    for (int tt = 0; tt < NT; ++tt)
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        P[tt][wv][kg * 4 + e][lr] = (acc[tt][0][e] + acc[tt][1][e]) + (acc[tt][2][e] + acc[tt][3][e]);
+    __syncthreads();
+#pragma unroll
+    for (int tt = 0; tt < NT; ++tt) {
+      const int b = (tb + tt) * 16 + bl, n = threadIdx.x & 15;
+      if (b >= B || tb + tt >= ntiles) continue;
+      float hn = hp_v[tt];
+      if (b < a.nact) {
+        hn = rnn_cell_fwd((P[tt][0][bl][n] + P[tt][1][bl][n]) + (P[tt][2][bl][n] + P[tt][3][bl][n]), x[tt], a.act);
+        a.y[(size_t)ridx[tt] * (a.ndir * H) + (size_t)dir * H + j] = hn;
+      }
+      hnext[blocked(b, j, B)] = hn;
+    }
+  }
+}
+
 // ---- backward step ----------------------------------------------------------------------------------
 // Processes recurrence step s = a.step (called with s = T-1 ... 0). For row b active at s:
 //   dh = dy[t] + dG[t_{s+1}] W_hh   (second term only if the row is active at s+1; GRU: dGh, and + the carry)
 //   the cell's gate gradients (rnn_common.h) -> dG[t] and the running carry (LSTM: dc * f in the cs buffers,
-//   GRU: dh * z in the hs buffers; parity by step)
+//   GRU: dh * z in the hs buffers; parity by step; the vanilla RNN, G = 1, has none and reads only y and dy)
 // dG (GRU: dGh) of a step is written twice: row-major for the dW / dX GEMMs and K-blocked into dgb,
 // which is what the next launch reads as its MFMA operand.
 // Workgroup = 16 hidden units x 16 batch rows; up to 4 G waves split the K = G H gate rows so that
@@ -246,7 +344,7 @@ __global__ __launch_bounds__(256 * G) void rnn_step_bwd_kernel(RnnStepArgs a) {
   const int b = b0 + bl, j = j0 + n;
   const bool ew = threadIdx.x < 256 && b < B;
   const bool act = ew && b < a.nact;
-  // gs: the saved gates; v1: LSTM c_t, GRU h_{t-1}; v2: LSTM c_{t-1}
+  // gs: the saved gates; v1: LSTM c_t, GRU h_{t-1}, RNN y_t; v2: LSTM c_{t-1}
   float4 gs = make_float4(0.f, 0.f, 0.f, 0.f);
   float v1 = 0.f, v2 = 0.f, dyv = 0.f, carry = 0.f;
   // packed-row indices first (see the forward kernel): the saved tensors they address are then
@@ -269,12 +367,16 @@ __global__ __launch_bounds__(256 * G) void rnn_step_bwd_kernel(RnnStepArgs a) {
     }
     if (c == 0 && act) {
       r = (size_t)ridx;
-      gs = reinterpret_cast<const float4*>(a.gates)[(r * a.ndir + dir) * H + j];
-      v1 = a.aux[r * ldh + (size_t)dir * H + j];
+      if constexpr (G == 1) {
+        v1 = a.y[r * ldh + (size_t)dir * H + j];
+      } else {
+        gs = reinterpret_cast<const float4*>(a.gates)[(r * a.ndir + dir) * H + j];
+        v1 = a.aux[r * ldh + (size_t)dir * H + j];
+      }
       if constexpr (G == 4)
         v2 = a.step > 0 ? a.aux[(size_t)rpidx * ldh + (size_t)dir * H + j] : (a.c0 ? a.c0[dir * H + j] : 0.f);
       dyv = a.dy[r * ldh + (size_t)dir * H + j];
-      carry = carry_in[(size_t)b * H + j];
+      if constexpr (G != 1) carry = carry_in[(size_t)b * H + j];
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -299,23 +401,28 @@ __global__ __launch_bounds__(256 * G) void rnn_step_bwd_kernel(RnnStepArgs a) {
       if constexpr (G == 4) {
         lstm_cell_bwd(gs.x, gs.y, gs.z, gs.w, v1, v2, dyv + dhr, carry, d[0], d[1], d[2], d[3]);
         dgo[0] = d[0]; dgo[H] = d[1]; dgo[2 * H] = d[2]; dgo[3 * H] = d[3];
-      } else {
+      } else if constexpr (G == 3) {
         float dan;
         gru_cell_bwd(gs.x, gs.y, gs.z, gs.w, v1, dyv + dhr, carry, d[0], d[1], dan, d[2]);
         float* gh = a.dg2 + r * ldg + (size_t)dir * GH + j;
         dgo[0] = d[0]; dgo[H] = d[1]; dgo[2 * H] = dan;
         gh[0] = d[0]; gh[H] = d[1]; gh[2 * H] = d[2];
+      } else {
+        d[0] = rnn_cell_bwd(v1, dyv + dhr, a.act);
+        dgo[0] = d[0];
       }
 #pragma unroll
       for (int g = 0; g < G; ++g) dgb_out[blocked(b, g * H + j, B)] = d[g];
     }
-    carry_out[(size_t)b * H + j] = carry;      // 0 for a row that is not active yet
+    if constexpr (G != 1) carry_out[(size_t)b * H + j] = carry;      // 0 for a row that is not active yet
   }
 }
 
 // ---- host driver ------------------------------------------------------------------------------------
 // Forward recurrence: one launch per step, kernels[n - 1] taking n batch tiles of 16 rows per pass (NT = 1 .. 4).
-static void rnn_fwd_steps(void (*const kernels[4])(RnnStepArgs), RnnStepArgs& a, const int* h_lengths, hipStream_t s) {
+// Each workgroup owns `units` hidden units.
+static void rnn_fwd_steps(void (*const kernels[4])(RnnStepArgs), int units, RnnStepArgs& a, const int* h_lengths,
+                          hipStream_t s) {
   int p = a.B;
   int row_base = 0;
   for (int step = 0; step < a.T; ++step) {
@@ -323,7 +430,7 @@ static void rnn_fwd_steps(void (*const kernels[4])(RnnStepArgs), RnnStepArgs& a,
     a.nact = rnn_active_rows(h_lengths, a.B, step, &p);
     a.row_base = row_base;          // row_off[step] = rows active in all earlier steps
     row_base += a.nact;
-    hipLaunchKernelGGL(kernels[std::min((a.nact + 15) / 16, 4) - 1], dim3(a.H / FW_UNITS, a.ndir), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(kernels[std::min((a.nact + 15) / 16, 4) - 1], dim3(a.H / units, a.ndir), dim3(256), 0, s, a);
   }
 }
 
@@ -345,12 +452,12 @@ static void rnn_bwd_steps(void (*kernel)(RnnStepArgs), RnnStepArgs& a, const int
   }
 }
 
-// d_state of either cell: [hs | cs (LSTM only) | dgb, G st | re-tiled W_hh, ndir*4H*H (the GRU's forward tiling pads
-// the 4th gate)] floats, st = 2*ndir*B*H (two parities)
+// d_state of any cell: [hs | cs (LSTM only) | dgb, G st | re-tiled W_hh, ndir*4H*H (the GRU's forward tiling pads
+// the 4th gate; the vanilla RNN's one gate: ndir*H*H)] floats, st = 2*ndir*B*H (two parities)
 static inline int64_t rnn_state_bytes(int G, int B, int H, int ndir) {
   if (B <= 0 || H <= 0 || ndir <= 0) return 0;
   const int nst = (G == 4 ? 2 : 1) + G;
-  return ((int64_t)nst * 2 * ndir * B * H + (int64_t)ndir * 4 * H * H) * 4;
+  return ((int64_t)nst * 2 * ndir * B * H + (int64_t)ndir * (G == 1 ? 1 : 4) * H * H) * 4;
 }
 template <int G>
 static float* rnn_carve_state(RnnStepArgs& a, void* d_state) {
@@ -377,9 +484,15 @@ static int rnn_step_forward(RnnStepArgs a, const float* d_whh, const float* d_h0
   ITTS_LAUNCH_CHECK();
   a.ksplit = (H % 64 == 0) ? 4 : ((H % 32 == 0) ? 2 : 1);
   a.kiter = H / (16 * a.ksplit);
-  static void (*const step_kernels[4])(RnnStepArgs) = {rnn_step_fwd_kernel<G, 1>, rnn_step_fwd_kernel<G, 2>,
-                                                       rnn_step_fwd_kernel<G, 3>, rnn_step_fwd_kernel<G, 4>};
-  rnn_fwd_steps(step_kernels, a, h_lengths, s);
+  if constexpr (G == 1) {
+    static void (*const step_kernels[4])(RnnStepArgs) = {rnn1_step_fwd_kernel<1>, rnn1_step_fwd_kernel<2>,
+                                                         rnn1_step_fwd_kernel<3>, rnn1_step_fwd_kernel<4>};
+    rnn_fwd_steps(step_kernels, FW_UNITS_1, a, h_lengths, s);
+  } else {
+    static void (*const step_kernels[4])(RnnStepArgs) = {rnn_step_fwd_kernel<G, 1>, rnn_step_fwd_kernel<G, 2>,
+                                                         rnn_step_fwd_kernel<G, 3>, rnn_step_fwd_kernel<G, 4>};
+    rnn_fwd_steps(step_kernels, FW_UNITS, a, h_lengths, s);
+  }
   ITTS_LAUNCH_CHECK();
   if (d_hn) hipLaunchKernelGGL(rnn_final_state_kernel, rnn_ew_grid(n), dim3(256), 0, s, a.hs, d_lengths, d_hn, ndir, a.B, H);
   if (G == 4 && d_cn) hipLaunchKernelGGL(rnn_final_state_kernel, rnn_ew_grid(n), dim3(256), 0, s, a.cs, d_lengths, d_cn, ndir, a.B, H);
@@ -389,7 +502,7 @@ static int rnn_step_forward(RnnStepArgs a, const float* d_whh, const float* d_h0
 
 // The backward recurrence of one layer on the step kernels: fills a.dg (and the GRU's a.dg2) from a.dy and the saved
 // forward tensors; d_d0, if given, receives the gradient of the initial state the carry belongs to (LSTM: c_0,
-// GRU: h_0), [ndir][B][H].
+// GRU: h_0), [ndir][B][H].  The vanilla RNN has no carry and no d_d0.
 template <int G>
 static int rnn_step_backward(RnnStepArgs a, const float* d_whh, const int* h_lengths, float* d_d0, void* d_state,
                              hipStream_t s) {
@@ -398,14 +511,14 @@ static int rnn_step_backward(RnnStepArgs a, const float* d_whh, const int* h_len
   float* carry = G == 4 ? a.cs : a.hs;
   hipLaunchKernelGGL(rnn_pack_w_bwd_kernel, rnn_ew_grid((int64_t)ndir * H * H), dim3(256), 0, s, d_whh, wp, ndir, G, H);
   ITTS_LAUNCH_CHECK();
-  ITTS_HIP_CHECK(hipMemsetAsync(carry, 0, (size_t)2 * ndir * a.B * H * 4, s));   // carry of rows that are not active yet
+  if (G != 1) ITTS_HIP_CHECK(hipMemsetAsync(carry, 0, (size_t)2 * ndir * a.B * H * 4, s));   // carry of rows that are not active yet
   a.ksplit = G * ((H % 64 == 0) ? 4 : ((H % 32 == 0) ? 2 : 1));   // waves that share K = G H: G H / 16 k-steps in all
   a.kiter = G * H / 16 / a.ksplit;
   rnn_bwd_steps(rnn_step_bwd_kernel<G>, a, h_lengths, s);
   ITTS_LAUNCH_CHECK();
   // step 0 has every row active and leaves its carry (LSTM dc * f, GRU dh * z), the gradient of the initial
   // state, in the parity-0 carry buffer [ndir][B][H]
-  if (d_d0) ITTS_HIP_CHECK(hipMemcpyAsync(d_d0, carry, (size_t)ndir * a.B * H * 4, hipMemcpyDeviceToDevice, s));
+  if (G != 1 && d_d0) ITTS_HIP_CHECK(hipMemcpyAsync(d_d0, carry, (size_t)ndir * a.B * H * 4, hipMemcpyDeviceToDevice, s));
   return ITTS_OK;
 }
 

@@ -162,6 +162,10 @@ _SIGNATURES = {
                                    _P, _P, _P, _P]),
     "itts_gru_layer_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P,
                                    _P, _P, _P, _P]),
+    "itts_rnn_layer_state_bytes": (c_int64, [c_int, c_int, c_int]),
+    "itts_rnn_layer_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
+    "itts_rnn_layer_bwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    "itts_rnn_layer_counts": (c_int, [POINTER(c_int64)]),
     "itts_rnn_path_counts": (c_int, [POINTER(c_int64)]),
     "itts_gemm_path_counts": (c_int, [POINTER(c_int64)]),
     "itts_adam_step": (c_int, [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float,

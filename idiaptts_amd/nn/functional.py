@@ -358,6 +358,15 @@ class PackedBatch(object):
             cache[d] = (self.prev_row[d] == self.N).nonzero().reshape(-1)
         return cache[d]
 
+    def last_rows(self, d):
+        """Packed row of the last frame direction d processes in every sequence ([B] indices in sorted row order):
+        where the final state h_n comes from.  Forward: frame len_b - 1, the reverse direction's first; reverse:
+        frame 0."""
+        cache = self.__dict__.setdefault("_last_rows", {})
+        if d not in cache:
+            cache[d] = self.d_rev_row[0].long() if d == 0 else torch.arange(self.B, device=self.d_rev_row.device)
+        return cache[d]
+
     def _hptr(self):
         return ctypes.c_void_p(self.h_lengths.data_ptr())
 
@@ -750,3 +759,58 @@ class GRULayerFunction(torch.autograd.Function):
         dw_ih, db_ih, dw_hh, db_hh = _weight_grads(dgi, dgh, x2, hprev, F, ndir, want_hh_bias=True)
         dx = _input_grad(dgi, w_ih_cat, F, pre_padded) if ctx.needs_input_grad[0] else None
         return dx, None, dw_ih, dw_hh, db_ih.reshape(ndir, G3), db_hh, dh0, None
+
+
+class RNNLayerFunction(torch.autograd.Function):
+    """One (bi)directional vanilla RNN layer, h_t = act(gin_t + W_hh h_{t-1}) with act = ops.ACT_TANH / ACT_RELU, on
+    packed rows x [N, F] (torch.nn.RNN on a PackedSequence, rnn_dyn/RNNWrapper.py:45-107).  Saves nothing of the
+    recurrence but y.  Unlike the LSTM / GRU functions it takes a gradient into h_n: h_n of a row is y at the last
+    frame its direction processes, so that gradient is added to dy there."""
+
+    @staticmethod
+    def forward(ctx, x2, pb, w_ih, w_hh, b_ih, b_hh, h0, training, act):
+        L = _lib.load()
+        N = x2.shape[0]
+        F = w_ih.shape[-1]
+        ndir, H, _ = w_hh.shape
+        x2, w_ih_cat, gin, pre_padded = _input_projection(x2, w_ih, b_ih, b_hh)
+        dev = x2.device
+        y = torch.empty((N, ndir * H), dtype=torch.float32, device=dev)
+        hn = torch.empty((ndir, pb.B, H), dtype=torch.float32, device=dev)
+        state = torch.empty(L.itts_rnn_layer_state_bytes(pb.B, H, ndir), dtype=torch.uint8, device=dev)
+        w_hh_c = w_hh.contiguous()
+        h0c = h0.contiguous() if h0 is not None else None
+        _lib.check(L.itts_rnn_layer_fwd(_iptr(gin), _iptr(w_hh_c), _iptr(h0c), _iptr(pb.d_lengths), pb._hptr(),
+                                        _iptr(pb.d_row_off), _iptr(pb.d_rev_row), pb.T, pb.B, H, ndir, act, _iptr(y),
+                                        _iptr(hn), _iptr(state), ops._stream()), "itts_rnn_layer_fwd")
+        ctx.set_materialize_grads(False)
+        if training:
+            ctx.save_for_backward(x2, w_ih_cat, w_hh_c, y, h0c if h0c is not None else torch.empty(0, device=dev))
+            ctx.pb = pb
+            ctx.dims = (F, H, ndir, h0c is not None, pre_padded, act)
+        else:
+            ctx.mark_non_differentiable(y, hn)
+        return y, hn
+
+    @staticmethod
+    def backward(ctx, dy, dhn):
+        L = _lib.load()
+        x2, w_ih_cat, w_hh, y, h0 = ctx.saved_tensors
+        pb = ctx.pb
+        F, H, ndir, has_h0, pre_padded, act = ctx.dims
+        dy2 = torch.zeros_like(y) if dy is None else dy.contiguous()
+        if dhn is not None:
+            dy2 = dy2.clone() if dy2 is dy else dy2
+            for d in range(ndir):
+                dy2[:, d * H:(d + 1) * H].index_add_(0, pb.last_rows(d), dhn[d])
+        hprev = pb.shift(y, h0 if has_h0 else None, ndir, H)
+        dg = torch.empty((pb.N, ndir * H), dtype=torch.float32, device=y.device)
+        state = torch.empty(L.itts_rnn_layer_state_bytes(pb.B, H, ndir), dtype=torch.uint8, device=y.device)
+        _lib.check(L.itts_rnn_layer_bwd(_iptr(dy2), _iptr(w_hh), _iptr(y), pb._hptr(), _iptr(pb.d_row_off),
+                                        _iptr(pb.d_rev_row), pb.T, pb.B, H, ndir, act, _iptr(dg), _iptr(state),
+                                        ops._stream()), "itts_rnn_layer_bwd")
+        dh0 = _initial_state_grad(dg, w_hh, pb, ndir) if ctx.needs_input_grad[6] else None
+        dw_ih, db, dw_hh, _ = _weight_grads(dg, dg, x2, hprev, F, ndir, want_hh_bias=False)
+        dx = _input_grad(dg, w_ih_cat, F, pre_padded) if ctx.needs_input_grad[0] else None
+        db = db.reshape(ndir, H)
+        return dx, None, dw_ih, dw_hh, db, db.clone(), dh0, None, None

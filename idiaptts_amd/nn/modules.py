@@ -9,7 +9,7 @@ from torch import nn
 
 from .. import ops
 from .functional import (Conv1dActFunction, GRULayerFunction, LayerNormActFunction, LinearActFunction,
-                         LSTMLayerFunction, PackedBatch, StatesToCallerOrder)
+                         LSTMLayerFunction, PackedBatch, RNNLayerFunction, StatesToCallerOrder)
 
 
 class LinearAct(nn.Linear):
@@ -120,14 +120,14 @@ def _persistent_width(H, rows, ndir, device):
     return 512 if rounds <= allowed else None
 
 
-def _pad_hidden(w_ih, w_hh, biases, h0s, G, H, rows=0):
+def _pad_hidden(w_ih, w_hh, biases, h0s, G, H, rows=0, persistent=True):
     """The recurrence kernels tile the hidden units in groups of 16.  Any other hidden size runs
     zero-padded to the next multiple -- or to 512 where that puts the layer on the persistent recurrences
-    (_persistent_width) --: a padded unit has zero weights and biases, so its gates sit
-    at sigma(0) / tanh(0), its state stays exactly 0 and -- its W_hh columns being zero -- it never
+    (_persistent_width; `persistent`: the cell has them) --: a padded unit has zero weights and biases, so its gates sit
+    at sigma(0) / tanh(0) / relu(0), its state stays exactly 0 and -- its W_hh columns being zero -- it never
     reaches a real unit.  Differentiable torch ops: autograd slices the gradients back.
     w_ih [ndir, G*H, F], w_hh [ndir, G*H, H], biases [ndir, G*H] each, h0s [ndir, H] or None."""
-    Hp = _persistent_width(H, rows, w_ih.shape[0], w_ih.device) or (H + 15) // 16 * 16
+    Hp = (persistent and _persistent_width(H, rows, w_ih.shape[0], w_ih.device)) or (H + 15) // 16 * 16
     if Hp == H:
         return w_ih, w_hh, biases, h0s, H
     ndir, _, F = w_ih.shape
@@ -162,6 +162,8 @@ class _RNNBase(nn.Module):
     bias_hh_.. per layer and direction, in torch.nn's order -- the checkpoints' and the Adam arena's layout) with
     `_gates` blocks of hidden_size rows, their initialisation, packing and inter-layer dropout."""
     _gates = 1
+    _persistent = True       # the cell has persistent recurrences (rnn_persist.h) worth padding a layer to 512 for
+    _layer_extra = ()        # what the cell's layer function takes behind `training`
 
     def __init__(self, input_size, hidden_size, num_layers=1, bias=True, batch_first=False,
                  dropout=0.0, bidirectional=False):
@@ -205,7 +207,7 @@ class _RNNBase(nn.Module):
         return x
 
     def _recurrent_forward(self, input_, h0s, lengths):
-        """LSTM / GRU on the recurrence kernels: h0s = the initial states ((h_0, c_0) / (h_0,), each
+        """The layers on the recurrence kernels: h0s = the initial states ((h_0, c_0) / (h_0,), each
         [num_layers*ndir, B, H] or None) -> (output, the final states, each [num_layers*ndir, B, H] in the
         caller's row order)."""
         ndir = 2 if self.bidirectional else 1
@@ -223,10 +225,12 @@ class _RNNBase(nn.Module):
             states = [h[layer * ndir:(layer + 1) * ndir, 0, :] if h is not None else None for h in h0s]
             operands.append(_pad_hidden(
                 self._stack("weight_ih", layer), self._stack("weight_hh", layer),
-                [self._stack("bias_ih", layer), self._stack("bias_hh", layer)], states, self._gates, H, rows=pb.B))
+                [self._stack("bias_ih", layer), self._stack("bias_hh", layer)], states, self._gates, H, rows=pb.B,
+                persistent=self._persistent))
         finals = []
         for layer, (w_ih, w_hh, (b_ih, b_hh), states, Hp) in enumerate(operands):
-            x, *fin = self._layer_function.apply(x, pb, w_ih, w_hh, b_ih, b_hh, *states, torch.is_grad_enabled())
+            x, *fin = self._layer_function.apply(x, pb, w_ih, w_hh, b_ih, b_hh, *states, torch.is_grad_enabled(),
+                                                  *self._layer_extra)
             x = self._dropout(_unpad_rows(x, ndir, H, Hp), layer)
             finals.append(fin)
         out = pb.unpack(x, input_.shape)
@@ -266,11 +270,11 @@ class RNN(_RNNBase):
     batch_first) as RNNWrapper builds it for 'RNNTANH' / 'RNNRELU' groups (rnn_dyn/RNNWrapper.py:
     45-54, RNNDyn.py:268-272); same parameter names.
         output, h_n = rnn(padded, h_0, lengths)
-    The cell is one fused linear layer per step, h_t = act([h_{t-1} | W_ih x_t + b] [W_hh | I]^T):
-    the input projection of all frames is one GEMM on packed rows, every step one launch of the
-    same fp32-MFMA kernel on the rows still active (the identity block adds the projection), and
-    autograd chains the steps.  Unlike LSTM / GRU there is no dedicated recurrence kernel -- this
-    cell type is kept for completeness, not speed."""
+    h_t = act(W_ih x_t + b_ih + b_hh + W_hh h_{t-1}): the input projection of all frames is one GEMM on packed rows,
+    the recurrence runs on the step kernels of csrc/rnn_step.h (one launch per time step, both directions in it) at
+    the hidden size rounded up to a multiple of 16.  Unlike LSTM / GRU, a loss may use h_n."""
+    _layer_function = RNNLayerFunction
+    _persistent = False
 
     def __init__(self, input_size, hidden_size, num_layers=1, nonlinearity='tanh', bias=True,
                  batch_first=False, dropout=0.0, bidirectional=False):
@@ -279,51 +283,10 @@ class RNN(_RNNBase):
         super().__init__(input_size, hidden_size, num_layers, bias, batch_first, dropout, bidirectional)
         self.nonlinearity = nonlinearity.lower()
 
-    def _direction(self, x, pb, layer, d, h0):
-        """x [N, F] packed rows -> (y [N, H] packed, h_n [B, H] in sorted row order)"""
-        H = self.hidden_size
-        sfx = "_l{}{}".format(layer, "_reverse" if d == 1 else "")
-        w_ih, w_hh = getattr(self, "weight_ih" + sfx), getattr(self, "weight_hh" + sfx)
-        bias = getattr(self, "bias_ih" + sfx) + getattr(self, "bias_hh" + sfx)
-        act = ops.ACT_TANH if self.nonlinearity == "tanh" else ops.ACT_RELU
-        gin = LinearActFunction.apply(x, w_ih, bias, ops.ACT_NONE)                    # [N, H]
-        w_step = torch.cat((w_hh, torch.eye(H, dtype=w_hh.dtype, device=w_hh.device)), dim=1)
-        lengths = pb.h_lengths.tolist()
-        row_off = pb.d_row_off.tolist()
-        h = h0.unsqueeze(0).expand(pb.B, H) if h0 is not None else x.new_zeros((pb.B, H))
-        steps, finished = [], []
-        nact_prev = pb.B
-        for s in range(pb.T):
-            nact = sum(1 for n in lengths if n > s)             # sorted: the first nact rows
-            if d == 0:
-                g = gin[row_off[s]:row_off[s] + nact]
-            else:
-                g = gin.index_select(0, pb.d_rev_row[s, :nact].long())
-            if nact < nact_prev:
-                finished.append(h[nact:nact_prev])               # their last state is final
-            h = LinearActFunction.apply(torch.cat((h[:nact], g), dim=1), w_step, None, act)
-            steps.append(h)
-            nact_prev = nact
-        finished.append(h)
-        h_n = torch.cat(finished[::-1], dim=0)                   # rows 0 .. B-1 (sorted order)
-        if d == 0:
-            y = torch.cat(steps, dim=0)                          # packed order is step order
-        else:
-            idx = torch.cat([pb.d_rev_row[s, :steps[s].shape[0]].long() for s in range(pb.T)])
-            y = torch.empty_like(gin).index_copy(0, idx, torch.cat(steps, dim=0))
-        return y, h_n
+    @property
+    def _layer_extra(self):
+        return (ops.ACT_TANH if self.nonlinearity == "tanh" else ops.ACT_RELU,)
 
     def forward(self, input_, hx=None, lengths=None):
-        ndir = 2 if self.bidirectional else 1
-        pb, x = self._pack(input_, lengths, pad_cols=False)
-        _shared_initial_state(hx)
-        hn_all = []
-        for layer in range(self.num_layers):
-            outs = []
-            for d in range(ndir):
-                h0 = hx[layer * ndir + d, 0, :] if hx is not None else None   # shared by all rows
-                y, h_n = self._direction(x, pb, layer, d, h0)
-                outs.append(y)
-                hn_all.append(h_n.index_select(0, pb.inv_perm))
-            x = self._dropout(outs[0] if ndir == 1 else torch.cat(outs, dim=1), layer)
-        return pb.unpack(x, input_.shape), torch.stack(hn_all, 0)
+        out, (hn,) = self._recurrent_forward(input_, (hx,), lengths)
+        return out, hn

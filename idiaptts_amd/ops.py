@@ -1021,6 +1021,17 @@ def rnn_path_counts():
     return RnnPathCounts(*[int(v) for v in out])
 
 
+RnnLayerCounts = collections.namedtuple("RnnLayerCounts", "fwd bwd")
+
+
+def rnn_layer_counts():
+    """Forward and backward vanilla RNN layer calls of this process so far (itts_rnn_layer_counts; no device call).
+    rnn_path_counts() does not count them: they have no persistent kernel to run on or be declined by."""
+    out = (ctypes.c_int64 * 2)()
+    _lib.check(_lib.load().itts_rnn_layer_counts(out), "itts_rnn_layer_counts")
+    return RnnLayerCounts(int(out[0]), int(out[1]))
+
+
 
 # ------------------------------------------------------------------------- WORLD frame kernels
 def _c_int_ptr(t):

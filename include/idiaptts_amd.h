@@ -740,6 +740,34 @@ int itts_gru_layer_bwd(const float* d_dy, const float* d_whh, const float* d_gat
                        const int* d_row_off, const int* d_rev_row, int T, int B, int H, int ndir,
                        float* d_dgi, float* d_dgh, float* d_dh0, void* d_state, void* stream);
 
+/* ---- vanilla (Bi)RNN recurrence (torch.nn.RNN behind rnn_dyn/RNNWrapper.py:45-107 for `..RNNTANH..` / `..RNNRELU..`
+ *      groups): h_t = act(gin_t + W_hh h_{t-1}), act = ITTS_ACT_TANH or ITTS_ACT_RELU; packed rows, lengths, row
+ *      offsets and the reverse row table as for the LSTM entry points.
+ * d_gin [N, ndir*H] = X W_ih^T + b_ih + b_hh for all frames (one itts_linear_fwd call), d_whh [ndir][H][H], d_h0
+ * [ndir][H] or NULL (zeros), d_y [N, ndir*H], d_hn [ndir][B][H] in sorted row order (may be NULL; row b's is d_y at
+ * the last frame its direction processes).  H is a multiple of 16 (run other sizes zero-padded).  Nothing but d_y is
+ * saved for backward, so a training and an inference call are the same call.
+ * d_state >= itts_rnn_layer_state_bytes(B, H, ndir) = 4 * (4 * ndir * B * H + ndir * H * H) bytes: the running state
+ * and the carried gradient, two step parities each, and the re-tiled W_hh; 0 for a size that is not positive.
+ * Backward takes d_y and fills d_dg [N, ndir*H] = (d_dy + d_dg[next processed frame] W_hh) * act'(d_y), act' = 1 - y^2
+ * or y > 0, the gradient wrt d_gin and wrt the hidden projection alike: dX, dW_ih and both bias gradients follow from
+ * it as for the LSTM, dW_hh from it and d_y shifted by one frame along each sequence (h0 at the first frame);
+ * dLoss/d(initial hidden state) of row b is W_hh^T d_dg[first processed frame of b].  A gradient into d_hn is added to
+ * d_dy at the row's last processed frame before the call.
+ * Bad arguments (H % 16, another activation code, a null operand, lengths that are not sorted / T not the longest)
+ * return ITTS_E_INVALID before any device work.  These layers always run on the per-step kernels. */
+int64_t itts_rnn_layer_state_bytes(int B, int H, int ndir);
+int itts_rnn_layer_fwd(const float* d_gin, const float* d_whh, const float* d_h0, const int* d_lengths,
+                       const int* h_lengths, const int* d_row_off, const int* d_rev_row, int T, int B, int H,
+                       int ndir, int act /* ITTS_ACT_TANH | ITTS_ACT_RELU */, float* d_y, float* d_hn,
+                       void* d_state, void* stream);
+int itts_rnn_layer_bwd(const float* d_dy, const float* d_whh, const float* d_y, const int* h_lengths,
+                       const int* d_row_off, const int* d_rev_row, int T, int B, int H, int ndir, int act,
+                       float* d_dg, void* d_state, void* stream);
+/* out = forward, backward vanilla RNN layer calls of this process that passed their argument checks (process-wide
+ * atomic counts, no device call).  itts_rnn_path_counts below does not count them. */
+int itts_rnn_layer_counts(int64_t out[2]);
+
 /* Which kernel the dense-layer products (itts_linear_*) of this process ran on (process-wide atomic counts, no device
  * call): out[e] = products on the LDS-DMA ring kernel, out[4 + e] = on the register-staged kernel, e = the epilogue
  * kind: 0 plain store (weight gradients, input gradients without an activation), 1 bias + activation (forward),
