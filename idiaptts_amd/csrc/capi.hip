@@ -4,6 +4,7 @@
 #include <mutex>
 #include <vector>
 
+#include "allpass.h"
 #include "common.h"
 
 namespace itts {
@@ -107,4 +108,52 @@ extern "C" int itts_wav2world(const double* d_x, const int64_t* h_x_off, const i
                   nullptr, 0, stream);
   ITTS_HIP_CHECK(itts::scratch_free(d_f0_raw, s));
   return rc;
+}
+
+// layers/AllPassWarp.py:148-173 (forward: halve, bmm(feature, warp_matrix) per block, double) between
+// layers/AllPassWarpLayer.py:141-150's _denormalise and _normalise, on csrc/allpass.hip
+static int allpass_check(const char* func, int64_t M, int D, int N, int64_t ld_in, int64_t ld_x, int64_t ld_out) {
+  std::string bad;
+  if (N < 1 || N > itts::kAllpassMaxN)
+    bad = "warp matrix size N = " + std::to_string(N) + " is outside 1 .. " + std::to_string(itts::kAllpassMaxN);
+  else if (D < N || D % N != 0)
+    bad = "width D = " + std::to_string(D) + " is not a positive multiple of N = " + std::to_string(N);
+  else if (M < 0 || M > (int64_t)64 * 0x7fffffff)
+    bad = "row count M = " + std::to_string(M) + " is out of range";
+  else
+    for (int64_t ld : {ld_in, ld_x, ld_out})
+      if (ld < D) {
+        bad = "row pitch " + std::to_string(ld) + " is below the width D = " + std::to_string(D);
+        break;
+      }
+  if (bad.empty()) return ITTS_OK;
+  itts::set_error(std::string(func) + ": " + bad);
+  return ITTS_E_INVALID;
+}
+
+extern "C" int itts_allpass_warp_fwd(const float* d_x, int64_t ldx, const float* d_alpha, const float* d_mean,
+                                     const float* d_std_dev, float* d_y, int64_t ldy, int64_t M, int D, int N,
+                                     void* stream) {
+  if (int rc = allpass_check(__func__, M, D, N, ldx, ldx, ldy)) return rc;
+  if (M == 0) return ITTS_OK;
+  ITTS_REQUIRE(d_x && d_alpha && d_y, "null pointer with M = " + std::to_string(M) + " rows");
+  itts::AllpassArgs a{};
+  a.x = d_x; a.ldx = ldx; a.alpha = d_alpha; a.mean = d_mean; a.sd = d_std_dev; a.y = d_y; a.ldy = ldy;
+  a.M = M; a.N = N; a.nb = D / N;
+  ITTS_HIP_CHECK(itts::allpass_launch_fwd(a, itts::as_stream(stream)));
+  return ITTS_OK;
+}
+
+extern "C" int itts_allpass_warp_bwd(const float* d_dy, int64_t lddy, const float* d_x, int64_t ldx,
+                                     const float* d_alpha, const float* d_mean, const float* d_std_dev,
+                                     float* d_dx, int64_t lddx, float* d_dalpha, int64_t M, int D, int N,
+                                     void* stream) {
+  if (int rc = allpass_check(__func__, M, D, N, lddy, ldx, lddx)) return rc;
+  if (M == 0) return ITTS_OK;
+  ITTS_REQUIRE(d_dy && d_x && d_alpha && d_dx && d_dalpha, "null pointer with M = " + std::to_string(M) + " rows");
+  itts::AllpassArgs a{};
+  a.dy = d_dy; a.lddy = lddy; a.x = d_x; a.ldx = ldx; a.alpha = d_alpha; a.mean = d_mean; a.sd = d_std_dev;
+  a.dx = d_dx; a.lddx = lddx; a.dalpha = d_dalpha; a.M = M; a.N = N; a.nb = D / N;
+  ITTS_HIP_CHECK(itts::allpass_launch_bwd(a, itts::as_stream(stream)));
+  return ITTS_OK;
 }

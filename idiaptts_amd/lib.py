@@ -120,6 +120,9 @@ _SIGNATURES = {
     "itts_layernorm_workspace_bytes": (c_int64, [c_int64, c_int]),
     "itts_layernorm_bwd": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P, _P, c_int64, _P, _P, c_int64,
                                    c_int, c_int, _P, _P]),
+    "itts_allpass_warp_fwd": (c_int, [_P, c_int64, _P, _P, _P, _P, c_int64, c_int64, c_int, c_int, _P]),
+    "itts_allpass_warp_bwd": (c_int, [_P, c_int64, _P, c_int64, _P, _P, _P, _P, c_int64, _P, c_int64, c_int, c_int,
+                                      _P]),
     "itts_masked_mse_workspace_bytes": (c_int64, [c_int64, c_int]),
     "itts_masked_mse": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, c_int, c_double, c_float,
                                 _P, _P, c_int64, _P, _P]),

@@ -187,6 +187,55 @@ class LayerNormActFunction(torch.autograd.Function):
         return (dx if ctx.needs_input_grad[0] else None), dw, db, None, None, None
 
 
+class AllPassWarpFunction(torch.autograd.Function):
+    """y = all-pass warp of x by alpha (layers/AllPassWarp.py forward, with layers/AllPassWarpLayer.py's
+    de-normalisation before and normalisation after inside the same kernel).  x: [.., .., D] with D = nb * N,
+    alpha: the same leading shape with a last extent of 1 (or none); mean / std_dev: [D] or None.  One node: saves
+    x and alpha only, the backward recomputes the warp; gradients for x and alpha, none for mean / std_dev.  x is
+    never written."""
+
+    @staticmethod
+    def forward(ctx, x, alpha, mean, std_dev, N):
+        shape = x.shape
+        x2 = x.reshape(-1, shape[-1])
+        if x2.stride(-1) != 1 or (x2.shape[0] > 1 and x2.stride(0) < shape[-1]):
+            x2 = x2.contiguous()
+        if alpha.numel() != x2.shape[0]:
+            raise ValueError("alpha of shape {} does not hold one factor per frame of an input of shape {}"
+                             .format(tuple(alpha.shape), tuple(shape)))
+        a1 = alpha.reshape(-1).contiguous()
+        mean = mean.contiguous() if mean is not None else None
+        std_dev = std_dev.contiguous() if std_dev is not None else None
+        y = ops.allpass_warp_fwd(x2, a1, N, mean, std_dev)
+        ctx.save_for_backward(x2, a1)
+        ctx.norm = (mean, std_dev)            # (buffers, not differentiated: no graph hangs on them)
+        ctx.N, ctx.in_shape, ctx.alpha_shape = N, shape, alpha.shape
+        return y.reshape(shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, a1 = ctx.saved_tensors
+        dy2 = dy.reshape(-1, dy.shape[-1])
+        if dy2.stride(-1) != 1 or (dy2.shape[0] > 1 and dy2.stride(0) < dy2.shape[1]):
+            dy2 = dy2.contiguous()
+        dx, da = ops.allpass_warp_bwd(dy2, x2, a1, ctx.N, *ctx.norm)
+        return (dx.reshape(ctx.in_shape) if ctx.needs_input_grad[0] else None,
+                da.reshape(ctx.alpha_shape) if ctx.needs_input_grad[1] else None, None, None, None)
+
+
+class grad_scaling(torch.autograd.Function):
+    """Identity whose gradient is multiplied by a constant (reference GradientScaling.py: grad_scaling)."""
+
+    @staticmethod
+    def forward(ctx, input_, lambda_):
+        ctx.lambda_ = float(lambda_)
+        return input_.view_as(input_)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        return grad_output * ctx.lambda_, None
+
+
 def _rows_padded(M, N, device):
     """[M, N] view of a fresh buffer whose row pitch is N rounded up to four floats, pad columns zero"""
     Np = (N + 3) // 4 * 4

@@ -8,8 +8,9 @@ import torch
 from torch import nn
 
 from .. import ops
-from .functional import (Conv1dActFunction, GRULayerFunction, LayerNormActFunction, LinearActFunction,
-                         LSTMLayerFunction, PackedBatch, RNNLayerFunction, StatesToCallerOrder)
+from .functional import (AllPassWarpFunction, Conv1dActFunction, GRULayerFunction, LayerNormActFunction,
+                         LinearActFunction, LSTMLayerFunction, PackedBatch, RNNLayerFunction, StatesToCallerOrder,
+                         grad_scaling)
 
 
 class LinearAct(nn.Linear):
@@ -86,6 +87,66 @@ class LayerNormAct(nn.LayerNorm):
             return y if self.act == ops.ACT_NONE else getattr(nn, ops.ACT_TORCH_NAME[self.act])()(y)
         return LayerNormActFunction.apply(input_, self.weight, self.bias, self.normalized_shape[0], self.eps,
                                           self.act)
+
+
+class AllPassWarp(nn.Module):
+    """All-pass frequency warping of cepstral features, the reference's layers/AllPassWarp.py: every block of
+    `warp_matrix_size` coefficients of a frame is multiplied by the all-pass matrix of the frame's warping factor.
+    `forward(in_tensor, alphas) -> (out, combined_alphas)` with in_tensor [B, T, D] or [T, B, D] and alphas one
+    tensor, or a list / tuple of tensors, of the same two leading extents and a last extent of 1.  The matrix is
+    never built: csrc/allpass.hip applies its recursion per frame, so there is no coefficient buffer (the
+    reference's `w_matrix_3d` is non-persistent: state dicts are the same), the results are finite at any size up
+    to ops.ALLPASS_MAX_SIZE, and the input is not modified (the reference halves columns of it in place).  `mean` /
+    `std_dev` [D] de-normalise the input and normalise the output inside the same kernel."""
+
+    def __init__(self, warp_matrix_size):
+        super().__init__()
+        warp_matrix_size = int(warp_matrix_size)
+        if warp_matrix_size < 1:
+            raise ValueError("warp_matrix_size must be at least 1, got {}".format(warp_matrix_size))
+        if warp_matrix_size > ops.ALLPASS_MAX_SIZE:
+            raise NotImplementedError("warp_matrix_size={}: the kernel takes at most {}"
+                                      .format(warp_matrix_size, ops.ALLPASS_MAX_SIZE))
+        self.warp_matrix_size = warp_matrix_size
+
+    def init_hidden(self, batch_size=1):
+        return None
+
+    @staticmethod
+    def combine_warping_parameters(alphas):
+        """Successive all-pass warps by a1, a2, .. are one warp by the reduction (a1 + a2) / (1 + a1 a2)."""
+        if not isinstance(alphas, (list, tuple)):
+            return alphas
+        combined = alphas[0]
+        for alpha in alphas[1:]:
+            combined = (combined + alpha) / (1 + combined * alpha)
+        return combined
+
+    def forward(self, in_tensor, alphas, mean=None, std_dev=None):
+        width = in_tensor.shape[-1]
+        if width % self.warp_matrix_size != 0:
+            raise ValueError("feature width {} is not a multiple of warp_matrix_size {}"
+                             .format(width, self.warp_matrix_size))
+        combined = AllPassWarp.combine_warping_parameters(alphas)
+        out = AllPassWarpFunction.apply(in_tensor, combined, mean, std_dev, self.warp_matrix_size)
+        return out, combined
+
+    def extra_repr(self):
+        return "warp_matrix_size={}".format(self.warp_matrix_size)
+
+
+class GradientScaling(nn.Module):
+    """Identity in the forward, gradient times `lambda_` in the backward (reference GradientScaling.py)."""
+
+    def __init__(self, lambda_):
+        super().__init__()
+        self.lambda_ = float(lambda_)
+
+    def forward(self, input_):
+        return grad_scaling.apply(input_, self.lambda_)
+
+    def extra_repr(self):
+        return "lambda={}".format(self.lambda_)
 
 
 def _first(v):

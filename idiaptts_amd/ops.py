@@ -902,6 +902,51 @@ def layer_norm_bwd(dy, x, mean, rstd, gamma, y=None, act=ACT_NONE, want_gamma=Tr
     return dx, dgamma, dbeta
 
 
+ALLPASS_MAX_SIZE = 64            # kAllpassMaxN of csrc/allpass.h
+
+
+def _allpass_operands(x, alpha, mean, std_dev, N):
+    _need(x, torch.float32, "x")
+    _need(alpha, torch.float32, "alpha")
+    M, D = x.shape
+    if alpha.shape != (M,) or not alpha.is_contiguous():
+        raise ValueError("alpha must be a contiguous [{}] vector, one factor per row".format(M))
+    for name, t in (("mean", mean), ("std_dev", std_dev)):
+        if t is not None:
+            _need(t, torch.float32, name)
+            if t.shape != (D,) or not t.is_contiguous():
+                raise ValueError("{} must be a contiguous [{}] vector".format(name, D))
+    return M, D
+
+
+def allpass_warp_fwd(x, alpha, N, mean=None, std_dev=None, out=None):
+    """All-pass warping of [M, D] rows, D = nb * N, by one factor per row (layers/AllPassWarp.py forward between
+    layers/AllPassWarpLayer.py's _denormalise / _normalise): returns y [M, D]; x is not modified."""
+    L = _lib.load()
+    M, D = _allpass_operands(x, alpha, mean, std_dev, N)
+    if out is None:
+        out = torch.empty((M, D), dtype=torch.float32, device=x.device)
+    _need(out, torch.float32, "out")
+    _lib.check(L.itts_allpass_warp_fwd(_ptr(x), _rows(x, "x"), _ptr(alpha), _ptr(mean), _ptr(std_dev), _ptr(out),
+                                       _rows(out, "out"), M, D, int(N), _stream()), "itts_allpass_warp_fwd")
+    return out
+
+
+def allpass_warp_bwd(dy, x, alpha, N, mean=None, std_dev=None):
+    """(dx [M, D], dalpha [M]) of allpass_warp_fwd for dy = dL/dy; the warp is recomputed from alpha."""
+    L = _lib.load()
+    M, D = _allpass_operands(x, alpha, mean, std_dev, N)
+    _need(dy, torch.float32, "dy")
+    if dy.shape != x.shape:
+        raise ValueError("dy must have the shape of x")
+    dx = torch.empty((M, D), dtype=torch.float32, device=x.device)
+    dalpha = torch.empty((M,), dtype=torch.float32, device=x.device)
+    _lib.check(L.itts_allpass_warp_bwd(_ptr(dy), _rows(dy, "dy"), _ptr(x), _rows(x, "x"), _ptr(alpha), _ptr(mean),
+                                       _ptr(std_dev), _ptr(dx), _rows(dx, "dx"), _ptr(dalpha), M, D, int(N),
+                                       _stream()), "itts_allpass_warp_bwd")
+    return dx, dalpha
+
+
 def weighted_loss(pred, target, row_weight, kind, want_grad=True, want_elem=False):
     """sum_r w[r] sum_c e(pred - target) on [M, D] rows, e squared (kind 0) / absolute (kind 1)
     error: (loss [1], grad or None, elementwise values or None)."""

@@ -499,6 +499,28 @@ int itts_layernorm_bwd(const float* d_dy, int64_t lddy, const float* d_x, int64_
                        const float* d_gamma, float* d_dx, int64_t lddx, float* d_dgamma,
                        float* d_dbeta, int64_t N, int D, int act, void* d_workspace, void* stream);
 
+/* ---- all-pass frequency warping, the VTLN layer (csrc/allpass.hip) ------------------------------------------
+ * Rows of D = nb * N floats are nb blocks of N cepstral coefficients, each warped by the row's own factor:
+ * y_b = x_b' W(alpha), W the N x N all-pass matrix of the recursion W[0][0] = 1, W[0][c] = 0,
+ * W[r][0] = alpha W[r-1][0], W[r][c] = W[r-1][c-1] + alpha (W[r-1][c] - W[r][c-1]), applied inside the kernel
+ * (no matrix is stored).  In blocks 0..2 the first coefficient is halved before and doubled after.  With d_mean /
+ * d_std_dev [D] (each may be NULL) the input is first taken as x * std_dev + mean and the output written as
+ * (y - mean) / std_dev.  1 <= N <= 64, D a multiple of N, row pitches >= D; anything else is refused with
+ * ITTS_E_INVALID and a message naming the value before any device work; M == 0 succeeds and does nothing.
+ * d_x is never written.
+ * Reference: layers/AllPassWarp.py:148-173 (AllPassWarp.forward) inside layers/AllPassWarpLayer.py:141-150
+ * (forward_fixed_alphas: _denormalise, warp, _normalise). */
+int itts_allpass_warp_fwd(const float* d_x, int64_t ldx, const float* d_alpha, const float* d_mean,
+                          const float* d_std_dev, float* d_y, int64_t ldy, int64_t M, int D, int N,
+                          void* stream);
+/* Gradients of the above for d_dy = dL/dy: d_dx [M, D] and d_dalpha [M].  W and dW/dalpha are recomputed from
+ * alpha (only x and alpha are needed from the forward); a row's dalpha is summed by the lane that owns the row,
+ * in a fixed order and without atomics, so repeated calls give identical bits.
+ * Reference: autograd through layers/AllPassWarp.py:157-171 (get_warp_matrix's einsum and the bmm). */
+int itts_allpass_warp_bwd(const float* d_dy, int64_t lddy, const float* d_x, int64_t ldx,
+                          const float* d_alpha, const float* d_mean, const float* d_std_dev, float* d_dx,
+                          int64_t lddx, float* d_dalpha, int64_t M, int D, int N, void* stream);
+
 /* ---- masked MSE, reduction 'mean_per_frame' (loss/NamedLoss.py:70-117) -------------------- */
 /*
  * loss = mean_d( sum_{valid frames} (pred-target)^2 / n_valid ), grad = dloss/dpred.
