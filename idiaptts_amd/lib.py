@@ -123,6 +123,14 @@ _SIGNATURES = {
     "itts_allpass_warp_fwd": (c_int, [_P, c_int64, _P, _P, _P, _P, c_int64, c_int64, c_int, c_int, _P]),
     "itts_allpass_warp_bwd": (c_int, [_P, c_int64, _P, c_int64, _P, _P, _P, _P, c_int64, _P, c_int64, c_int, c_int,
                                       _P]),
+    "itts_time_pool_plan": (c_int, [c_int, c_int64, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int64)]),
+    "itts_time_pool_fwd": (c_int, [_P, c_int64, _P, c_int, c_int64, c_int, c_int, c_int, _P, c_int64, _P, _P]),
+    "itts_time_pool_bwd": (c_int, [_P, c_int64, _P, c_int, c_int64, c_int, c_int, c_int, _P, c_int64, _P]),
+    "itts_vae_reparam_fwd": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, c_int64, c_int, _P]),
+    "itts_vae_reparam_bwd": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64,
+                                     c_int64, c_int, _P]),
+    "itts_vae_kld_workspace_bytes": (c_int64, [c_int64, c_int]),
+    "itts_vae_kld": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, c_int, _P, _P, c_int64, _P, c_int64, _P, _P, _P]),
     "itts_masked_mse_workspace_bytes": (c_int64, [c_int64, c_int]),
     "itts_masked_mse": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, c_int, c_double, c_float,
                                 _P, _P, c_int64, _P, _P]),

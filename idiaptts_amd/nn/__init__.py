@@ -1,1 +1,2 @@
-from .modules import GRU, LSTM, RNN, AllPassWarp, GradientScaling, LinearAct  # noqa: F401
+from .modules import (GRU, LSTM, RNN, AllPassWarp, GradientScaling, LinearAct, MeanPooling,  # noqa: F401
+                      SelectLastPooling, VanillaVAE)

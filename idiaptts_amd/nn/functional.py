@@ -223,6 +223,98 @@ class AllPassWarpFunction(torch.autograd.Function):
                 da.reshape(ctx.alpha_shape) if ctx.needs_input_grad[1] else None, None, None, None)
 
 
+def _pitched3(x):
+    """x ([B, T, D] / [T, B, D]) as the pooling kernels take it: unit stride on the features, evenly spaced
+    positions; anything else is copied"""
+    if x.dim() != 3:
+        raise ValueError("pooling over time needs a 3-D padded batch, got shape {}".format(tuple(x.shape)))
+    return x if ops.pool_pitch(x) is not None else x.contiguous()
+
+
+class TimePoolFunction(torch.autograd.Function):
+    """[B, T, D] / [T, B, D] -> the same with a time extent of 1 (rnn_dyn/Pooling.py: SelectLastPooling row
+    len_b - 1, MeanPooling sum over ALL T positions / len_b).  Saves the lengths only; the backward writes every
+    position of dx in one launch."""
+
+    @staticmethod
+    def forward(ctx, x, lens, batch_first, mode):
+        x = _pitched3(x)
+        time_dim = 1 if batch_first else 0
+        n_utts, t_max = x.shape[1 - time_dim], x.shape[time_dim]
+        lens = ops._pool_lens(lens, n_utts, t_max, mode, x.device)
+        y = ops.time_pool_fwd(x, lens, batch_first, mode)
+        ctx.lens, ctx.t_max, ctx.batch_first, ctx.mode = lens, t_max, batch_first, mode
+        return y.unsqueeze(time_dim)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy2 = dy.reshape(-1, dy.shape[-1])
+        if dy2.stride(-1) != 1 or (dy2.shape[0] > 1 and dy2.stride(0) < dy2.shape[1]):
+            dy2 = dy2.contiguous()
+        return ops.time_pool_bwd(dy2, ctx.lens, ctx.t_max, ctx.batch_first, ctx.mode), None, None, None
+
+
+def _rows2(t, width):
+    """[.., width] -> [M, width] rows the kernels take (unit stride on the last extent, rows not overlapping)"""
+    t2 = t.reshape(-1, width)
+    if t2.stride(-1) != 1 or (t2.shape[0] > 1 and t2.stride(0) < width):
+        t2 = t2.contiguous()
+    return t2
+
+
+class VAEReparamFunction(torch.autograd.Function):
+    """(z, mu, log_var) of hidden = mu | log_var and a standard-normal draw eps (rnn_dyn/VAE.py:19-27).  mu and
+    log_var are views of hidden; the three outputs hang on this ONE node, so the gradient of a reconstruction loss
+    into z and the gradient of the KL term into mu / log_var meet in one kernel that writes the whole d(hidden)."""
+
+    @staticmethod
+    def forward(ctx, hidden, eps):
+        lat = hidden.shape[-1] // 2
+        h2 = _rows2(hidden, 2 * lat)
+        e2 = _rows2(eps, lat)
+        z = ops.vae_reparam_fwd(h2, e2)
+        ctx.save_for_backward(h2, e2)
+        ctx.set_materialize_grads(False)
+        ctx.in_shape = hidden.shape
+        mu, log_var = torch.split(hidden, lat, dim=-1)
+        return z.reshape(*hidden.shape[:-1], lat), mu, log_var
+
+    @staticmethod
+    def backward(ctx, dz, dmu, dlv):
+        h2, e2 = ctx.saved_tensors
+        lat = e2.shape[1]
+        if dz is None and dmu is None and dlv is None:
+            return None, None
+        grads = [_rows2(g, lat) if g is not None else None for g in (dz, dmu, dlv)]
+        return ops.vae_reparam_bwd(grads[0], grads[1], grads[2], h2, e2).reshape(ctx.in_shape), None
+
+
+class VAEKLDFunction(torch.autograd.Function):
+    """sum_r w[r] * 0.5 * sum_c (exp(log_var) + mu^2 - 1 - log_var), or with `elementwise` the weighted per-row
+    values [.., 1] (reduction 'none'); loss/VAEKLDLoss.py:56-58 with the mask and the reduction folded into w as in
+    WeightedLossFunction.  Loss and both gradients come from one launch."""
+
+    @staticmethod
+    def forward(ctx, mu, log_var, row_weight, elementwise):
+        lat = mu.shape[-1]
+        m2, l2 = _rows2(mu, lat), _rows2(log_var, lat)
+        # (under no_grad -- validation -- nobody reads the gradients: the kernel then writes none)
+        want_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        loss, dmu, dlv, elem = ops.vae_kld(m2, l2, row_weight, want_grad=want_grad, want_elem=elementwise)
+        if want_grad:
+            ctx.save_for_backward(dmu, dlv)
+        ctx.shape, ctx.elementwise = mu.shape, elementwise
+        return elem.reshape(*mu.shape[:-1], 1) if elementwise else loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        dmu, dlv = ctx.saved_tensors
+        dmu, dlv = dmu.reshape(ctx.shape), dlv.reshape(ctx.shape)
+        if not is_unit_gradient(dloss):
+            dmu, dlv = dmu * dloss, dlv * dloss       # (elementwise: [.., 1] broadcasts over the latent axis)
+        return dmu, dlv, None, None
+
+
 class grad_scaling(torch.autograd.Function):
     """Identity whose gradient is multiplied by a constant (reference GradientScaling.py: grad_scaling)."""
 

@@ -10,7 +10,7 @@ from torch import nn
 from .. import ops
 from .functional import (AllPassWarpFunction, Conv1dActFunction, GRULayerFunction, LayerNormActFunction,
                          LinearActFunction, LSTMLayerFunction, PackedBatch, RNNLayerFunction, StatesToCallerOrder,
-                         grad_scaling)
+                         TimePoolFunction, VAEReparamFunction, grad_scaling)
 
 
 class LinearAct(nn.Linear):
@@ -133,6 +133,74 @@ class AllPassWarp(nn.Module):
 
     def extra_repr(self):
         return "warp_matrix_size={}".format(self.warp_matrix_size)
+
+
+class Pooling(nn.Module):
+    """A padded batch [B, T, D] (batch_first) or [T, B, D] reduced to a time extent of 1 (reference
+    rnn_dyn/Pooling.py); `forward` takes the pair `(input, seq_lengths_input)` that `select_inputs` makes.
+    Deviation: `get_output_length` returns ones of the argument's kind WITHOUT writing into it -- the reference's
+    `seq_lengths_input.fill_(1)` overwrites the caller's length tensor (the handler's own lengths of the input
+    feature), and fails on the plain integers kept in `max_lengths`, which are accepted here."""
+    mode = None
+
+    def __init__(self, batch_first):
+        super().__init__()
+        self.batch_first = batch_first
+
+    def extra_repr(self):
+        return "batch_first={}".format(self.batch_first)
+
+    def get_output_length(self, seq_lengths_input):
+        if seq_lengths_input is None:
+            return None
+        if torch.is_tensor(seq_lengths_input):
+            return torch.ones_like(seq_lengths_input)
+        if isinstance(seq_lengths_input, (list, tuple)):
+            return type(seq_lengths_input)(1 for _ in seq_lengths_input)
+        return 1
+
+    def select_inputs(self, input_, **kwargs):
+        return input_, kwargs.pop("seq_lengths_input", None)
+
+    def forward(self, input_):
+        input_, lengths = input_
+        return TimePoolFunction.apply(input_, lengths, self.batch_first, self.mode)
+
+
+class SelectLastPooling(Pooling):
+    """Each utterance's frame `length - 1` (frame T - 1 without lengths): reference Pooling.py:26-44."""
+    mode = ops.POOL_LAST
+
+
+class MeanPooling(Pooling):
+    """The sum over ALL T positions of the padded batch, padding included, divided by the utterance's length:
+    what the reference's MeanPooling.forward computes (Pooling.py:55-64) and what its checkpoints were trained
+    with.  After a recurrent group the padding is zero and this is the masked mean; after Linear groups the padding
+    rows hold act(bias) and are counted."""
+    mode = ops.POOL_MEAN
+
+    def __init__(self, batch_first):
+        super().__init__(batch_first)
+        self.time_dim = 1 if batch_first else 0
+
+
+class VanillaVAE(nn.Module):
+    """hidden = linear(input) (no bias, [2 * latent_dim, dim_in]: the reference's state-dict key `linear.weight`),
+    mu | log_var = the two halves of hidden (views), z = eps * exp(0.5 * log_var) + mu; returns (z, mu, log_var)
+    -- reference rnn_dyn/VAE.py.  eps comes from exactly one torch.randn_like call per forward on a dense tensor of
+    z's shape, in training AND in evaluation, as the reference's `randn_like(std)`: under the same seed on the same
+    device the draw is `randn_like` of such a tensor (pinned by tests/test_gpu_latent.py), and a test can substitute
+    it."""
+
+    def __init__(self, dim_in, latent_dim):
+        super().__init__()
+        self.linear = LinearAct(dim_in, latent_dim * 2, bias=False)
+
+    def forward(self, input):
+        hidden = self.linear(input)
+        # (on a dense tensor of z's shape, like the reference's `randn_like(std)`)
+        eps = torch.randn_like(hidden.new_empty(hidden.shape[:-1] + (hidden.shape[-1] // 2,)))
+        return VAEReparamFunction.apply(hidden, eps)
 
 
 class GradientScaling(nn.Module):

@@ -947,6 +947,169 @@ def allpass_warp_bwd(dy, x, alpha, N, mean=None, std_dev=None):
     return dx, dalpha
 
 
+POOL_LAST, POOL_MEAN = 0, 1      # ITTS_POOL_* in include/idiaptts_amd.h
+
+
+def time_pool_plan(n_utts, t_max, width):
+    """(segments, split, workspace bytes) of a MEAN pooling call of that shape (itts_time_pool_plan; no device work):
+    `split` when every 128-row segment of time gets a workgroup and a second launch adds the segment sums."""
+    L = _lib.load()
+    seg, split, nbytes = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
+    if L.itts_time_pool_plan(int(n_utts), int(t_max), int(width), ctypes.byref(seg), ctypes.byref(split),
+                             ctypes.byref(nbytes)) != 0:
+        raise ValueError("no pooling plan for n_utts={}, t_max={}, width={}".format(n_utts, t_max, width))
+    return seg.value, bool(split.value), nbytes.value
+
+
+def pool_pitch(t):
+    """The position pitch of a padded batch [B, T, D] / [T, B, D] whose positions are evenly spaced rows of unit
+    stride, else None.  (The stride of an extent of 1 says nothing: `contiguous()` leaves any value there.)"""
+    if t.dim() != 3 or (t.shape[2] > 1 and t.stride(2) != 1):
+        return None
+    n0, n1, width = t.shape
+    if n1 > 1:
+        ld = t.stride(1)
+        if n0 > 1 and t.stride(0) != ld * n1:
+            return None
+    else:
+        ld = t.stride(0) if n0 > 1 else width
+    return ld if ld >= max(width, 1) else None
+
+
+def _pool_pitch(t, name):
+    ld = pool_pitch(t)
+    if ld is None:
+        raise ValueError("{} must be a 3-D padded batch of evenly spaced rows with unit stride".format(name))
+    return ld
+
+
+def _pool_lens(lens, n_utts, t_max, mode, device):
+    """int64 lengths on the device; a host tensor (or list) is checked for 1 <= len <= t_max first"""
+    if lens is None:
+        if mode == POOL_MEAN:
+            raise ValueError("mean pooling divides by the lengths: lens is None")
+        return None
+    if torch.is_tensor(lens) and lens.is_cuda and lens.dtype == torch.int64 and lens.dim() == 1 \
+            and lens.is_contiguous() and lens.numel() == n_utts:
+        return lens                      # (what the autograd node hands over: nothing to convert on the step's path)
+    if not torch.is_tensor(lens) or not lens.is_cuda:
+        lens = torch.as_tensor(lens, dtype=torch.int64).reshape(-1)
+        if lens.numel() and (int(lens.min()) < 1 or int(lens.max()) > t_max):
+            raise ValueError("sequence lengths must lie in 1 .. t_max = {}, got {} .. {}"
+                             .format(t_max, int(lens.min()), int(lens.max())))
+        lens = lens.to(device)
+    lens = lens.reshape(-1).to(torch.int64).contiguous()
+    if lens.numel() != n_utts:
+        raise ValueError("{} lengths for {} utterances".format(lens.numel(), n_utts))
+    return lens
+
+
+def time_pool_fwd(x, lens, batch_first, mode, out=None):
+    """[B, T, D] (batch_first) or [T, B, D] -> [B, D]: row len_b - 1 (POOL_LAST; row T - 1 when lens is None) or the
+    sum over ALL T positions divided by len_b (POOL_MEAN) -- rnn_dyn/Pooling.py."""
+    L = _lib.load()
+    _need(x, torch.float32, "x")
+    ld = _pool_pitch(x, "x")
+    n_utts, t_max = (x.shape[0], x.shape[1]) if batch_first else (x.shape[1], x.shape[0])
+    width = x.shape[2]
+    lens = _pool_lens(lens, n_utts, t_max, mode, x.device)
+    if out is None:
+        out = torch.empty((n_utts, width), dtype=torch.float32, device=x.device)
+    _need(out, torch.float32, "out")
+    ws = None
+    if mode == POOL_MEAN and n_utts > 0 and t_max > 0 and width > 0:
+        nbytes = time_pool_plan(n_utts, t_max, width)[2]
+        if nbytes:                       # (the segment sums of a time-split call, read back by its second launch)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    _lib.check(L.itts_time_pool_fwd(_ptr(x), ld, _ptr(lens), n_utts, t_max, width, 1 if batch_first else 0, int(mode),
+                                    _ptr(out), _rows(out, "out"), _ptr(ws), _stream()), "itts_time_pool_fwd")
+    return out
+
+
+def time_pool_bwd(dy, lens, t_max, batch_first, mode, out=None):
+    """dx [B, T, D] / [T, B, D] of time_pool_fwd for dy [B, D]; every position is written."""
+    L = _lib.load()
+    _need(dy, torch.float32, "dy")
+    n_utts, width = dy.shape
+    lens = _pool_lens(lens, n_utts, t_max, mode, dy.device)
+    if out is None:
+        shape = (n_utts, int(t_max), width) if batch_first else (int(t_max), n_utts, width)
+        out = torch.empty(shape, dtype=torch.float32, device=dy.device)
+    _need(out, torch.float32, "out")
+    _lib.check(L.itts_time_pool_bwd(_ptr(dy), _rows(dy, "dy"), _ptr(lens), n_utts, int(t_max), width,
+                                    1 if batch_first else 0, int(mode), _ptr(out), _pool_pitch(out, "out"),
+                                    _stream()), "itts_time_pool_bwd")
+    return out
+
+
+def vae_reparam_fwd(h, eps, out=None):
+    """z = eps * exp(0.5 * log_var) + mu for h [M, 2L] = mu | log_var and eps [M, L] (rnn_dyn/VAE.py:19-27)."""
+    L = _lib.load()
+    _need(h, torch.float32, "h")
+    _need(eps, torch.float32, "eps")
+    M, two_l = h.shape
+    if two_l % 2 or eps.shape != (M, two_l // 2):
+        raise ValueError("h must be [M, 2L] and eps [M, L], got {} and {}".format(tuple(h.shape), tuple(eps.shape)))
+    lat = two_l // 2
+    if out is None:
+        out = torch.empty((M, lat), dtype=torch.float32, device=h.device)
+    _need(out, torch.float32, "out")
+    _lib.check(L.itts_vae_reparam_fwd(_ptr(h), _rows(h, "h"), _ptr(eps), _rows(eps, "eps"), _ptr(out),
+                                      _rows(out, "out"), M, lat, _stream()), "itts_vae_reparam_fwd")
+    return out
+
+
+def vae_reparam_bwd(dz, dmu, dlv, h, eps, out=None):
+    """dh [M, 2L] from the gradients into z, mu and log_var (each [M, L] or None) in one pass."""
+    L = _lib.load()
+    _need(h, torch.float32, "h")
+    M, two_l = h.shape
+    lat = two_l // 2
+    for name, t in (("dz", dz), ("dmu", dmu), ("dlv", dlv), ("eps", eps)):
+        if t is not None:
+            _need(t, torch.float32, name)
+            if t.shape != (M, lat):
+                raise ValueError("{} must be [{}, {}], got {}".format(name, M, lat, tuple(t.shape)))
+    if out is None:
+        out = torch.empty((M, two_l), dtype=torch.float32, device=h.device)
+    _need(out, torch.float32, "out")
+
+    def ld(t, name):
+        return _rows(t, name) if t is not None else 0
+    _lib.check(L.itts_vae_reparam_bwd(_ptr(dz), ld(dz, "dz"), _ptr(dmu), ld(dmu, "dmu"), _ptr(dlv), ld(dlv, "dlv"),
+                                      _ptr(h), _rows(h, "h"), _ptr(eps), ld(eps, "eps"), _ptr(out), _rows(out, "out"),
+                                      M, lat, _stream()), "itts_vae_reparam_bwd")
+    return out
+
+
+def vae_kld(mu, log_var, row_weight, want_grad=True, want_elem=False, dmu=None, dlv=None):
+    """sum_r w[r] * 0.5 * sum_c (exp(lv) + mu^2 - 1 - lv) on [M, L] rows (loss/VAEKLDLoss.py:56-58):
+    (loss [1], dmu or None, dlv or None, per-row values [M] or None).  mu and log_var may be the two halves of one
+    [M, 2L] tensor; rows of weight 0 may hold anything."""
+    L = _lib.load()
+    _need(mu, torch.float32, "mu")
+    _need(log_var, torch.float32, "log_var")
+    _need(row_weight, torch.float32, "row_weight")
+    M, lat = mu.shape
+    if log_var.shape != mu.shape or row_weight.numel() != M:
+        raise ValueError("mu {} / log_var {} / row_weight {} do not match".format(
+            tuple(mu.shape), tuple(log_var.shape), tuple(row_weight.shape)))
+    loss = torch.empty((1,), dtype=torch.float32, device=mu.device)
+    if want_grad:
+        dmu = torch.empty((M, lat), dtype=torch.float32, device=mu.device) if dmu is None else dmu
+        dlv = torch.empty((M, lat), dtype=torch.float32, device=mu.device) if dlv is None else dlv
+    else:
+        dmu = dlv = None
+    elem = torch.empty((M,), dtype=torch.float32, device=mu.device) if want_elem else None
+    ws = torch.empty(max(L.itts_vae_kld_workspace_bytes(M, lat), 8), dtype=torch.uint8, device=mu.device)
+    _lib.check(L.itts_vae_kld(_ptr(mu), _rows(mu, "mu"), _ptr(log_var), _rows(log_var, "log_var"),
+                              _ptr(row_weight.reshape(-1).contiguous()), M, lat, _ptr(loss),
+                              _ptr(dmu), _rows(dmu, "dmu") if dmu is not None else 0,
+                              _ptr(dlv), _rows(dlv, "dlv") if dlv is not None else 0, _ptr(elem), _ptr(ws), _stream()),
+               "itts_vae_kld")
+    return loss, dmu, dlv, elem
+
+
 def weighted_loss(pred, target, row_weight, kind, want_grad=True, want_elem=False):
     """sum_r w[r] sum_c e(pred - target) on [M, D] rows, e squared (kind 0) / absolute (kind 1)
     error: (loss [1], grad or None, elementwise values or None)."""

@@ -1,7 +1,9 @@
 """rnn_dyn.Config / LayerConfig with the reference's fields
 (idiaptts/src/neural_networks/pytorch/models/rnn_dyn/Config.py:12-138), restricted to the layer
 types on the accelerated path: Linear (+ activation, RNNDyn.LINEAR_NONLINS) groups, LSTM / GRU / RNN groups, Conv1d
-groups and LayerNorm (+ activation) groups; LayerNorm takes no in_dim and has no spelling in the legacy model string."""
+groups, LayerNorm (+ activation) groups, the pooling groups PoolLast / PoolMean (`LayerConfig("PoolLast",
+batch_first=True)`) and the VAE / VanillaVAE group (`LayerConfig("VAE", out_dim=latent_dim)`, last group only);
+LayerNorm, the pooling groups and VAE have no spelling in the legacy model string (the reference's grammar has none)."""
 import copy
 import re
 from typing import List

@@ -521,6 +521,62 @@ int itts_allpass_warp_bwd(const float* d_dy, int64_t lddy, const float* d_x, int
                           const float* d_alpha, const float* d_mean, const float* d_std_dev, float* d_dx,
                           int64_t lddx, float* d_dalpha, int64_t M, int D, int N, void* stream);
 
+/* ---- utterance-level latents: time pooling, VAE reparameterisation, KL term (csrc/latent.hip) ----------------
+ * All float32; row pitches in floats; 16-byte loads when a pitch is a multiple of 4 floats and its base is 16-byte
+ * aligned, plain loads otherwise (the same bits either way).  Every refusal is ITTS_E_INVALID with a message that
+ * names the value, before any device work; empty calls (n_utts == 0, M == 0) succeed.  No float atomics: repeated
+ * calls give identical bits.
+ *
+ * Pooling of a padded batch over time: d_x is [n_utts, t_max, width] (batch_first != 0) or [t_max, n_utts, width],
+ * position pitch ldx, d_y [n_utts, width] with pitch ldy; d_lens int64 [n_utts] on the device, as for
+ * itts_batch_pad_gather_f32.
+ *   ITTS_POOL_LAST  y[b] = x[b, len_b - 1], the row index clamped into [0, t_max); d_lens == NULL: row t_max - 1.
+ *   ITTS_POOL_MEAN  y[b] = (sum of ALL t_max positions of x[b], padding included) / len_b; d_lens == NULL is
+ *                   refused.  After a recurrent group the padding is zero and this is the masked mean; after
+ *                   Linear groups it is not (the reference divides the plain sum the same way).
+ * An utterance's result depends on its own rows, t_max and the layout only, never on its batch index or on n_utts:
+ * time is summed in segments of 128 rows in one fixed order.  With few (utterance, 256-column tile) pairs every
+ * segment gets a workgroup and a second launch adds the segment sums from d_workspace in that same order;
+ * itts_time_pool_plan says, without device work, how many segments a shape has, whether the call is split that way
+ * and how many workspace bytes it then needs (0 otherwise; d_workspace may be NULL then).  Any of its three
+ * outputs may be NULL; it returns 0, or -1 for sizes the MEAN forward refuses (a split call takes at most
+ * 128 * 65 535 frames: its segments are one extent of the grid; LAST and the backward have no such limit).
+ * Reference: rnn_dyn/Pooling.py:30-44 (SelectLastPooling.forward), :52-65 (MeanPooling.forward). */
+#define ITTS_POOL_LAST 0
+#define ITTS_POOL_MEAN 1
+int itts_time_pool_plan(int n_utts, int64_t t_max, int width, int* segments, int* split, int64_t* workspace_bytes);
+int itts_time_pool_fwd(const float* d_x, int64_t ldx, const int64_t* d_lens, int n_utts, int64_t t_max, int width,
+                       int batch_first, int mode, float* d_y, int64_t ldy, void* d_workspace, void* stream);
+/* d_dx (layout and pitch as d_x above) for d_dy [n_utts, width]: EVERY position is written, zeros included, so the
+ * caller needs no memset.  MEAN: dx[b, t] = dy[b] / len_b for every t < t_max; LAST: dy[b] at the selected row.
+ * Reference: autograd through rnn_dyn/Pooling.py:42-44 (the index select) and :55-64 (sum and division). */
+int itts_time_pool_bwd(const float* d_dy, int64_t lddy, const int64_t* d_lens, int n_utts, int64_t t_max, int width,
+                       int batch_first, int mode, float* d_dx, int64_t lddx, void* stream);
+/* z = eps * exp(0.5 * log_var) + mu for d_h [M, 2L] = mu | log_var (the torch.split of rnn_dyn/VAE.py:19), d_eps and
+ * d_z [M, L]; L >= 1 (an L that is no multiple of 4 takes the plain loads: the second half is off the 16-byte grid).
+ * Reference: rnn_dyn/VAE.py:23-27 (VanillaVAE._reparametrize). */
+int itts_vae_reparam_fwd(const float* d_h, int64_t ldh, const float* d_eps, int64_t lde, float* d_z, int64_t ldz,
+                         int64_t M, int L, void* stream);
+/* The whole d_dh [M, 2L] in one pass from the gradients into z, mu and log_var, each [M, L] or NULL (= zero):
+ *   dh[:, :L] = dz + dmu,   dh[:, L:] = 0.5 * dz * eps * exp(0.5 * log_var) + dlog_var
+ * d_h and d_eps are read only when d_dz is given.
+ * Reference: autograd through rnn_dyn/VAE.py:19-27. */
+int itts_vae_reparam_bwd(const float* d_dz, int64_t lddz, const float* d_dmu, int64_t lddmu, const float* d_dlv,
+                         int64_t lddlv, const float* d_h, int64_t ldh, const float* d_eps, int64_t lde, float* d_dh,
+                         int64_t lddh, int64_t M, int L, void* stream);
+/* KL divergence of N(mu, exp(log_var)) to the standard normal with one weight per row (the sequence mask and the
+ * reduction, as for itts_weighted_loss):
+ *   kl_r = 0.5 * sum_c (exp(lv) + mu^2 - 1 - lv),  d_loss[0] = sum_r w[r] kl_r,
+ *   d_dmu = w[r] mu,  d_dlv = 0.5 w[r] (exp(lv) - 1)  (each [M, L] or NULL),  d_elem [M] = w[r] kl_r or NULL.
+ * d_mu and d_lv carry their own pitches: the two halves of h go in without a copy.  Rows of weight 0 may hold
+ * anything and contribute exactly 0 to the loss and to both gradients.  A row is summed by one wave in a fixed
+ * order, the rows in double through d_workspace (>= itts_vae_kld_workspace_bytes(M, L)) and a second launch.
+ * Reference: loss/VAEKLDLoss.py:56-58 (loss_fn) under loss/NamedLoss.py:93-131 (mask and reduction). */
+int64_t itts_vae_kld_workspace_bytes(int64_t M, int L);
+int itts_vae_kld(const float* d_mu, int64_t ldmu, const float* d_lv, int64_t ldlv, const float* d_w, int64_t M, int L,
+                 float* d_loss, float* d_dmu, int64_t lddmu, float* d_dlv, int64_t lddlv, float* d_elem,
+                 void* d_workspace, void* stream);
+
 /* ---- masked MSE, reduction 'mean_per_frame' (loss/NamedLoss.py:70-117) -------------------- */
 /*
  * loss = mean_d( sum_{valid frames} (pred-target)^2 / n_valid ), grad = dloss/dpred.
