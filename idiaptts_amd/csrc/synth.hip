@@ -819,7 +819,7 @@ __global__ __launch_bounds__(NT, 5) void syn_pulse_kernel(PulseArgs a) {
 // ---- one WAVE per pulse (fft = 1024: 16 .. 24 kHz) ------------------------------------------------
 // The same pulse as syn_pulse_kernel, by one wavefront: the 513 bins of a spectrum live eight per
 // lane in registers (bin lane + 64 q in register q; bin 512 is carried by every lane), the seven real
-// transforms are wf::rfft1024 / irfft1024 (wave_fft.h: register passes, the wave's own 8.5 KB of LDS
+// transforms are wf::rfft<8> / irfft<8> (wave_fft.h: register passes, the wave's own 8.5 KB of LDS
 // for the transposes, no workgroup barrier), the responses stay in registers up to the overlap-add.
 // Persistent: 8 or 12 waves per CU take the pulses from a counter, a few neighbours at a time (SYN_WAVE_DEAL_*), so the
 // host no longer needs the pulse count.
@@ -855,8 +855,8 @@ __device__ __forceinline__ void min_phase_wave(double (&v)[9], const wf::Plan512
     double v8[8];
 #pragma unroll
     for (int q = 0; q < 8; ++q) v8[q] = v[q];
-    wf::pack_real(v8, v[8], z, P, r == 0);
-    wf::rfft1024(z, x512, P);            // r = 0: real even input -> real spectrum = fft * cepstrum
+    wf::pack_real<8>(v8, v[8], z, P, r == 0);
+    wf::rfft<8>(z, x512, P);            // r = 0: real even input -> real spectrum = fft * cepstrum
     if (r == 0) {
       // fold: c[0], 2 c[1 .. h-1], c[h], zeros
 #pragma unroll
@@ -1064,7 +1064,7 @@ __global__ __launch_bounds__(NT, UNV ? 3 : SYN_WAVE_OCC) void syn_pulse_wave_ker
             if (i + 1 < noise_size) z[q].y -= avg;
           }
         }
-        wf::rfft1024(z, x512, P);
+        wf::rfft<8>(z, x512, P);
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
           const double2 m = mp[q], n = z[q];
@@ -1073,7 +1073,7 @@ __global__ __launch_bounds__(NT, UNV ? 3 : SYN_WAVE_OCC) void syn_pulse_wave_ker
         const double nx = wave_bcast0(x512.x), ny = wave_bcast0(x512.y);
         x512 = make_double2(mp[8].x * nx - mp[8].y * ny, mp[8].x * ny + mp[8].y * nx);
       }
-      wf::irfft1024(z, x512, P);       // z[q] = (x[2m], x[2m+1]), m = lane + 64 q
+      wf::irfft<8>(z, x512, P);       // z[q] = (x[2m], x[2m+1]), m = lane + 64 q
       if (half == 0) {
         // fftshift + DC removal: the kept half of the shifted response is x[0 .. h)
         double dc = 0.0;

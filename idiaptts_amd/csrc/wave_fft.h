@@ -1,9 +1,11 @@
 // Wave-per-transform fp64 FFT for the WORLD frame kernels (gfx950): ONE wavefront owns a 512-point
-// complex transform (= a 1024-point real transform), eight points per lane in registers, no
-// workgroup barrier anywhere.
+// complex transform (= a 1024-point real transform), eight points per lane in registers, or a 1024-point
+// one (2048 real), sixteen per lane; no workgroup barrier anywhere.  cfft512 / cfft1024, their plans and
+// tables are written per size; the real transforms on top (rfft<R> / irfft<R> / pack_real<R>, R = 8 or 16
+// registers) once.
 //
 // Why (DESIGN.md sections 11b / 12): the workgroup-per-frame kernels are bound by VALU issue, 61 % of it
-// integer address arithmetic, moves and the idle waves of the short transforms.  Here a transform is
+// integer address arithmetic, moves and the idle waves of the short transforms.  Here a 512-point transform is
 // three register passes of three radix-2 stages each; between the passes the wave transposes through
 // its own 8.5 KB of LDS with addresses of the form (per-lane base + immediate); the twiddles come
 // as wave-uniform constants (pass 1) or from a per-lane table the workgroup builds once in LDS (pass
@@ -18,6 +20,7 @@
 // Layout "A" (input and output of every transform here): element m = lane + 64 q in register q.
 #pragma once
 #include "common.h"
+#include "fft_split.h"
 
 namespace itts {
 namespace wf {
@@ -147,111 +150,6 @@ __device__ __forceinline__ void cfft512(double2 (&z)[8], const Plan512& p, const
   wave_sync();          // the buffer is free for the caller (and for the next transform)
 }
 
-// Stores layout A to the natural slots; partner(q) then fetches the mirror element 512 - m of register q
-// (lane 0, register 0 reads slot 512: unused by the callers).  The callers fetch the partners four at
-// a time (eight more complex registers in flight do not fit beside a frame kernel's own state).
-__device__ __forceinline__ void partners_store(const double2 (&z)[8], const Plan512& p) {
-#pragma unroll
-  for (int q = 0; q < 8; ++q) p.x2r[64 * q] = z[q];
-  wave_sync();
-}
-__device__ __forceinline__ double2 partner(const Plan512& p, int q) { return p.xpr[64 * (7 - q)]; }
-
-// Real transform of 1024 samples x, packed as z[m] = (x[2m], x[2m+1]) in layout A.  On return
-// z[q] = X[lane + 64 q] (numpy.fft.rfft), and x512 = X[512] (valid in lane 0, computed by all).
-__device__ __forceinline__ void rfft1024(double2 (&z)[8], double2& x512, const Plan512& p) {
-  cfft512(z, p, -1.0);
-  partners_store(z, p);
-  const int l = lane_id();
-  const double2 z0 = z[0];
-#pragma unroll
-  for (int q0 = 0; q0 < 8; q0 += 4) {
-    double2 pz[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) pz[i] = partner(p, q0 + i);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int q = q0 + i;
-      const bool lo = q < 4;                        // m < 256: the "k" output of the pair (k, 512 - k); else its "j" output
-      const double2 zk = lo ? z[q] : pz[i], zj = lo ? pz[i] : z[q];
-      const double2 w = lo ? p.tw_lo[64 * q] : p.tw_hi[64 * (7 - q)];
-      const double er = 0.5 * (zk.x + zj.x), ei = 0.5 * (zk.y - zj.y);
-      const double dr = 0.5 * (zk.x - zj.x), di = 0.5 * (zk.y + zj.y);
-      const double orr = di, oi = -dr;  // O = -i D
-      const double wr = w.x, wi = -w.y;  // w^k = e^{-2 pi i k / n}
-      const double tr = orr * wr - oi * wi, ti = orr * wi + oi * wr;
-      z[q] = lo ? make_double2(er + tr, ei + ti) : make_double2(er - tr, -(ei - ti));
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  wave_sync();
-  if (l == 0) z[0] = make_double2(z0.x + z0.y, 0.0);
-  x512 = make_double2(z0.x - z0.y, 0.0);
-}
-
-// Inverse real transform: z[q] = X[lane + 64 q], x512 = X[512] (read in lane 0) -> 1024 real samples
-// packed as z[m] = (x[2m], x[2m+1]) in layout A, normalised like numpy.fft.irfft.
-__device__ __forceinline__ void irfft1024(double2 (&z)[8], const double2 x512, const Plan512& p) {
-  const int l = lane_id();
-  partners_store(z, p);
-  if (l == 0) z[0].y = 0.0;          // k = 0: the imaginary parts of X[0] and X[512] are ignored
-#pragma unroll
-  for (int q0 = 0; q0 < 8; q0 += 4) {
-    double2 pz[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) pz[i] = partner(p, q0 + i);
-    if (q0 == 0 && l == 0) pz[0] = make_double2(x512.x, 0.0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int q = q0 + i;
-      const bool lo = q < 4;
-      const double2 xk = lo ? z[q] : pz[i], xj = lo ? pz[i] : z[q];
-      const double2 w = lo ? p.tw_lo[64 * q] : p.tw_hi[64 * (7 - q)];  // conj(w^k) = e^{+2 pi i k / n}
-      const double er = 0.5 * (xk.x + xj.x), ei = 0.5 * (xk.y - xj.y);
-      const double dr = 0.5 * (xk.x - xj.x), di = 0.5 * (xk.y + xj.y);
-      const double orr = dr * w.x - di * w.y, oi = dr * w.y + di * w.x;
-      const double2 zk = make_double2(er - oi, ei + orr);
-      const double2 zj = make_double2(er + oi, -ei + orr);
-      // m = 256 (lane 0, register 4) pairs with itself and takes the "k" form, like every m <= 256
-      z[q] = (lo || (q == 4 && l == 0)) ? zk : zj;
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  wave_sync();
-  cfft512(z, p, +1.0);
-  const double s = 1.0 / (double)WF_N;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    z[q].x *= s;
-    z[q].y *= s;
-  }
-}
-
-// A real sequence given per spectral index in layout A (v[q] = x[lane + 64 q], v512 = x[512]) ->
-// packed z[m] = (x[2m], x[2m+1]) in layout A.  even: x[1024 - n] = x[n]; otherwise zero beyond 512.
-// (`even` is a run-time flag so that the two transforms of a minimum-phase construction share code.)
-__device__ __forceinline__ void pack_real(const double (&v)[8], const double v512, double2 (&z)[8], const Plan512& p,
-                                          const bool even) {
-  const int l = lane_id();
-  double* s = reinterpret_cast<double*>(p.x2r) - l * 2;      // the wave's buffer as doubles
-#pragma unroll
-  for (int q = 0; q < 8; ++q) s[l + 64 * q] = v[q];
-  if (l == 0) { s[512] = v512; s[513] = 0.0; }
-  wave_sync();
-  const double2* s2 = reinterpret_cast<const double2*>(s);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) z[q] = s2[l + 64 * q];                  // m < 256: (x[2m], x[2m+1])
-  // m >= 256, even: (x[1024 - 2m], x[1023 - 2m]); m = 256 (lane 0): (x[512], x[511] or 0)
-#pragma unroll
-  for (int q = 4; q < 8; ++q) {
-    const int n = 1024 - 2 * (l + 64 * q);        // 512 .. 2
-    const double a = s[n], b = s[n - 1];
-    const bool first = q == 4 && l == 0;          // m = 256
-    z[q] = make_double2((even || first) ? a : 0.0, even ? b : 0.0);
-  }
-  wave_sync();
-}
-
 // ---- 1024 complex points (2048-point real transforms: 44.1 / 48 kHz) ----------------------------------
 // Sixteen points per lane; passes of 4 + 3 + 3 stages (passes 2 and 3 work on two independent groups of
 // eight registers); same rules as above (scripts/wave_fft_sim.py checks this plan as well).
@@ -373,7 +271,9 @@ __device__ __forceinline__ void cfft(double2 (&z)[8], const Plan512& p, double s
 __device__ __forceinline__ void cfft(double2 (&z)[16], const Plan1024& p, double sgn) { cfft1024(z, p, sgn); }
 
 // Real transform of 128 R samples packed as z[m] = (x[2m], x[2m+1]) in layout A.  On return
-// z[q] = X[lane + 64 q], xh = X[64 R] (valid in lane 0).  Same arithmetic as rfft1024 above.
+// z[q] = X[lane + 64 q] (numpy.fft.rfft), xh = X[64 R] (valid in lane 0, computed by all).  The partners (the
+// mirror elements 64 R - m) come from the natural slots four at a time: R more complex registers in flight do not
+// fit beside a frame kernel's own state.
 template <int R, class Plan>
 __device__ __forceinline__ void rfft(double2 (&z)[R], double2& xh, const Plan& p) {
   cfft(z, p, -1.0);
@@ -393,12 +293,9 @@ __device__ __forceinline__ void rfft(double2 (&z)[R], double2& xh, const Plan& p
       const bool lo = q < R / 2;
       const double2 zk = lo ? z[q] : pz[i], zj = lo ? pz[i] : z[q];
       const double2 w = lo ? p.tw_lo[64 * q] : p.tw_hi[64 * (R - 1 - q)];
-      const double er = 0.5 * (zk.x + zj.x), ei = 0.5 * (zk.y - zj.y);
-      const double dr = 0.5 * (zk.x - zj.x), di = 0.5 * (zk.y + zj.y);
-      const double orr = di, oi = -dr;  // O = -i D
-      const double wr = w.x, wi = -w.y;  // w^k = e^{-2 pi i k / n}
-      const double tr = orr * wr - oi * wi, ti = orr * wi + oi * wr;
-      z[q] = lo ? make_double2(er + tr, ei + ti) : make_double2(er - tr, -(ei - ti));
+      double2 Xk, Xj;
+      rsplit_fwd(zk, zj, w, Xk, Xj);
+      z[q] = lo ? Xk : Xj;                          // m < 32 R: the "k" output of the pair (k, 64 R - k); else its "j" output
     }
     __builtin_amdgcn_sched_barrier(0);
   }
@@ -407,11 +304,12 @@ __device__ __forceinline__ void rfft(double2 (&z)[R], double2& xh, const Plan& p
   xh = make_double2(z0.x - z0.y, 0.0);
 }
 
-// pack_real for either size: a real sequence per spectral index in layout A (v[q] = x[lane + 64 q], vh = x[64 R])
-// -> packed z[m] = (x[2m], x[2m+1]) in layout A.  even: x[128 R - n] = x[n]; otherwise zero beyond 64 R.
+// A real sequence given per spectral index in layout A (v[q] = x[lane + 64 q], vh = x[64 R]) -> packed
+// z[m] = (x[2m], x[2m+1]) in layout A.  even: x[128 R - n] = x[n]; otherwise zero beyond 64 R.
+// (`even` is a run-time flag so that the two transforms of a minimum-phase construction share code.)
 template <int R, class Plan>
-__device__ __forceinline__ void pack_real_r(const double (&v)[R], const double vh, double2 (&z)[R], const Plan& p,
-                                            const bool even) {
+__device__ __forceinline__ void pack_real(const double (&v)[R], const double vh, double2 (&z)[R], const Plan& p,
+                                          const bool even) {
   const int l = lane_id();
   double* s = reinterpret_cast<double*>(p.x2r) - l * 2;      // the wave's buffer as doubles
 #pragma unroll
@@ -431,7 +329,8 @@ __device__ __forceinline__ void pack_real_r(const double (&v)[R], const double v
   wave_sync();
 }
 
-// Inverse: z[q] = X[lane + 64 q], xh = X[64 R] (read in lane 0) -> 128 R real samples packed in layout A.
+// Inverse: z[q] = X[lane + 64 q], xh = X[64 R] (read in lane 0; the imaginary parts of X[0] and X[64 R] are
+// ignored) -> 128 R real samples packed as z[m] = (x[2m], x[2m+1]) in layout A, normalised like numpy.fft.irfft.
 template <int R, class Plan>
 __device__ __forceinline__ void irfft(double2 (&z)[R], const double2 xh, const Plan& p) {
   const int l = lane_id();
@@ -451,11 +350,8 @@ __device__ __forceinline__ void irfft(double2 (&z)[R], const double2 xh, const P
       const bool lo = q < R / 2;
       const double2 xk = lo ? z[q] : pz[i], xj = lo ? pz[i] : z[q];
       const double2 w = lo ? p.tw_lo[64 * q] : p.tw_hi[64 * (R - 1 - q)];
-      const double er = 0.5 * (xk.x + xj.x), ei = 0.5 * (xk.y - xj.y);
-      const double dr = 0.5 * (xk.x - xj.x), di = 0.5 * (xk.y + xj.y);
-      const double orr = dr * w.x - di * w.y, oi = dr * w.y + di * w.x;
-      const double2 zk = make_double2(er - oi, ei + orr);
-      const double2 zj = make_double2(er + oi, -ei + orr);
+      double2 zk, zj;
+      rsplit_inv(xk, xj, w, zk, zj);
       // m = 32 R pairs with itself: the "k" form (selected per component: a select of the whole pair can go
       // through scratch memory)
       const bool use_k = lo || (q == R / 2 && l == 0);

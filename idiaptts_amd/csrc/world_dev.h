@@ -11,6 +11,7 @@
 #pragma once
 #include "common.h"
 #include "fastmath.h"
+#include "fft_split.h"
 
 namespace itts {
 namespace wd {
@@ -128,20 +129,36 @@ __device__ __forceinline__ int fft_phys(int i) {
   return i ^ (((i >> 4) ^ (int)(__brev((unsigned)(i >> 6)) >> 28)) & 15);
 }
 
-constexpr int FFT_PAIR_MAX = 4 * NT;  // largest transform whose first pass is one butterfly per thread (fft_lds_pair)
+// f(a) for the array indices a < NA, written out: a loop, even one of a single trip, lets the compiler hoist and
+// regroup the address arithmetic in front of it, and the one-array form compiles to other registers
+template <int NA, class F>
+__device__ __forceinline__ void each_array(const F& f) {
+  static_assert(NA == 1 || NA == 2, "one or two arrays");
+  f(0);
+  if constexpr (NA == 2) f(1);
+}
+
+constexpr int FFT_PAIR_MAX = 4 * NT;  // largest transform whose first pass is one butterfly per thread (the two-array form)
 constexpr int FFT_SWZ_MAX = 8 * NT;   // .. two per thread: the swizzled layout up to 2 048 complex points (the 4 096-point real transforms of D4C at 48 kHz)
 
-// In-place complex FFT of z[0..n) (n = 2^logn <= tw_n). tw holds exp(+2 pi i k / tw_n).
+// In-place complex FFT of NA arrays zz[a][0..n) (n = 2^logn <= tw_n) in lockstep. tw holds exp(+2 pi i k / tw_n).
 // sign = -1: forward (e^{-i..}), +1: unnormalised inverse. Ends with a barrier.  Input and output
 // are in natural order; in between the elements live at fft_phys(i) (64 <= n <= FFT_SWZ_MAX).
 // CLOGN / CTSHIFT > 0: n = 2^CLOGN and log2(tw_n) - 1 = CTSHIFT are compile-time constants (the passes unroll, their
 // shifts, masks and swizzle constants fold: about a third of a pass's integer instructions go) -- same butterflies,
 // same twiddle entries, same order: same bits.
-template <bool SWZ = true, int CLOGN = 0, int CTSHIFT = 0>
-__device__ inline void fft_lds(double2* z, int n_rt, int logn_rt, const double2* tw, int tw_n, int sign) {
+// NA = 2: one set of barriers, index arithmetic and twiddle loads serves both arrays -- the workgroup transforms are
+// bound by exactly those (61 % of the instructions); per array the operations are those of NA = 1, the
+// results are bit-identical.  Preconditions: the swizzled path only, 64 <= n <= FFT_PAIR_MAX (one first-pass
+// butterfly per thread: the registers for two are not there).
+template <bool SWZ, int CLOGN, int CTSHIFT, int NA>
+__device__ __forceinline__ void fft_lds_arrays(double2* const (&zz)[NA], int n_rt, int logn_rt, const double2* tw, int tw_n, int sign) {
+  static_assert(NA == 1 || (NA == 2 && SWZ && (CLOGN == 0 || (CLOGN >= 6 && (1 << CLOGN) <= FFT_PAIR_MAX))),
+                "two arrays: the swizzled path, 64 <= n <= FFT_PAIR_MAX");
   const int n = CLOGN ? (1 << CLOGN) : n_rt, logn = CLOGN ? CLOGN : logn_rt;
-  const bool swz = SWZ && n >= 64 && n <= FFT_SWZ_MAX;
+  const bool swz = NA > 1 || (SWZ && n >= 64 && n <= FFT_SWZ_MAX);
   if (!swz) {
+    double2* z = zz[0];
     for (int i = tid(); i < n; i += NT) {
       const int j = (int)(__brev((unsigned)i) >> (32 - logn));
       if (i < j) {
@@ -168,16 +185,18 @@ __device__ inline void fft_lds(double2* z, int n_rt, int logn_rt, const double2*
     // generic pass below with h = 1.
     // (one butterfly per thread up to 4 NT points, two from there to 8 NT: everything is read before anything is
     // written)
-    constexpr int FIRST = FFT_SWZ_MAX / (4 * NT);
-    double2 f0[FIRST], f1[FIRST], f2[FIRST], f3[FIRST];
+    constexpr int FIRST = (NA == 1 ? FFT_SWZ_MAX : FFT_PAIR_MAX) / (4 * NT);
+    double2 f0[FIRST][NA], f1[FIRST][NA], f2[FIRST][NA], f3[FIRST][NA];
 #pragma unroll
     for (int rep = 0; rep < FIRST; ++rep) {
       const int u = tid() + rep * NT;
       if (u < n / 4) {
-        f0[rep] = z[u];
-        f1[rep] = z[u + n / 2];
-        f2[rep] = z[u + n / 4];
-        f3[rep] = z[u + n / 2 + n / 4];
+        each_array<NA>([&](int a) {
+          f0[rep][a] = zz[a][u];
+          f1[rep][a] = zz[a][u + n / 2];
+          f2[rep][a] = zz[a][u + n / 4];
+          f3[rep][a] = zz[a][u + n / 2 + n / 4];
+        });
       }
     }
     __syncthreads();
@@ -185,20 +204,23 @@ __device__ inline void fft_lds(double2* z, int n_rt, int logn_rt, const double2*
     for (int rep = 0; rep < FIRST; ++rep) {
       const int u = tid() + rep * NT;
       if (u < n / 4) {
-        const double2 z0 = f0[rep], z1 = f1[rep], z2 = f2[rep], z3 = f3[rep];
         const int a0 = 4 * (int)(__brev((unsigned)u) >> (32 - (logn - 2)));
         const double2 w1 = tw[0];
         const double2 w2 = tw[0];
         const double2 w3 = tw[1 << (tshift - 1)];
-        const double2 x1 = twmul(z1, w1), x3 = twmul(z3, w1);
-        const double2 y0 = make_double2(z0.x + x1.x, z0.y + x1.y), y1 = make_double2(z0.x - x1.x, z0.y - x1.y);
-        const double2 y2 = make_double2(z2.x + x3.x, z2.y + x3.y), y3 = make_double2(z2.x - x3.x, z2.y - x3.y);
-        const double2 u2 = twmul(y2, w2), u3 = twmul(y3, w3);
-        const int p0 = fft_phys(a0);  // the swizzle is linear over GF(2) and leaves 1, 2, 3 alone
-        z[p0] = make_double2(y0.x + u2.x, y0.y + u2.y);
-        z[p0 ^ 2] = make_double2(y0.x - u2.x, y0.y - u2.y);
-        z[p0 ^ 1] = make_double2(y1.x + u3.x, y1.y + u3.y);
-        z[p0 ^ 3] = make_double2(y1.x - u3.x, y1.y - u3.y);
+        each_array<NA>([&](int a) {
+          double2* z = zz[a];
+          const double2 z0 = f0[rep][a], z1 = f1[rep][a], z2 = f2[rep][a], z3 = f3[rep][a];
+          const double2 x1 = twmul(z1, w1), x3 = twmul(z3, w1);
+          const double2 y0 = make_double2(z0.x + x1.x, z0.y + x1.y), y1 = make_double2(z0.x - x1.x, z0.y - x1.y);
+          const double2 y2 = make_double2(z2.x + x3.x, z2.y + x3.y), y3 = make_double2(z2.x - x3.x, z2.y - x3.y);
+          const double2 u2 = twmul(y2, w2), u3 = twmul(y3, w3);
+          const int p0 = fft_phys(a0);  // the swizzle is linear over GF(2) and leaves 1, 2, 3 alone
+          z[p0] = make_double2(y0.x + u2.x, y0.y + u2.y);
+          z[p0 ^ 2] = make_double2(y0.x - u2.x, y0.y - u2.y);
+          z[p0 ^ 1] = make_double2(y1.x + u3.x, y1.y + u3.y);
+          z[p0 ^ 3] = make_double2(y1.x - u3.x, y1.y - u3.y);
+        });
       }
     }
     __syncthreads();
@@ -224,138 +246,19 @@ __device__ inline void fft_lds(double2* z, int n_rt, int logn_rt, const double2*
       const double2 w2 = tw[r << (tshift - s)];
       const double2 w3 = tw[(r + h) << (tshift - s)];
       const int p0 = at(a0), p1 = p0 ^ c1, p2 = p0 ^ c2, p3 = p1 ^ c2;
-      const double2 z0 = z[p0], z1 = z[p1], z2 = z[p2], z3 = z[p3];
-      const double2 x1 = twmul(z1, w1), x3 = twmul(z3, w1);
-      const double2 y0 = make_double2(z0.x + x1.x, z0.y + x1.y), y1 = make_double2(z0.x - x1.x, z0.y - x1.y);
-      const double2 y2 = make_double2(z2.x + x3.x, z2.y + x3.y), y3 = make_double2(z2.x - x3.x, z2.y - x3.y);
-      const double2 u2 = twmul(y2, w2), u3 = twmul(y3, w3);
-      const int o0 = last ? a0 : p0, o1 = last ? a1 : p1, o2 = last ? a2 : p2, o3 = last ? a3 : p3;
-      z[o0] = make_double2(y0.x + u2.x, y0.y + u2.y);
-      z[o2] = make_double2(y0.x - u2.x, y0.y - u2.y);
-      z[o1] = make_double2(y1.x + u3.x, y1.y + u3.y);
-      z[o3] = make_double2(y1.x - u3.x, y1.y - u3.y);
-    }
-    __syncthreads();
-  }
-  for (; s <= logn; ++s) {   // odd log2(n): one plain radix-2 stage is left (always the last pass)
-    const int h = 1 << (s - 1);
-    for (int t = tid(); t < n / 2; t += NT) {
-      const int r = t & (h - 1);
-      const int a = ((t >> (s - 1)) << s) + r;
-      const int b = a + h;
-      const int pa = at(a), pb = swz ? pa ^ fft_phys(h) : b;
-      const double2 x = twmul(z[pb], tw[r << (tshift - (s - 1))]);
-      const double2 za = z[pa];
-      z[b] = make_double2(za.x - x.x, za.y - x.y);
-      z[a] = make_double2(za.x + x.x, za.y + x.y);
-    }
-    __syncthreads();
-  }
-}
-
-// Real FFT: z viewed as n real samples (z[k] = (x[2k], x[2k+1])), needs n/2+1 complex slots.
-// On return z[k] = X[k], k = 0..n/2 (numpy.fft.rfft).
-template <bool SWZ = true, int CLOGN = 0, int CTSHIFT = 0>     // (CLOGN: log2 of the REAL transform's size)
-__device__ inline void rfft_lds(double2* z, int n_rt, int logn, const double2* tw, int tw_n_rt) {
-  const int n = CLOGN ? (1 << CLOGN) : n_rt, tw_n = CTSHIFT ? (2 << CTSHIFT) : tw_n_rt;
-  const int h = n / 2;
-  fft_lds<SWZ, CLOGN ? CLOGN - 1 : 0, CTSHIFT>(z, h, logn - 1, tw, tw_n, -1);
-  const int tstride = tw_n / n;
-  for (int k = tid(); k <= h / 2; k += NT) {
-    if (k == 0) {
-      const double2 z0 = z[0];
-      z[0] = make_double2(z0.x + z0.y, 0.0);
-      z[h] = make_double2(z0.x - z0.y, 0.0);
-    } else {
-      const int j = h - k;
-      const double2 zk = z[k], zj = z[j];
-      const double er = 0.5 * (zk.x + zj.x), ei = 0.5 * (zk.y - zj.y);
-      const double dr = 0.5 * (zk.x - zj.x), di = 0.5 * (zk.y + zj.y);
-      const double orr = di, oi = -dr;  // O = -i D
-      const double2 w = tw[k * tstride];
-      const double wr = w.x, wi = -w.y;  // w^k = e^{-2 pi i k / n}
-      const double tr = orr * wr - oi * wi, ti = orr * wi + oi * wr;
-      z[k] = make_double2(er + tr, ei + ti);
-      z[j] = make_double2(er - tr, -(ei - ti));
-    }
-  }
-  __syncthreads();
-}
-
-// TWO transforms of the same size in lockstep (arrays z0, z1): one set of barriers, index arithmetic and
-// twiddle loads serves both -- the workgroup transforms are bound by exactly those (61 %
-// of the instructions).  Per array the butterflies, twiddle entries and order of operations are those of
-// fft_lds: the results are bit-identical.  64 <= n <= FFT_PAIR_MAX (the swizzled path only).
-template <int CLOGN = 0, int CTSHIFT = 0>
-__device__ inline void fft_lds_pair(double2* z0, double2* z1, int n_rt, int logn_rt, const double2* tw, int tw_n, int sign) {
-  const int n = CLOGN ? (1 << CLOGN) : n_rt, logn = CLOGN ? CLOGN : logn_rt;
-  double2* zz[2] = {z0, z1};
-  const int tshift = CTSHIFT ? CTSHIFT : ilog2(tw_n) - 1;
-  auto twmul = [&](const double2 v, const double2 w) {
-    const double wi = sign < 0 ? -w.y : w.y;
-    return make_double2(v.x * w.x - v.y * wi, v.x * wi + v.y * w.x);
-  };
-  {
-    const int u = tid();
-    const bool on = u < n / 4;
-    double2 q0[2], q1[2], q2[2], q3[2];
-    if (on) {
-#pragma unroll
-      for (int a = 0; a < 2; ++a) {
-        q0[a] = zz[a][u];
-        q1[a] = zz[a][u + n / 2];
-        q2[a] = zz[a][u + n / 4];
-        q3[a] = zz[a][u + n / 2 + n / 4];
-      }
-    }
-    __syncthreads();
-    if (on) {
-      const int a0 = 4 * (int)(__brev((unsigned)u) >> (32 - (logn - 2)));
-      const double2 w1 = tw[0];
-      const double2 w2 = tw[0];
-      const double2 w3 = tw[1 << (tshift - 1)];
-      const int p0 = fft_phys(a0);
-#pragma unroll
-      for (int a = 0; a < 2; ++a) {
-        const double2 x1 = twmul(q1[a], w1), x3 = twmul(q3[a], w1);
-        const double2 y0 = make_double2(q0[a].x + x1.x, q0[a].y + x1.y), y1 = make_double2(q0[a].x - x1.x, q0[a].y - x1.y);
-        const double2 y2 = make_double2(q2[a].x + x3.x, q2[a].y + x3.y), y3 = make_double2(q2[a].x - x3.x, q2[a].y - x3.y);
+      each_array<NA>([&](int a) {
+        double2* z = zz[a];
+        const double2 z0 = z[p0], z1 = z[p1], z2 = z[p2], z3 = z[p3];
+        const double2 x1 = twmul(z1, w1), x3 = twmul(z3, w1);
+        const double2 y0 = make_double2(z0.x + x1.x, z0.y + x1.y), y1 = make_double2(z0.x - x1.x, z0.y - x1.y);
+        const double2 y2 = make_double2(z2.x + x3.x, z2.y + x3.y), y3 = make_double2(z2.x - x3.x, z2.y - x3.y);
         const double2 u2 = twmul(y2, w2), u3 = twmul(y3, w3);
-        zz[a][p0] = make_double2(y0.x + u2.x, y0.y + u2.y);
-        zz[a][p0 ^ 2] = make_double2(y0.x - u2.x, y0.y - u2.y);
-        zz[a][p0 ^ 1] = make_double2(y1.x + u3.x, y1.y + u3.y);
-        zz[a][p0 ^ 3] = make_double2(y1.x - u3.x, y1.y - u3.y);
-      }
-    }
-    __syncthreads();
-  }
-  int s = 3;
-#pragma unroll
-  for (; s + 1 <= logn; s += 2) {
-    const int h = 1 << (s - 1);
-    const bool last = s + 1 == logn;
-    const int c1 = fft_phys(h), c2 = fft_phys(2 * h);
-    for (int t = tid(); t < n / 4; t += NT) {
-      const int r = t & (h - 1);
-      const int a0 = ((t >> (s - 1)) << (s + 1)) + r;
-      const int a1 = a0 + h, a2 = a0 + 2 * h, a3 = a0 + 3 * h;
-      const double2 w1 = tw[r << (tshift - (s - 1))];
-      const double2 w2 = tw[r << (tshift - s)];
-      const double2 w3 = tw[(r + h) << (tshift - s)];
-      const int p0 = fft_phys(a0), p1 = p0 ^ c1, p2 = p0 ^ c2, p3 = p1 ^ c2;
-      const int o0 = last ? a0 : p0, o1 = last ? a1 : p1, o2 = last ? a2 : p2, o3 = last ? a3 : p3;
-#pragma unroll
-      for (int a = 0; a < 2; ++a) {
-        const double2 q0 = zz[a][p0], q1 = zz[a][p1], q2 = zz[a][p2], q3 = zz[a][p3];
-        const double2 x1 = twmul(q1, w1), x3 = twmul(q3, w1);
-        const double2 y0 = make_double2(q0.x + x1.x, q0.y + x1.y), y1 = make_double2(q0.x - x1.x, q0.y - x1.y);
-        const double2 y2 = make_double2(q2.x + x3.x, q2.y + x3.y), y3 = make_double2(q2.x - x3.x, q2.y - x3.y);
-        const double2 u2 = twmul(y2, w2), u3 = twmul(y3, w3);
-        zz[a][o0] = make_double2(y0.x + u2.x, y0.y + u2.y);
-        zz[a][o2] = make_double2(y0.x - u2.x, y0.y - u2.y);
-        zz[a][o1] = make_double2(y1.x + u3.x, y1.y + u3.y);
-        zz[a][o3] = make_double2(y1.x - u3.x, y1.y - u3.y);
-      }
+        const int o0 = last ? a0 : p0, o1 = last ? a1 : p1, o2 = last ? a2 : p2, o3 = last ? a3 : p3;
+        z[o0] = make_double2(y0.x + u2.x, y0.y + u2.y);
+        z[o2] = make_double2(y0.x - u2.x, y0.y - u2.y);
+        z[o1] = make_double2(y1.x + u3.x, y1.y + u3.y);
+        z[o3] = make_double2(y1.x - u3.x, y1.y - u3.y);
+      });
     }
     __syncthreads();
   }
@@ -365,53 +268,64 @@ __device__ inline void fft_lds_pair(double2* z0, double2* z1, int n_rt, int logn
       const int r = t & (h - 1);
       const int ia = ((t >> (s - 1)) << s) + r;
       const int ib = ia + h;
-      const int pa = fft_phys(ia), pb = pa ^ fft_phys(h);
+      const int pa = at(ia), pb = swz ? pa ^ fft_phys(h) : ib;
       const double2 w = tw[r << (tshift - (s - 1))];
-#pragma unroll
-      for (int a = 0; a < 2; ++a) {
-        const double2 x = twmul(zz[a][pb], w);
-        const double2 za = zz[a][pa];
-        zz[a][ib] = make_double2(za.x - x.x, za.y - x.y);
-        zz[a][ia] = make_double2(za.x + x.x, za.y + x.y);
-      }
+      each_array<NA>([&](int a) {
+        double2* z = zz[a];
+        const double2 x = twmul(z[pb], w);
+        const double2 za = z[pa];
+        z[ib] = make_double2(za.x - x.x, za.y - x.y);
+        z[ia] = make_double2(za.x + x.x, za.y + x.y);
+      });
     }
     __syncthreads();
   }
 }
 
-// Two real transforms in lockstep (see rfft_lds): z0 / z1 hold n real samples each on entry, X[0 .. n/2] on return.
-template <int CLOGN = 0, int CTSHIFT = 0>
-__device__ inline void rfft_lds_pair(double2* z0, double2* z1, int n_rt, int logn, const double2* tw, int tw_n_rt) {
+template <bool SWZ = true, int CLOGN = 0, int CTSHIFT = 0>
+__device__ inline void fft_lds(double2* z, int n, int logn, const double2* tw, int tw_n, int sign) {
+  double2* const zz[1] = {z};
+  fft_lds_arrays<SWZ, CLOGN, CTSHIFT>(zz, n, logn, tw, tw_n, sign);
+}
+
+// Real FFT of NA arrays in lockstep (see fft_lds_arrays): each viewed as n real samples (z[k] = (x[2k], x[2k+1])),
+// needs n/2+1 complex slots.  On return z[k] = X[k], k = 0..n/2 (numpy.fft.rfft).
+template <bool SWZ, int CLOGN, int CTSHIFT, int NA>            // (CLOGN: log2 of the REAL transform's size)
+__device__ __forceinline__ void rfft_lds_arrays(double2* const (&zz)[NA], int n_rt, int logn, const double2* tw, int tw_n_rt) {
   const int n = CLOGN ? (1 << CLOGN) : n_rt, tw_n = CTSHIFT ? (2 << CTSHIFT) : tw_n_rt;
   const int h = n / 2;
-  fft_lds_pair<CLOGN ? CLOGN - 1 : 0, CTSHIFT>(z0, z1, h, logn - 1, tw, tw_n, -1);
-  double2* zz[2] = {z0, z1};
+  fft_lds_arrays<SWZ, CLOGN ? CLOGN - 1 : 0, CTSHIFT>(zz, h, logn - 1, tw, tw_n, -1);
   const int tstride = tw_n / n;
   for (int k = tid(); k <= h / 2; k += NT) {
     if (k == 0) {
-#pragma unroll
-      for (int a = 0; a < 2; ++a) {
-        const double2 q0 = zz[a][0];
-        zz[a][0] = make_double2(q0.x + q0.y, 0.0);
-        zz[a][h] = make_double2(q0.x - q0.y, 0.0);
-      }
+      each_array<NA>([&](int a) {
+        double2* z = zz[a];
+        const double2 z0 = z[0];
+        z[0] = make_double2(z0.x + z0.y, 0.0);
+        z[h] = make_double2(z0.x - z0.y, 0.0);
+      });
     } else {
       const int j = h - k;
       const double2 w = tw[k * tstride];
-      const double wr = w.x, wi = -w.y;  // w^k = e^{-2 pi i k / n}
-#pragma unroll
-      for (int a = 0; a < 2; ++a) {
-        const double2 zk = zz[a][k], zj = zz[a][j];
-        const double er = 0.5 * (zk.x + zj.x), ei = 0.5 * (zk.y - zj.y);
-        const double dr = 0.5 * (zk.x - zj.x), di = 0.5 * (zk.y + zj.y);
-        const double orr = di, oi = -dr;  // O = -i D
-        const double tr = orr * wr - oi * wi, ti = orr * wi + oi * wr;
-        zz[a][k] = make_double2(er + tr, ei + ti);
-        zz[a][j] = make_double2(er - tr, -(ei - ti));
-      }
+      each_array<NA>([&](int a) {
+        double2* z = zz[a];
+        rsplit_fwd(z[k], z[j], w, z[k], z[j]);
+      });
     }
   }
   __syncthreads();
+}
+
+template <bool SWZ = true, int CLOGN = 0, int CTSHIFT = 0>
+__device__ inline void rfft_lds(double2* z, int n, int logn, const double2* tw, int tw_n) {
+  double2* const zz[1] = {z};
+  rfft_lds_arrays<SWZ, CLOGN, CTSHIFT>(zz, n, logn, tw, tw_n);
+}
+// two arrays of the same size (the preconditions of fft_lds_arrays with NA = 2 apply to n / 2 points)
+template <bool SWZ = true, int CLOGN = 0, int CTSHIFT = 0>
+__device__ inline void rfft_lds(double2* z0, double2* z1, int n, int logn, const double2* tw, int tw_n) {
+  double2* const zz[2] = {z0, z1};
+  rfft_lds_arrays<SWZ, CLOGN, CTSHIFT>(zz, n, logn, tw, tw_n);
 }
 
 // Inverse real FFT: z[k] = X[k], k = 0..n/2 (imag of X[0], X[n/2] ignored) -> z viewed as n real
@@ -428,12 +342,8 @@ __device__ inline void irfft_lds(double2* z, int n_rt, int logn, const double2* 
       xk.y = 0.0;
       xj.y = 0.0;
     }
-    const double er = 0.5 * (xk.x + xj.x), ei = 0.5 * (xk.y - xj.y);
-    const double dr = 0.5 * (xk.x - xj.x), di = 0.5 * (xk.y + xj.y);
-    const double2 w = tw[k * tstride];  // conj(w^k) = e^{+2 pi i k / n}
-    const double orr = dr * w.x - di * w.y, oi = dr * w.y + di * w.x;
-    const double2 zk = make_double2(er - oi, ei + orr);
-    const double2 zj = make_double2(er + oi, -ei + orr);
+    double2 zk, zj;
+    rsplit_inv(xk, xj, tw[k * tstride], zk, zj);
     if (k == 0) {
       z[0] = zk;
     } else {

@@ -541,19 +541,21 @@ __global__ __launch_bounds__(NT, AREG ? 2 : D4C_OCC) void d4c_kernel(D4cArgs a) 
     win_make(W, fs, f0, 1, 4.0);               // one Blackman window serves all four centroid transforms
     for (int side = 0; side < 2; ++side) {
       const double cpos = side == 0 ? pos - 0.25 / f0 : pos + 0.25 / f0;
-      if (!AREG && h <= FFT_PAIR_MAX) {
-        // the segment and its ramped copy transformed in LOCKSTEP (the ramped one in B / C's storage,
-        // which only held the first spectrum until it was multiplied in): one set of barriers, index
-        // arithmetic and twiddle loads for two transforms; same values bit for bit
-        double2* z2 = reinterpret_cast<double2*>(L.B);
-        windowed_to(x, xl, fs, cpos, W, zr, fft + 2, true, false, L.red, seg, reinterpret_cast<double*>(z2));
-        rfft_lds_pair<CFFT, CTS>(L.z, z2, fft, logfft, L.tw, fmax);
-        for (int k = threadIdx.x; k <= h; k += NT) {
-          const double v = z2[k].x * L.z[k].x + L.z[k].y * z2[k].y;
-          L.A[k] = side == 0 ? v : L.A[k] + v;
+      if constexpr (!AREG) {      // (AREG is the 4096-point kernel: beyond the two-array transform)
+        if (h <= FFT_PAIR_MAX) {
+          // the segment and its ramped copy transformed in LOCKSTEP (the ramped one in B / C's storage,
+          // which only held the first spectrum until it was multiplied in): one set of barriers, index
+          // arithmetic and twiddle loads for two transforms; same values bit for bit
+          double2* z2 = reinterpret_cast<double2*>(L.B);
+          windowed_to(x, xl, fs, cpos, W, zr, fft + 2, true, false, L.red, seg, reinterpret_cast<double*>(z2));
+          rfft_lds<true, CFFT, CTS>(L.z, z2, fft, logfft, L.tw, fmax);
+          for (int k = threadIdx.x; k <= h; k += NT) {
+            const double v = z2[k].x * L.z[k].x + L.z[k].y * z2[k].y;
+            L.A[k] = side == 0 ? v : L.A[k] + v;
+          }
+          __syncthreads();
+          continue;
         }
-        __syncthreads();
-        continue;
       }
       windowed_to(x, xl, fs, cpos, W, zr, fft + 2, true, false, L.red, seg);
       rfft();

@@ -470,7 +470,7 @@ __global__ __launch_bounds__(TH) void cheaptrick_wave_kernel(FrameArgs a, int64_
         if (q < R) lp[q < R ? q : 0] = v; else lp512 = v;
         __builtin_amdgcn_sched_barrier(0);
       }
-      wf::pack_real_r<R>(lp, lp512, z, P, true);
+      wf::pack_real<R>(lp, lp512, z, P, true);
     }
     wf::rfft<R>(z, xh, P);
 #pragma unroll

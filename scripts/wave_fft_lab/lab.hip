@@ -1,6 +1,7 @@
 // Lab for csrc/wave_fft.h (run on the GPU box: bash scripts/wave_fft_lab/run.sh):
-//  1. bits: cfft512 / rfft1024 / irfft1024 of a wave against wd::fft_lds / rfft_lds / irfft_lds of a
-//     256-thread workgroup on the same random inputs (must be identical bit for bit, up to the sign of zeros);
+//  1. bits: wf::cfft / rfft<R> / irfft<R> of a wave (R = 8: 512 complex points, R = 16: 1024) against wd::fft_lds /
+//     rfft_lds / irfft_lds of a 256-thread workgroup on the same random inputs (must be identical bit for bit, up
+//     to the sign of zeros); the two-array wd::rfft_lds against the one-array one (every bit);
 //  2. time: R transforms in a loop per wave (8 waves per CU, persistent) against R transforms per
 //     workgroup (the structure of the frame kernels), same total number of transforms.
 #include <hip/hip_runtime.h>
@@ -140,10 +141,67 @@ int run(const std::vector<double2>& tw_full) {
   return bad_total;
 }
 
+// Real transforms of n samples of two arrays per workgroup: both in one two-array wd::rfft_lds (two != 0; CLOGN /
+// CTSHIFT as there), or one after the other through the one-array form with run-time sizes.
+template <int CLOGN, int CTSHIFT>
+__global__ __launch_bounds__(256) void pair_kernel(const double2* in, double2* out, const double2* g_tw, int n, int logn, int two) {
+  extern __shared__ __attribute__((aligned(16))) char sm[];
+  const int h = n / 2, P = h + 1;
+  double2* tw = reinterpret_cast<double2*>(sm);
+  double2* z0 = tw + h;
+  double2* z1 = z0 + P;
+  wd::load_twiddles(tw, g_tw, n);
+  for (int i = threadIdx.x; i < 2 * P; i += 256) z0[i] = i % P < h ? in[(size_t)blockIdx.x * 2 * P + i] : make_double2(0, 0);
+  __syncthreads();
+  if (two) {
+    wd::rfft_lds<true, CLOGN, CTSHIFT>(z0, z1, n, logn, tw, n);
+  } else {
+    wd::rfft_lds(z0, n, logn, tw, n);
+    wd::rfft_lds(z1, n, logn, tw, n);
+  }
+  for (int i = threadIdx.x; i < 2 * P; i += 256) out[(size_t)blockIdx.x * 2 * P + i] = z0[i];
+}
+
+// 256 pairs of random arrays: every bit of the two-array transform's outputs against the one-array transform's
+template <int CLOGN, int CTSHIFT>
+int run_pair(const std::vector<double2>& tw_full, int n, int logn) {
+  const int B = 256, P = n / 2 + 1;
+  std::vector<double2> in((size_t)B * 2 * P), o1(in.size()), o2(in.size());
+  std::mt19937_64 rng(100 + n);
+  std::normal_distribution<double> nd(0.0, 1.0);
+  for (auto& v : in) v = make_double2(nd(rng), nd(rng));
+  double2 *d_twf, *d_in, *d_o1, *d_o2;
+  CK(hipMalloc(&d_twf, tw_full.size() * 16));
+  CK(hipMalloc(&d_in, in.size() * 16)); CK(hipMalloc(&d_o1, in.size() * 16)); CK(hipMalloc(&d_o2, in.size() * 16));
+  CK(hipMemcpy(d_twf, tw_full.data(), tw_full.size() * 16, hipMemcpyHostToDevice));
+  CK(hipMemcpy(d_in, in.data(), in.size() * 16, hipMemcpyHostToDevice));
+  CK(hipMemset(d_o1, 0, in.size() * 16)); CK(hipMemset(d_o2, 0, in.size() * 16));
+  const size_t lds = (size_t)(n / 2 + 2 * P) * 16;
+  CK(hipFuncSetAttribute((const void*)pair_kernel<0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  CK(hipFuncSetAttribute((const void*)pair_kernel<CLOGN, CTSHIFT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((pair_kernel<0, 0>), dim3(B), dim3(256), lds, 0, d_in, d_o1, d_twf, n, logn, 0);
+  hipLaunchKernelGGL((pair_kernel<CLOGN, CTSHIFT>), dim3(B), dim3(256), lds, 0, d_in, d_o2, d_twf, n, logn, 1);
+  CK(hipDeviceSynchronize());
+  CK(hipMemcpy(o1.data(), d_o1, in.size() * 16, hipMemcpyDeviceToHost));
+  CK(hipMemcpy(o2.data(), d_o2, in.size() * 16, hipMemcpyDeviceToHost));
+  long bad = 0;
+  for (size_t i = 0; i < in.size(); ++i) {
+    bad += memcmp(&o1[i].x, &o2[i].x, 8) != 0;
+    bad += memcmp(&o1[i].y, &o2[i].y, 8) != 0;
+  }
+  printf("rfft x 2%s %4d : %ld of %ld values differ\n", CLOGN ? " sized" : "", n, bad, (long)in.size() * 2);
+  CK(hipFree(d_twf)); CK(hipFree(d_in)); CK(hipFree(d_o1)); CK(hipFree(d_o2));
+  return bad != 0;
+}
+
 int main() {
   std::vector<double2> tw_full((size_t)wd::TW_N / 2);
   for (size_t k = 0; k < tw_full.size(); ++k)
     tw_full[k] = make_double2(std::cos(2.0 * M_PI * k / wd::TW_N), std::sin(2.0 * M_PI * k / wd::TW_N));
-  const int bad = run<8>(tw_full) + run<16>(tw_full);
+  int bad = run<8>(tw_full) + run<16>(tw_full);
+  // the two-array form: 64 complex points (the smallest swizzled size; even log2), 128 (odd log2: the radix-2 tail),
+  // FFT_PAIR_MAX, and there the compile-time sizes of D4C at 16 .. 24 kHz
+  bad += run_pair<0, 0>(tw_full, 128, 7) + run_pair<0, 0>(tw_full, 256, 8) + run_pair<0, 0>(tw_full, 2048, 11);
+  bad += run_pair<11, 10>(tw_full, 2048, 11);
   return bad;
 }
