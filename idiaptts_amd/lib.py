@@ -188,6 +188,12 @@ _SIGNATURES = {
     "itts_sgd_step": (c_int, [_P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_int,
                               c_int, c_float, _P]),
     "itts_ema_update": (c_int, [_P, _P, c_int64, c_float, _P]),
+    "itts_fir_filtfilt_workspace_bytes": (c_int64, [c_int64, c_int, c_int]),
+    "itts_fir_filtfilt_batch": (c_int, [_P, POINTER(c_int64), c_int, _P, c_int, _P, _P, _P]),
+    "itts_resample_poly_batch": (c_int, [_P, POINTER(c_int64), POINTER(c_int64), c_int, c_int, c_int, _P, c_int, _P,
+                                         _P]),
+    "itts_loudness_normalise_batch": (c_int, [_P, POINTER(c_int64), c_int, c_double, _P, _P]),
+    "itts_frame_rms_batch": (c_int, [_P, POINTER(c_int64), POINTER(c_int64), c_int, c_int, c_int, c_int, _P, _P]),
 }
 
 

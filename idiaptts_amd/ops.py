@@ -1515,3 +1515,89 @@ def world_synthesize(f0, sp, ap, f_off, fs, frame_period=5.0, preemphasis=0.0,
         sp.record_stream(cur)
         ap.record_stream(cur)
     return y, y_off
+
+
+# ------------------------------------------------------------------------- corpus audio preparation
+FIR_MAX_TAPS = 2047              # FIR_MAX_TAPS of csrc/audio_prep.hip
+RESAMPLE_MAX_RATE = 1024         # RS_MAX_RATE
+RMS_PAD = {"constant": 0, "reflect": 1}     # ITTS_PAD_*
+
+
+def fir_filtfilt(x, offsets, taps, out=None):
+    """scipy.signal.filtfilt(taps, [1], x_s) (padtype "odd", padlen 3 * len(taps)) of every float64 signal
+    x[offsets[s]:offsets[s + 1]]; taps: float64 [numtaps] on the device, numtaps odd.  Returns y like x."""
+    L = _lib.load()
+    _need(x, torch.float64, "x")
+    _need(taps, torch.float64, "taps")
+    x, taps = x.contiguous(), taps.contiguous()
+    n_sig, numtaps = len(offsets) - 1, int(taps.numel())
+    if out is None:
+        out = torch.empty_like(x)
+    _need(out, torch.float64, "out")
+    # (torch's allocator, not the cached _workspace: a corpus batch's first pass is as large as the batch)
+    ws = torch.empty((max(int(L.itts_fir_filtfilt_workspace_bytes(int(offsets[-1]), n_sig, numtaps)), 8),),
+                     dtype=torch.uint8, device=x.device)
+    _lib.check(L.itts_fir_filtfilt_batch(_ptr(x), _lib.offsets_array(offsets), n_sig, _ptr(taps), numtaps, _ptr(out),
+                                         _ptr(ws), _stream()), "itts_fir_filtfilt_batch")
+    return out
+
+
+def resample_out_offsets(offsets, up, down):
+    """Offsets of the resampled signals: ceil(n * up / down) samples each."""
+    out = [0]
+    for s in range(len(offsets) - 1):
+        out.append(out[-1] + -((int(offsets[s + 1]) - int(offsets[s])) * up // -down))
+    return out
+
+
+def resample_poly(x, offsets, up, down, taps):
+    """scipy.signal.resample_poly(x_s, up, down) of every float64 signal with the filter `taps` (float64 [2 * half + 1]
+    on the device, already times up).  Returns (y, out_offsets)."""
+    L = _lib.load()
+    _need(x, torch.float64, "x")
+    _need(taps, torch.float64, "taps")
+    x, taps = x.contiguous(), taps.contiguous()
+    out_off = resample_out_offsets(offsets, up, down)
+    y = torch.empty((out_off[-1],), dtype=torch.float64, device=x.device)
+    _lib.check(L.itts_resample_poly_batch(_ptr(x), _lib.offsets_array(offsets), _lib.offsets_array(out_off),
+                                          len(offsets) - 1, int(up), int(down), _ptr(taps), int(taps.numel()),
+                                          _ptr(y), _stream()), "itts_resample_poly_batch")
+    return y, out_off
+
+
+def loudness_normalise(x, offsets, ref_rms=0.1, out=None):
+    """(x_s - mean) * sqrt(n * ref_rms^2 / sum((x_s - mean)^2)) of every float64 signal."""
+    L = _lib.load()
+    _need(x, torch.float64, "x")
+    x = x.contiguous()
+    if out is None:
+        out = torch.empty_like(x)
+    _need(out, torch.float64, "out")
+    _lib.check(L.itts_loudness_normalise_batch(_ptr(x), _lib.offsets_array(offsets), len(offsets) - 1, float(ref_rms),
+                                               _ptr(out), _stream()), "itts_loudness_normalise_batch")
+    return out
+
+
+def frame_rms_offsets(offsets, frame_length, hop):
+    """Frame offsets of librosa.feature.rms(center=True): 1 + n // hop frames per signal for an even frame_length."""
+    out = [0]
+    for s in range(len(offsets) - 1):
+        padded = int(offsets[s + 1]) - int(offsets[s]) + 2 * (frame_length // 2)
+        out.append(out[-1] + (1 + (padded - frame_length) // hop if padded >= frame_length else 0))
+    return out
+
+
+def frame_rms(x, offsets, frame_length, hop, pad_mode="constant"):
+    """librosa.feature.rms(y=x_s, frame_length, hop_length=hop, center=True, pad_mode) of every float64 signal.
+    Returns (rms [frames of all signals], frame offsets)."""
+    L = _lib.load()
+    _need(x, torch.float64, "x")
+    x = x.contiguous()
+    if pad_mode not in RMS_PAD:
+        raise ValueError("unknown pad_mode {!r} (constant, reflect)".format(pad_mode))
+    f_off = frame_rms_offsets(offsets, int(frame_length), max(int(hop), 1))
+    rms = torch.empty((f_off[-1],), dtype=torch.float64, device=x.device)
+    _lib.check(L.itts_frame_rms_batch(_ptr(x), _lib.offsets_array(offsets), _lib.offsets_array(f_off),
+                                      len(offsets) - 1, int(frame_length), int(hop), RMS_PAD[pad_mode], _ptr(rms),
+                                      _stream()), "itts_frame_rms_batch")
+    return rms, f_off

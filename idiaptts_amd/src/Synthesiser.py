@@ -16,6 +16,7 @@ import scipy.io.wavfile
 
 from .. import world as _world
 from .data_preparation.audio.AudioProcessing import AudioProcessing
+from .data_preparation.audio.audio_batch import write_pcm16
 from .data_preparation.world.WorldFeatLabelGen import WorldFeatLabelGen
 
 
@@ -82,8 +83,7 @@ class Synthesiser(object):
                          + '_' + str(hparams.num_coded_sps) + hparams.sp_type + "_WORLD")
             file_path = os.path.join(save_dir, file_name)
             # soundfile.write(float) default subtype for .wav is PCM_16
-            pcm = np.clip(np.rint(waveform * 32768.0), -32768, 32767).astype(np.int16)
-            scipy.io.wavfile.write(file_path + ".wav", fs, pcm)
+            write_pcm16(file_path + ".wav", waveform, fs)
             if getattr(hparams, "synth_ext", "wav").lower() != 'wav':
                 raise NotImplementedError("Only wav output is supported (pydub is out of scope).")
         if return_waveforms:

@@ -860,6 +860,47 @@ int itts_gemm_path_counts(int64_t out[8]);
  * the per-step kernels redid the layer. */
 int itts_rnn_path_counts(int64_t out[6]);
 
+/* ---- corpus audio preparation (csrc/audio_prep.hip): the four steps that scripts/bash_utils.sh runs over the wav
+ *      corpus before gen_data -- src/data_preparation/audio/down_sampling.py, silence_remove.py,
+ *      normalize_loudness.py, high_pass_filter.py.  float64 throughout; the signals of a batch lie back to back in
+ *      d_x, signal s = d_x[h_offsets[s] .. h_offsets[s + 1]), h_offsets [n_signals + 1] ascending from 0.  Every sum
+ *      runs in a fixed order that depends on the signal alone: a signal's result has the same bits alone and at any
+ *      place of any batch.  Bad arguments (a null pointer, the cases named below) return ITTS_E_INVALID with a message
+ *      naming the value before any device work -- a size that would need more than 2^24 - 1 workgroups in one launch
+ *      (16 M signals, 16 M frames of one signal, a signal of 3e10 samples) among them; n_signals == 0 succeeds and does
+ *      nothing.
+ *
+ * itts_fir_filtfilt_batch: scipy.signal.filtfilt(b, [1], x) (high_pass_filter.py:57; padtype "odd", padlen =
+ *   3 * numtaps) with the numtaps coefficients d_taps, into d_y (same offsets).  numtaps is odd, 1 .. 2047; every
+ *   signal is longer than padlen.  d_workspace >= itts_fir_filtfilt_workspace_bytes(h_offsets[n_signals], n_signals,
+ *   numtaps) bytes (the first pass: n + padlen values per signal; 0 for sizes that are not positive).
+ * itts_resample_poly_batch: scipy.signal.resample_poly(x, up, down) (the librosa.load(sr=...) of
+ *   down_sampling.py:43, on scipy's polyphase resampler) with the filter d_taps designed by the caller --
+ *   firwin(2 * half + 1, 1 / max(up, down), window=("kaiser", 5.0)) * up, half = 10 * max(up, down), for scipy's
+ *   defaults; numtaps odd, its centre tap aligned with the first sample -- zeros outside the signal.  up and down are
+ *   1 .. 1024 (reduce them by their gcd first).  Signal s fills d_y[h_out_offsets[s] .. h_out_offsets[s + 1]), which
+ *   has to be ceil(n * up / down) long.
+ * itts_loudness_normalise_batch: y = (x - mean(x)) * sqrt(n * ref_rms^2 / sum((x - mean(x))^2))
+ *   (normalize_loudness.py:41-42), ref_rms > 0; d_y may be d_x.  A constant signal gives non-finite values, as there.
+ * itts_frame_rms_batch: librosa.feature.rms(y=x, frame_length, hop_length=hop, center=True)
+ *   (librosa.effects.trim behind silence_remove.py:75-79): the signal padded by frame_length / 2 on both sides --
+ *   ITTS_PAD_CONSTANT with zeros (librosa >= 0.10), ITTS_PAD_REFLECT mirrored (librosa 0.8 / 0.9) -- and one
+ *   sqrt(mean square) per frame into d_rms[h_frame_offsets[s] ..]; signal s has
+ *   1 + (n + 2 * (frame_length / 2) - frame_length) / hop frames (1 + n / hop for an even frame_length) and is not
+ *   empty; hop >= 1. */
+#define ITTS_PAD_CONSTANT 0
+#define ITTS_PAD_REFLECT 1
+int64_t itts_fir_filtfilt_workspace_bytes(int64_t n_total, int n_signals, int numtaps);
+int itts_fir_filtfilt_batch(const double* d_x, const int64_t* h_offsets, int n_signals, const double* d_taps,
+                            int numtaps, double* d_y, void* d_workspace, void* stream);
+int itts_resample_poly_batch(const double* d_x, const int64_t* h_offsets, const int64_t* h_out_offsets,
+                             int n_signals, int up, int down, const double* d_taps, int numtaps, double* d_y,
+                             void* stream);
+int itts_loudness_normalise_batch(const double* d_x, const int64_t* h_offsets, int n_signals, double ref_rms,
+                                  double* d_y, void* stream);
+int itts_frame_rms_batch(const double* d_x, const int64_t* h_offsets, const int64_t* h_frame_offsets, int n_signals,
+                         int frame_length, int hop, int pad_mode, double* d_rms, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
