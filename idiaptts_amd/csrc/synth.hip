@@ -591,6 +591,138 @@ __global__ __launch_bounds__(128) void syn_kind_offsets_kernel(const int* __rest
     wave_offsets(n_utts, [&](int u) { return (int64_t)kcnt[kind * n_utts + u]; }, kgp + kind * (n_utts + 1));
 }
 
+// ---- one pulse, written once for the two pulse kernels below -------------------------------------------------------
+// wave-uniform values said so (the pulse's scalars then live in SGPRs instead of one VGPR each)
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ int64_t uni(int64_t v) {
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ double uni(double v) { return bcast0(v); }
+// how a kernel holds the pulse's scalars: as they come (a workgroup per pulse) or said to be uniform (a wave per pulse)
+struct AsIs {
+  template <class T> __device__ __forceinline__ T operator()(T v) const { return v; }
+};
+struct Uniform {
+  template <class T> __device__ __forceinline__ T operator()(T v) const { return uni(v); }
+};
+// the transcendentals of a pulse: the total forms of world_dev.h for the workgroup kernel, the short reductions of
+// fastmath.h directly for the wave kernel (see min_phase_wave)
+struct MathMid {
+  static __device__ __forceinline__ double exp(double x) { return ::exp(x); }
+  static __device__ __forceinline__ double cos(double x) { return cos_mid(x); }
+  static __device__ __forceinline__ void sincos(double x, double* sn, double* cs) { sincos_mid(x, sn, cs); }
+};
+struct MathShort {
+  static __device__ __forceinline__ double exp(double x) { return fm::fexp(x); }
+  static __device__ __forceinline__ double cos(double x) { return fm::fcos(x); }
+  static __device__ __forceinline__ void sincos(double x, double* sn, double* cs) { fm::fsincos(x, sn, cs); }
+};
+
+struct Pulse {
+  int idx, idx_first;      // the pulse's sample, the utterance's first pulse's
+  int noise_size;          // samples up to the next pulse
+  double tshift;           // the zero crossing of the phase behind sample idx, in seconds
+  int fl, ce;              // the frames around the pulse ..
+  double al;               // .. and its place between them
+  const double *sp0, *sp1, *ap0, *ap1;   // their envelope and aperiodicity rows
+  int u_yl;                // the utterance: samples, offsets of its output and of its per-sample scratch
+  int64_t u_yoff, u_soff;
+};
+// pulse number kn of its kind (UNV: the unvoiced ones) in utterance lo; K bins per spectrum row.  The arrays are those
+// of PulseArgs, handed over one by one: a kernel that passes its argument struct by address keeps it in memory past the
+// point where the compiler decides which loads are scalar, and every uniform load of the kernel becomes a vector one.
+template <bool UNV, class U>
+__device__ __forceinline__ Pulse pulse_at(const SynUtt* utts, const double* ptot, const int* kq, const int* pidx_all,
+                                          const double* wrap_all, const double* sp, const double* ap, const SynParams p,
+                                          int K, int lo, int kn, U u) {
+  Pulse pu;
+  const int64_t u_foff = u(utts[lo].f_off);
+  pu.u_yoff = u(utts[lo].y_off);
+  pu.u_soff = u(utts[lo].s_off);
+  const int T = u(utts[lo].T);
+  pu.u_yl = u(utts[lo].yl);
+  const int Pn = u((int)ptot[lo]);
+  const int qi = u(kq[pu.u_soff + (UNV ? kn : pu.u_yl - 1 - kn)]);
+  const int* pidx = pidx_all + pu.u_soff;
+  pu.idx = u(pidx[qi]);
+  const int idx_next = u(pidx[min(Pn - 1, qi + 1)]);
+  pu.idx_first = u(pidx[0]);
+  pu.noise_size = idx_next - pu.idx;
+  const double* wrap = wrap_all + pu.u_soff;
+  const double y1 = u(wrap[pu.idx]) - 2.0 * kPi, y2 = u(wrap[pu.idx + 1]);
+  pu.tshift = u((-y1 / (y2 - y1)) / p.fs);
+  const double t = pu.idx / (double)p.fs;
+  pu.fl = u((int)floor(t / p.fp));
+  pu.ce = u((int)ceil(t / p.fp));
+  if (pu.fl > T - 1) pu.fl = T - 1;
+  if (pu.ce > T - 1) pu.ce = T - 1;
+  pu.al = u(t / p.fp - pu.fl);
+  pu.sp0 = sp + (u_foff + pu.fl) * K;
+  pu.sp1 = sp + (u_foff + pu.ce) * K;
+  pu.ap0 = ap + (u_foff + pu.fl) * K;
+  pu.ap1 = ap + (u_foff + pu.ce) * K;
+  return pu;
+}
+// spectral envelope and (clamped, squared) aperiodicity ratio of bin k at the pulse.  UNV: the envelope alone, the
+// ratio is one (the aperiodicity rows are not read)
+template <bool UNV>
+__device__ __forceinline__ void pulse_se_ar(const Pulse& pu, int k, double& se, double& ar) {
+  const double s0 = fabs(pu.sp0[k]);
+  if (UNV) {
+    se = pu.fl == pu.ce ? s0 : (1.0 - pu.al) * s0 + pu.al * fabs(pu.sp1[k]);
+    ar = 1.0;
+    return;
+  }
+  double a0 = pu.ap0[k];
+  a0 = a0 > 0.999999999999 ? 0.999999999999 : a0;
+  a0 = a0 < 0.001 ? 0.001 : a0;
+  if (pu.fl == pu.ce) {
+    se = s0;
+    ar = a0 * a0;                    // pow(x, 2.0): compilers fold it to x * x
+  } else {
+    const double s1 = fabs(pu.sp1[k]);
+    double a1 = pu.ap1[k];
+    a1 = a1 > 0.999999999999 ? 0.999999999999 : a1;
+    a1 = a1 < 0.001 ? 0.001 : a1;
+    se = (1.0 - pu.al) * s0 + pu.al * s1;
+    ar = (1.0 - pu.al) * (a0 * a0) + pu.al * (a1 * a1);
+  }
+}
+// a voiced pulse has a periodic response unless its frame is aperiodic down to DC
+__device__ __forceinline__ bool pulse_has_per(const Pulse& pu) {
+  double se0, ar0;
+  pulse_se_ar<false>(pu, 0, se0, ar0);
+  return !(ar0 > 0.999);
+}
+// log amplitudes of the periodic and of the aperiodic response
+__device__ __forceinline__ double pulse_lg_per(double se, double ar) { return log_pos(se * (1.0 - ar) + kEps) / 2.0; }
+__device__ __forceinline__ double pulse_lg_aper(double se, double ar) { return log_pos(se * ar) / 2.0; }
+// bin of a minimum-phase spectrum from the second transform's (over fft points)
+template <class M>
+__device__ __forceinline__ double2 min_phase_bin(double zr, double zi, int fft) {
+  const double t = M::exp(zr / fft);      // (the log amplitude of a spectrum: within +-373)
+  double sn, cs;
+  M::sincos(zi / fft, &sn, &cs);
+  return make_double2(t * cs, t * sn);
+}
+// the periodic response's bin k: the minimum-phase bin m turned by the pulse's place between two samples
+__device__ __forceinline__ double pulse_shift_coef(const Pulse& pu, int fs, int fft) { return 2.0 * kPi * pu.tshift * fs / fft; }
+template <class M>
+__device__ __forceinline__ double2 pulse_shift(const double2 m, double coef, int k) {
+  const double re2 = M::cos(coef * k);        // |coef * k| <= pi: the time shift is below one sample
+  const double im2 = sqrt(1.0 - re2 * re2);
+  return make_double2(m.x * re2 + m.y * im2, m.y * re2 - m.x * im2);
+}
+// the aperiodic response's bin: minimum-phase bin m times the noise's n
+__device__ __forceinline__ double2 pulse_noise_mul(const double2 m, const double2 n) {
+  return make_double2(m.x * n.x - m.y * n.y, m.x * n.y + m.y * n.x);
+}
+// a sample of the pulse: the periodic response's pv (scaled by sq = sqrt(noise_size)) plus the aperiodic one's apv
+__device__ __forceinline__ double pulse_sample(bool has_per, double pv, double sq, double apv) {
+  return (has_per ? pv * sq : 0.0) + apv;
+}
+
 // minimum phase spectrum of the log-amplitude lg[0..h] (in z.x of the first h+1 entries is NOT
 // assumed): input array `lg`, output mp[0..h] complex. Uses z as FFT scratch.  lg is consumed by
 // the first loop, so it may live inside mp's storage.
@@ -614,12 +746,7 @@ __device__ inline void min_phase(const double* lg, int fft_rt, int logfft, doubl
   for (int k = h + 1 + tid(); k < fft + 2; k += NT) zr[k] = 0.0;
   __syncthreads();
   rfft_lds<true, CFFT, CFFT ? CFFT - 1 : 0>(z, fft, logfft, tw, fft);
-  for (int k = tid(); k <= h; k += NT) {
-    const double t = exp(z[k].x / fft);
-    double sn, cs;
-    sincos_mid(z[k].y / fft, &sn, &cs);
-    mp[k] = make_double2(t * cs, t * sn);
-  }
+  for (int k = tid(); k <= h; k += NT) mp[k] = min_phase_bin<MathMid>(z[k].x, z[k].y, fft);
   __syncthreads();
 }
 
@@ -674,76 +801,21 @@ __global__ __launch_bounds__(NT, 5) void syn_pulse_kernel(PulseArgs a) {
     // utterance of pulse g of this kind: every wave reads the offsets 64 at a time and counts (a binary search is
     // log2(U) dependent trips to memory in front of everything else the pulse does)
     const int lo = find_utt_wave(a.kgpoff, a.p.n_utts, g);
-    const SynUtt u = a.utts[lo];
-    const int P = (int)a.ptot[lo];
-    const int kn = (int)(g - a.kgpoff[lo]);
-    const int qi = a.kq[u.s_off + (UNV ? kn : u.yl - 1 - kn)];
-    const int* pidx = a.pidx + u.s_off;
-    const int idx = pidx[qi];
-    const int idx_next = pidx[min(P - 1, qi + 1)];
-    const int noise_size = idx_next - idx;
-    const double* wrap = a.wrap + u.s_off;
-    const double y1 = wrap[idx] - 2.0 * kPi, y2 = wrap[idx + 1];
-    const double tshift = (-y1 / (y2 - y1)) / a.p.fs;
-    const double t = idx / (double)a.p.fs;
-    const double vuv = UNV ? 0.0 : 1.0;            // (the kind of the list)
-    const int T = u.T;
-    int fl = (int)floor(t / a.p.fp), ce = (int)ceil(t / a.p.fp);
-    if (fl > T - 1) fl = T - 1;
-    if (ce > T - 1) ce = T - 1;
-    const double al = t / a.p.fp - fl;
-    const double* sp0 = a.sp + (u.f_off + fl) * K;
-    const double* sp1 = a.sp + (u.f_off + ce) * K;
-    const double* ap0 = a.ap + (u.f_off + fl) * K;
-    const double* ap1 = a.ap + (u.f_off + ce) * K;
-    // spectral envelope and aperiodicity ratio of bin k at the pulse
-    auto se_ar = [&](int k, double& se, double& ar) {
-      const double s0 = fabs(sp0[k]);
-      double a0 = ap0[k];
-      a0 = a0 > 0.999999999999 ? 0.999999999999 : a0;
-      a0 = a0 < 0.001 ? 0.001 : a0;
-      if (fl == ce) {
-        se = s0;
-        ar = a0 * a0;                    // pow(x, 2.0): compilers fold it to x * x
-      } else {
-        const double s1 = fabs(sp1[k]);
-        double a1 = ap1[k];
-        a1 = a1 > 0.999999999999 ? 0.999999999999 : a1;
-        a1 = a1 < 0.001 ? 0.001 : a1;
-        se = (1.0 - al) * s0 + al * s1;
-        ar = (1.0 - al) * (a0 * a0) + al * (a1 * a1);
-      }
-    };
-    // ---- periodic response
-    bool has_per = false;
-    if (vuv != 0.0) {
-      double se0, ar0;
-      se_ar(0, se0, ar0);
-      has_per = !(ar0 > 0.999);
-      for (int k = tid(); k < K; k += NT) {
-        double se, ar;
-        se_ar(k, se, ar);
-        if (has_per) lg[k] = log_pos(se * (1.0 - ar) + kEps) / 2.0;
-        lgs[k] = log_pos(se * ar) / 2.0;
-      }
-    } else {
-      // an unvoiced pulse: the envelope alone (the aperiodicity rows are not read)
-      for (int k = tid(); k < K; k += NT) {
-        const double s0 = fabs(sp0[k]);
-        lgs[k] = log_pos(fl == ce ? s0 : (1.0 - al) * s0 + al * fabs(sp1[k])) / 2.0;
-      }
+    const Pulse pu = pulse_at<UNV>(a.utts, a.ptot, a.kq, a.pidx, a.wrap, a.sp, a.ap, a.p, K, lo, (int)(g - a.kgpoff[lo]), AsIs());
+    const bool has_per = UNV ? false : pulse_has_per(pu);
+    // ---- log amplitudes of the periodic response (into lg) and of the aperiodic one
+    for (int k = tid(); k < K; k += NT) {
+      double se, ar;
+      pulse_se_ar<UNV>(pu, k, se, ar);
+      if (has_per) lg[k] = pulse_lg_per(se, ar);
+      lgs[k] = pulse_lg_aper(se, ar);
     }
     __syncthreads();
     double per_dc = 0.0, per_dsum = 1.0;
     if (has_per) {
       min_phase<CFFT>(lg, fft, logfft, z, tw, mp);
-      const double coef = 2.0 * kPi * tshift * a.p.fs / fft;
-      for (int k = tid(); k < K; k += NT) {
-        const double re2 = cos_mid(coef * k);
-        const double im2 = sqrt(1.0 - re2 * re2);
-        const double2 m = mp[k];
-        z[k] = make_double2(m.x * re2 + m.y * im2, m.y * re2 - m.x * im2);
-      }
+      const double coef = pulse_shift_coef(pu, a.p.fs, fft);
+      for (int k = tid(); k < K; k += NT) z[k] = pulse_shift<MathMid>(mp[k], coef, k);
       __syncthreads();
       irfft_lds<true, CFFT, CFFT ? CFFT - 1 : 0>(z, fft, logfft, tw, fft);
       // fftshift + DC removal
@@ -767,7 +839,8 @@ __global__ __launch_bounds__(NT, 5) void syn_pulse_kernel(PulseArgs a) {
     // multiplied in place
     min_phase<CFFT>(lgs, fft, logfft, z, tw, mp);
     {
-      const double* R = a.R + u.s_off + (idx - pidx[0]);
+      const double* R = a.R + pu.u_soff + (pu.idx - pu.idx_first);
+      const int noise_size = pu.noise_size;
       double s = 0.0;
       for (int i = tid(); i < fft + 2; i += NT) {
         double v = 0.0;
@@ -785,19 +858,16 @@ __global__ __launch_bounds__(NT, 5) void syn_pulse_kernel(PulseArgs a) {
       __syncthreads();
       rfft_lds<true, CFFT, CFFT ? CFFT - 1 : 0>(z, fft, logfft, tw, fft);
     }
-    for (int k = tid(); k < K; k += NT) {
-      const double2 m = mp[k], n = z[k];
-      z[k] = make_double2(m.x * n.x - m.y * n.y, m.x * n.y + m.y * n.x);
-    }
+    for (int k = tid(); k < K; k += NT) z[k] = pulse_noise_mul(mp[k], z[k]);
     __syncthreads();
     irfft_lds<true, CFFT, CFFT ? CFFT - 1 : 0>(z, fft, logfft, tw, fft);
     // ---- overlap-add
-    const double sq = sqrt((double)noise_size);
-    const int off = idx - h + 1;
-    double* y = a.y + u.y_off;
+    const double sq = sqrt((double)pu.noise_size);
+    const int off = pu.idx - h + 1;
+    double* y = a.y + pu.u_yoff;
     for (int j = tid(); j < fft; j += NT) {
       const int tgt = j + off;
-      if (tgt >= 0 && tgt < u.yl) {
+      if (tgt >= 0 && tgt < pu.u_yl) {
         const double apv = (j < h) ? zr[j + h] : zr[j - h];  // fftshift
         double pv = 0.0;
         if (has_per) {
@@ -808,8 +878,7 @@ __global__ __launch_bounds__(NT, 5) void syn_pulse_kernel(PulseArgs a) {
             pv = per[j - h];
           }
         }
-        const double v = (has_per ? pv * sq : 0.0) + apv;
-        atomicAdd(&y[tgt], v);
+        atomicAdd(&y[tgt], pulse_sample(has_per, pv, sq, apv));
       }
     }
     __syncthreads();
@@ -825,25 +894,6 @@ __global__ __launch_bounds__(NT, 5) void syn_pulse_kernel(PulseArgs a) {
 // host no longer needs the pulse count.
 // Spectra and responses are those of syn_pulse_kernel bit for bit; the two wave-wide sums (DC of the
 // periodic response, mean of the noise) add up in another order.
-// wave-uniform values said so (the pulse's scalars then live in SGPRs instead of one VGPR each)
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ int64_t uni(int64_t v) {
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-__device__ __forceinline__ double uni(double v) {
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)__double2loint(v));
-  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)__double2hiint(v));
-  return __hiloint2double((int)hi, (int)lo);
-}
-template <class T>
-__device__ __forceinline__ const T* uni(const T* p) { return reinterpret_cast<const T*>(uni((int64_t)reinterpret_cast<uintptr_t>(p))); }
-
-__device__ __forceinline__ double wave_bcast0(double v) {
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)__double2loint(v));
-  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)__double2hiint(v));
-  return __hiloint2double((int)hi, (int)lo);
-}
 
 // minimum phase spectrum of the log-amplitude v (layout A; v[8] = bin 512, the same in every lane) ->
 // mp (same layout).  The two real transforms run as two trips through one copy of the code.
@@ -861,38 +911,23 @@ __device__ __forceinline__ void min_phase_wave(double (&v)[9], const wf::Plan512
       // fold: c[0], 2 c[1 .. h-1], c[h], zeros
 #pragma unroll
       for (int q = 0; q < 8; ++q) v[q] = z[q].x * ((q == 0 && wf::lane_id() == 0) ? 1.0 : 2.0);
-      v[8] = wave_bcast0(x512.x) * 1.0;
+      v[8] = bcast0(x512.x) * 1.0;
     }
   }
 #pragma unroll
   for (int q = 0; q < 9; ++q) {
-    const double zr = q < 8 ? z[q].x : wave_bcast0(x512.x), zi = q < 8 ? z[q].y : wave_bcast0(x512.y);
-    const double t = fm::fexp(zr / fft);      // (the log amplitude of a spectrum: within +-373)
-    double sn, cs;
     // The short reduction of fastmath.h directly: sincos_mid's out-of-line fallback for |x| > 1e5 is a CALL,
     // and one call in the kernel costs its whole register allocation (75 -> 19 spilled registers
     // without it).  The phase cannot get there: it is the conjugate function of the log amplitude lg,
     // |phase| <= (4 / pi) (1 + 1/3 + ... + 1/511) max|lg| < 5.3 max|lg|, and |lg| <= 373 for anything a
     // double holds -- below 2 000 rad.  (A NaN or an infinite phase gives NaN here as it does there.)
-    fm::fsincos(zi / fft, &sn, &cs);
-    mp[q] = make_double2(t * cs, t * sn);
+    mp[q] = min_phase_bin<MathShort>(q < 8 ? z[q].x : bcast0(x512.x), q < 8 ? z[q].y : bcast0(x512.y), fft);
     if (q % 3 == 2) __builtin_amdgcn_sched_barrier(0);     // three bins in flight are enough; nine do not fit the registers
   }
 }
 
-#ifndef SYN_WAVE_OCC
-#define SYN_WAVE_OCC 2
-#endif
-#ifndef SYN_WAVE_DIAG
-#define SYN_WAVE_DIAG 0
-#endif
-// pulses a wave takes from its kind's list at a time (0: dealt by stride, as until late in round 5)
-#ifndef SYN_WAVE_DEAL_UNV
-#define SYN_WAVE_DEAL_UNV 4
-#endif
-#ifndef SYN_WAVE_DEAL_VOI
-#define SYN_WAVE_DEAL_VOI 2
-#endif
+constexpr int SYN_WAVE_OCC = 2;            // waves per SIMD of the voiced pulses' kernel
+constexpr int SYN_WAVE_DEAL_UNV = 4, SYN_WAVE_DEAL_VOI = 2;      // pulses a wave takes from its kind's list at a time (WaveDeal)
 // A kernel per kind of pulse (round 5): UNV = the unvoiced ones -- nine in ten for speech: a pulse every 2 ms in
 // unvoiced frames, one per pitch period in voiced ones --, which have no periodic response: without its registers (and
 // the DC remover's table and the stash of log amplitudes in LDS) the kernel fits THREE waves per SIMD (168 registers,
@@ -921,85 +956,18 @@ __global__ __launch_bounds__(NT, UNV ? 3 : SYN_WAVE_OCC) void syn_pulse_wave_ker
   wf::plan512_init(P, a.g_tw, wave_lds, smem);
   const double2* dcrn2 = reinterpret_cast<const double2*>(dcrn);
   const int64_t total = a.kgpoff[a.p.n_utts];
-  const int64_t nw = (int64_t)gridDim.x * (NT / 64);
   int lo = 0;
-  constexpr int kDeal = UNV ? SYN_WAVE_DEAL_UNV : SYN_WAVE_DEAL_VOI;
-#if SYN_WAVE_DEAL_UNV && SYN_WAVE_DEAL_VOI
-  // The pulses are handed out kDeal at a time behind a counter (a wave's pulses still only grow).  Dealt by stride
-  // -- pulse g to wave g mod nw -- the kernel lasted as long as its last workgroup to START: one that finds its CU
-  // taken by the tail of another stream's kernel (the caller's decode_aperiodicity) starts when some workgroup has
-  // FINISHED its share, and does its own share behind everybody else's (7.2 instead of 5.4 ms when the two met,
-  // profiles/r5ap_timeline_noise_on_side_stream.txt).
-  (void)nw;
-  int64_t g = 0, g_end = 0;
-  for (;; ++g) {
-    if (g >= g_end) {
-      int base = 0;
-      if (l0 == 0) base = atomicAdd(a.next, kDeal);
-      g = uni(base);
-      if (g >= total) break;
-      g_end = min(g + kDeal, total);
-    }
-#else
-  (void)kDeal;
-  for (int64_t g = (int64_t)blockIdx.x * (NT / 64) + wv; g < total; g += nw) {
-#endif
+  for (WaveDeal<UNV ? SYN_WAVE_DEAL_UNV : SYN_WAVE_DEAL_VOI> deal; deal.next(a.next, total, l0 == 0); ++deal.g) {
+    const int64_t g = deal.g;
     // opaque per pulse: what derives from the lane number is a few integer operations; hoisted out of the
     // loop it is a dozen registers held for the whole kernel
     int l = l0;
     asm volatile("" : "+v"(l));
     while (uni(a.kgpoff[lo + 1]) <= g) ++lo;          // utterance of pulse g of this kind (g only grows)
-    const int64_t u_foff = uni(a.utts[lo].f_off), u_yoff = uni(a.utts[lo].y_off), u_soff = uni(a.utts[lo].s_off);
-    const int T = uni(a.utts[lo].T), u_yl = uni(a.utts[lo].yl);
-    const int Pn = uni((int)a.ptot[lo]);
-    const int kn = (int)(g - uni(a.kgpoff[lo]));
-    const int qi = uni(a.kq[u_soff + (UNV ? kn : u_yl - 1 - kn)]);
-    const int* pidx = a.pidx + u_soff;
-    const int idx = uni(pidx[qi]);
-    const int idx_next = uni(pidx[min(Pn - 1, qi + 1)]);
-    const int idx_first = uni(pidx[0]);
-    const int noise_size = idx_next - idx;
-    const double* wrap = a.wrap + u_soff;
-    const double y1 = uni(wrap[idx]) - 2.0 * kPi, y2 = uni(wrap[idx + 1]);
-    const double tshift = uni((-y1 / (y2 - y1)) / a.p.fs);
-    const double t = idx / (double)a.p.fs;
-    const double vuv = UNV ? 0.0 : 1.0;                 // (the kind of the list)
-    int fl = uni((int)floor(t / a.p.fp)), ce = uni((int)ceil(t / a.p.fp));
-    if (fl > T - 1) fl = T - 1;
-    if (ce > T - 1) ce = T - 1;
-    const double al = uni(t / a.p.fp - fl);
-    const double* sp0 = a.sp + (u_foff + fl) * K;
-    const double* sp1 = a.sp + (u_foff + ce) * K;
-    const double* ap0 = a.ap + (u_foff + fl) * K;
-    const double* ap1 = a.ap + (u_foff + ce) * K;
-    // spectral envelope and aperiodicity ratio of bin k at the pulse
-    auto se_ar = [&](int k, double& se, double& ar) {
-      const double s0 = fabs(sp0[k]);
-      if (vuv == 0.0) {
-        // an unvoiced pulse: the envelope alone (its aperiodicity ratio is never used: the rows are not read)
-        se = fl == ce ? s0 : (1.0 - al) * s0 + al * fabs(sp1[k]);
-        ar = 1.0;
-        return;
-      }
-      double a0 = ap0[k];
-      a0 = a0 > 0.999999999999 ? 0.999999999999 : a0;
-      a0 = a0 < 0.001 ? 0.001 : a0;
-      if (fl == ce) {
-        se = s0;
-        ar = a0 * a0;
-      } else {
-        const double s1 = fabs(sp1[k]);
-        double a1 = ap1[k];
-        a1 = a1 > 0.999999999999 ? 0.999999999999 : a1;
-        a1 = a1 < 0.001 ? 0.001 : a1;
-        se = (1.0 - al) * s0 + al * s1;
-        ar = (1.0 - al) * (a0 * a0) + al * (a1 * a1);
-      }
-    };
-    double se0, ar0;
-    se_ar(0, se0, ar0);
-    const bool has_per = UNV ? false : !(ar0 > 0.999);
-    const double coef = uni(2.0 * kPi * tshift * a.p.fs / fft);
+    const Pulse pu =
+        pulse_at<UNV>(a.utts, a.ptot, a.kq, a.pidx, a.wrap, a.sp, a.ap, a.p, K, lo, (int)(g - uni(a.kgpoff[lo])), Uniform());
+    const bool has_per = UNV ? false : pulse_has_per(pu);
+    const double coef = uni(pulse_shift_coef(pu, a.p.fs, fft));
     double2 per[4] = {make_double2(0.0, 0.0), make_double2(0.0, 0.0), make_double2(0.0, 0.0), make_double2(0.0, 0.0)};
     double per_dc = 0.0;
     double2 z[8], x512;
@@ -1017,14 +985,13 @@ __global__ __launch_bounds__(NT, UNV ? 3 : SYN_WAVE_OCC) void syn_pulse_wave_ker
 #pragma unroll
         for (int q = 0; q < 9; ++q) {
           double se, ar;
-          se_ar(q < 8 ? l + 64 * q : h, se, ar);
-          const double xa = (vuv != 0.0) ? se * ar : se;
+          pulse_se_ar<UNV>(pu, q < 8 ? l + 64 * q : h, se, ar);
           if (half == 0) {
-            v[q] = log_pos(se * (1.0 - ar) + kEps) / 2.0;
-            const double w = log_pos(xa) / 2.0;
+            v[q] = pulse_lg_per(se, ar);
+            const double w = pulse_lg_aper(se, ar);
             if (q < 8) lgs[l + 64 * q] = w; else lgs[h] = w;
           } else {
-            v[q] = log_pos(xa) / 2.0;
+            v[q] = pulse_lg_aper(se, ar);
           }
           if (q % 3 == 2) __builtin_amdgcn_sched_barrier(0);
         }
@@ -1035,16 +1002,13 @@ __global__ __launch_bounds__(NT, UNV ? 3 : SYN_WAVE_OCC) void syn_pulse_wave_ker
       if (half == 0) {
 #pragma unroll
         for (int q = 0; q < 9; ++q) {
-          const int k = q < 8 ? l + 64 * q : h;
-          const double re2 = fm::fcos(coef * k);        // |coef * k| <= pi: the time shift is below one sample
-          const double im2 = sqrt(1.0 - re2 * re2);
-          const double2 m = mp[q];
-          const double2 r = make_double2(m.x * re2 + m.y * im2, m.y * re2 - m.x * im2);
+          const double2 r = pulse_shift<MathShort>(mp[q], coef, q < 8 ? l + 64 * q : h);
           if (q < 8) z[q] = r; else x512 = r;
           if (q % 3 == 2) __builtin_amdgcn_sched_barrier(0);
         }
       } else {
-        const double* R = a.R + u_soff + (idx - idx_first);
+        const double* R = a.R + pu.u_soff + (pu.idx - pu.idx_first);
+        const int noise_size = pu.noise_size;
         double sacc = 0.0;
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
@@ -1066,12 +1030,8 @@ __global__ __launch_bounds__(NT, UNV ? 3 : SYN_WAVE_OCC) void syn_pulse_wave_ker
         }
         wf::rfft<8>(z, x512, P);
 #pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const double2 m = mp[q], n = z[q];
-          z[q] = make_double2(m.x * n.x - m.y * n.y, m.x * n.y + m.y * n.x);
-        }
-        const double nx = wave_bcast0(x512.x), ny = wave_bcast0(x512.y);
-        x512 = make_double2(mp[8].x * nx - mp[8].y * ny, mp[8].x * ny + mp[8].y * nx);
+        for (int q = 0; q < 8; ++q) z[q] = pulse_noise_mul(mp[q], z[q]);
+        x512 = pulse_noise_mul(mp[8], make_double2(bcast0(x512.x), bcast0(x512.y)));
       }
       wf::irfft<8>(z, x512, P);       // z[q] = (x[2m], x[2m+1]), m = lane + 64 q
       if (half == 0) {
@@ -1090,9 +1050,9 @@ __global__ __launch_bounds__(NT, UNV ? 3 : SYN_WAVE_OCC) void syn_pulse_wave_ker
     }
     // ---- overlap-add: sample i of a response lands at j = (i + h) mod fft (fftshift).  The sums go
     // through the wave's LDS once so that an atomic instruction covers 64 consecutive samples.
-    const double sq = sqrt((double)noise_size);
-    const int off = idx - h + 1;
-    double* y = a.y + u_yoff;
+    const double sq = sqrt((double)pu.noise_size);
+    const int off = pu.idx - h + 1;
+    double* y = a.y + pu.u_yoff;
     {
       double2* s2 = reinterpret_cast<double2*>(wave_lds);
 #pragma unroll
@@ -1106,8 +1066,8 @@ __global__ __launch_bounds__(NT, UNV ? 3 : SYN_WAVE_OCC) void syn_pulse_wave_ker
             pv = per[q];
           }
         }
-        const double2 v = make_double2((has_per ? pv.x * sq : 0.0) + z[q].x, (has_per ? pv.y * sq : 0.0) + z[q].y);
-        s2[l + 64 * ((q + 4) & 7)] = v;                     // slot j / 2
+        s2[l + 64 * ((q + 4) & 7)] =                        // slot j / 2
+            make_double2(pulse_sample(has_per, pv.x, sq, z[q].x), pulse_sample(has_per, pv.y, sq, z[q].y));
       }
       wf::wave_sync();
       const double* s1 = reinterpret_cast<const double*>(wave_lds);
@@ -1116,13 +1076,7 @@ __global__ __launch_bounds__(NT, UNV ? 3 : SYN_WAVE_OCC) void syn_pulse_wave_ker
         const int j = 64 * r + l;
         const int tgt = j + off;
         const double v = s1[j];
-        if (tgt >= 0 && tgt < u_yl) {
-#if SYN_WAVE_DIAG == 1
-          if (v == 1.2345e300) y[tgt] = v;
-#else
-          atomicAdd(&y[tgt], v);
-#endif
-        }
+        if (tgt >= 0 && tgt < pu.u_yl) atomicAdd(&y[tgt], v);
       }
       wf::wave_sync();
     }
@@ -1173,6 +1127,19 @@ __global__ __launch_bounds__(64) void syn_deemph_kernel(const double* __restrict
 }  // namespace itts
 
 using namespace itts;
+
+// one workgroup per pulse of a kind (a.kgpoff: that kind's numbering; n_pulses: its total, read back by the host)
+template <int CFFT, bool UNV>
+static int launch_pulse_kernel(const PulseArgs& a, int64_t n_pulses, hipStream_t s) {
+  if (n_pulses == 0) return ITTS_OK;
+  const size_t lds = syn_pulse_lds_bytes(a.p.fft / 2, UNV);
+  ITTS_REQUIRE(lds <= 160 * 1024, "LDS budget exceeded");
+  ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)syn_pulse_kernel<CFFT, UNV>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)lds));
+  hipLaunchKernelGGL((syn_pulse_kernel<CFFT, UNV>), dim3((unsigned)n_pulses), dim3(NT), lds, s, a);
+  ITTS_LAUNCH_CHECK();
+  return ITTS_OK;
+}
 
 // spectra_ready / ap_ready: events behind which d_sp / d_ap are complete (or null: it is, on `stream`).  Everything up
 // to the pulse kernels -- the per-sample phase, the pulse positions, the noise -- reads d_f0 only (a third of a 16 kHz
@@ -1336,24 +1303,11 @@ static int world_synthesize_impl(const double* d_f0, const double* d_sp, const d
     const int64_t n_unv = *h_totals[0], n_voi = *h_totals[1];
     ITTS_REQUIRE(n_unv >= 0 && n_voi >= 0 && n_unv + n_voi <= y_total, "corrupt pulse count");
     if (spectra_ready) ITTS_HIP_CHECK(hipStreamWaitEvent(s, spectra_ready, 0));
-    const bool sized = 2 * h == 2048 && !getenv("ITTS_SYN_GENERIC");
-    for (int kind = 0; kind < 2; ++kind) {
-      const int64_t n_pulses = kind == 0 ? n_unv : n_voi;
-      if (n_pulses == 0) continue;
-      const bool unv = kind == 0;
-      const size_t lds = syn_pulse_lds_bytes(h, unv);
-      ITTS_REQUIRE(lds <= 160 * 1024, "LDS budget exceeded");
-      const void* kern = sized ? (unv ? (const void*)syn_pulse_kernel<11, true> : (const void*)syn_pulse_kernel<11, false>)
-                               : (unv ? (const void*)syn_pulse_kernel<0, true> : (const void*)syn_pulse_kernel<0, false>);
-      ITTS_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      a.kgpoff = d_kgp + kind * (n_utts + 1);
-      if (!unv && ap_ready) ITTS_HIP_CHECK(hipStreamWaitEvent(s, ap_ready, 0));
-      if (sized && unv) hipLaunchKernelGGL((syn_pulse_kernel<11, true>), dim3((unsigned)n_pulses), dim3(NT), lds, s, a);
-      else if (sized) hipLaunchKernelGGL((syn_pulse_kernel<11, false>), dim3((unsigned)n_pulses), dim3(NT), lds, s, a);
-      else if (unv) hipLaunchKernelGGL((syn_pulse_kernel<0, true>), dim3((unsigned)n_pulses), dim3(NT), lds, s, a);
-      else hipLaunchKernelGGL((syn_pulse_kernel<0, false>), dim3((unsigned)n_pulses), dim3(NT), lds, s, a);
-      ITTS_LAUNCH_CHECK();
-    }
+    const bool sized = 2 * h == 2048;
+    if (int rc = sized ? launch_pulse_kernel<11, true>(a, n_unv, s) : launch_pulse_kernel<0, true>(a, n_unv, s)) return rc;
+    if (n_voi > 0 && ap_ready) ITTS_HIP_CHECK(hipStreamWaitEvent(s, ap_ready, 0));
+    a.kgpoff = d_kgp + (n_utts + 1);
+    if (int rc = sized ? launch_pulse_kernel<11, false>(a, n_voi, s) : launch_pulse_kernel<0, false>(a, n_voi, s)) return rc;
   }
   ITTS_HIP_CHECK(itts::scratch_free(d_dcr, s));
   ITTS_HIP_CHECK(itts::scratch_free(d_kq, s));

@@ -84,6 +84,35 @@ __device__ __forceinline__ double wave_sum_at(double v, int lane) {   // same bu
   return v;
 }
 
+// Lane 0's value in every lane, held in SGPRs.
+__device__ __forceinline__ double bcast0(double v) {
+  const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)u);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(u >> 32));
+  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+
+// The items of a persistent one-wave-per-item kernel, handed out DEAL neighbours at a time behind a counter (zero at
+// launch): `for (WaveDeal<DEAL> d; d.next(counter, total, lane == 0); ++d.g)` visits items d.g, which only grow.
+// Dealt by stride -- item g to wave g mod the number of waves -- such a kernel lasted as long as its last workgroup to
+// START: one that finds its CU taken by the tail of another stream's kernel starts when some workgroup has FINISHED
+// its share, and does its own share behind everybody else's (the pulses: 7.2 instead of 5.4 ms when the two met,
+// profiles/r5ap_timeline_noise_on_side_stream.txt; CheapTrick's frames: 4.42 -> 4.00 ms at 16 kHz).
+template <int DEAL>
+struct WaveDeal {
+  int64_t g = 0, g_end = 0;
+  __device__ __forceinline__ bool next(int* counter, int64_t total, bool lane0) {
+    if (g >= g_end) {
+      int base = 0;
+      if (lane0) base = atomicAdd(counter, DEAL);
+      g = __builtin_amdgcn_readfirstlane(base);
+      if (g >= total) return false;
+      g_end = min(g + (int64_t)DEAL, total);
+    }
+    return true;
+  }
+};
+
 // Utterance of global frame g (off[u] <= g < off[u + 1]) for a WHOLE WAVE asking about the same g (all 64 lanes
 // active): the offsets are compared 64 at a time -- loads that do not depend on each other -- instead of by a
 // binary search, whose eight dependent trips to the cache were 4 us at the start of every frame's life (a third

@@ -455,10 +455,8 @@ __global__ void d4c_nuttall_kernel(int wl, double* __restrict__ nwin) {
   }
 }
 
+constexpr int D4C_OCC = 3;       // workgroups per CU of the three-array form (see AREG above)
 // CFFT: log2 of BOTH transform sizes (fftd = fftl = 2^CFFT: 11 at 16 .. 24 kHz) as a compile-time constant, 0: any sizes.
-#ifndef D4C_OCC
-#define D4C_OCC 3
-#endif
 template <bool AREG, int CFFT = 0>
 __global__ __launch_bounds__(NT, AREG ? 2 : D4C_OCC) void d4c_kernel(D4cArgs a) {
   constexpr int CTS = CFFT ? CFFT - 1 : 0;       // log2 of the twiddle table's size - 1
@@ -851,9 +849,6 @@ extern "C" int itts_d4c(const double* d_x, const int64_t* h_x_off, const double*
                                   (size_t)(hmax + 2 * a.bmax + 2) * 8 + (size_t)(NT + 8) * 8);
   const bool areg = hmax > 1024;            // 4096-point transforms: two bin arrays, see the kernel
   size_t lds = z_bytes + (areg ? 2 : 3) * (size_t)(hmax + 2) * 8 + 32 * 8;
-#if D4C_OCC != 3
-  if (const char* e = getenv("ITTS_D4C_LAB_LDS")) lds = (size_t)atol(e);   // lab only: timing with a smaller claim (results invalid)
-#endif
   ITTS_REQUIRE(lds <= 160 * 1024, "LDS budget exceeded");
   // both transforms of the usual sizes (2048 at 16 .. 24 kHz, 4096 at 44.1 / 48 kHz) have a kernel with the size
   // compiled in (ITTS_D4C_GENERIC=1: the any-size kernel, for the A/B test)

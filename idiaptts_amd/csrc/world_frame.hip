@@ -251,53 +251,28 @@ __global__ __launch_bounds__(NT) void cheaptrick_kernel(FrameArgs a) {
 // The cosines and sines take fastmath.h's short forms directly: their arguments are bounded by
 // 2 pi * 512 * f0 / fs here, far inside the reduction's range, and the out-of-line fallback of
 // cos_mid / sin_mid -- a call the kernel never takes -- would cost the register allocation of the whole kernel.
-#ifndef CTW_THREADS_N
-#define CTW_THREADS_N 512     // eight frames in flight per CU, 218 registers per lane (twelve at 168 spill 49 of them: 5.1 against 4.4 ms)
-#endif
-constexpr int CTW_THREADS = CTW_THREADS_N;
+constexpr int CTW_THREADS = 512;     // eight frames in flight per CU, 218 registers per lane (twelve at 168 spill 49 of them: 5.1 against 4.4 ms)
 // running-sum elements per lane: the smoothing's scratch is the wave's exchange rows (64 * 17 = 1088 doubles at
 // 1024 points, 64 * 33 = 2112 at 2048)
 template <int R> constexpr int ctw_scan() { return wf::lds_bytes<R>() / 8 / 64; }
-
-__device__ __forceinline__ double ct_bcast0(double v) {
-  const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)u);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(u >> 32));
-  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
 
 // TH: threads per workgroup = 64 x frames in flight per CU.  2048-point transforms (R = 16: 44.1 / 48 kHz) hold twice
 // the bins per lane: with eight waves per CU (256 registers) 146 of them live in scratch; four waves per CU (one per
 // SIMD, 256 + 98 registers, no scratch) measured SLOWER (round 5: 3.48 against 3.05 ms for 64 utterances): the second
 // wave of a SIMD covers more than the scratch traffic costs.
-#ifndef CTW_DEAL
-#define CTW_DEAL 2      // frames a wave takes from the counter at a time (0: dealt by stride, as until late in round 5: 4.42 -> 4.00 ms at 16 kHz)
-#endif
+constexpr int CTW_DEAL = 2;      // frames a wave takes from the counter at a time (WaveDeal)
 template <int R, int TH = CTW_THREADS>
 __global__ __launch_bounds__(TH) void cheaptrick_wave_kernel(FrameArgs a, int64_t t_total, int* __restrict__ next) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int FFT = 128 * R, H = 64 * R, K = H + 1, NW = TH / 64, CTW_SCAN = ctw_scan<R>();
+  constexpr int FFT = 128 * R, H = 64 * R, K = H + 1, CTW_SCAN = ctw_scan<R>();
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), l0 = wf::lane_id();
   typename wf::PlanOf<R>::type P;
   wf::table_init<R>(smem, a.g_tw_compact);
   char* rows = smem + wf::table_bytes<R>() + (size_t)wv * wf::lds_bytes<R>();
   wf::plan_init(P, a.g_tw_compact, rows, smem);
   double* S = reinterpret_cast<double*>(rows);       // the exchange rows as 1088 doubles of scratch
-#if CTW_DEAL
-  // frames from a counter, CTW_DEAL neighbours at a time (as the pulses of syn_pulse_wave_kernel)
-  int64_t g = 0, g_end = 0;
-  for (;; ++g) {
-    if (g >= g_end) {
-      int base = 0;
-      if (l0 == 0) base = atomicAdd(next, CTW_DEAL);
-      g = __builtin_amdgcn_readfirstlane(base);
-      if (g >= t_total) break;
-      g_end = min(g + (int64_t)CTW_DEAL, t_total);
-    }
-#else
-  (void)next;
-  for (int64_t g = (int64_t)blockIdx.x * NW + wv; g < t_total; g += (int64_t)gridDim.x * NW) {
-#endif
+  for (WaveDeal<CTW_DEAL> deal; deal.next(next, t_total, l0 == 0); ++deal.g) {
+    const int64_t g = deal.g;
     // opaque per frame: what derives from the lane number, the sampling rate and q1 is a handful of
     // integer and fp64 operations -- hoisted out of the loop it is sixty registers held for the
     // whole kernel
@@ -386,7 +361,7 @@ __global__ __launch_bounds__(TH) void cheaptrick_wave_kernel(FrameArgs a, int64_
     double pw[R], p512;
 #pragma unroll
     for (int q = 0; q < R; ++q) pw[q] = z[q].x * z[q].x + z[q].y * z[q].y;
-    p512 = ct_bcast0(xh.x * xh.x + xh.y * xh.y);
+    p512 = bcast0(xh.x * xh.x + xh.y * xh.y);
     // ---- DC correction (wd::dc_correction): the replica is interpolated from the uncorrected bins
 #pragma unroll
     for (int q = 0; q < R; ++q) S[l + 64 * q] = pw[q];
