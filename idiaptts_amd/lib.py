@@ -131,6 +131,12 @@ _SIGNATURES = {
                                      c_int64, c_int, _P]),
     "itts_vae_kld_workspace_bytes": (c_int64, [c_int64, c_int]),
     "itts_vae_kld": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, c_int, _P, _P, c_int64, _P, c_int64, _P, _P, _P]),
+    "itts_xent_plan": (c_int, [c_int64, c_int, c_int, POINTER(c_int), POINTER(c_int)]),
+    "itts_softmax_xent_workspace_bytes": (c_int64, [c_int64, c_int]),
+    "itts_softmax_xent": (c_int, [_P, c_int64, _P, _P, _P, c_int64, c_int, c_int64, _P, _P, _P, c_int64, _P, _P]),
+    "itts_softmax_xent_strided_workspace_bytes": (c_int64, [c_int, c_int64]),
+    "itts_softmax_xent_strided": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int64, c_int, c_int64, _P, _P, _P, _P, _P]),
+    "itts_class_counts": (c_int, [_P, c_int64, _P, c_int64, c_int, _P, _P, _P, _P]),
     "itts_masked_mse_workspace_bytes": (c_int64, [c_int64, c_int]),
     "itts_masked_mse": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, c_int, c_double, c_float,
                                 _P, _P, c_int64, _P, _P]),

@@ -315,6 +315,61 @@ class VAEKLDFunction(torch.autograd.Function):
         return dmu, dlv, None, None
 
 
+class SoftmaxXentFunction(torch.autograd.Function):
+    """sum_r w[r] cw[t_r] (lse_r - x[r, t_r]) on logits [.., C] with int64 targets [..], or with `elementwise` the
+    weighted per-row values [..] (reduction 'none'); torch.nn.CrossEntropyLoss(reduction='none') with the mask and
+    the reduction folded into w as in WeightedLossFunction.  Loss and gradient come from one launch."""
+
+    @staticmethod
+    def forward(ctx, logits, target, row_weight, class_weight, ignore_index, elementwise):
+        C = logits.shape[-1]
+        x2 = _rows2(logits, C)
+        want_grad = ctx.needs_input_grad[0]         # (validation runs under no_grad: the kernel then writes none)
+        loss, grad, elem = ops.softmax_xent(x2, target.reshape(-1), row_weight, class_weight, ignore_index,
+                                            want_grad=want_grad, want_elem=elementwise)
+        if want_grad:
+            ctx.save_for_backward(grad)
+        ctx.shape, ctx.elementwise = logits.shape, elementwise
+        return elem.reshape(logits.shape[:-1]) if elementwise else loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        (grad,) = ctx.saved_tensors
+        grad = grad.reshape(ctx.shape)
+        if ctx.elementwise:
+            grad = grad * dloss.unsqueeze(-1)
+        elif not is_unit_gradient(dloss):
+            grad = grad * dloss
+        return grad, None, None, None, None, None
+
+
+class SoftmaxXentStridedFunction(torch.autograd.Function):
+    """The same loss on class-strided logits [B, C, T] against a one-hot target of the same shape, input frame t
+    scored against target frame t + shift (loss/OneHotCrossEntropyLoss.py:16-30); the per-frame values are
+    [B, T - shift].  The shift is applied by offsets inside the kernel: no sliced copy."""
+
+    @staticmethod
+    def forward(ctx, logits, onehot, row_weight, class_weight, ignore_index, shift, elementwise):
+        want_grad = ctx.needs_input_grad[0]
+        loss, grad, elem = ops.softmax_xent_strided(logits, onehot, row_weight, class_weight, ignore_index, shift,
+                                                    want_grad=want_grad, want_elem=elementwise)
+        if want_grad:
+            ctx.save_for_backward(grad)
+        ctx.elementwise, ctx.shift = elementwise, int(shift or 0)
+        return elem if elementwise else loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        (grad,) = ctx.saved_tensors
+        if ctx.elementwise:
+            if ctx.shift:                            # [B, T - shift] -> [B, 1, T]: the last frames have no loss
+                dloss = torch.nn.functional.pad(dloss, (0, ctx.shift))
+            grad = grad * dloss.unsqueeze(1)
+        elif not is_unit_gradient(dloss):
+            grad = grad * dloss
+        return grad, None, None, None, None, None, None
+
+
 class grad_scaling(torch.autograd.Function):
     """Identity whose gradient is multiplied by a constant (reference GradientScaling.py: grad_scaling)."""
 

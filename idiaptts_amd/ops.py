@@ -1110,6 +1110,126 @@ def vae_kld(mu, log_var, row_weight, want_grad=True, want_elem=False, dmu=None, 
     return loss, dmu, dlv, elem
 
 
+XENT_ROWS, XENT_STRIDED = 0, 1      # ITTS_XENT_* in include/idiaptts_amd.h
+XENT_LAYOUTS = {"rows": XENT_ROWS, "strided": XENT_STRIDED, XENT_ROWS: XENT_ROWS, XENT_STRIDED: XENT_STRIDED}
+XENT_MAX_CLASSES = 4096
+CONF_MAX_CLASSES = 1024
+
+
+def xent_plan(N, C, layout="rows"):
+    """(lanes a row, steps of 4 * lanes columns) of a softmax cross-entropy call (itts_xent_plan; no device work):
+    class-contiguous rows ("rows") share 1, 2, 4 .. 64 lanes, the smallest power of two with 4 * lanes >= C, and
+    take 2 .. 16 steps from C = 257 on; the class-strided layout ("strided") reports (4, ceil(C / 4)): the waves
+    that share a frame and the classes each of them takes (kept in registers up to 64, read again above)."""
+    L = _lib.load()
+    if layout not in XENT_LAYOUTS:
+        raise ValueError("unknown layout {!r}".format(layout))
+    lanes, steps = ctypes.c_int(0), ctypes.c_int(0)
+    if L.itts_xent_plan(int(N), int(C), XENT_LAYOUTS[layout], ctypes.byref(lanes), ctypes.byref(steps)) != 0:
+        raise ValueError("no cross-entropy plan for N={}, C={}".format(N, C))
+    return lanes.value, steps.value
+
+
+def _xent_common(class_weight, row_weight, C, n_rows):
+    _need(row_weight, torch.float32, "row_weight")
+    if row_weight.numel() != n_rows:
+        raise ValueError("row_weight has {} entries for {} rows".format(row_weight.numel(), n_rows))
+    if class_weight is not None:
+        _need(class_weight, torch.float32, "class_weight")
+        if class_weight.numel() != C:
+            raise ValueError("class_weight has {} entries for {} classes".format(class_weight.numel(), C))
+        class_weight = class_weight.reshape(-1).contiguous()
+    return class_weight, row_weight.reshape(-1).contiguous()
+
+
+def softmax_xent(x, target, row_weight, class_weight=None, ignore_index=-100, want_grad=True, want_elem=False,
+                 grad=None):
+    """Row-weighted softmax cross-entropy of class-contiguous logits x [N, C] (contiguous rows, any pitch) with
+    int64 targets [N] (itts_softmax_xent): (loss [1] = sum_r w[r] l_r, grad [N, C] or None, w[r] l_r [N] or None)."""
+    L = _lib.load()
+    _need(x, torch.float32, "x")
+    _need(target, torch.int64, "target")
+    N, C = x.shape
+    if target.numel() != N:
+        raise ValueError("target has {} entries for {} rows".format(target.numel(), N))
+    class_weight, row_weight = _xent_common(class_weight, row_weight, C, N)
+    loss = torch.empty((1,), dtype=torch.float32, device=x.device)
+    if want_grad and grad is None:
+        grad = torch.empty((N, C), dtype=torch.float32, device=x.device)
+    if not want_grad:
+        grad = None
+    if grad is not None:
+        _need(grad, torch.float32, "grad")
+        if grad.shape != x.shape:
+            raise ValueError("grad must have the shape of x")
+    elem = torch.empty((N,), dtype=torch.float32, device=x.device) if want_elem else None
+    ws = torch.empty(max(L.itts_softmax_xent_workspace_bytes(N, C), 8), dtype=torch.uint8, device=x.device)
+    _lib.check(L.itts_softmax_xent(_ptr(x), _rows(x, "x"), _ptr(target.reshape(-1).contiguous()), _ptr(class_weight),
+                                   _ptr(row_weight), N, C, int(ignore_index), _ptr(loss), _ptr(elem), _ptr(grad),
+                                   _rows(grad, "grad") if grad is not None else 0, _ptr(ws), _stream()),
+               "itts_softmax_xent")
+    return loss, grad, elem
+
+
+def softmax_xent_strided(x, onehot, row_weight, class_weight=None, ignore_index=-100, shift=None, want_grad=True,
+                         want_elem=False):
+    """The same loss on class-strided logits x [B, C, T] (contiguous) with a one-hot target of the same shape
+    (itts_softmax_xent_strided; loss/OneHotCrossEntropyLoss.py): frame t of the input is scored against the arg-max
+    of onehot[:, :, t + shift]; row_weight and the per-frame values are [B, T - shift], grad is [B, C, T]."""
+    L = _lib.load()
+    _need(x, torch.float32, "x")
+    _need(onehot, torch.float32, "onehot")
+    if x.dim() != 3 or onehot.shape != x.shape:
+        raise ValueError("x and onehot must both be [B, C, T], got {} and {}".format(tuple(x.shape),
+                                                                                   tuple(onehot.shape)))
+    x, onehot = x.contiguous(), onehot.contiguous()
+    B, C, T = x.shape
+    shift = int(shift or 0)
+    if B > 0 and not 0 <= shift < max(T, 1):
+        raise ValueError("shift = {} is outside 0 .. T - 1 = {}".format(shift, T - 1))
+    Tn = T - shift
+    class_weight, row_weight = _xent_common(class_weight, row_weight, C, B * Tn)
+    loss = torch.empty((1,), dtype=torch.float32, device=x.device)
+    grad = torch.empty((B, C, T), dtype=torch.float32, device=x.device) if want_grad else None
+    elem = torch.empty((B, Tn), dtype=torch.float32, device=x.device) if want_elem else None
+    ws = torch.empty(max(L.itts_softmax_xent_strided_workspace_bytes(B, T), 8), dtype=torch.uint8, device=x.device)
+    _lib.check(L.itts_softmax_xent_strided(_ptr(x), _ptr(onehot), _ptr(class_weight), _ptr(row_weight), B, C, T,
+                                           shift, int(ignore_index), _ptr(loss), _ptr(elem), _ptr(grad), _ptr(ws),
+                                           _stream()), "itts_softmax_xent_strided")
+    return loss, grad, elem
+
+
+def class_counts(x, target=None, want_pred=True, correct=None, conf=None):
+    """Arg-max over the classes of x [N, C] with torch.argmax's order (itts_class_counts): (pred [N] int64 or None,
+    correct [1] int64, conf [C, C] int64).  `correct` and `conf` (rows = true class) are ADDED to when given, fresh
+    zeros otherwise; without `target` only the predictions are made and both come back as None."""
+    L = _lib.load()
+    _need(x, torch.float32, "x")
+    N, C = x.shape
+    pred = torch.empty((N,), dtype=torch.int64, device=x.device) if want_pred else None
+    if target is None:
+        correct = conf = None
+    else:
+        _need(target, torch.int64, "target")
+        if target.numel() != N:
+            raise ValueError("target has {} entries for {} rows".format(target.numel(), N))
+        target = target.reshape(-1).contiguous()
+        if C > CONF_MAX_CLASSES and conf is None:
+            raise ValueError("a confusion matrix of C = {} classes exceeds the {} it takes".format(
+                C, CONF_MAX_CLASSES))
+        if correct is None:
+            correct = torch.zeros((1,), dtype=torch.int64, device=x.device)
+        if conf is None:
+            conf = torch.zeros((C, C), dtype=torch.int64, device=x.device)
+        for name, t, shape in (("correct", correct, (1,)), ("conf", conf, (C, C))):
+            _need(t, torch.int64, name)
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError("{} must be a contiguous int64 {}".format(name, shape))
+    _lib.check(L.itts_class_counts(_ptr(x), _rows(x, "x"), _ptr(target), N, C, _ptr(pred), _ptr(correct), _ptr(conf),
+                                   _stream()), "itts_class_counts")
+    return pred, correct, conf
+
+
 def weighted_loss(pred, target, row_weight, kind, want_grad=True, want_elem=False):
     """sum_r w[r] sum_c e(pred - target) on [M, D] rows, e squared (kind 0) / absolute (kind 1)
     error: (loss [1], grad or None, elementwise values or None)."""

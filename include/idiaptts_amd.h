@@ -577,6 +577,55 @@ int itts_vae_kld(const float* d_mu, int64_t ldmu, const float* d_lv, int64_t ldl
                  float* d_loss, float* d_dmu, int64_t lddmu, float* d_dlv, int64_t lddlv, float* d_elem,
                  void* d_workspace, void* stream);
 
+/* ---- classification: softmax cross-entropy and accuracy counts (csrc/xent.hip) ------------------------------
+ * Row-weighted softmax cross-entropy, loss and gradient from one call.  Per row r with target t_r, m = max_c x[r,c]:
+ *   lse = m + log(sum_c exp(x[r,c] - m)),   l_r = cw[t_r] * (lse - x[r,t_r]),
+ *   d_loss[0] = sum_r w[r] l_r,   d_elem[r] = w[r] l_r (or NULL),
+ *   d_grad[r,c] = w[r] cw[t_r] (softmax_c - [c == t_r]) (or NULL: evaluation).
+ * d_cw [C] are the class weights (NULL: ones), d_w [N] the row weights: the sequence mask and the reduction, as
+ * for itts_weighted_loss and itts_vae_kld.  A row whose target is ignore_index has loss 0 and gradient 0.  A target
+ * outside [0, C) that is not ignore_index is never used as an index: the row's loss is NaN (d_loss too) and its
+ * gradient row zeros.  Rows of weight 0 may hold anything (bad targets, non-finite logits): they are not read and
+ * contribute exactly 0.  A row's results depend on the row alone -- the same bits for any N, any row index and either
+ * load form (16-byte loads when pitches are multiples of 4 floats and bases 16-byte aligned); the row losses are
+ * added in double through d_workspace in one fixed order by a second launch: repeated calls give identical bits.
+ * C is 1 .. 4096; everything else is refused (ITTS_E_INVALID, the message names the value) before any device work;
+ * N == 0 (B == 0) succeeds and writes loss 0.
+ *
+ * itts_softmax_xent: class-contiguous rows d_x [N, C] with pitch ld >= C, int64 targets [N], d_grad with pitch ldg.
+ * A row is shared by 1, 2, 4 .. 64 lanes (the smallest power of two with 4 * lanes >= C), from C = 257 on in
+ * 2, 4, 8 or 16 steps of 256 columns; itts_xent_plan reports (lanes, steps) without device work, for the strided
+ * layout (4, ceil(C / 4)): the waves that share a frame and the classes of each (kept in registers up to 64); it returns -1 for what the entry points refuse; either output may be NULL.
+ * Reference: torch.nn.CrossEntropyLoss(reduction='none') under loss/NamedLoss.py:77-104 (squeeze_inputs, mask) and
+ * :113-131 (_reduce).
+ *
+ * itts_softmax_xent_strided: class-strided d_x [B, C, T] contiguous (class c of frame (b, t) at b*C*T + c*T + t),
+ * lanes along t, a frame's classes shared by the four waves of a workgroup.  The target of frame t is the arg-max over c of d_onehot (same layout) at frame t + shift, the
+ * lowest index among equal maxima; the loss has T - shift frames per batch entry: d_w and d_elem are
+ * [B, T - shift], d_grad is [B, C, T] and every element of it is written (zeros for t >= T - shift).
+ * 0 <= shift < T.  d_workspace >= itts_softmax_xent_strided_workspace_bytes(B, T).
+ * Reference: loss/OneHotCrossEntropyLoss.py:16-30.
+ *
+ * itts_class_counts: per row of d_x [N, C] (pitch ld) the arg-max over the classes with torch.argmax's order (the
+ * lowest index among equal maxima, the first NaN if there is one).  Each output may be NULL: d_pred [N] int64;
+ * d_correct[0] += rows with pred == target; d_conf [C, C] int64, [target, pred] += 1 -- both ADD to what is
+ * there, so an epoch sums its batches (integer atomics: the order cannot change the sums).  Rows whose target lies
+ * outside [0, C) are counted nowhere.  d_conf takes at most 1024 classes.
+ * Reference: loss/UnWeightedAccuracy.py:20-35, model_trainers/ClassificationTrainer.py:34-59. */
+#define ITTS_XENT_ROWS 0
+#define ITTS_XENT_STRIDED 1
+int itts_xent_plan(int64_t N, int C, int layout, int* lanes, int* steps);
+int64_t itts_softmax_xent_workspace_bytes(int64_t N, int C);
+int itts_softmax_xent(const float* d_x, int64_t ld, const int64_t* d_target, const float* d_cw, const float* d_w,
+                      int64_t N, int C, int64_t ignore_index, float* d_loss, float* d_elem, float* d_grad,
+                      int64_t ldg, void* d_workspace, void* stream);
+int64_t itts_softmax_xent_strided_workspace_bytes(int B, int64_t T);
+int itts_softmax_xent_strided(const float* d_x, const float* d_onehot, const float* d_cw, const float* d_w, int B,
+                              int C, int64_t T, int shift, int64_t ignore_index, float* d_loss, float* d_elem,
+                              float* d_grad, void* d_workspace, void* stream);
+int itts_class_counts(const float* d_x, int64_t ld, const int64_t* d_target, int64_t N, int C, int64_t* d_pred,
+                      int64_t* d_correct, int64_t* d_conf, void* stream);
+
 /* ---- masked MSE, reduction 'mean_per_frame' (loss/NamedLoss.py:70-117) -------------------- */
 /*
  * loss = mean_d( sum_{valid frames} (pred-target)^2 / n_valid ), grad = dloss/dpred.
