@@ -200,6 +200,12 @@ _SIGNATURES = {
                                          _P]),
     "itts_loudness_normalise_batch": (c_int, [_P, POINTER(c_int64), c_int, c_double, _P, _P]),
     "itts_frame_rms_batch": (c_int, [_P, POINTER(c_int64), POINTER(c_int64), c_int, c_int, c_int, c_int, _P, _P]),
+    "itts_mol_loss_workspace_bytes": (c_int64, [c_int, c_int64]),
+    "itts_mol_loss": (c_int, [_P, _P, _P, c_int, c_int, c_int64, c_int, c_int, c_double, c_int, _P, _P, _P, _P, _P]),
+    "itts_mulaw_encode_f64": (c_int, [_P, POINTER(c_int64), c_int, c_int, _P, _P]),
+    "itts_mulaw_decode": (c_int, [_P, POINTER(c_int64), c_int, c_int, _P, _P]),
+    "itts_mulaw_onehot": (c_int, [_P, POINTER(c_int64), POINTER(c_int64), c_int, c_int, _P, _P]),
+    "itts_sample_linearly": (c_int, [_P, c_int, POINTER(c_int64), c_int, c_int, c_int, _P, c_int, _P]),
 }
 
 

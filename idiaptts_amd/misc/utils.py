@@ -61,3 +61,67 @@ def interpolate_lin(data):
 def compute_deltas(labels):
     """np.gradient along time, float32 (reference: misc/utils.py:103-105)."""
     return np.gradient(labels, axis=0).astype(dtype=np.float32)
+
+
+def _multiplier(in_to_out_multiplier):
+    if in_to_out_multiplier < 1:
+        raise NotImplementedError("sample_linearly with in_to_out_multiplier = {} < 1 (down-sampling) is not "
+                                  "implemented, as in the reference.".format(in_to_out_multiplier))
+    return int(in_to_out_multiplier)          # (truncated, as the reference's int(...))
+
+
+def sample_linearly_batch(samples, in_to_out_multiplier, dtype=np.float32):
+    """`sample_linearly` of a list of [T_s, D] arrays (numpy, or float32 / float64 tensors on the device) from one
+    launch of itts_sample_linearly: a list of device tensors [m * T_s, D] of `dtype` (views of one buffer).  The
+    conditioning features of a sample-level vocoder go through this to reach the sample rate
+    (reference WaveNetVocoderTrainer.py:141-173)."""
+    import torch
+    from idiaptts_amd import lib, ops
+    m = _multiplier(in_to_out_multiplier)
+    out_dtype = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}.get(np.dtype(dtype))
+    if out_dtype is None:
+        raise NotImplementedError("sample_linearly to dtype {} is not implemented (float32, float64).".format(dtype))
+    if len(samples) == 0:
+        return []
+    rows = []
+    for n, s in enumerate(samples):
+        t = s if torch.is_tensor(s) else torch.from_numpy(np.ascontiguousarray(s))
+        if not t.is_floating_point():
+            t = t.double()                    # (interp1d takes integers as float64)
+        if t.dim() == 1:
+            t = t.unsqueeze(-1)
+        if t.dim() != 2:
+            raise ValueError("sample {} must be [T, D], got {}.".format(n, tuple(t.shape)))
+        if t.shape[0] < 2:
+            raise ValueError("sample {} has T = {} frame(s): linear interpolation needs at least 2 (scipy's interp1d "
+                             "gives NaN for a single point).".format(n, t.shape[0]))
+        if t.shape[1] != (rows[0].shape[1] if rows else t.shape[1]):
+            raise ValueError("sample {} has {} features, sample 0 has {}.".format(n, t.shape[1], rows[0].shape[1]))
+        rows.append(t)
+    lib.require_gpu()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    in_dtype = torch.float64 if any(t.dtype == torch.float64 for t in rows) else torch.float32
+    x = torch.cat([t.to(device=dev, dtype=in_dtype) for t in rows], dim=0)
+    offsets = [0]
+    for t in rows:
+        offsets.append(offsets[-1] + t.shape[0])
+    if m == 1:
+        y, out_off = x.to(out_dtype), offsets
+    else:
+        y, out_off = ops.sample_linearly(x, offsets, m, out_dtype)
+    return [y[out_off[s]:out_off[s + 1]] for s in range(len(rows))]
+
+
+def sample_linearly(sample, in_to_out_multiplier, dtype=np.float32):
+    """[T, D] -> [m T, D] at x_new = linspace(0, T - 1, m T), m = int(in_to_out_multiplier), interpolated linearly
+    in float64 and cast to dtype (reference: misc/utils.py:89-100, on scipy's interp1d); numpy in, numpy out, through
+    the same kernel as `sample_linearly_batch`.  A multiplier of 1 returns the input itself, one below 1 raises
+    NotImplementedError, as there.  T = 1 is refused by name: interp1d returns NaN for it."""
+    m = _multiplier(in_to_out_multiplier)
+    if not in_to_out_multiplier > 1:
+        return sample
+    if m == 1:                                  # (1 < multiplier < 2: linspace with T points is the input's own grid)
+        return np.array(sample, dtype=dtype)
+    sample = np.asarray(sample)
+    out = sample_linearly_batch([sample], m, dtype)[0].cpu().numpy()
+    return out.reshape((out.shape[0],) + sample.shape[1:])

@@ -370,6 +370,33 @@ class SoftmaxXentStridedFunction(torch.autograd.Function):
         return grad, None, None, None, None, None, None
 
 
+class MolLossFunction(torch.autograd.Function):
+    """Discretized mixture-of-logistics loss of x [B, 3K, T] against y [B, 1, T], input frame t scored against
+    target frame t + shift (loss/DiscretizedMixturelogisticLoss.py): sum of the weighted per-frame values
+    [B, T - shift], or with `elementwise` the values themselves.  Loss and gradient come from one launch."""
+
+    @staticmethod
+    def forward(ctx, x, y, row_weight, num_classes, log_scale_min, shift, hinge, elementwise):
+        want_grad = ctx.needs_input_grad[0]
+        loss, grad, elem = ops.mol_loss(x, y, row_weight, num_classes, log_scale_min, shift, hinge,
+                                        want_grad=want_grad, want_elem=elementwise)
+        if want_grad:
+            ctx.save_for_backward(grad)
+        ctx.elementwise, ctx.shift = elementwise, int(shift or 0)
+        return elem if elementwise else loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        (grad,) = ctx.saved_tensors
+        if ctx.elementwise:
+            if ctx.shift:                            # [B, T - shift] -> [B, 1, T]: the last frames have no loss
+                dloss = torch.nn.functional.pad(dloss, (0, ctx.shift))
+            grad = grad * dloss.unsqueeze(1)
+        elif not is_unit_gradient(dloss):
+            grad = grad * dloss
+        return grad, None, None, None, None, None, None, None
+
+
 class grad_scaling(torch.autograd.Function):
     """Identity whose gradient is multiplied by a constant (reference GradientScaling.py: grad_scaling)."""
 

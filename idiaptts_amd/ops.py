@@ -1721,3 +1721,125 @@ def frame_rms(x, offsets, frame_length, hop, pad_mode="constant"):
                                       len(offsets) - 1, int(frame_length), int(hop), RMS_PAD[pad_mode], _ptr(rms),
                                       _stream()), "itts_frame_rms_batch")
     return rms, f_off
+
+
+# ----------------------------------------------------------------------------- raw-waveform targets
+MOL_MAX_MIXTURES = 64            # MOL_MAX_K of csrc/mol.hip
+MULAW_MAX_MU = 65535
+
+
+def mol_loss(x, y, row_weight, num_classes=256, log_scale_min=-7.0, shift=None, hinge=True, want_grad=True,
+             want_elem=False):
+    """Discretized mixture-of-logistics loss of x [B, 3K, T] (logits, means, log-scales; contiguous float32) against
+    the targets y [B, 1, T] in [-1, 1] (itts_mol_loss; loss/DiscretizedMixturelogisticLoss.py): frame t of the input
+    is scored against y[t + shift]; row_weight and the per-frame values are [B, T - shift], grad is [B, 3K, T].
+    Returns (loss [1] = sum w l, grad or None, w l or None)."""
+    L = _lib.load()
+    _need(x, torch.float32, "x")
+    _need(y, torch.float32, "y")
+    if x.dim() != 3:
+        raise ValueError("x must be [B, 3K, T], got {}".format(tuple(x.shape)))
+    B, C, T = x.shape
+    if C % 3 != 0:
+        raise ValueError("C = {} channels is no multiple of 3 (logits, means, log-scales)".format(C))
+    if y.numel() != B * T:
+        raise ValueError("y must be [B, 1, T] = [{}, 1, {}], got {}".format(B, T, tuple(y.shape)))
+    x, y = x.contiguous(), y.reshape(B, T).contiguous()
+    shift = int(shift or 0)
+    if B > 0 and not 0 <= shift < max(T, 1):
+        raise ValueError("shift = {} is outside 0 .. T - 1 = {}".format(shift, T - 1))
+    Tn = T - shift
+    _need(row_weight, torch.float32, "row_weight")
+    if row_weight.numel() != B * Tn:
+        raise ValueError("row_weight has {} entries for {} rows".format(row_weight.numel(), B * Tn))
+    row_weight = row_weight.reshape(-1).contiguous()
+    loss = torch.empty((1,), dtype=torch.float32, device=x.device)
+    grad = torch.empty((B, C, T), dtype=torch.float32, device=x.device) if want_grad else None
+    elem = torch.empty((B, Tn), dtype=torch.float32, device=x.device) if want_elem else None
+    ws = torch.empty(max(L.itts_mol_loss_workspace_bytes(B, T), 8), dtype=torch.uint8, device=x.device)
+    _lib.check(L.itts_mol_loss(_ptr(x), _ptr(y), _ptr(row_weight), B, C // 3, T, shift, int(num_classes),
+                               float(log_scale_min), int(bool(hinge)), _ptr(loss), _ptr(elem), _ptr(grad), _ptr(ws),
+                               _stream()), "itts_mol_loss")
+    return loss, grad, elem
+
+
+def _signal_offsets(offsets, total, name):
+    offsets = [int(o) for o in offsets]
+    if len(offsets) < 1 or offsets[0] != 0 or offsets[-1] != total:
+        raise ValueError("offsets must run from 0 to the {} values of {}, got {} .. {}".format(
+            total, name, offsets[0] if offsets else None, offsets[-1] if offsets else None))
+    return offsets
+
+
+def mulaw_encode(x, offsets, mu=255):
+    """RawWaveformLabelGen.mu_law_companding of every float64 signal x[offsets[s]:offsets[s + 1]]: int64 indices in
+    [0, mu], truncated toward zero (itts_mulaw_encode_f64)."""
+    L = _lib.load()
+    _need(x, torch.float64, "x")
+    x = x.reshape(-1).contiguous()
+    offsets = _signal_offsets(offsets, x.numel(), "x")
+    out = torch.empty(x.shape, dtype=torch.int64, device=x.device)
+    _lib.check(L.itts_mulaw_encode_f64(_ptr(x), _lib.offsets_array(offsets), len(offsets) - 1, int(mu), _ptr(out),
+                                       _stream()), "itts_mulaw_encode_f64")
+    return out
+
+
+def mulaw_decode(index, offsets, mu=255):
+    """RawWaveformLabelGen.mu_law_companding_reversed of int64 indices: float64 (itts_mulaw_decode)."""
+    L = _lib.load()
+    _need(index, torch.int64, "index")
+    index = index.reshape(-1).contiguous()
+    offsets = _signal_offsets(offsets, index.numel(), "index")
+    out = torch.empty(index.shape, dtype=torch.float64, device=index.device)
+    _lib.check(L.itts_mulaw_decode(_ptr(index), _lib.offsets_array(offsets), len(offsets) - 1, int(mu), _ptr(out),
+                                   _stream()), "itts_mulaw_decode")
+    return out
+
+
+def mulaw_onehot(x, begins, lengths, mu=255, out=None):
+    """The [n, mu + 1] float32 one-hot targets of every float64 signal x[begins[s]:begins[s] + lengths[s]], back to
+    back, from one launch (itts_mulaw_onehot).  Returns (onehot [sum(lengths), mu + 1], row offsets)."""
+    L = _lib.load()
+    _need(x, torch.float64, "x")
+    x = x.reshape(-1).contiguous()
+    begins, lengths = [int(b) for b in begins], [int(n) for n in lengths]
+    if len(begins) != len(lengths):
+        raise ValueError("{} begins for {} lengths".format(len(begins), len(lengths)))
+    out_off = [0]
+    for s, (b, n) in enumerate(zip(begins, lengths)):
+        if b < 0 or n < 0 or b + n > x.numel():
+            raise ValueError("signal {} = x[{}:{}] lies outside the {} samples of x".format(s, b, b + n, x.numel()))
+        out_off.append(out_off[-1] + n)
+    if not 1 <= int(mu) <= MULAW_MAX_MU:
+        raise ValueError("mu = {} is outside 1 .. {}".format(mu, MULAW_MAX_MU))
+    if out is None:
+        out = torch.empty((out_off[-1], int(mu) + 1), dtype=torch.float32, device=x.device)
+    _need(out, torch.float32, "out")
+    if tuple(out.shape) != (out_off[-1], int(mu) + 1) or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 [{}, {}]".format(out_off[-1], int(mu) + 1))
+    if begins:
+        _lib.check(L.itts_mulaw_onehot(_ptr(x), _lib.offsets_array(begins), _lib.offsets_array(out_off), len(begins),
+                                       int(mu), _ptr(out), _stream()), "itts_mulaw_onehot")
+    return out, out_off
+
+
+def sample_linearly(x, offsets, m, dtype=torch.float32):
+    """misc.utils.sample_linearly of every signal x[offsets[s]:offsets[s + 1]] (rows of D float32 / float64 values):
+    [T, D] becomes [m T, D] at linspace(0, T - 1, m T), interpolated in float64 and stored as `dtype`
+    (itts_sample_linearly).  Returns (y [m * rows, D], output offsets)."""
+    L = _lib.load()
+    if x.dtype not in (torch.float32, torch.float64):
+        raise TypeError("x must be float32 or float64, got {}".format(x.dtype))
+    if dtype not in (torch.float32, torch.float64):
+        raise TypeError("dtype must be float32 or float64, got {}".format(dtype))
+    _need(x, x.dtype, "x")
+    if x.dim() != 2:
+        raise ValueError("x must be [rows, D], got {}".format(tuple(x.shape)))
+    x = x.contiguous()
+    offsets = _signal_offsets(offsets, x.shape[0], "x")
+    m = int(m)
+    y = torch.empty((x.shape[0] * m, x.shape[1]), dtype=dtype, device=x.device)
+    _lib.check(L.itts_sample_linearly(_ptr(x), int(x.dtype == torch.float64), _lib.offsets_array(offsets),
+                                      len(offsets) - 1, x.shape[1], m, _ptr(y), int(dtype == torch.float64),
+                                      _stream()), "itts_sample_linearly")
+    return y, [o * m for o in offsets]

@@ -1,5 +1,5 @@
-"""Synthesiser.run_world_synth and run_griffin_lim with the reference's interface (idiaptts/src/Synthesiser.py:38-106,
-:320-351).
+"""Synthesiser.run_world_synth, run_griffin_lim and run_raw_synth with the reference's interface
+(idiaptts/src/Synthesiser.py:38-106, :155-179, :320-351).
 
 The reference walks the utterances one by one (decode_sp -> world_features_to_raw -> write);
 here all utterances of the call are decoded (mgc2sp, or the mel inversion kernel for sp_type "mfbanks"),
@@ -130,6 +130,50 @@ class Synthesiser(object):
             Synthesiser.raw_to_file(os.path.join(save_dir, file_name), raw, fs, bit_depth)
         if return_waveforms:
             return dict(zip(ids, waveforms))
+
+    @staticmethod
+    def copy_synth(hparams, file_id_list, epoch=None, step=None, feature_dir=None):
+        """Reference audio of synth_vocoder "raw" (reference :155-165): every file of file_id_list (paths of wav
+        files) is loaded with RawWaveformLabelGen.load_sample(id_name, hparams.frame_rate_output_Hz) and written
+        back with the suffix "_ref", without the model name; the suffix of hparams is restored afterwards.  The other
+        vocoders copy-synthesise from a trainer's data readers (ModularTrainer.copy_synth)."""
+        if hparams.synth_vocoder != "raw":
+            raise NotImplementedError("Synthesiser.copy_synth is implemented for synth_vocoder \"raw\", not {}: use "
+                                      "the trainer's copy_synth.".format(hparams.synth_vocoder))
+        from .data_preparation.audio.RawWaveformLabelGen import RawWaveformLabelGen
+        logging.info("Copy synthesis with {} for [{}].".format(hparams.synth_vocoder, ", ".join(file_id_list)))
+        synth_dict = {id_name: RawWaveformLabelGen.load_sample(id_name, _get(hparams, "frame_rate_output_Hz", None))
+                      for id_name in file_id_list}
+        old_synth_file_suffix = getattr(hparams, "synth_file_suffix", "")
+        hparams.synth_file_suffix = "_ref"
+        try:
+            Synthesiser.run_raw_synth(synth_dict, hparams, epoch=epoch, step=step, use_model_name=False)
+        finally:
+            hparams.synth_file_suffix = old_synth_file_suffix
+
+    @staticmethod
+    def raw_file_name(id_name, hparams, use_model_name=True):
+        """<basename>[_<model_name>]<synth_file_suffix>.<synth_ext>"""
+        return "{}{}{}.{}".format(os.path.basename(id_name).rsplit('.', 1)[0],
+                                  "_" + hparams.model_name if use_model_name else "",
+                                  getattr(hparams, "synth_file_suffix", ""), hparams.synth_ext)
+
+    @staticmethod
+    def run_raw_synth(synth_output: Dict[str, np.ndarray], hparams, epoch: int = None, step: int = None,
+                      use_model_name: bool = True):
+        """Write the raw waveforms in synth_output (id -> samples in [-1, 1]) with raw_to_file (reference :167-179),
+        to <basename>[_<model_name>]<synth_file_suffix>.<synth_ext>.  That is the name the reference intends: its
+        expression at :174-177 has a precedence slip (the conditional swallows everything after "_" + model_name, so
+        with use_model_name the suffix is lost and without it the basename is) and a stray comma that makes the name
+        a tuple, which os.path.join refuses.  Only wav output is supported."""
+        if getattr(hparams, "synth_ext", "wav").lower() != "wav":
+            raise NotImplementedError("Only wav output is supported (pydub is out of scope).")
+        save_dir = Synthesiser._get_synth_dir(hparams, use_model_name, epoch=epoch, step=step)
+        bit_depth = _get(hparams, "bit_depth", 16)
+        for id_name, raw in synth_output.items():
+            file_name = Synthesiser.raw_file_name(id_name, hparams, use_model_name)
+            Synthesiser.raw_to_file(os.path.join(save_dir, file_name), np.asarray(raw).reshape(-1), hparams.synth_fs,
+                                    bit_depth)
 
     @staticmethod
     def raw_to_file(file_path, raw, fs, bit_depth=16):

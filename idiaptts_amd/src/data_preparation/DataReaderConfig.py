@@ -46,6 +46,10 @@ class DataReaderConfig(object):
             from idiaptts_amd.src.data_preparation.phonemes.PhonemeDurationLabelGen import \
                 PhonemeDurationLabelGen
             return PhonemeDurationLabelGen
+        if self.type == "RawWaveformLabelGen":
+            from idiaptts_amd.src.data_preparation.audio.RawWaveformLabelGen import \
+                RawWaveformLabelGen
+            return RawWaveformLabelGen
         raise NotImplementedError("Unknown data reader type {}.".format(self.type))
 
     def create_reader(self):

@@ -559,7 +559,7 @@ class ModularTrainer(object):
     # ------------------------------------------------------------------------------ waveforms
     def gen_waveform(self, id_list, data, hparams, use_model_name=True, has_deltas=False):
         """reference :1014-1085; the WORLD and Griffin-Lim ("GL", "GL_on_log") vocoders are on the accelerated
-        path."""
+        path, "raw" writes the waveforms it is given."""
         if type(next(iter(data.values()))) is dict:
             if hparams.has_value("synth_feature_names"):
                 feature_names = hparams.synth_feature_names
@@ -575,6 +575,11 @@ class ModularTrainer(object):
         if hparams.synth_vocoder == "GL":
             Synthesiser.run_griffin_lim(data, hparams, epoch=self.total_epoch, step=self.total_steps)
             return
+        if hparams.synth_vocoder == "raw":
+            # (the features in the data dictionary are raw waveforms and are written to the files as they are)
+            Synthesiser.run_raw_synth(data, hparams, epoch=self.total_epoch, step=self.total_steps,
+                                      use_model_name=use_model_name)
+            return
         if hparams.synth_vocoder != "WORLD":
             raise NotImplementedError("Unknown vocoder type {}.".format(hparams.synth_vocoder))
         return Synthesiser.run_world_synth(data, hparams, use_model_name=use_model_name,
@@ -589,7 +594,11 @@ class ModularTrainer(object):
 
     def copy_synth(self, hparams, id_list):
         """Vocoder round trip of the stored (un-normalised) features, written with the suffix
-        `_ref` (reference :1093-1119)."""
+        `_ref` (reference :1093-1119).  With synth_vocoder "raw" the ids are wav files, copied by
+        Synthesiser.copy_synth."""
+        if hparams.synth_vocoder == "raw":
+            return Synthesiser.copy_synth(hparams, self._input_to_str_list(id_list), epoch=self.total_epoch,
+                                          step=self.total_steps)
         assert hparams.has_value("synth_feature_names"), \
             "hparams.synth_feature_names has to be given."
         feature_names = hparams.synth_feature_names

@@ -10,6 +10,8 @@ squeeze_inputs), "OneHotCrossEntropyLoss" ([B, C, T] logits against a one-hot ta
 score without gradient) -- run on csrc/xent.hip: softmax, loss and gradient from one launch, the mask and the
 reduction again one weight per row.  Their keyword arguments are torch's `weight` and `ignore_index` (plus `shift` /
 `num_per_class` of the reference's two classes); a non-zero `label_smoothing` and anything else is refused by name.
+"DiscretizedMixturelogisticLoss" ([B, 3K, T] mixture parameters against samples [B, 1, T]; keywords `num_classes`,
+`log_scale_min`, `shift`, `hinge_loss`) runs on csrc/mol.hip in the same way.
 CPU tensors of these types go through torch."""
 import torch
 from torch import nn
@@ -17,6 +19,7 @@ from torch import nn
 from idiaptts_amd import ops
 from idiaptts_amd.nn.functional import SoftmaxXentFunction, is_unit_gradient
 
+from .DiscretizedMixturelogisticLoss import DiscretizedMixturelogisticLoss
 from .OneHotCrossEntropyLoss import OneHotCrossEntropyLoss
 from .UnWeightedAccuracy import UnWeightedAccuracy
 
@@ -104,17 +107,20 @@ class NamedLoss(nn.Module):
             return NamedLoss(self)
 
     KINDS = {"MSELoss": 0, "L1Loss": 1}
-    CLASS_TYPES = ("CrossEntropyLoss", "OneHotCrossEntropyLoss", "UnWeightedAccuracy")
+    CLASS_TYPES = ("CrossEntropyLoss", "OneHotCrossEntropyLoss", "UnWeightedAccuracy",
+                   "DiscretizedMixturelogisticLoss")
     CLASS_KWARGS = {"CrossEntropyLoss": ("weight", "ignore_index", "label_smoothing"),
                     "OneHotCrossEntropyLoss": ("weight", "ignore_index", "label_smoothing", "shift"),
-                    "UnWeightedAccuracy": ("num_per_class",)}
+                    "UnWeightedAccuracy": ("num_per_class",),
+                    "DiscretizedMixturelogisticLoss": ("num_classes", "log_scale_min", "shift", "hinge_loss")}
     REDUCTIONS = ("mean_per_frame", "mean_per_sample", "mean", "sum", "none")
 
     def __init__(self, config):
         super().__init__()
         if config.type not in self.KINDS and config.type not in self.CLASS_TYPES:
             raise NotImplementedError("Loss type {} has no kernel here (element-wise MSELoss and L1Loss, "
-                                      "CrossEntropyLoss, OneHotCrossEntropyLoss and UnWeightedAccuracy do)."
+                                      "CrossEntropyLoss, OneHotCrossEntropyLoss, UnWeightedAccuracy and "
+                                      "DiscretizedMixturelogisticLoss do)."
                                       .format(config.type))
         if config.reduction not in self.REDUCTIONS:
             raise NotImplementedError("Unknown reduction type {}.".format(config.reduction))
@@ -172,6 +178,14 @@ class NamedLoss(nn.Module):
         if len(config.input_names) != 2:
             raise ValueError("{} takes input_names = [prediction, target], got {}."
                              .format(config.type, config.input_names))
+        if config.type == "DiscretizedMixturelogisticLoss":
+            for key in ("num_classes", "log_scale_min"):
+                if key not in kwargs:
+                    raise ValueError("DiscretizedMixturelogisticLoss needs {}.".format(key))
+            self.loss_fn = DiscretizedMixturelogisticLoss(kwargs["num_classes"], kwargs["log_scale_min"],
+                                                          shift=kwargs.get("shift", 1),
+                                                          hinge_loss=kwargs.get("hinge_loss", True))
+            return
         if config.type == "UnWeightedAccuracy":
             if "num_per_class" not in kwargs:
                 raise ValueError("UnWeightedAccuracy needs num_per_class.")
@@ -257,6 +271,17 @@ class NamedLoss(nn.Module):
             shift = self.loss_fn.shift or 0
             if shift >= T:
                 raise ValueError("shift = {} leaves no frame of T = {}.".format(shift, T))
+            w = self._class_row_weight((B, T - shift), mask, length_dict, pred.device)
+            if pred.is_cuda:
+                loss = self.loss_fn.frame_losses(pred, target, w, elementwise)
+            else:
+                loss = self.loss_fn(pred, target)[..., 0] * w.reshape(B, T - shift)
+                loss = loss if elementwise else loss.sum()
+            if elementwise:
+                loss = loss.unsqueeze(-1)
+        elif self.type == "DiscretizedMixturelogisticLoss":
+            shift = self.loss_fn._check(pred, target)
+            B, _, T = pred.shape
             w = self._class_row_weight((B, T - shift), mask, length_dict, pred.device)
             if pred.is_cuda:
                 loss = self.loss_fn.frame_losses(pred, target, w, elementwise)

@@ -950,6 +950,54 @@ int itts_loudness_normalise_batch(const double* d_x, const int64_t* h_offsets, i
 int itts_frame_rms_batch(const double* d_x, const int64_t* h_offsets, const int64_t* h_frame_offsets, int n_signals,
                          int frame_length, int hop, int pad_mode, double* d_rms, void* stream);
 
+/* ---- raw-waveform targets (csrc/mol.hip): the discretized mixture-of-logistics loss of a 16-bit sample-level
+ *      vocoder, the mu-law reader behind the one-hot loss, and the linear up-sampling of conditioning features.
+ *
+ * itts_mol_loss: loss/DiscretizedMixturelogisticLoss.py:23-136, loss and gradient from one launch.  d_x [B, 3K, T]
+ * contiguous float32 (channels 0 .. K mixture logits, K .. 2K means, 2K .. 3K log-scales), d_y [B, 1, T] targets in
+ * [-1, 1]; lanes run along t; frame t of the input is scored against y[t + shift], so the loss has T - shift frames
+ * per batch entry: d_w (row weights: mask and reduction) and d_elem (w l, or NULL) are [B, T - shift], d_grad (or NULL)
+ * is [B, 3K, T] and every element of it is written (zeros for t >= T - shift and for rows of weight 0).  Per frame and
+ * mixture, with s = max(log-scale, log_scale_min), h = 1 / (num_classes - 1), u = e^-s (y - mean + h),
+ * v = e^-s (y - mean - h), m = e^-s (y - mean):
+ *   y < -0.999: log sigmoid(u);   y > 0.999: log(1 - sigmoid(v));   else with
+ *   delta = sigmoid(u) - sigmoid(v) = sigmoid(u) sigmoid(-v) (1 - e^-(2 h e^-s)) (no cancellation):
+ *   delta > 1e-5: log delta;   else m - s - 2 softplus(m) - log((num_classes - 1) / 2);
+ * plus log_softmax of the logits; l = -logsumexp over the K mixtures, with hinge != 0 plus
+ * sum_k max(0, -log-scale_k - log(num_classes)) on the UNCLAMPED log-scales (:124-132).  The gradient is autograd's
+ * of exactly this: the selected branch only, nothing through the clamp below log_scale_min,
+ * softmax(logit) - responsibility on the logits, -1 from an active hinge term.  d_loss[0] = sum w l, added in double
+ * through d_workspace (>= itts_mol_loss_workspace_bytes(B, T)) by a second launch in a fixed order: repeated calls
+ * give identical bits; a frame's results depend on that frame alone (any B, any position); rows of weight 0 are never
+ * read and contribute exactly 0.  No float atomics.  B == 0 succeeds with loss 0.  K outside 1 .. 64, num_classes < 2,
+ * shift outside 0 .. T - 1 and T < 1 are refused (ITTS_E_INVALID, the message names the value) before any device work.
+ *
+ * The three below take a batch of signals back to back behind host offsets, as the audio preparation does; a
+ * signal's values do not depend on its place in the batch; n_signals == 0 succeeds and does nothing.
+ * itts_mulaw_encode_f64: RawWaveformLabelGen.py:164-167, float64 in, int64 index out:
+ *   trunc((sign(x) log(1 + mu |x|) / log(1 + mu) + 1) mu / 2), mu 1 .. 65535.
+ * itts_mulaw_decode: :169-173, int64 index in, float64 out: r = i / (mu / 2) - 1, sign(r) / mu ((1 + mu)^|r| - 1).
+ * itts_mulaw_onehot: the [n, mu + 1] float32 one-hot targets of :92-94 from the float64 signals in one launch;
+ *   signal s reads d_x[h_begin[s] ..] (after the silence trim) and fills the rows h_out_offsets[s] ..
+ *   h_out_offsets[s + 1] of d_onehot, every element of them written.
+ * itts_sample_linearly: misc/utils.py:89-100, [T, D] rows to [m T, D] at linspace(0, T - 1, m T), interpolated as
+ *   scipy's interp1d does it -- the slope y_hi - y_lo in the input's precision, slope (x - lo) + y_lo in float64 --
+ *   and stored as float32 (out_f64 == 0) or float64; in_f64 says which the input is.  Signal s has
+ *   h_offsets[s + 1] - h_offsets[s] >= 2 rows of D values and fills the rows m h_offsets[s] .. of d_y; m >= 1, D >= 1.
+ *   The first and the last output row are the input's. */
+int64_t itts_mol_loss_workspace_bytes(int B, int64_t T);
+int itts_mol_loss(const float* d_x, const float* d_y, const float* d_w, int B, int K, int64_t T, int shift,
+                  int num_classes, double log_scale_min, int hinge, float* d_loss, float* d_elem, float* d_grad,
+                  void* d_workspace, void* stream);
+int itts_mulaw_encode_f64(const double* d_x, const int64_t* h_offsets, int n_signals, int mu, int64_t* d_index,
+                          void* stream);
+int itts_mulaw_decode(const int64_t* d_index, const int64_t* h_offsets, int n_signals, int mu, double* d_y,
+                      void* stream);
+int itts_mulaw_onehot(const double* d_x, const int64_t* h_begin, const int64_t* h_out_offsets, int n_signals, int mu,
+                      float* d_onehot, void* stream);
+int itts_sample_linearly(const void* d_x, int in_f64, const int64_t* h_offsets, int n_signals, int D, int m,
+                         void* d_y, int out_f64, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
