@@ -1,0 +1,280 @@
+// First dense layer on a sparse input for gfx950.  Layer 0 of the acoustic model reads min-max-normalised question
+// vectors: binary answers plus a few numeric columns, 7-10 % non-zeros, and (x - min) / range keeps a zero an exact
+// zero.  The dense product multiplies by those zeros; here every row of x becomes a list of its (k, value) pairs once
+// per batch (sparse_rows_build_kernel), and the forward product walks the lists against a slab of w^T held in LDS
+// (sparse_linear_fwd_kernel): per non-zero one 16-byte LDS read and four fmaf give four outputs.
+//   * roofline: instruction issue.  A list slot of four rows costs a wave about seven instructions (two DPP
+//     broadcasts, the slab address, a ds_read_b128, two packed fmaf and its share of the loads and loop), and the
+//     walk runs to the longest of four lists; the LDS reads themselves (nnz x N x 4 bytes at 256 B/clk/CU) take
+//     under a fifth of the kernel's time.
+#include <algorithm>
+#include <atomic>
+#include <utility>
+
+#include "activations.h"
+#include "common.h"
+
+namespace itts {
+
+constexpr int kSparseMaxK = 512;      // the LDS slab holds (K + 1) x 64 floats: 131 KB of the CU's 160 KB
+constexpr int kSlabCols = 64;         // output columns of a workgroup
+constexpr int kFwdWaves = 16;         // one workgroup per CU (LDS), four waves per SIMD
+constexpr int kRowsPerWave = 4;       // a quarter wave per row: 16 lanes x 4 columns
+constexpr int kStep = 8;              // list slots per trip of the walk; the build pads every list to whole trips
+constexpr int kFetch = 16;            // list entries per load: one per lane of a quarter wave
+
+static std::atomic<int64_t> g_sparse_path[3];
+
+struct ListLayout {
+  int64_t counts_off, entries_off, pitch, bytes;
+};
+
+static ListLayout list_layout(int64_t M, int K) {
+  ListLayout l;
+  l.counts_off = 16;
+  l.entries_off = 16 + (M * 4 + 15) / 16 * 16;
+  l.pitch = ((int64_t)K + kFetch - 1) / kFetch * kFetch;   // a load of the walk never leaves its row
+  l.bytes = l.entries_off + M * l.pitch * 8;
+  return l;
+}
+
+// One wave per row, 256 columns per trip: the four loads of a trip go out together, then each 64-column group
+// appends its non-zeros behind the ones before it (ballot + prefix count: ascending k without any sorting).  Behind
+// the row's count the list is filled up to a multiple of kStep with neutral entries (k = K, value +0): the forward
+// walk takes kStep slots per trip and needs no mask inside one, its slab has an all-zero row K.
+__global__ __launch_bounds__(256) void sparse_rows_build_kernel(const uint32_t* __restrict__ x, int64_t ldx, int64_t M,
+                                                                int K, int* __restrict__ counts,
+                                                                int2* __restrict__ entries, int64_t pitch,
+                                                                unsigned long long* __restrict__ record) {
+  const int lane = threadIdx.x & 63;
+  const int64_t w0 = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), wn = (int64_t)gridDim.x * 4;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  unsigned long long total = 0, most = 0;
+  for (int64_t m = w0; m < M; m += wn) {
+    const uint32_t* row = x + m * ldx;
+    int2* out = entries + m * pitch;
+    int cnt = 0;
+    for (int k0 = 0; k0 < K; k0 += 256) {
+      uint32_t bits[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int k = k0 + 64 * u + lane;
+        bits[u] = k < K ? row[k] : 0u;
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const bool nz = (bits[u] & 0x7fffffffu) != 0u;   // +-0.0 out; NaN and denormals stay (no float compare)
+        const unsigned long long mask = __ballot(nz);
+        if (nz) out[cnt + __popcll(mask & below)] = make_int2(k0 + 64 * u + lane, (int)bits[u]);
+        cnt += __popcll(mask);
+      }
+    }
+    if (lane < ((kStep - cnt % kStep) % kStep)) out[cnt + lane] = make_int2(K, 0);   // neutral up to a whole trip
+    if (lane == 0) counts[m] = cnt;
+    total += (unsigned long long)cnt;
+    most = std::max(most, (unsigned long long)cnt);
+  }
+  if (record && lane == 0 && total) {
+    atomicAdd(&record[0], total);
+    atomicMax(&record[1], most);
+  }
+}
+
+// Slot J of the 16 list entries a quarter wave holds, entry j in its lane j: the DPP row broadcast hands lane J's
+// (k, value) to the quarter's 16 lanes, which read their 16 bytes of slab row k and do four fmaf (two packed ones).
+template <int J>
+__device__ __forceinline__ void walk_slot(const float4* slab4, int i16, int2 e, float4& acc) {
+  const int k = __builtin_amdgcn_update_dpp(0, e.x, 0x150 + J, 0xf, 0xf, false);   // row_newbcast:J
+  const float v = __int_as_float(__builtin_amdgcn_update_dpp(0, e.y, 0x150 + J, 0xf, 0xf, false));
+  const float4 wk = slab4[k * (kSlabCols / 4) + i16];
+  acc.x = fmaf(v, wk.x, acc.x); acc.y = fmaf(v, wk.y, acc.y);
+  acc.z = fmaf(v, wk.z, acc.z); acc.w = fmaf(v, wk.w, acc.w);
+}
+template <int FIRST, int... U>
+__device__ __forceinline__ void walk_trip(const float4* slab4, int i16, int2 e, float4& acc,
+                                          std::integer_sequence<int, U...>) {
+  (walk_slot<FIRST + U>(slab4, i16, e, acc), ...);
+}
+
+// Workgroup = (64-column slab of w^T in LDS, row range); wave = four rows at a time, one per quarter wave; lane = four
+// adjacent output columns of its quarter's row.  A quarter reads 16 entries of its row's list per load, entry j into
+// lane j, and a DPP row broadcast hands entry j to its 16 lanes when slot j's turn comes, so k and the value sit in
+// VGPRs and nothing has to be made wave-uniform (with every lane loading the entry itself the vector memory path
+// moves 16 times the bytes and sets the kernel's time).  Per list slot a lane forms the slab address, reads 16 bytes
+// and does four fmaf (two packed ones).  The neutral entries that fill a list's last trip read the slab's extra
+// all-zero row K with a zero value: acc + 0 * 0.  The slab's rows are 64 floats apart, so the four rows a
+// ds_read_b128 touches all start on bank 0 and every 16 lanes the hardware serves together cover the 64 banks once,
+// whatever the four k are.  The walk runs to the longest of the four lists in trips of kStep slots, its loads one
+// fetch of kFetch entries ahead, and a quarter whose list has ended sits the trips out; the first fetch and the
+// counts of the next four rows are requested before the current rows are walked.  One fmaf chain per output, in
+// ascending k, from +0; the bias is added last.
+// (A list entry with k > K would read LDS out of range, which returns zeros; the lists come from the build.)
+template <int AF>
+__global__ __launch_bounds__(kFwdWaves * 64) void sparse_linear_fwd_kernel(
+    const int* __restrict__ counts, const int2* __restrict__ entries, int64_t pitch, const float* __restrict__ w,
+    const float* __restrict__ bias, float* __restrict__ y, int64_t ldy, int64_t M, int N, int K, int act, int ranges,
+    int store_cols, int wide_out) {
+  extern __shared__ float4 slab4[];   // [K + 1][16] float4
+  float* slab = reinterpret_cast<float*>(slab4);
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int n0 = (int)(blockIdx.x / ranges) * kSlabCols;
+  const int range = (int)(blockIdx.x % ranges);
+  const int64_t per = (M + ranges - 1) / ranges;
+  const int64_t m_begin = range * per, m_end = std::min<int64_t>(M, m_begin + per);
+  const int q = lane >> 4, c4 = (lane & 15) * 4;   // this lane's row of the group and its first column in the slab
+
+  // slab[k][c] = w[n0 + c][k]: a lane per column, the waves take turns at k (each lane walks along its own row of w,
+  // whose cache lines the other waves' turns reuse)
+  {
+    const bool col_ok = n0 + lane < N;
+    const float* wr = w + (int64_t)(col_ok ? n0 + lane : 0) * K;
+    for (int k = wave; k < K; k += kFwdWaves) slab[k * kSlabCols + lane] = col_ok ? wr[k] : 0.f;
+    if (wave == 0) slab[K * kSlabCols + lane] = 0.f;
+  }
+
+  // rows behind the range re-read the last row and are never used: no branch around a load
+  auto row_of = [&](int64_t group) { return m_begin + (group * kRowsPerWave + q); };
+  const int i16 = lane & 15;
+  auto fetch = [&](int64_t m, int j0) { return entries[std::min<int64_t>(m, M - 1) * pitch + (j0 + i16)]; };
+  int64_t group = wave;
+  int2 first = fetch(row_of(group), 0);
+  int cnt_next = counts[std::min<int64_t>(row_of(group), M - 1)];
+  __syncthreads();
+
+  float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
+  const int n = n0 + c4;
+  if (bias) {
+    if (n < N) bv.x = bias[n];
+    if (n + 1 < N) bv.y = bias[n + 1];
+    if (n + 2 < N) bv.z = bias[n + 2];
+    if (n + 3 < N) bv.w = bias[n + 3];
+  }
+  const bool vec_store = wide_out && n + 4 <= store_cols;
+  const int last_fetch = (int)pitch - kFetch;
+
+  for (; m_begin + group * kRowsPerWave < m_end; group += kFwdWaves) {
+    const int64_t m = row_of(group);
+    const int cnt = m < m_end ? cnt_next : 0;
+    int2 cur = first;
+    first = fetch(row_of(group + kFwdWaves), 0);
+    cnt_next = counts[std::min<int64_t>(row_of(group + kFwdWaves), M - 1)];
+    int longest = std::max(cnt, __shfl_xor(cnt, 16, 64));
+    longest = __builtin_amdgcn_readfirstlane(std::max(longest, __shfl_xor(longest, 32, 64)));
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    // a quarter whose list has ended sits the trips out (the loads stay outside the branch and inside the row)
+    for (int j0 = 0; j0 < longest; j0 += kFetch) {
+      const int2 nxt = fetch(m, std::min(j0 + kFetch, last_fetch));
+      if (j0 < cnt) walk_trip<0>(slab4, i16, cur, acc, std::make_integer_sequence<int, kStep>());
+      if (j0 + kStep < cnt) walk_trip<kStep>(slab4, i16, cur, acc, std::make_integer_sequence<int, kStep>());
+      cur = nxt;
+    }
+    if (m < m_end) {
+      float4 o;
+      o.x = n < N ? act_fwd_af<AF>(acc.x + bv.x, act) : 0.f;
+      o.y = n + 1 < N ? act_fwd_af<AF>(acc.y + bv.y, act) : 0.f;
+      o.z = n + 2 < N ? act_fwd_af<AF>(acc.z + bv.z, act) : 0.f;
+      o.w = n + 3 < N ? act_fwd_af<AF>(acc.w + bv.w, act) : 0.f;
+      float* yr = y + m * ldy + n;
+      if (vec_store) {
+        *reinterpret_cast<float4*>(yr) = o;
+      } else {
+        if (n < store_cols) yr[0] = o.x;
+        if (n + 1 < store_cols) yr[1] = o.y;
+        if (n + 2 < store_cols) yr[2] = o.z;
+        if (n + 3 < store_cols) yr[3] = o.w;
+      }
+    }
+  }
+}
+
+}  // namespace itts
+
+using namespace itts;
+
+extern "C" int itts_sparse_rows_layout(int64_t M, int K, int64_t out[4]) {
+  ITTS_REQUIRE(out != nullptr, "null pointer");
+  ITTS_REQUIRE(M >= 0 && K > 0 && K <= 65535, "bad sizes (K <= 65535)");
+  const ListLayout l = list_layout(M, K);
+  out[0] = l.counts_off; out[1] = l.entries_off; out[2] = l.pitch; out[3] = l.bytes;
+  return ITTS_OK;
+}
+
+extern "C" int itts_sparse_rows_build(const float* d_x, int64_t ldx, int64_t M, int K, void* d_lists, int want_record,
+                                      void* stream) {
+  ITTS_REQUIRE(d_lists && (M == 0 || d_x), "null pointer");
+  ITTS_REQUIRE(M >= 0 && K > 0 && K <= 65535 && ldx >= K, "bad sizes (K <= 65535)");
+  ITTS_REQUIRE(aligned16(d_lists), "the list block must be 16-byte aligned");
+  hipStream_t s = as_stream(stream);
+  char* base = static_cast<char*>(d_lists);
+  if (want_record) ITTS_HIP_CHECK(hipMemsetAsync(base, 0, 16, s));
+  if (M == 0) return ITTS_OK;
+  const ListLayout l = list_layout(M, K);
+  const unsigned grid = (unsigned)std::min<int64_t>((M + 3) / 4, 8192);
+  hipLaunchKernelGGL(sparse_rows_build_kernel, dim3(grid), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(d_x), ldx,
+                     M, K, reinterpret_cast<int*>(base + l.counts_off), reinterpret_cast<int2*>(base + l.entries_off),
+                     l.pitch, want_record ? reinterpret_cast<unsigned long long*>(base) : nullptr);
+  ITTS_LAUNCH_CHECK();
+  g_sparse_path[0].fetch_add(1, std::memory_order_relaxed);
+  return ITTS_OK;
+}
+
+static int fwd_compute_units() {
+  static int cus = 0;
+  if (cus == 0) {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+      n = 256;
+    cus = n;
+  }
+  return cus;
+}
+
+template <int AF>
+static int launch_sparse_fwd(const void* d_lists, const float* d_w, const float* d_b, float* d_y, int64_t ldy, int64_t M,
+                             int N, int K, int act, hipStream_t s) {
+  static bool lds_set = false;
+  if (!lds_set) {
+    ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)sparse_linear_fwd_kernel<AF>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (kSparseMaxK + 1) * kSlabCols * 4));
+    lds_set = true;
+  }
+  const ListLayout l = list_layout(M, K);
+  const char* base = static_cast<const char*>(d_lists);
+  const int slabs = (N + kSlabCols - 1) / kSlabCols;
+  // one workgroup per CU where the shape allows it; a range is worth its slab fill from about 64 rows on
+  const int64_t ranges = std::max<int64_t>(1, std::min<int64_t>(fwd_compute_units() / slabs, (M + 63) / 64));
+  // the pad columns inside a 16-byte row pitch are written as zeros, as the dense epilogue does
+  const bool wide_out = (ldy % 4 == 0) && aligned16(d_y);
+  const int store_cols = wide_out ? (int)std::min<int64_t>((N + 3) / 4 * 4, ldy) : N;
+  hipLaunchKernelGGL(sparse_linear_fwd_kernel<AF>, dim3((unsigned)(slabs * ranges)), dim3(kFwdWaves * 64),
+                     (size_t)(K + 1) * kSlabCols * 4, s, reinterpret_cast<const int*>(base + l.counts_off),
+                     reinterpret_cast<const int2*>(base + l.entries_off), l.pitch, d_w, d_b, d_y, ldy, M, N, K, act,
+                     (int)ranges, store_cols, wide_out ? 1 : 0);
+  ITTS_LAUNCH_CHECK();
+  return ITTS_OK;
+}
+
+extern "C" int itts_linear_fwd_sparse(const void* d_lists, const float* d_x, int64_t ldx, const float* d_w,
+                                      const float* d_b, float* d_y, int64_t ldy, int64_t M, int N, int K, int act,
+                                      void* stream) {
+  ITTS_REQUIRE(d_w && (M == 0 || (d_lists && d_x && d_y)), "null pointer");
+  ITTS_REQUIRE(M >= 0 && N > 0 && K > 0 && K <= 65535 && ldx >= K && ldy >= N, "bad sizes");
+  ITTS_REQUIRE(act >= ITTS_ACT_NONE && act <= ITTS_ACT_HARDSIGMOID, "unknown activation");
+  if (M == 0) return ITTS_OK;
+  if (K > kSparseMaxK) {   // the slab does not fit: the dense product, decided from the shape alone
+    g_sparse_path[2].fetch_add(1, std::memory_order_relaxed);
+    return itts_linear_fwd(d_x, ldx, d_w, d_b, d_y, ldy, M, N, K, act, stream);
+  }
+  g_sparse_path[1].fetch_add(1, std::memory_order_relaxed);
+  if (act_family(act) == AF_EXT) return launch_sparse_fwd<AF_EXT>(d_lists, d_w, d_b, d_y, ldy, M, N, K, act, as_stream(stream));
+  return launch_sparse_fwd<AF_BASE>(d_lists, d_w, d_b, d_y, ldy, M, N, K, act, as_stream(stream));
+}
+
+extern "C" int itts_sparse_path_counts(int64_t out[3]) {
+  ITTS_REQUIRE(out != nullptr, "null pointer");
+  for (int i = 0; i < 3; ++i) out[i] = g_sparse_path[i].load(std::memory_order_relaxed);
+  return ITTS_OK;
+}

@@ -98,6 +98,10 @@ _SIGNATURES = {
     "itts_linear_fwd_mse_workspace_bytes": (c_int64, [c_int64, c_int]),
     "itts_linear_fwd_mse": (c_int, [_P, c_int64, _P, _P, _P, c_int64, _P, c_double, c_float, c_int64,
                                     c_int, c_int, _P, _P, c_int64, _P, _P]),
+    "itts_sparse_rows_layout": (c_int, [c_int64, c_int, POINTER(c_int64)]),
+    "itts_sparse_rows_build": (c_int, [_P, c_int64, c_int64, c_int, _P, c_int, _P]),
+    "itts_linear_fwd_sparse": (c_int, [_P, _P, c_int64, _P, _P, _P, c_int64, c_int64, c_int, c_int, c_int, _P]),
+    "itts_sparse_path_counts": (c_int, [POINTER(c_int64)]),
     "itts_act_bwd": (c_int, [_P, _P, _P, c_int64, c_int, _P]),
     "itts_linear_bwd_input": (c_int, [_P, c_int64, _P, _P, c_int64, _P, c_int64, c_int, c_int64,
                                       c_int, c_int, _P]),

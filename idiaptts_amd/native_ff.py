@@ -26,12 +26,24 @@ def _pad4(n):
     return (n + 3) // 4 * 4
 
 
+# Largest share of non-zeros in the first batch's input at which sparse_input=None takes the row-list path for
+# layer 0's forward product.  From the density sweep at the bench shape in DESIGN.md section 21 (list build + sparse
+# forward against the dense forward launch, kernel time): 0.69 of the dense time at 10 % non-zeros, 1.02 at 20 %,
+# equal at 19 % by interpolation; the constant stays a little below that.
+SPARSE_INPUT_MAX_DENSITY = 0.18
+
+
 class FlatFFModel:
     """Dense stack dims[0] -> dims[1] -> ... with activations `acts` (one per layer: a name of ops.ACT_BY_NAME in
-    any case, e.g. "tanh" / "Sigmoid", an ops.ACT_* code, or None)."""
+    any case, e.g. "tanh" / "Sigmoid", an ops.ACT_* code, or None).
+
+    sparse_input: True / False sends layer 0's forward product of a training step through the row lists of its
+    input (ops.sparse_rows_build + ops.linear_fwd_sparse) / through the dense product.  None decides once, at the
+    first loss_and_backward, from the density of that batch (one host synchronisation in the model's life) and keeps
+    the decision: a later dense batch is slower on the sparse path, never wrong."""
 
     def __init__(self, dims=(425, 512, 512, 187), acts=("tanh", "tanh", None), device="cuda",
-                 seed=0, state_dict=None):
+                 seed=0, state_dict=None, sparse_input=None):
         assert len(acts) == len(dims) - 1
         self.dims = tuple(int(d) for d in dims)
         self.acts = [ops.act_code(a) for a in acts]
@@ -56,6 +68,8 @@ class FlatFFModel:
         self.exp_avg_sq = torch.zeros_like(self.params)
         self.step_count = 0
         self._buffers = {}
+        self.sparse_input = None if sparse_input is None else bool(sparse_input)
+        self._lists = None        # the row lists of the current batch: the model's own storage
         if state_dict is None:
             state_dict = self.reference_init(self.dims, seed)
         self.load_layers(state_dict)
@@ -153,16 +167,26 @@ class FlatFFModel:
             self._buffers[name] = buf
         return buf[:M, :width]
 
-    def forward(self, x, n_layers=None):
-        """x [M, dims[0]] fp32 packed frames -> list of layer outputs (of the first n_layers)."""
+    def forward(self, x, n_layers=None, sparse=False):
+        """x [M, dims[0]] fp32 packed frames -> list of layer outputs (of the first n_layers).  sparse: layer 0
+        walks the row lists of x, built here, instead of the dense product."""
         acts = []
         h = self.pack_input(x)
         M = h.shape[0]
         for i in range(len(self.layout) if n_layers is None else n_layers):
-            h = ops.linear_fwd(h, self.weight_padded(i), self.bias(i), self.acts[i],
-                               out=self._rows_buffer("h%d" % i, M, self.layout[i][2]))
+            out = self._rows_buffer("h%d" % i, M, self.layout[i][2])
+            if i == 0 and sparse:
+                self._lists = ops.sparse_rows_build(h, lists=self._lists, want_record=False)
+                h = ops.linear_fwd_sparse(self._lists, h, self.weight_padded(i), self.bias(i), self.acts[i], out=out)
+            else:
+                h = ops.linear_fwd(h, self.weight_padded(i), self.bias(i), self.acts[i], out=out)
             acts.append(h)
         return acts
+
+    def _decide_sparse_input(self, x):
+        """sparse_input=None: the density of this (the first) batch against the measured crossover."""
+        self._lists = ops.sparse_rows_build(x, lists=self._lists, want_record=True)
+        self.sparse_input = self._lists.density() <= SPARSE_INPUT_MAX_DENSITY
 
     def loss_and_backward(self, x, target, row_valid, n_valid_global, reduce_group=None, reduce=False):
         """Fills self.grads with d(loss)/d(params) of this rank's frames; returns loss tensor
@@ -172,6 +196,8 @@ class FlatFFModel:
         and the handles are left in self._pending for train_step to wait on before Adam."""
         self._pending = []
         x = self.pack_input(x)
+        if self.sparse_input is None:
+            self._decide_sparse_input(x)
         if reduce:
             return self._loss_and_backward(x, target, row_valid, n_valid_global, reduce_group, reduce)
         # one process: the loss sum and the layers' split-K slab reductions are queued and run as ONE
@@ -186,13 +212,13 @@ class FlatFFModel:
         if self.acts[-1] in (None, ops.ACT_NONE) and n > 1:
             # the output layer never materialises: its GEMM epilogue forms the masked difference
             # to the target, the loss partial sums and d loss / d output
-            hs = self.forward(x, n_layers=n - 1)
+            hs = self.forward(x, n_layers=n - 1, sparse=bool(self.sparse_input))
             loss, dz = ops.linear_fwd_mse(hs[-1], self.weight_padded(n - 1), self.bias(n - 1), target,
                                           row_valid, n_valid_global,
                                           grad=self._rows_buffer("dz_out", M, self.dims[-1]))
             hs.append(None)
         else:
-            hs = self.forward(x)
+            hs = self.forward(x, sparse=bool(self.sparse_input))
             loss, dz = ops.masked_mse(hs[-1], target, row_valid, n_valid_global,
                                       grad=self._rows_buffer("dz_out", M, self.dims[-1]))
             if self.acts[-1] != ops.ACT_NONE:

@@ -394,6 +394,86 @@ def linear_fwd(x, w, b, act=ACT_NONE, out=None):
     return out
 
 
+class SparseRows(object):
+    """Row lists of a sparse [M, K] matrix (itts_sparse_rows_build): per row the (k, value) pairs of its non-zeros
+    in ascending k, in one device block that the caller owns (it must live as long as the lists are used, so it
+    is never the shared workspace).  A block is reused for any shape it is large enough for."""
+
+    def __init__(self, M, K, device, block=None):
+        out = (ctypes.c_int64 * 4)()
+        _lib.check(_lib.load().itts_sparse_rows_layout(M, K, out), "itts_sparse_rows_layout")
+        self.M, self.K = int(M), int(K)
+        self._counts_off, self._entries_off, self.pitch, self.nbytes = (int(v) for v in out)
+        if block is None or block.numel() < self.nbytes:
+            block = torch.empty(self.nbytes, dtype=torch.uint8, device=device)
+        self.block = block
+
+    def counts(self):
+        """int32 [M]: non-zeros per row"""
+        return self.block[self._counts_off:self._counts_off + 4 * self.M].view(torch.int32)
+
+    def entries(self):
+        """int32 [M, pitch, 2]: (k, bits of the float32 value); row m holds counts()[m] of them, then neutral (K, +0.0)
+        entries up to the next multiple of 8, then nothing defined"""
+        n = 8 * self.M * self.pitch
+        return self.block[self._entries_off:self._entries_off + n].view(torch.int32).view(self.M, self.pitch, 2)
+
+    def record(self):
+        """(total non-zeros, largest count of a row) of a build with want_record=True; reads the device (one
+        synchronisation)"""
+        total, most = self.block[:16].view(torch.int64).tolist()
+        return total, most
+
+    def density(self):
+        return self.record()[0] / float(max(self.M * self.K, 1))
+
+
+def sparse_rows_build(x, K=None, lists=None, want_record=True):
+    """Row lists of the first K (default: all) columns of x [M, >= K] fp32; `lists`: a SparseRows whose block is
+    reused when it is large enough."""
+    _need(x, torch.float32, "x")
+    ldx = _rows(x, "x")
+    M = x.shape[0]
+    K = x.shape[1] if K is None else int(K)
+    if K > x.shape[1]:
+        raise ValueError("K exceeds the width of x")
+    rows = SparseRows(M, K, x.device, lists.block if lists is not None else None)
+    _lib.check(_lib.load().itts_sparse_rows_build(_ptr(x), ldx, M, K, _ptr(rows.block), 1 if want_record else 0,
+                                                  _stream()), "itts_sparse_rows_build")
+    return rows
+
+
+def linear_fwd_sparse(rows, x, w, b, act=ACT_NONE, out=None):
+    """ops.linear_fwd(x, w, b, act) through the row lists `rows` built from x (one fmaf chain per output over the
+    row's non-zeros in ascending k); x itself is read only where the shape sends the call to the dense product
+    (K > 512)."""
+    L = _lib.load()
+    _need(x, torch.float32, "x")
+    _need(w, torch.float32, "w")
+    M, K = x.shape
+    N = w.shape[0]
+    if w.shape[1] != K or not w.is_contiguous():
+        raise ValueError("w must be contiguous [N, K]")
+    if rows.M != M or rows.K != K:
+        raise ValueError("the row lists were built for another shape")
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=x.device)
+    _lib.check(L.itts_linear_fwd_sparse(_ptr(rows.block), _ptr(x), _rows(x, "x"), _ptr(w), _ptr(b), _ptr(out),
+                                        _rows(out, "out"), M, N, K, act, _stream()), "itts_linear_fwd_sparse")
+    return out
+
+
+SparsePathCounts = collections.namedtuple("SparsePathCounts", "builds fwd_sparse fwd_dense")
+
+
+def sparse_path_counts():
+    """How the sparse-input entry points of this process went so far (itts_sparse_path_counts; no device call): list
+    builds, linear_fwd_sparse calls that ran the sparse kernel, and those that ran the dense product (K > 512)."""
+    out = (ctypes.c_int64 * 3)()
+    _lib.check(_lib.load().itts_sparse_path_counts(out), "itts_sparse_path_counts")
+    return SparsePathCounts(*[int(v) for v in out])
+
+
 def linear_fwd_mse(x, w, b, target, row_valid, n_valid, loss_weight=1.0, grad=None):
     """Output layer + masked MSE ('mean_per_frame') of a training step in one launch:
     (loss [1], d loss / d output [M, N]); the layer's output itself is not materialised."""

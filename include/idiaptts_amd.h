@@ -438,6 +438,29 @@ int itts_linear_bwd(const float* d_dz, int64_t lddz, const float* d_x, int64_t l
                     int64_t ldyp, int act_prev, int64_t M, int N, int K, void* d_workspace,
                     int accumulate, void* stream);
 
+/* ---- dense layer on a sparse input (the min-max-normalised question vectors of layer 0: binary answers, mostly
+ * exact zeros) -------------------------------------------------------------------------------------------------
+ * Row lists of x [M, ldx]: per row the (k, x[m,k]) pairs with x[m,k] != 0 in ascending k (+-0.0 dropped; NaN and
+ * denormals kept; columns >= K never listed), K <= 65535.  They live in ONE caller-owned block d_lists whose layout
+ * itts_sparse_rows_layout gives: out = {byte offset of the int32 counts [M], byte offset of the entries
+ * [M][pitch] of {int32 k, float value}, pitch in entries, size of the block in bytes}.  Bytes 0..15 of the block
+ * are the record {int64 total non-zeros, int64 largest count of a row}, written only when want_record != 0 (one
+ * more memset; a caller that has decided leaves it out).  A row of K non-zeros gives K entries: nothing is capped.
+ * No float atomics, no host synchronisation. */
+int itts_sparse_rows_layout(int64_t M, int K, int64_t out[4]);
+int itts_sparse_rows_build(const float* d_x, int64_t ldx, int64_t M, int K, void* d_lists, int want_record,
+                           void* stream);
+/* y[M,N] = act(b[N] + sum over the listed (k, v) of row m of v * w[n,k]) with d_lists built from x [M, K]: one fmaf
+ * chain per output in ascending k, starting from +0, the bias added last; activations and the pad columns of y
+ * as itts_linear_fwd (written as zeros where that writes them).  Each workgroup keeps a 64-column slab of w^T in
+ * LDS, which holds K <= 512; a larger K runs itts_linear_fwd on d_x instead (decided from the shape alone), so
+ * d_x / ldx must be the matrix the lists were built from. */
+int itts_linear_fwd_sparse(const void* d_lists, const float* d_x, int64_t ldx, const float* d_w, const float* d_b,
+                           float* d_y, int64_t ldy, int64_t M, int N, int K, int act, void* stream);
+/* Process-wide atomic counts, no device call: out = {itts_sparse_rows_build launches, itts_linear_fwd_sparse calls
+ * that ran the sparse kernel, itts_linear_fwd_sparse calls that ran the dense product instead}. */
+int itts_sparse_path_counts(int64_t out[3]);
+
 /* ---- acoustic model: Conv1d groups (rnn_dyn/CNNWrapper.py:28-61 -> torch.nn.Conv1d + act) ---
  * 1-D convolution over the time axis of a zero-padded batch of B utterances, stride 1, groups 1,
  * padding_mode 'zeros': T_out = T_in + 2 pad - dil (Kw - 1) (> 0, else ITTS_E_INVALID).  Activations
