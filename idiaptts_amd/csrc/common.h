@@ -106,6 +106,10 @@ class ScratchScope {
   int n_live_ = 0;
 };
 
+// Sum of S split-K slabs of n floats (slab s at slabs + s * n) into out (nn.hip): the reduction of
+// itts_linear_bwd_weight, queued instead of launched inside itts_defer_reductions.
+int reduce_slabs(const float* slabs, int S, int64_t n, float* out, int accumulate, hipStream_t s);
+
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 // 16-byte aligned: with a pitch that is a multiple of 4 floats, rows may be read as float4

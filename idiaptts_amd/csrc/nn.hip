@@ -506,6 +506,10 @@ static int launch_reduce_slabs(const float* slabs, int S, int64_t n, float* out,
   return ITTS_OK;
 }
 
+int reduce_slabs(const float* slabs, int S, int64_t n, float* out, int accumulate, hipStream_t s) {
+  return launch_reduce_slabs(slabs, S, n, out, accumulate, s);
+}
+
 extern "C" int itts_defer_reductions(int on) {
   ITTS_REQUIRE(on || t_pending.nseg == 0,
                "queued reductions must be run (itts_reduce_deferred) before deferral is switched off");

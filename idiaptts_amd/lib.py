@@ -102,6 +102,13 @@ _SIGNATURES = {
     "itts_sparse_rows_build": (c_int, [_P, c_int64, c_int64, c_int, _P, c_int, _P]),
     "itts_linear_fwd_sparse": (c_int, [_P, _P, c_int64, _P, _P, _P, c_int64, c_int64, c_int, c_int, c_int, _P]),
     "itts_sparse_path_counts": (c_int, [POINTER(c_int64)]),
+    "itts_sparse_cols_plan_ints": (c_int, []),
+    "itts_sparse_cols_layout": (c_int, [c_int64, c_int, POINTER(c_int64)]),
+    "itts_sparse_cols_build": (c_int, [_P, c_int64, c_int64, c_int, _P, _P, _P]),
+    "itts_linear_bwd_weight_sparse_workspace_bytes": (c_int64, [c_int64, c_int, c_int, c_int64]),
+    "itts_linear_bwd_weight_sparse": (c_int, [_P, c_int64, _P, _P, _P, c_int64, _P, c_int64, _P, c_int64, c_int,
+                                              c_int, _P, c_int, _P]),
+    "itts_sparse_wgrad_counts": (c_int, [POINTER(c_int64)]),
     "itts_act_bwd": (c_int, [_P, _P, _P, c_int64, c_int, _P]),
     "itts_linear_bwd_input": (c_int, [_P, c_int64, _P, _P, c_int64, _P, c_int64, c_int, c_int64,
                                       c_int, c_int, _P]),

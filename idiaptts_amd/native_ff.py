@@ -32,6 +32,11 @@ def _pad4(n):
 # equal at 19 % by interpolation; the constant stays a little below that.
 SPARSE_INPUT_MAX_DENSITY = 0.18
 
+# The same for sparse_wgrad=None and layer 0's weight gradient, from the dW columns of the same sweep (column build +
+# sparse launch against the dense launch): 0.85 of the dense time at 7 % non-zeros, 0.98 at 10 %, 1.34 at 20 %.  The
+# column form crosses over much earlier than the forward's row form, so it has a constant of its own.
+SPARSE_WGRAD_MAX_DENSITY = 0.09
+
 
 class FlatFFModel:
     """Dense stack dims[0] -> dims[1] -> ... with activations `acts` (one per layer: a name of ops.ACT_BY_NAME in
@@ -40,10 +45,16 @@ class FlatFFModel:
     sparse_input: True / False sends layer 0's forward product of a training step through the row lists of its
     input (ops.sparse_rows_build + ops.linear_fwd_sparse) / through the dense product.  None decides once, at the
     first loss_and_backward, from the density of that batch (one host synchronisation in the model's life) and keeps
-    the decision: a later dense batch is slower on the sparse path, never wrong."""
+    the decision: a later dense batch is slower on the sparse path, never wrong.
+
+    sparse_wgrad: True / False sends layer 0's weight gradient through column lists of the same input
+    (ops.sparse_cols_build + ops.linear_bwd_weight_sparse) / through the dense product; None takes the lists where
+    sparse_input does and the first batch's density is at most SPARSE_WGRAD_MAX_DENSITY.  The column plan is made
+    once, from the column counts of the first batch (read where the density decision is made), and is a hint for
+    speed only."""
 
     def __init__(self, dims=(425, 512, 512, 187), acts=("tanh", "tanh", None), device="cuda",
-                 seed=0, state_dict=None, sparse_input=None):
+                 seed=0, state_dict=None, sparse_input=None, sparse_wgrad=None):
         assert len(acts) == len(dims) - 1
         self.dims = tuple(int(d) for d in dims)
         self.acts = [ops.act_code(a) for a in acts]
@@ -70,6 +81,9 @@ class FlatFFModel:
         self._buffers = {}
         self.sparse_input = None if sparse_input is None else bool(sparse_input)
         self._lists = None        # the row lists of the current batch: the model's own storage
+        self.sparse_wgrad = None if sparse_wgrad is None else bool(sparse_wgrad)
+        self._col_plan = None     # ops.SparseColsPlan of layer 0's input, made once
+        self._cols = None         # the column data of the current batch: the model's own storage
         if state_dict is None:
             state_dict = self.reference_init(self.dims, seed)
         self.load_layers(state_dict)
@@ -188,6 +202,22 @@ class FlatFFModel:
         self._lists = ops.sparse_rows_build(x, lists=self._lists, want_record=True)
         self.sparse_input = self._lists.density() <= SPARSE_INPUT_MAX_DENSITY
 
+    def _use_sparse_wgrad(self, x):
+        """whether layer 0's weight gradient takes the column lists of x; the first call that says yes makes the
+        plan (it reads the column counts of x: a synchronisation, at the same place as the density decision)"""
+        fits = self.dims[0] <= ops.SPARSE_COLS_MAX_K
+        if self.sparse_wgrad is None:
+            self.sparse_wgrad = False
+            if self.sparse_input and fits:
+                plan = ops.sparse_cols_plan(x, K=self.dims[0])
+                if plan.density <= SPARSE_WGRAD_MAX_DENSITY:
+                    self.sparse_wgrad, self._col_plan = True, plan
+        if not self.sparse_wgrad:
+            return False
+        if self._col_plan is None and fits:
+            self._col_plan = ops.sparse_cols_plan(x, K=self.dims[0])
+        return True
+
     def loss_and_backward(self, x, target, row_valid, n_valid_global, reduce_group=None, reduce=False):
         """Fills self.grads with d(loss)/d(params) of this rank's frames; returns loss tensor
         (this rank's contribution, already divided by the global frame count).  reduce=True (data
@@ -198,6 +228,7 @@ class FlatFFModel:
         x = self.pack_input(x)
         if self.sparse_input is None:
             self._decide_sparse_input(x)
+        self._wgrad_sparse_now = self._use_sparse_wgrad(x)
         if reduce:
             return self._loss_and_backward(x, target, row_valid, n_valid_global, reduce_group, reduce)
         # one process: the loss sum and the layers' split-K slab reductions are queued and run as ONE
@@ -232,6 +263,13 @@ class FlatFFModel:
                 dz_in = self._rows_buffer("dz%d" % (i & 1), M, self.layout[i][3])
                 ops.linear_bwd(dz, inp, self.weight_padded(i), self.weight_padded(i, self.grads),
                                self.bias(i, self.grads), dz_in, yprev=hs[i - 1], act_prev=self.acts[i - 1])
+            elif self._wgrad_sparse_now:
+                # without a plan (dims[0] > 512) the entry point runs the dense product and counts it
+                if self._col_plan is not None:
+                    self._cols = ops.sparse_cols_build(x, self._col_plan, K=self.dims[0], cols=self._cols)
+                ops.linear_bwd_weight_sparse(dz, x, self._cols if self._col_plan is not None else None,
+                                             self._col_plan, dw=self.weight_padded(i, self.grads),
+                                             db=self.bias(i, self.grads), K=self.dims[0])
             else:
                 ops.linear_bwd_weight(dz, inp, dw=self.weight_padded(i, self.grads),
                                       db=self.bias(i, self.grads))

@@ -730,6 +730,134 @@ def linear_bwd_weight(dz, x, dw=None, db=None, accumulate=False, want_bias=True)
     return dw, db
 
 
+SPARSE_COLS_MAX_K = 512
+SPARSE_COLS_HEAVY = 31          # strip columns for x; the 32nd is the ones of the bias
+SPARSE_COLS_OWNERS = 64
+SPARSE_COLS_SLOTS = 8
+# share of non-zeros above which a column goes to the strip
+SPARSE_COLS_HEAVY_DENSITY = 0.25
+
+
+class SparseColsPlan(object):
+    """Which columns of a sparse [M, K] input (K <= 512) the sparse weight gradient treats as heavy (a dense strip
+    and MFMAs) and which quarter wave owns each light one (lists).  Made from the non-zero counts per column of one
+    batch; it only moves time: every column is served whatever a later batch looks like.
+      heavy: the columns with more than heavy_density * rows non-zeros, at most 31, the fullest first
+      light: all others, fullest first, each to the owner (of 64, at most 8 columns each) with the least so far"""
+
+    def __init__(self, col_counts, rows, device, heavy_density=SPARSE_COLS_HEAVY_DENSITY):
+        counts = [int(c) for c in col_counts]
+        K = len(counts)
+        if not 0 < K <= SPARSE_COLS_MAX_K:
+            raise ValueError("a column plan holds 1 .. {} columns, got {}".format(SPARSE_COLS_MAX_K, K))
+        order = sorted(range(K), key=lambda k: (-counts[k], k))
+        self.heavy = [k for k in order if counts[k] > heavy_density * rows][:SPARSE_COLS_HEAVY]
+        taken = set(self.heavy)
+        self.owners = [[] for _ in range(SPARSE_COLS_OWNERS)]
+        load = [0] * SPARSE_COLS_OWNERS
+        for k in order:
+            if k in taken:
+                continue
+            o = min((o for o in range(SPARSE_COLS_OWNERS) if len(self.owners[o]) < SPARSE_COLS_SLOTS),
+                    key=lambda o: (load[o], len(self.owners[o]), o))
+            self.owners[o].append(k)
+            load[o] += counts[k]
+        self.K = K
+        self.density = sum(counts) / float(max(rows * K, 1))   # of the batch the plan was made from
+        table = [-1] * int(_lib.load().itts_sparse_cols_plan_ints())
+        inverse = SPARSE_COLS_HEAVY + 1 + SPARSE_COLS_OWNERS * SPARSE_COLS_SLOTS
+        for h, k in enumerate(self.heavy):
+            table[h] = k
+            table[inverse + k] = 0x1000 + h
+        for o, cols in enumerate(self.owners):
+            for s, k in enumerate(cols):
+                table[SPARSE_COLS_HEAVY + 1 + o * SPARSE_COLS_SLOTS + s] = k
+                table[inverse + k] = o * SPARSE_COLS_SLOTS + s
+        self.table = torch.tensor(table, dtype=torch.int32, device=device)
+
+
+def sparse_cols_plan(x, K=None, heavy_density=SPARSE_COLS_HEAVY_DENSITY):
+    """SparseColsPlan from the columns of x [M, >= K] itself (reads the device: one synchronisation)"""
+    K = x.shape[1] if K is None else int(K)
+    counts = (x[:, :K] != 0).sum(dim=0).tolist()
+    return SparseColsPlan(counts, x.shape[0], x.device, heavy_density)
+
+
+class SparseCols(object):
+    """Column data of a sparse [M, K] matrix for the sparse weight gradient (itts_sparse_cols_build): per tile of 256
+    rows the light columns' (row, value) lists and the strip of the heavy columns, in one device block that the
+    caller owns.  A block is reused for any shape it is large enough for."""
+
+    def __init__(self, M, K, device, block=None):
+        out = (ctypes.c_int64 * 3)()
+        _lib.check(_lib.load().itts_sparse_cols_layout(M, K, out), "itts_sparse_cols_layout")
+        self.M, self.K = int(M), int(K)
+        self._strip_off, self._streams_off, self.nbytes = (int(v) for v in out)
+        if block is None or block.numel() < self.nbytes:
+            block = torch.empty(max(self.nbytes, 16), dtype=torch.uint8, device=device)
+        self.block = block
+
+    def strip(self):
+        """float32 [tiles * 256, 32]: the heavy columns' values, column 31 ones, rows behind M zeros"""
+        return self.block[self._strip_off:self._streams_off].view(torch.float32).view(-1, 32)
+
+
+def sparse_cols_build(x, plan, K=None, cols=None):
+    """Column data of the first K (default: all) columns of x [M, >= K] fp32 under `plan`; `cols`: a SparseCols whose
+    block is reused when it is large enough."""
+    _need(x, torch.float32, "x")
+    ldx = _rows(x, "x")
+    M = x.shape[0]
+    K = x.shape[1] if K is None else int(K)
+    if K > x.shape[1]:
+        raise ValueError("K exceeds the width of x")
+    if plan.K != K:
+        raise ValueError("the plan was made for {} columns, not {}".format(plan.K, K))
+    out = SparseCols(M, K, x.device, cols.block if cols is not None else None)
+    _lib.check(_lib.load().itts_sparse_cols_build(_ptr(x), ldx, M, K, _ptr(plan.table), _ptr(out.block), _stream()),
+               "itts_sparse_cols_build")
+    return out
+
+
+def linear_bwd_weight_sparse(dz, x, cols, plan, dw=None, db=None, accumulate=False, want_bias=True, K=None):
+    """ops.linear_bwd_weight(dz, x[:, :K]) through the column data `cols` built from x under `plan`.  dw may be
+    [N, lddw] with lddw >= K: its pad columns become zeros.  Without cols / plan (None), or with a shape the kernel
+    does not serve, the dense product runs on x (ops.sparse_wgrad_counts says which)."""
+    L = _lib.load()
+    _need(dz, torch.float32, "dz")
+    _need(x, torch.float32, "x")
+    M, N = dz.shape
+    K = (cols.K if cols is not None else x.shape[1]) if K is None else int(K)
+    if cols is not None and (cols.M != M or cols.K != K or plan is None or plan.K != K):
+        raise ValueError("the column data were built for another shape or without this plan")
+    if dw is None:
+        dw = torch.empty((N, K), dtype=torch.float32, device=dz.device)
+    if dw.dim() != 2 or dw.shape[0] != N or dw.shape[1] < K or not dw.is_contiguous():
+        raise ValueError("dw must be contiguous [N, >= K]")
+    if db is None and want_bias:
+        db = torch.empty((N,), dtype=torch.float32, device=dz.device)
+    lddw = dw.shape[1]
+    ws = _workspace(L.itts_linear_bwd_weight_sparse_workspace_bytes(M, N, K, lddw), dz.device)
+    _lib.check(L.itts_linear_bwd_weight_sparse(_ptr(dz), _rows(dz, "dz"),
+                                               _ptr(cols.block) if cols is not None else None,
+                                               _ptr(plan.table) if plan is not None else None, _ptr(x), _rows(x, "x"),
+                                               _ptr(dw), lddw, _ptr(db), M, N, K, _ptr(ws), 1 if accumulate else 0,
+                                               _stream()), "itts_linear_bwd_weight_sparse")
+    return dw, db
+
+
+SparseWgradCounts = collections.namedtuple("SparseWgradCounts", "col_builds dw_sparse dw_dense")
+
+
+def sparse_wgrad_counts():
+    """How the sparse weight-gradient entry points of this process went so far (itts_sparse_wgrad_counts; no device
+    call): column builds, linear_bwd_weight_sparse calls that ran the sparse kernel, and those sent to the dense
+    product."""
+    out = (ctypes.c_int64 * 3)()
+    _lib.check(_lib.load().itts_sparse_wgrad_counts(out), "itts_sparse_wgrad_counts")
+    return SparseWgradCounts(*[int(v) for v in out])
+
+
 # ------------------------------------------------------------------------------ Conv1d groups
 # Activations stay in the model's layout: [B, T, C] (batch_first) or [T, B, C], channels last, so that
 # row (b, t) of the padded batch is one row of a 2-D [B*T, ld] view; no transpose to torch's [B, C, T].

@@ -461,6 +461,39 @@ int itts_linear_fwd_sparse(const void* d_lists, const float* d_x, int64_t ldx, c
  * that ran the sparse kernel, itts_linear_fwd_sparse calls that ran the dense product instead}. */
 int itts_sparse_path_counts(int64_t out[3]);
 
+/* Weight gradient of the same layer, dw[N][lddw] = dz^T x (+ db[N] = column sums of dz), without the products by
+ * x's zeros (csrc/sparse_wgrad.hip).  The non-zeros are walked by column, K <= 512 and lddw <= 512.
+ * Plan (d_plan, itts_sparse_cols_plan_ints() = 1056 int32 on the device): plan[0..30] are the heavy columns of x
+ * (-1: none; plan[31] is ignored, that strip column is the ones of the bias), plan[32 + 8 o + s] is the light column
+ * in slot s of owner o (64 owners, -1: none), and plan[544 + k] says the same from column k's side: 8 o + s, or
+ * 0x1000 + h for the heavy column in strip column h.  Every column < K must stand in it exactly once.  Which column
+ * is heavy and who owns a light one only moves time: any such plan gives the same sums up to their order.
+ * Column data of one batch (itts_sparse_cols_build into the caller-owned, 16-byte aligned block d_cols;
+ * itts_sparse_cols_layout: out = {byte offset of the strip, byte offset of the streams, size in bytes}): x is cut into
+ * tiles of 256 rows; the strip float [tiles * 256][32] holds the heavy columns' values (column 31: 1.0, rows behind M:
+ * 0); the streams are uint16 counts[tiles * 64][8], then block 0 of every list, [tiles * 64 * 8][16] entries, then
+ * blocks 1..15 of every list, [tiles * 64 * 8][15][16] entries, list (tile * 64 + owner) * 8 + slot; an entry is {int32
+ * byte offset of the row in a [257][64] float tile, float value}, rows ascending, the last block of a list filled
+ * up with {row 256, +0.0}.  -0.0 / NaN / denormals as in
+ * itts_sparse_rows_build; a column of 256 non-zeros gives 256 entries: nothing is capped.
+ * itts_linear_bwd_weight_sparse: the result goes through the split-K slab workspace and the reduction of
+ * itts_linear_bwd_weight (itts_defer_reductions applies, accumulate likewise; workspace size from the _sparse query);
+ * dw's pad columns K..lddw-1 become zeros.  Deterministic, no float atomics: a light column's fmaf chain runs in
+ * ascending m per row range, a heavy column's per wave share, the shares in wave order, the ranges in slab order.
+ * What the kernel does not serve -- K or lddw > 512, lddz % 4 != 0, dz or d_cols not 16-byte aligned, d_plan or
+ * d_cols NULL -- runs itts_linear_bwd_weight on d_x over lddw columns instead (decided on the host; then lddw == K,
+ * or ldx >= lddw with x's pad columns zero).  itts_sparse_wgrad_counts: out = {itts_sparse_cols_build launches,
+ * calls that ran the sparse kernel, calls that ran the dense product}; process-wide, no device call. */
+int itts_sparse_cols_plan_ints(void);
+int itts_sparse_cols_layout(int64_t M, int K, int64_t out[3]);
+int itts_sparse_cols_build(const float* d_x, int64_t ldx, int64_t M, int K, const int* d_plan, void* d_cols,
+                           void* stream);
+int64_t itts_linear_bwd_weight_sparse_workspace_bytes(int64_t M, int N, int K, int64_t lddw);
+int itts_linear_bwd_weight_sparse(const float* d_dz, int64_t lddz, const void* d_cols, const int* d_plan,
+                                  const float* d_x, int64_t ldx, float* d_dw, int64_t lddw, float* d_db, int64_t M,
+                                  int N, int K, void* d_workspace, int accumulate, void* stream);
+int itts_sparse_wgrad_counts(int64_t out[3]);
+
 /* ---- acoustic model: Conv1d groups (rnn_dyn/CNNWrapper.py:28-61 -> torch.nn.Conv1d + act) ---
  * 1-D convolution over the time axis of a zero-padded batch of B utterances, stride 1, groups 1,
  * padding_mode 'zeros': T_out = T_in + 2 pad - dil (Kw - 1) (> 0, else ITTS_E_INVALID).  Activations
