@@ -531,7 +531,9 @@ __device__ __forceinline__ void epilogue(const Args& g, const Tile& pc, const f3
       // the whole offset in the VGPR: a 16-byte store with an SGPR offset may fetch its data registers
       // after a following VALU write to them (seen as lost elements when the CU's memory queue was
       // busy with the loaders' DMA)
-      const uint32_t vo = col < g.ldc ? cofs + (uint32_t)(rl * g.ldc * 4) : 0xfffffff0u;
+      // (a float4 that begins at or beyond N is not stored: a tile reaches past N by up to a tile width, and with C
+      // a column slice of a wider buffer those columns -- or, past the pitch, the next row's -- are not this call's)
+      const uint32_t vo = k0 ? cofs + (uint32_t)(rl * g.ldc * 4) : 0xfffffff0u;
       if (RING_DBG & 64) asm volatile("" ::"v"(o[0]), "v"(o[1]), "v"(o[2]), "v"(o[3]));
       else __builtin_amdgcn_raw_buffer_store_b128(o, rc, vo, 0, 0);
     }

@@ -12,6 +12,7 @@
 //     fwd+bwd 3.45 M (first-layer input gradient skipped: 3.01 M) -- SURVEY.md section 8d.
 #include <algorithm>
 #include <atomic>
+#include <cstdint>
 #include <cstdlib>
 
 #include "common.h"
@@ -204,12 +205,52 @@ __global__ __launch_bounds__(256, STAGES == 1 ? 4 : 2) void gemm_f32_kernel(Gemm
 // LDS-DMA ring kernel (a pair launch counts its two products), [1][epi] the register-staged kernel.
 static std::atomic<int64_t> g_gemm_path[2][4];
 
+// What the last dense call of this host thread launched (itts_gemm_last_plan): every entry is written at its launch
+// site from the template parameters and arguments of that launch.  A dense entry point opens the record (PlanScope);
+// launches made for other callers (conv1d.hip and rnn.hip reduce their slabs here too) leave it alone.
+constexpr int kPlanMax = 8, kPlanInts = 16;
+enum { PLAN_STAGED = 1, PLAN_RING = 2, PLAN_RING_PAIR = 3, PLAN_REDUCE = 4 };
+struct GemmPlan {
+  int32_t e[kPlanMax][kPlanInts];
+  int n;       // entries appended (those beyond kPlanMax are counted, not kept)
+  int depth;   // open dense entry points (itts_linear_bwd calls the two separate ones)
+};
+static thread_local GemmPlan t_plan{};
+
+struct PlanScope {
+  PlanScope() { if (t_plan.depth++ == 0) t_plan.n = 0; }
+  ~PlanScope() { --t_plan.depth; }
+};
+
+static void plan_gemm(int kernel, bool a_row, bool b_row, int epi, int tn, int stages, int wm, bool va, bool vb,
+                      bool wide, bool grouped, int splitk, int af, int64_t tiles, int64_t grid) {
+  if (t_plan.depth == 0) return;
+  if (t_plan.n < kPlanMax) {
+    const int32_t v[kPlanInts] = {kernel, a_row, b_row, epi, tn, stages, wm, va, vb, wide, grouped, splitk, af,
+                                  (int32_t)std::min<int64_t>(tiles, INT32_MAX), (int32_t)grid, 0};
+    std::copy(v, v + kPlanInts, t_plan.e[t_plan.n]);
+  }
+  ++t_plan.n;
+}
+
+static void plan_reduce(bool vec, bool merged, bool deferred, int S) {
+  if (t_plan.depth == 0) return;
+  if (t_plan.n < kPlanMax) {
+    const int32_t v[kPlanInts] = {PLAN_REDUCE, vec, merged, deferred, S};
+    std::copy(v, v + kPlanInts, t_plan.e[t_plan.n]);
+  }
+  ++t_plan.n;
+}
+
 template <bool A_ROW, bool B_ROW, int EPI, int TN, int STAGES, int AF = AF_BASE>
 static int launch_gemm_tn(const GemmArgs& g, int splitk, hipStream_t s) {
   g_gemm_path[1][EPI].fetch_add(1, std::memory_order_relaxed);
   const int64_t tiles = ((g.M + BM - 1) / BM) * ((g.N + 64 * TN - 1) / (64 * TN));
   dim3 grid((unsigned)tiles, 1, (unsigned)splitk);
   const bool va = g.vecA, vb = g.vecB;   // pitch and alignment allow 16-byte loads (see load_tile)
+  // (the wide-store branch of gemm_f32_kernel: behind the EPI_MSE epilogue, single-stage 128 x 64 tiles only)
+  plan_gemm(PLAN_STAGED, A_ROW, B_ROW, EPI, TN, STAGES, 0, va, vb, EPI != EPI_MSE && STAGES == 1 && TN == 1 && g.wide_out,
+            false, splitk, AF, tiles * splitk, tiles * splitk);
   if (va && vb)
     hipLaunchKernelGGL((gemm_f32_kernel<A_ROW, B_ROW, EPI, true, true, TN, STAGES, AF>), grid, dim3(256), 0, s, g);
   else if (va)
@@ -286,7 +327,9 @@ static int launch_ring_wm(const GemmArgs& g, int splitk, hipStream_t s) {
   const int64_t ntiles = (int64_t)r.tiles_m * r.tiles_n * splitk;
   ITTS_REQUIRE(ntiles < ((int64_t)1 << 31), "too many tiles");
   const int grid = (int)std::min<int64_t>(kRingGrid, (ntiles + 7) / 8 * 8);
-  if (A_ROW && B_ROW && EPI == ring::EPI_BIAS_ACT && r.gn < r.tiles_n)
+  const bool grouped = A_ROW && B_ROW && EPI == ring::EPI_BIAS_ACT && r.gn < r.tiles_n;
+  plan_gemm(PLAN_RING, A_ROW, B_ROW, EPI, 0, 0, WM, true, true, false, grouped, splitk, AF, ntiles, grid);
+  if (grouped)
     hipLaunchKernelGGL((ring::gemm_ring_kernel<A_ROW, B_ROW, EPI, WM, A_ROW && B_ROW && EPI == ring::EPI_BIAS_ACT, AF>),
                        dim3(grid), dim3(ring::THREADS), 0, s, r);
   else
@@ -326,6 +369,10 @@ static int launch_ring_bwd_pair(const GemmArgs& gw, int splitk, const GemmArgs& 
   g_gemm_path[0][EPI_STORE].fetch_add(1, std::memory_order_relaxed);
   g_gemm_path[0][EPI_X].fetch_add(1, std::memory_order_relaxed);
   const ring::Args rw = ring_args<WM_W>(gw, splitk), rx = ring_args<2>(gx, 1);
+  plan_gemm(PLAN_RING_PAIR, false, false, EPI_STORE, 0, 0, WM_W, true, true, false, false, splitk, AF_BASE,
+            (int64_t)rw.tiles_m * rw.tiles_n * splitk, kRingGrid);
+  plan_gemm(PLAN_RING_PAIR, true, false, EPI_X, 0, 0, 2, true, true, false, false, 1, AF_X,
+            (int64_t)rx.tiles_m * rx.tiles_n, kRingGrid);
   hipLaunchKernelGGL((ring::gemm_ring_pair_kernel<false, false, EPI_STORE, WM_W, true, false, EPI_X, 2, AF_X>),
                      dim3(kRingGrid), dim3(ring::THREADS), 0, s, rw, rx);
   ITTS_LAUNCH_CHECK();
@@ -489,8 +536,9 @@ static int queue_deferred(ReduceSeg g, hipStream_t s) {
 }
 
 static int launch_reduce_slabs(const float* slabs, int S, int64_t n, float* out, int accumulate,
-                               hipStream_t s) {
+                               hipStream_t s, bool merged = false) {
   const bool vec = n % 4 == 0 && aligned16(slabs) && aligned16(out);
+  plan_reduce(vec, merged, t_defer, S);
   if (t_defer) {
     ReduceSeg g{};
     g.src = slabs; g.out = out; g.n = n; g.S = S; g.accumulate = accumulate; g.kind = vec ? 0 : 1;
@@ -765,6 +813,7 @@ using namespace itts;
 extern "C" int itts_linear_fwd(const float* d_x, int64_t ldx, const float* d_w, const float* d_b,
                                float* d_y, int64_t ldy, int64_t M, int N, int K, int act,
                                void* stream) {
+  const PlanScope plan_scope;
   ITTS_REQUIRE(d_w && (M == 0 || (d_x && d_y)), "null pointer");
   ITTS_REQUIRE(M >= 0 && N > 0 && K > 0 && ldx >= K && ldy >= N, "bad sizes");
   ITTS_REQUIRE(act >= ITTS_ACT_NONE && act <= ITTS_ACT_HARDSIGMOID, "unknown activation");
@@ -832,6 +881,13 @@ extern "C" int itts_gemm_path_counts(int64_t out[8]) {
   return ITTS_OK;
 }
 
+extern "C" int itts_gemm_last_plan(int32_t* out, int max_entries) {
+  const int n = std::min(t_plan.n, kPlanMax);
+  if (out)
+    for (int i = 0; i < std::min(n, max_entries); ++i) std::copy(t_plan.e[i], t_plan.e[i] + kPlanInts, out + i * kPlanInts);
+  return t_plan.n;
+}
+
 extern "C" int64_t itts_linear_fwd_mse_workspace_bytes(int64_t M, int N) {
   const int64_t tiles = ((M + BM - 1) / BM) * ((N + 63) / 64);
   return std::max<int64_t>(tiles, kRingGrid) * 8;   // one partial sum per tile, or per persistent workgroup
@@ -847,6 +903,7 @@ extern "C" int itts_linear_fwd_mse(const float* d_x, int64_t ldx, const float* d
                                    double n_valid, float loss_weight, int64_t M, int N, int K,
                                    float* d_loss, float* d_dz, int64_t lddz, void* d_workspace,
                                    void* stream) {
+  const PlanScope plan_scope;
   ITTS_REQUIRE(d_w && d_loss && d_workspace && (M == 0 || (d_x && d_target && d_row_valid && d_dz)),
                "null pointer");
   ITTS_REQUIRE(M >= 0 && N > 0 && K > 0 && ldx >= K && ldt >= N && lddz >= N && n_valid > 0, "bad sizes");
@@ -899,6 +956,7 @@ extern "C" int itts_linear_bwd_input(const float* d_dz, int64_t lddz, const floa
                                      float* d_dx, int64_t lddx, const float* d_yprev,
                                      int64_t ldyp, int act_prev, int64_t M, int N, int K,
                                      void* stream) {
+  const PlanScope plan_scope;
   ITTS_REQUIRE(d_w && (M == 0 || (d_dz && d_dx)), "null pointer");
   ITTS_REQUIRE(M >= 0 && N > 0 && K > 0 && lddz >= N && lddx >= K, "bad sizes");
   ITTS_REQUIRE(!d_yprev || (act_prev >= ITTS_ACT_NONE && act_prev <= ITTS_ACT_HARDSIGMOID), "unknown activation");
@@ -928,6 +986,7 @@ extern "C" int64_t itts_linear_bwd_weight_workspace_bytes(int64_t M, int N, int 
 extern "C" int itts_linear_bwd_weight(const float* d_dz, int64_t lddz, const float* d_x,
                                       int64_t ldx, float* d_dw, float* d_db, int64_t M, int N,
                                       int K, void* d_workspace, int accumulate, void* stream) {
+  const PlanScope plan_scope;
   ITTS_REQUIRE(d_dw && d_workspace && (M == 0 || (d_dz && d_x)), "null pointer");
   ITTS_REQUIRE(M >= 0 && N > 0 && K > 0 && lddz >= N && ldx >= K, "bad sizes");
   hipStream_t s = as_stream(stream);
@@ -962,7 +1021,7 @@ extern "C" int itts_linear_bwd_weight(const float* d_dz, int64_t lddz, const flo
     g.bias_part_stride = merged ? stride : N;
     int rc = launch_gemm<false, false, EPI_STORE>(g, S_eff, s);
     if (rc) return rc;
-    if (merged) return launch_reduce_slabs(slabs, S_eff, n + N, d_dw, accumulate, s);
+    if (merged) return launch_reduce_slabs(slabs, S_eff, n + N, d_dw, accumulate, s, true);
     rc = launch_reduce_slabs(slabs, S_eff, n, d_dw, accumulate, s);
     if (rc) return rc;
     return launch_reduce_slabs(g.bias_part, S_eff, (int64_t)N, d_db, accumulate, s);
@@ -980,6 +1039,7 @@ extern "C" int itts_linear_bwd(const float* d_dz, int64_t lddz, const float* d_x
                                const float* d_w, float* d_dw, float* d_db, float* d_dx, int64_t lddx,
                                const float* d_yprev, int64_t ldyp, int act_prev, int64_t M, int N, int K,
                                void* d_workspace, int accumulate, void* stream) {
+  const PlanScope plan_scope;
   ITTS_REQUIRE(d_w && d_dw && d_workspace && (M == 0 || (d_dz && d_x && d_dx)), "null pointer");
   ITTS_REQUIRE(M >= 0 && N > 0 && K > 0 && lddz >= N && ldx >= K && lddx >= K, "bad sizes");
   ITTS_REQUIRE(!d_yprev || ldyp >= K, "ldyp too small");
@@ -1024,7 +1084,7 @@ extern "C" int itts_linear_bwd(const float* d_dz, int64_t lddz, const float* d_x
   else rc = wm == 1 ? launch_ring_bwd_pair<1, EPI_STORE>(gw, S_eff, gx, s) : launch_ring_bwd_pair<2, EPI_STORE>(gw, S_eff, gx, s);
   if (rc) return rc;
   float* slabs = reinterpret_cast<float*>(d_workspace);
-  rc = launch_reduce_slabs(slabs, S_eff, merged ? n + N : n, d_dw, accumulate, s);
+  rc = launch_reduce_slabs(slabs, S_eff, merged ? n + N : n, d_dw, accumulate, s, merged);
   if (rc || merged || !d_db) return rc;
   return launch_reduce_slabs(slabs + (int64_t)S_eff * n, S_eff, (int64_t)N, d_db, accumulate, s);
 }

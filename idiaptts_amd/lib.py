@@ -196,6 +196,7 @@ _SIGNATURES = {
     "itts_rnn_layer_counts": (c_int, [POINTER(c_int64)]),
     "itts_rnn_path_counts": (c_int, [POINTER(c_int64)]),
     "itts_gemm_path_counts": (c_int, [POINTER(c_int64)]),
+    "itts_gemm_last_plan": (c_int, [POINTER(ctypes.c_int32), c_int]),
     "itts_adam_step": (c_int, [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float,
                                c_float, c_int64, c_float, _P]),
     "itts_grad_norm_accum": (c_int, [_P, c_int64, c_int, _P, c_int, _P, _P]),

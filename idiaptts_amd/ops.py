@@ -1545,6 +1545,37 @@ def gemm_path_counts():
     return GemmPathCounts(tuple(v[:4]), tuple(v[4:]))
 
 
+GEMM_KERNELS = {1: "staged", 2: "ring", 3: "ring_pair"}
+GEMM_EPILOGUES = {0: "store", 1: "bias_act", 2: "dact", 3: "mse"}
+GemmLaunch = collections.namedtuple("GemmLaunch", "kernel a_row b_row epi tn stages wm vec_a vec_b wide grouped splitk "
+                                                  "family tiles grid")
+SlabReduction = collections.namedtuple("SlabReduction", "vec merged deferred slabs")
+GEMM_PLAN_MAX = 8                # kPlanMax of csrc/nn.hip
+
+
+def gemm_last_plan():
+    """What the last dense call of this host thread launched (linear_fwd, linear_fwd_mse, linear_bwd_input,
+    linear_bwd_weight, linear_bwd; itts_gemm_last_plan, no device call): a list, in launch order, of
+    GemmLaunch(kernel "staged" / "ring" / "ring_pair", a_row, b_row, epi "store" / "bias_act" / "dact" / "mse", tn and
+    stages (staged; 0 otherwise), wm (ring; 0 otherwise), vec_a, vec_b, wide (the wide-store epilogue), grouped (tile
+    order), splitk, family (0 base, 1 extended activations), tiles, grid) -- a pair launch gives two, the weight and
+    the input product -- and SlabReduction(vec: float4 or scalar columns, merged with the bias, deferred, slabs)."""
+    L = _lib.load()
+    out = (ctypes.c_int32 * (16 * GEMM_PLAN_MAX))()
+    n = L.itts_gemm_last_plan(out, GEMM_PLAN_MAX)
+    if n > GEMM_PLAN_MAX:
+        raise _lib.IttsError("the record holds {} launches, the call made {}".format(GEMM_PLAN_MAX, n))
+    plan = []
+    for i in range(n):
+        v = [int(x) for x in out[16 * i:16 * i + 16]]
+        if v[0] == 4:
+            plan.append(SlabReduction(bool(v[1]), bool(v[2]), bool(v[3]), v[4]))
+        else:
+            plan.append(GemmLaunch(GEMM_KERNELS[v[0]], bool(v[1]), bool(v[2]), GEMM_EPILOGUES[v[3]], v[4], v[5], v[6],
+                                   bool(v[7]), bool(v[8]), bool(v[9]), bool(v[10]), v[11], v[12], v[13], v[14]))
+    return plan
+
+
 RnnPathCounts = collections.namedtuple("RnnPathCounts", "fwd_ran fwd_declined fwd_gave_up bwd_ran bwd_declined bwd_gave_up")
 
 

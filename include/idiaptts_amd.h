@@ -399,7 +399,9 @@ int itts_batch_pad_colsum_f32(const float* d_x, int64_t ld_x, const int64_t* d_l
  * a row pitch (ld*) that is a multiple of 4 floats on a 16-byte aligned base selects 16-byte loads.
  * If the logical width is not a multiple of 4, the 1-3 floats between the width and the next
  * multiple of 4 are then read as well and must be finite (keep them zero): a padded reduction
- * element meets a zero of the other operand, a padded output column is never stored.
+ * element meets a zero of the other operand.  Of an output with such rows the same 1-3 floats are either left
+ * alone (the register-staged kernel) or written as zeros (the ring kernel); no call writes anything else outside
+ * its [M, width] slice, so outputs may be column slices of wider buffers.
  * y[M,N] = act(x[M,K] @ w[N,K]^T + b[N]); fp32 MFMA. */
 int itts_linear_fwd(const float* d_x, int64_t ldx, const float* d_w, const float* d_b,
                     float* d_y, int64_t ldy, int64_t M, int N, int K, int act, void* stream);
@@ -957,6 +959,19 @@ int itts_rnn_layer_counts(int64_t out[2]);
  * 2 activation derivative (input gradients), 3 masked MSE (itts_linear_fwd_mse).  The two products of a fused
  * itts_linear_bwd launch count one each. */
 int itts_gemm_path_counts(int64_t out[8]);
+/* What the last dense call of the calling host thread launched (itts_linear_fwd, itts_linear_fwd_mse,
+ * itts_linear_bwd_input, itts_linear_bwd_weight, itts_linear_bwd; thread-local, no device call).  Each of them clears
+ * the record on entry, each of its launches appends one entry of 16 int32, written at the launch site from the template
+ * parameters and arguments of that launch.  Returns the number of launches; the first min(that, max_entries, 8) entries
+ * go to out (may be NULL), in launch order:
+ *   a product      {kernel (1 register-staged, 2 ring, 3 ring pair launch), A_ROW, B_ROW, epilogue (as above), TN,
+ *                   STAGES (staged; 0 otherwise), WM (ring: 1 = 64 x 128 tiles, 2 = 128 x 64; 0 otherwise), vecA, vecB,
+ *                   the wide-store epilogue is the one taken, grouped tile order, split-K slabs, activation family
+ *                   (0 none / Tanh / ReLU, 1 the others), tiles, workgroups, 0}; a pair launch gives two entries, the
+ *                   weight-gradient product first
+ *   a reduction    {4, float4 (1) or scalar (0) columns, merged with the bias, deferred (itts_defer_reductions),
+ *                   slabs, 0 ...} */
+int itts_gemm_last_plan(int32_t* out, int max_entries);
 
 /* Which way the LSTM / GRU layer calls of this process went (process-wide atomic counts, no device call):
  * out = forward ran, declined, gave_up, backward ran, declined, gave_up.  `ran`: the persistent recurrence did
