@@ -218,6 +218,12 @@ _SIGNATURES = {
     "itts_mulaw_decode": (c_int, [_P, POINTER(c_int64), c_int, c_int, _P, _P]),
     "itts_mulaw_onehot": (c_int, [_P, POINTER(c_int64), POINTER(c_int64), c_int, c_int, _P, _P]),
     "itts_sample_linearly": (c_int, [_P, c_int, POINTER(c_int64), c_int, c_int, c_int, _P, c_int, _P]),
+    "itts_glu_gate_fwd": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, c_int64, c_int, _P]),
+    "itts_glu_gate_bwd": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int64, c_int, _P]),
+    "itts_wavenet_state_floats": (c_int64, [c_int, c_int, c_int, c_int, POINTER(c_int)]),
+    "itts_wavenet_generate": (c_int, [_P] * 10 + [POINTER(c_int), c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                      c_int, c_double, _P, c_int64, _P, POINTER(c_int), c_int, c_int64, c_int, _P,
+                                      c_int64, _P, _P, _P]),
 }
 
 

@@ -1,2 +1,3 @@
 from .modules import (GRU, LSTM, RNN, AllPassWarp, GradientScaling, LinearAct, MeanPooling,  # noqa: F401
                       SelectLastPooling, VanillaVAE)
+from .wavenet import WaveNet  # noqa: F401

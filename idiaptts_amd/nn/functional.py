@@ -397,6 +397,28 @@ class MolLossFunction(torch.autograd.Function):
         return grad, None, None, None, None, None, None, None
 
 
+class GluGateFunction(torch.autograd.Function):
+    """z [..., G / 2] = tanh(a + ca) * sigmoid(b + cb) of x [..., G] = a | b and an optional c [..., G] = ca | cb: the
+    gate of a WaveNet residual layer (csrc/wavenet.hip).  Saves the pre-activations; backward recomputes the two
+    activations and returns ONE buffer dx [..., G] for both x and c (c enters by addition)."""
+
+    @staticmethod
+    def forward(ctx, x, c):
+        G = x.shape[-1]
+        x2 = x.reshape(-1, G)
+        c2 = c.reshape(-1, G) if c is not None else None
+        z = ops.glu_gate(x2, c2)
+        ctx.save_for_backward(x2, c2)
+        ctx.in_shape = x.shape
+        return z.reshape(*x.shape[:-1], G // 2)
+
+    @staticmethod
+    def backward(ctx, dz):
+        x2, c2 = ctx.saved_tensors
+        dx = ops.glu_gate_bwd(dz.reshape(-1, dz.shape[-1]), x2, c2).reshape(ctx.in_shape)
+        return (dx if ctx.needs_input_grad[0] else None), (dx if c2 is not None and ctx.needs_input_grad[1] else None)
+
+
 class grad_scaling(torch.autograd.Function):
     """Identity whose gradient is multiplied by a constant (reference GradientScaling.py: grad_scaling)."""
 

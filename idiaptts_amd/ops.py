@@ -2082,3 +2082,173 @@ def sample_linearly(x, offsets, m, dtype=torch.float32):
                                       len(offsets) - 1, x.shape[1], m, _ptr(y), int(dtype == torch.float64),
                                       _stream()), "itts_sample_linearly")
     return y, [o * m for o in offsets]
+
+
+# ---------------------------------------------------------------------------------------- WaveNet
+def _gate_rows(t, name, width=None):
+    _need(t, torch.float32, name)
+    if t.dim() != 2:
+        raise ValueError("{} must be 2-D [N, {}]".format(name, "G" if width is None else width))
+    if t.shape[1] > 1 and t.stride(1) != 1:
+        t = t.contiguous()
+    return t, (t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1]))
+
+
+def glu_gate(x, c=None, out=None):
+    """z [N, G / 2] = tanh(a + ca) * sigmoid(b + cb) of x [N, G] = a | b and the optional c [N, G] = ca | cb
+    (itts_glu_gate_fwd): the gate of a WaveNet residual layer.  Rows of any pitch; float4 loads where the pitches
+    allow."""
+    L = _lib.load()
+    x, ldx = _gate_rows(x, "x")
+    N, G = x.shape
+    if G < 2 or G % 2:
+        raise ValueError("G = {} is not a positive even number".format(G))
+    ldc = 0
+    if c is not None:
+        c, ldc = _gate_rows(c, "c")
+        if tuple(c.shape) != (N, G):
+            raise ValueError("c must be [N, G] = [{}, {}], got {}".format(N, G, tuple(c.shape)))
+    if out is None:
+        out = torch.empty((N, G // 2), dtype=torch.float32, device=x.device)
+    _need(out, torch.float32, "out")
+    if tuple(out.shape) != (N, G // 2) or (G > 2 and out.stride(1) != 1):
+        raise ValueError("out must be float32 [{}, {}] with contiguous rows".format(N, G // 2))
+    ldz = out.stride(0) if N > 1 else max(out.stride(0), G // 2)
+    _lib.check(L.itts_glu_gate_fwd(_ptr(x), ldx, _ptr(c), ldc, _ptr(out), ldz, N, G, _stream()), "itts_glu_gate_fwd")
+    return out
+
+
+def glu_gate_bwd(dz, x, c=None):
+    """dx [N, G] of glu_gate from dz [N, G / 2], recomputed from x and c (itts_glu_gate_bwd); it is the gradient of c
+    as well."""
+    L = _lib.load()
+    x, ldx = _gate_rows(x, "x")
+    N, G = x.shape
+    dz, lddz = _gate_rows(dz, "dz")
+    if tuple(dz.shape) != (N, G // 2):
+        raise ValueError("dz must be [N, G / 2] = [{}, {}], got {}".format(N, G // 2, tuple(dz.shape)))
+    ldc = 0
+    if c is not None:
+        c, ldc = _gate_rows(c, "c")
+        if tuple(c.shape) != (N, G):
+            raise ValueError("c must be [N, G] = [{}, {}], got {}".format(N, G, tuple(c.shape)))
+    dx = torch.empty((N, G), dtype=torch.float32, device=x.device)
+    _lib.check(L.itts_glu_gate_bwd(_ptr(dz), lddz, _ptr(x), ldx, _ptr(c), ldc, _ptr(dx), G, N, G, _stream()),
+               "itts_glu_gate_bwd")
+    return dx
+
+
+# the envelope of itts_wavenet_generate (csrc/wavenet.hip)
+WAVENET_TILE_ROWS = 16
+WAVENET_MAX_WIDTH, WAVENET_MAX_CIN, WAVENET_MAX_CLASSES, WAVENET_MAX_MIXTURES = 512, 128, 256, 64
+WAVENET_MAX_LAYERS, WAVENET_MAX_DILATION = 64, 512
+
+
+def wavenet_check_envelope(layers, dilations, kernel_size, residual_channels, gate_channels, skip_out_channels,
+                           cin_channels, out_channels, scalar_input):
+    """NotImplementedError naming the first argument outside what the generation kernel covers"""
+    def refuse(name, value, what):
+        raise NotImplementedError("WaveNet {}={}: the generation kernel covers {}".format(name, value, what))
+    if kernel_size not in (2, 3):
+        refuse("kernel_size", kernel_size, "2 and 3")
+    if not 1 <= layers <= WAVENET_MAX_LAYERS:
+        refuse("layers", layers, "1 .. {}".format(WAVENET_MAX_LAYERS))
+    if max(dilations) > WAVENET_MAX_DILATION:
+        refuse("layers / stacks", "{} (dilation {})".format(layers, max(dilations)),
+               "dilations up to {}".format(WAVENET_MAX_DILATION))
+    for name, value in (("residual_channels", residual_channels), ("skip_out_channels", skip_out_channels)):
+        if value < 16 or value % 16 or value > WAVENET_MAX_WIDTH:
+            refuse(name, value, "multiples of 16 up to {}".format(WAVENET_MAX_WIDTH))
+    if gate_channels < 32 or gate_channels % 32 or gate_channels > WAVENET_MAX_WIDTH:
+        refuse("gate_channels", gate_channels, "multiples of 32 up to {}".format(WAVENET_MAX_WIDTH))
+    if not 0 <= cin_channels <= WAVENET_MAX_CIN:
+        refuse("cin_channels", cin_channels, "0 .. {}".format(WAVENET_MAX_CIN))
+    if scalar_input:
+        if out_channels < 3 or out_channels % 3 or out_channels // 3 > WAVENET_MAX_MIXTURES:
+            refuse("out_channels", out_channels, "3 K with K up to {} for scalar input".format(WAVENET_MAX_MIXTURES))
+    elif not 2 <= out_channels <= WAVENET_MAX_CLASSES:
+        refuse("out_channels", out_channels, "2 .. {} classes".format(WAVENET_MAX_CLASSES))
+
+
+def _c_ints(values):
+    values = [int(v) for v in values]
+    return (ctypes.c_int * len(values))(*values)
+
+
+def wavenet_state_floats(B, dilations, kernel_size, residual_channels):
+    """floats of the ring-buffer scratch of wavenet_generate for B rows (itts_wavenet_state_floats)"""
+    n = _lib.load().itts_wavenet_state_floats(int(B), len(dilations), int(kernel_size), int(residual_channels),
+                                              _c_ints(dilations))
+    if n < 0:
+        _lib.check(-1, "itts_wavenet_state_floats")
+    return n
+
+
+def wavenet_pack(w, rows=None, cols=None):
+    """The MFMA weight image of an operand w [K, N] (zero filled to `rows` x `cols`, multiples of 16):
+    image[kb][tile][lane][j] = w[16 kb + 4 (lane >> 4) + j][16 tile + (lane & 15)], flat.  Data movement only."""
+    K, N = w.shape
+    rows = (K + 15) // 16 * 16 if rows is None else rows
+    cols = (N + 15) // 16 * 16 if cols is None else cols
+    full = torch.zeros((rows, cols), dtype=torch.float32, device=w.device)
+    full[:K, :N] = w
+    # [kb, kg, j, tile, col] -> [kb, tile, kg, col, j]
+    return full.view(rows // 16, 4, 4, cols // 16, 16).permute(0, 3, 1, 4, 2).contiguous().reshape(-1)
+
+
+WaveNetWeights = collections.namedtuple(
+    "WaveNetWeights", "wf bf w1 b1 w2 b2 wh1 bh1 wh2 bh2 dilations kernel_size residual_channels gate_channels "
+    "skip_out_channels cin_channels out_channels scalar_input log_scale_min")
+
+
+def wavenet_generate(weights, c, lengths, uniforms, initial_class=-1, return_logits=False, state=None):
+    """Sample-by-sample generation of a batch in one launch (itts_wavenet_generate).  weights: a WaveNetWeights of
+    packed effective weights (nn.WaveNet.generation_weights()); c [B, Tc, cin] float32 conditioning at the sample rate
+    (None with cin 0); lengths: B ints; uniforms [B, T] (classes) or [B, T, 2] (scalar input), float32 in (0, 1), T >=
+    max(lengths).  Returns int32 classes [B, T] or float32 samples [B, T], zeros past each row's length, and with
+    return_logits the network outputs [B, T, out_channels] as well."""
+    L = _lib.load()
+    wt = weights
+    lengths = [int(n) for n in lengths]
+    B = len(lengths)
+    _need(uniforms, torch.float32, "uniforms")
+    want = 3 if wt.scalar_input else 2
+    if uniforms.dim() != want or uniforms.shape[0] != B or (wt.scalar_input and uniforms.shape[2] != 2):
+        raise ValueError("uniforms must be [B, T{}] with B = {}, got {}".format(", 2" if wt.scalar_input else "", B,
+                                                                                tuple(uniforms.shape)))
+    uniforms = uniforms.contiguous()
+    T = uniforms.shape[1]
+    if lengths and (min(lengths) < 0 or max(lengths) > T):
+        raise ValueError("lengths must lie in 0 .. T = {}, got {} .. {}".format(T, min(lengths), max(lengths)))
+    Tc = 0
+    if wt.cin_channels > 0:
+        if c is None:
+            raise ValueError("cin_channels = {} needs conditioning c".format(wt.cin_channels))
+        _need(c, torch.float32, "c")
+        if c.dim() != 3 or c.shape[0] != B or c.shape[2] != wt.cin_channels:
+            raise ValueError("c must be [B, Tc, cin] = [{}, Tc, {}], got {}".format(B, wt.cin_channels,
+                                                                                    tuple(c.shape)))
+        c = c.contiguous()
+        Tc = c.shape[1]
+        if lengths and Tc < max(lengths):
+            raise ValueError("c has {} steps, the longest row {}".format(Tc, max(lengths)))
+    else:
+        c = None
+    dev = uniforms.device
+    need = wavenet_state_floats(B, wt.dilations, wt.kernel_size, wt.residual_channels)
+    if state is None:
+        state = torch.empty((max(need, 4),), dtype=torch.float32, device=dev)
+    _need(state, torch.float32, "state")
+    if state.numel() < need or not state.is_contiguous():
+        raise ValueError("state must be a contiguous float32 tensor of {} elements, got {}".format(need,
+                                                                                                   state.numel()))
+    out = torch.zeros((B, T), dtype=torch.float32 if wt.scalar_input else torch.int32, device=dev)
+    logits = torch.zeros((B, T, wt.out_channels), dtype=torch.float32, device=dev) if return_logits else None
+    _lib.check(L.itts_wavenet_generate(
+        _ptr(wt.wf), _ptr(wt.bf), _ptr(wt.w1), _ptr(wt.b1), _ptr(wt.w2), _ptr(wt.b2), _ptr(wt.wh1), _ptr(wt.bh1),
+        _ptr(wt.wh2), _ptr(wt.bh2), _c_ints(wt.dilations), len(wt.dilations), int(wt.kernel_size),
+        int(wt.residual_channels), int(wt.gate_channels), int(wt.skip_out_channels), int(wt.cin_channels),
+        int(wt.out_channels), int(bool(wt.scalar_input)), float(wt.log_scale_min), _ptr(c), Tc, _ptr(uniforms),
+        _c_ints(lengths), B, T, int(initial_class), _ptr(state), state.numel(), _ptr(out), _ptr(logits), _stream()),
+        "itts_wavenet_generate")
+    return (out, logits) if return_logits else out

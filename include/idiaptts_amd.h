@@ -1069,6 +1069,50 @@ int itts_mulaw_onehot(const double* d_x, const int64_t* h_begin, const int64_t* 
 int itts_sample_linearly(const void* d_x, int in_f64, const int64_t* h_offsets, int n_signals, int D, int m,
                          void* d_y, int out_f64, void* stream);
 
+/* ---- the WaveNet vocoder network (csrc/wavenet.hip; models/WaveNetWrapper.py:110-132 wraps the external
+ *      wavenet_vocoder package: the teacher-forced forward of :117 and the per-sample incremental_forward of :126).
+ *
+ * itts_glu_gate_fwd (WaveNetWrapper.py:110-132, the gate of a residual layer inside :117): z [N, G / 2] =
+ *   tanh(a + ca) * sigmoid(b + cb) from x [N, G] = a | b and the optional c [N, G] = ca | cb (NULL: absent); row
+ *   pitches in floats.  float4 rows when G / 2 and every pitch are multiples of 4 and the bases 16-byte aligned, the
+ *   scalar form otherwise.  G even and >= 2.
+ * itts_glu_gate_bwd (WaveNetWrapper.py:110-132): dx [N, G] from dz [N, G / 2], recomputed from the same x and c; dx
+ *   is also the gradient of c.
+ * itts_wavenet_state_floats (WaveNetWrapper.py:110-132): floats of the ring-buffer scratch itts_wavenet_generate needs
+ *   for B rows: ceil(B / 16) * sum_l ((kernel_size - 1) * dilation_l + 1) * 16 * residual_channels; -1 (and a
+ *   message) for a geometry outside the envelope below.
+ * itts_wavenet_generate (WaveNetWrapper.py:110-132, the incremental_forward of :126 for whole batches): every sample
+ *   of every row in one launch; one workgroup per 16 rows, no synchronisation beyond the workgroup barrier.  Weights
+ *   are the EFFECTIVE ones (weight norm applied), packed by the caller: an operand W [K, N] (K, N multiples of 16,
+ *   zero filled) as image[K / 16][N / 16][64][4] with image[kb][tile][lane][j] = W[16 kb + 4 (lane >> 4) + j]
+ *   [16 tile + (lane & 15)].
+ *     d_wf [Cin0, R], d_bf [R]: first conv, row c = the weight column of class c (Cin0 = out_channels; scalar_input:
+ *       Cin0 = 1);
+ *     d_w1 [layers] images of [kernel_size R + cin16, G] (rows j R + r: tap j of conv, the tap at t - (kernel_size -
+ *       1 - j) dilation; rows kernel_size R + i: conv1x1c; cin16 = cin rounded up to 16), d_b1 [layers, G];
+ *     d_w2 [layers] images of [G / 2, R + S] (columns: conv1x1_out | conv1x1_skip), d_b2 [layers, R + S];
+ *     d_wh1 image of [S, S], d_bh1 [S]; d_wh2 image of [S, C16], d_bh2 [C16] (C16 = out_channels rounded up to 16).
+ *   d_c [B, Tc, cin] conditioning at the sample rate (NULL with cin 0), d_u the uniforms ([B, T_out], scalar_input:
+ *   [B, T_out, 2], in (0, 1)), h_lengths [B] host, each 0 .. T_out.  d_out [B, T_out]: int32 classes, or float
+ *   samples with scalar_input (then the output is 3 K mixture-of-logistics parameters); d_logits [B, T_out,
+ *   out_channels] or NULL.  Only positions t < h_lengths[b] are written.  initial_class: the class fed at step 0, -1
+ *   for the all-zero input.  A row's bits do not depend on B or its position; repeated calls give identical bits.
+ *   Envelope (anything else: ITTS_E_INVALID with a message, before any device work): kernel_size 2 or 3; R and S
+ *   multiples of 16 up to 512; G a multiple of 32 up to 512; cin 0 .. 128; out_channels 2 .. 256, scalar_input:
+ *   3 K with K <= 64; layers 1 .. 64; dilations 1 .. 512. */
+int itts_glu_gate_fwd(const float* d_x, int64_t ldx, const float* d_c, int64_t ldc, float* d_z, int64_t ldz, int64_t N,
+                      int G, void* stream);
+int itts_glu_gate_bwd(const float* d_dz, int64_t lddz, const float* d_x, int64_t ldx, const float* d_c, int64_t ldc,
+                      float* d_dx, int64_t lddx, int64_t N, int G, void* stream);
+int64_t itts_wavenet_state_floats(int B, int layers, int kernel_size, int residual_channels, const int* h_dilations);
+int itts_wavenet_generate(const float* d_wf, const float* d_bf, const float* d_w1, const float* d_b1,
+                          const float* d_w2, const float* d_b2, const float* d_wh1, const float* d_bh1,
+                          const float* d_wh2, const float* d_bh2, const int* h_dilations, int layers, int kernel_size,
+                          int residual_channels, int gate_channels, int skip_channels, int cin_channels,
+                          int out_channels, int scalar_input, double log_scale_min, const float* d_c, int64_t Tc,
+                          const float* d_u, const int* h_lengths, int B, int64_t T_out, int initial_class,
+                          float* d_state, int64_t state_floats, void* d_out, float* d_logits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
