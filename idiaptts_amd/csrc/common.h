@@ -48,6 +48,9 @@ static inline hipError_t itts_spin_sync(hipStream_t s) {
 
 constexpr int kWave = 64;  // gfx950 wavefront
 
+// one step of a butterfly sum: v plus the value of the lane whose number differs in the bits of mask
+__device__ __forceinline__ double xor_sum(double v, int mask) { return v + __shfl_xor(v, mask, 64); }
+
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);

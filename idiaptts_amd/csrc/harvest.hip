@@ -13,9 +13,9 @@
 //   hv_raw_kernel         per (channel, frame): mean of the four interpolated interval-f0
 //   hv_detect_kernel      per frame: runs of >= 10 voiced channels -> candidates
 //   hv_refine_kernel      per (frame, candidate incl. the +-3 frame overlap): instantaneous-
-//                         frequency refinement.  Only <= 6 harmonic bins of each windowed segment
-//                         are ever read, so the two FFTs per candidate are replaced by a direct
-//                         evaluation of those bins (one wave per candidate)
+//                         frequency refinement (f0_refine.h, shared with StoneMask: direct DFT sums
+//                         at the <= 6 harmonic bins instead of two FFTs), one wave per frame, then
+//                         the candidate's score
 //   hv_remove_kernel      candidates without a neighbour within 5 % in the adjacent frames
 //   hv_contour*_kernel    FixF0Contour steps 1-4 (sections extend in parallel, the merge walks
 //                         them in order) and the zero-phase 2nd-order smoothing per section
@@ -25,6 +25,7 @@
 
 #include "context.h"
 #include "world_dev.h"
+#include "f0_refine.h"
 
 namespace itts {
 using namespace wd;
@@ -481,24 +482,29 @@ __global__ __launch_bounds__(NT) void hv_detect_kernel(const HvUtt* __restrict__
 
 // ---- GetRefinedF0 for every (frame, candidate slot) --------------------------------------------------------
 // Slot j of frame i: column j % nc0 of frame i + shift(j / nc0), shift = 0,-1,-2,-3,+1,+2,+3
-// (OverlapF0Candidates).  One wave per frame walks the slots.  Per slot: (1) the Blackman-type
-// window on the wave's lanes (one sincos per lane, then rotations), (2) windowed / derivative-
-// windowed samples to LDS, (3) lanes regroup as 8 harmonics x 8 sample phases and accumulate the
-// harmonic bins of both spectra, (4) two short butterfly reductions.
-__device__ __forceinline__ double hv_xor_sum(double v, int mask) { return v + __shfl_xor(v, mask, 64); }
+// (OverlapF0Candidates).  One wave per frame walks the slots; per slot the three steps of f0_refine.h
+// (shared with StoneMask) with the lanes as 8 harmonics x 8 sample phases, then Harvest's score and gate.
 
 // The window's two rotations (by 64 samples and by one) depend on the half width hw only: tabulated per
 // call with the expressions the refinement used per slot (same values bit for bit), so that a slot
-// costs one sincospi instead of three.  rot[hw] = {sin, cos of 2 pi 64 / bl; sin, cos of 2 pi / bl}.
+// costs one sincospi instead of three.
 __global__ __launch_bounds__(64) void hv_rot_table_kernel(double fs, int hw_max, double4* __restrict__ rot) {
   const int hw = blockIdx.x * 64 + threadIdx.x;
   if (hw > hw_max) return;
-  const double wlt = (2.0 * hw + 1.0) / fs;
-  double rs, rc, ds1, dc1;
-  sincospi(2.0 * 64.0 / (fs * wlt), &rs, &rc);
-  sincospi(2.0 / (fs * wlt), &ds1, &dc1);
-  rot[hw] = make_double4(rs, rc, ds1, dc1);
+  rot[hw] = f0r::window_rotations(fs, (2.0 * hw + 1.0) / fs);
 }
+
+// The DFT factors of one lane's bin, sample after sample, from the LDS copy of the whole circle (a frame has
+// many slots to pay for it): a byte offset that wraps by a mask, no case split.
+struct HvFactor {
+  const char* twb;
+  uint32_t mb, stepb, maskb;
+  __device__ __forceinline__ double2 operator()() {
+    const double2 w = *reinterpret_cast<const double2*>(twb + mb);
+    mb = (mb + stepb) & maskb;
+    return w;
+  }
+};
 
 __global__ __launch_bounds__(NT) void hv_refine_kernel(const HvUtt* __restrict__ utts, HvParams p,
                                                        const double2* __restrict__ g_tw,
@@ -563,98 +569,19 @@ __global__ __launch_bounds__(NT) void hv_refine_kernel(const HvUtt* __restrict__
     const int tstride = p.fft_max >> lg;
     const double bt0 = (double)(-hw) / fs;
     const int basic = mround((pos + bt0) * fs + 0.001);
-    {  // window theta_k = 2 pi t_k / wlt, t_k = (basic + k - 1) / fs - pos: one sincos per lane, then
-       // rotations by 64 samples; the neighbours the derivative window needs are rotations by one
-      const double t = ((basic + lane) - 1.0) / fs - pos;
-      double sn, cs;
-      sincospi(2.0 * t / wlt, &sn, &cs);
-      const double4 rt = rot[hw];
-      const double rs = rt.x, rc = rt.y, ds1 = rt.z, dc1 = rt.w;
-      auto win = [](double c) { return 0.42 + 0.5 * c + 0.08 * (2.0 * c * c - 1.0); };
-      // four rows of 64 samples at a time, their loads in flight together (one trip to the cache per
-      // slot for windows of up to 256 samples instead of one per row)
-      for (int k0 = lane; k0 < bl; k0 += 256) {
-        double xq[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          int si = basic + (k0 + 64 * q) - 1;
-          si = si < 0 ? 0 : (si > u.yl - 1 ? u.yl - 1 : si);
-          xq[q] = y[si];
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int k = k0 + 64 * q;
-          if (k < bl) {
-            const double xv = xq[q];
-            const double mw = win(cs);
-            const double up = win(cs * dc1 - sn * ds1), dn = win(cs * dc1 + sn * ds1);  // mw[k + 1], mw[k - 1]
-            double dw;
-            if (k == 0) dw = -up / 2.0;
-            else if (k == bl - 1) dw = dn / 2.0;
-            else dw = -(up - dn) / 2.0;
-            wsamp[k] = make_double2(xv * mw, xv * dw);
-            const double c2 = cs * rc - sn * rs;
-            sn = sn * rc + cs * rs;
-            cs = c2;
-          }
-        }
-      }
-    }
+    // window angle of sample k: 2 t_k / wlt half turns, t_k = (basic + k - 1) / fs - pos
+    const double t = ((basic + lane) - 1.0) / fs - pos;
+    f0r::window_pass(2.0 * t / wlt, rot[hw], bl, lane,
+                     [&](int k) { return f0r::edge_sample(y, basic + k - 1, u.yl); }, wsamp);
     const int nh = min((int)(fs / 2.0 / f0), 6);
     const int idx = min(mround(f0 * fft / fs * (hh + 1)), fft / 2);
-    double mr = 0.0, mi = 0.0, dr = 0.0, di = 0.0;
-    if (hh < nh) {
-      // factor of sample k and bin idx: entry (idx k mod fft) * tstride of the circle, walked as a byte
-      // offset; four samples per trip with their LDS reads in flight together, the sums keep their
-      // order in k
-      const uint32_t maskb = (uint32_t)p.fft_max * 16u - 1u;
-      const uint32_t stepb = (uint32_t)(((idx * 8) & (fft - 1)) * tstride) * 16u;
-      uint32_t mb = (uint32_t)(((idx * g) & (fft - 1)) * tstride) * 16u;
-      const char* twb = reinterpret_cast<const char*>(tw);
-      auto factor = [&](uint32_t ofs) { return *reinterpret_cast<const double2*>(twb + ofs); };
-      int k = g;
-      for (; k + 24 < bl; k += 32) {
-        const uint32_t m1 = (mb + stepb) & maskb, m2 = (m1 + stepb) & maskb, m3 = (m2 + stepb) & maskb;
-        const double2 w0 = factor(mb), w1 = factor(m1), w2 = factor(m2), w3 = factor(m3);
-        const double2 s0 = wsamp[k], s1 = wsamp[k + 8], s2 = wsamp[k + 16], s3 = wsamp[k + 24];
-        mb = (m3 + stepb) & maskb;
-        mr += s0.x * w0.x; mi += s0.x * w0.y; dr += s0.y * w0.x; di += s0.y * w0.y;
-        mr += s1.x * w1.x; mi += s1.x * w1.y; dr += s1.y * w1.x; di += s1.y * w1.y;
-        mr += s2.x * w2.x; mi += s2.x * w2.y; dr += s2.y * w2.x; di += s2.y * w2.y;
-        mr += s3.x * w3.x; mi += s3.x * w3.y; dr += s3.y * w3.x; di += s3.y * w3.y;
-      }
-      for (; k < bl; k += 8) {
-        const double2 w0 = factor(mb);
-        const double2 s0 = wsamp[k];
-        mb = (mb + stepb) & maskb;
-        mr += s0.x * w0.x; mi += s0.x * w0.y; dr += s0.y * w0.x; di += s0.y * w0.y;
-      }
-    }
-#pragma unroll
-    for (int mask = 1; mask < 8; mask <<= 1) {
-      mr = hv_xor_sum(mr, mask);
-      mi = hv_xor_sum(mi, mask);
-      dr = hv_xor_sum(dr, mask);
-      di = hv_xor_sum(di, mask);
-    }
-    double num = 0.0, den = 0.0, sc = 0.0;
-    if (hh < nh) {
-      const double ps = mr * mr + mi * mi;
-      const double ni = mr * di - mi * dr;
-      const double inst = ps == 0.0 ? 0.0 : (double)idx * fs / fft + ni / ps * fs / 2.0 / kPi;
-      const double amp = sqrt(ps);
-      num = amp * inst;
-      den = amp * (hh + 1.0);
-      sc = fabs((inst / (hh + 1.0) - f0) / f0);
-    }
-#pragma unroll
-    for (int mask = 8; mask < 64; mask <<= 1) {
-      num = hv_xor_sum(num, mask);
-      den = hv_xor_sum(den, mask);
-      sc = hv_xor_sum(sc, mask);
-    }
-    double rf = num / (den + kEps);
-    double rs = 1.0 / (sc / nh + kEps);
+    // factor of sample k and bin idx: entry (idx k mod fft) * tstride of the circle, walked as a byte offset
+    const HvFactor factor{reinterpret_cast<const char*>(tw), (uint32_t)(((idx * g) & (fft - 1)) * tstride) * 16u,
+                          (uint32_t)(((idx * 8) & (fft - 1)) * tstride) * 16u, (uint32_t)p.fft_max * 16u - 1u};
+    const f0r::Spectra sp = f0r::harmonic_sums<3>(wsamp, bl, lane, hh < nh, factor);
+    const f0r::Refined r = f0r::refined_f0<3, true>(sp, hh < nh, idx, hh, fs, fft, f0);
+    double rf = r.f0;
+    double rs = 1.0 / (r.dev / nh + kEps);
     if (rf < p.f0_floor || rf > p.f0_ceil || rs < 2.5) {
       rf = 0.0;
       rs = 0.0;

@@ -3,18 +3,21 @@
 // Replaces the StoneMask and D4C stages of pyworld.wav2world
 // (src/data_preparation/world/WorldFeatLabelGen.py:792-793; also LF0LabelGen.py:263-264 for
 // stonemask) -- WORLD stonemask.cpp (two-stage refinement) and d4c.cpp (LoveTrain V/UV,
-// threshold 0.85).  One 256-thread workgroup per frame.
+// threshold 0.85).
 //
-// StoneMask only needs the spectra of the two windowed segments at <= 2 + 6 harmonic bins, so
-// the FFTs are replaced by direct DFT sums at those bins (twiddles from the same master table)
-// -- no LDS FFT buffer, any f0-dependent FFT size.  D4C keeps every spectrum in LDS.
+// StoneMask: one wave per frame.  It only needs the spectra of the two windowed segments at <= 2 + 6
+// harmonic bins, so the FFTs are replaced by direct DFT sums at those bins (twiddles from the same
+// master table) -- no LDS FFT buffer, any f0-dependent FFT size.  The refinement math (GetRefinedF0) is
+// f0_refine.h, shared with Harvest.  D4C: one 256-thread workgroup per frame, every spectrum in LDS.
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
 #include <cmath>
+#include <type_traits>
 
 #include "context.h"
 #include "world_dev.h"
+#include "f0_refine.h"
 #include "select_largest.h"
 
 namespace itts {
@@ -51,115 +54,23 @@ struct SmArgs {
   int nmax;  // LDS capacity (samples) per windowed segment
 };
 
-__global__ __launch_bounds__(NT) void stonemask_kernel(SmArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  double* sm = reinterpret_cast<double*>(smem);  // x * main window
-  double* sd = sm + a.nmax;                       // x * diff window
-  double* mw = sd + a.nmax;                       // main window
-  double* red = mw + a.nmax;                      // 4 * 32 doubles
-  const int64_t g = blockIdx.x;
-  const int u = find_utt_wave(a.f_off, a.n_utts, g);
-  const double* x = a.x + a.x_off[u];
-  const int64_t xl = a.x_off[u + 1] - a.x_off[u];
-  const int fs = a.fs;
-  const double f0 = a.f0_in[g];
-  const double pos = (double)(g - a.f_off[u]) * a.frame_period / 1000.0;
-  if (f0 <= 40.0 || f0 > fs / 12.0) {
-    if (threadIdx.x == 0) a.f0_out[g] = 0.0;
-    return;
+// The DFT factors of one lane's bin, sample after sample: a gather from the 128-KB master table (a trip to the
+// L2 each) -- a frame has two passes over its segment, too few to pay for an LDS copy of the table.
+struct SmFactor {
+  const double2* g_tw;
+  int k, step, fft;   // k = bin * sample mod fft, advancing by step = bin * phases mod fft
+  __device__ __forceinline__ double2 operator()() {
+    const double2 w = twiddle_neg(g_tw, k, fft);
+    k += step;
+    if (k >= fft) k -= fft;
+    return w;
   }
-  const int half = (int)(1.5 * fs / f0 + 1.0);
-  const double wlt = (2.0 * half + 1.0) / fs;
-  const int n = 2 * half + 1;
-  const int fft = 1 << (2 + (int)(log(half * 2.0 + 1.0) / log(2.0)));
-  const int64_t i0 = mround((pos - (double)half / fs) * fs + 0.001);
-  for (int i = threadIdx.x; i < n; i += NT) {
-    const double tmp = ((double)(i0 + i) - 1.0) / fs - pos;
-    mw[i] = 0.42 + 0.5 * cos(2.0 * kPi * tmp / wlt) + 0.08 * cos(4.0 * kPi * tmp / wlt);
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < n; i += NT) {
-    double dw;
-    if (i == 0) dw = -mw[1] / 2.0;
-    else if (i == n - 1) dw = mw[n - 2] / 2.0;
-    else dw = -(mw[i + 1] - mw[i - 1]) / 2.0;
-    int64_t idx = i0 + i - 1;
-    idx = idx < 0 ? 0 : (idx > xl - 1 ? xl - 1 : idx);
-    const double xv = x[idx];
-    sm[i] = xv * mw[i];
-    sd[i] = xv * dw;
-  }
-  __syncthreads();
+};
 
-  // spectra (main M, diff D) at `nh` harmonic bins of `base`: direct DFT sums
-  auto refine = [&](double base, int nh) -> double {
-    int bins[6];
-    double acc[24];
-#pragma unroll
-    for (int q = 0; q < 24; ++q) acc[q] = 0.0;
-#pragma unroll
-    for (int hq = 0; hq < 6; ++hq) bins[hq] = hq < nh ? mround(base * fft / fs * (hq + 1)) : 0;
-    for (int i = threadIdx.x; i < n; i += NT) {
-      const double vm = sm[i], vd = sd[i];
-#pragma unroll
-      for (int hq = 0; hq < 6; ++hq) {
-        if (hq < nh) {
-          const int k = (int)(((long long)bins[hq] * i) % fft);
-          const double2 w = twiddle_neg(a.g_tw, k, fft);
-          acc[4 * hq + 0] += vm * w.x;
-          acc[4 * hq + 1] += vm * w.y;
-          acc[4 * hq + 2] += vd * w.x;
-          acc[4 * hq + 3] += vd * w.y;
-        }
-      }
-    }
-    // block reduction of 4*nh values
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 24; ++q) {
-      if (q < 4 * nh) {
-        const double v = wave_sum(acc[q]);
-        if (lane == 0) red[wv * 32 + q] = v;
-      }
-    }
-    __syncthreads();
-    double num_sum = 0.0, den_sum = 0.0;
-    for (int hq = 0; hq < nh; ++hq) {
-      double v[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-        v[c] = (red[4 * hq + c] + red[32 + 4 * hq + c]) + (red[64 + 4 * hq + c] + red[96 + 4 * hq + c]);
-      const double Mr = v[0], Mi = v[1], Dr = v[2], Di = v[3];
-      const double numer = Mr * Di - Mi * Dr;
-      const double ps = Mr * Mr + Mi * Mi;
-      const int idx = bins[hq];
-      const double inst = ps == 0.0 ? 0.0 : (double)idx * fs / fft + numer / ps * fs / 2.0 / kPi;
-      const double amp = sqrt(ps);
-      num_sum += amp * inst;
-      den_sum += amp * (hq + 1);
-    }
-    return num_sum / (den_sum + kEps);
-  };
-
-  const double t = refine(f0, 2);
-  double mean = 0.0;
-  if (!(t <= 0.0 || t > f0 * 2)) {
-    int nh = (int)(fs / 2.0 / f0);
-    if (nh > 6) nh = 6;
-    mean = refine(t, nh);
-  }
-  if (threadIdx.x == 0) a.f0_out[g] = fabs(mean - f0) > f0 * 0.2 ? f0 : mean;
-}
-
-// One WAVE per frame (SM_WAVES frames per workgroup, no workgroup barriers): the windowed and
-// derivative-windowed samples go to the wave's LDS block once (window by one sincos per lane and
-// rotations), then both refinement passes regroup the lanes as harmonics x sample phases
-// (2 x 32 for the first pass, 8 x 8 for the second) so that the spectra at the harmonic bins need
-// one short butterfly reduction instead of a workgroup-wide one.  Same sums as stonemask_kernel in
-// a different order.
-__device__ __forceinline__ double sm_xor_sum(double v, int mask) { return v + __shfl_xor(v, mask, 64); }
-
+// One WAVE per frame (`waves` frames per workgroup, no workgroup barriers): the windowed and
+// derivative-windowed samples go to the wave's LDS block once, then both refinement passes of StoneMask regroup
+// the lanes as harmonics x sample phases (2 x 32 for the first pass at f0, 8 x 8 for the second at the first's
+// result) -- f0_refine.h.
 // f0_from / f0_to: the launch takes the frames with f0_from < f0 <= f0_to (their windows fit its LDS blocks: a.nmax is
 // sized for f0_from); frames outside (40 Hz, fs / 12] get their zero from the launch with f0_to = infinity.
 __global__ __launch_bounds__(NT) void stonemask_wave_kernel(SmArgs a, int waves, double f0_from, double f0_to) {
@@ -168,8 +79,7 @@ __global__ __launch_bounds__(NT) void stonemask_wave_kernel(SmArgs a, int waves,
   if (wv >= waves) return;
   const int64_t g = (int64_t)blockIdx.x * waves + wv;
   if (g >= a.f_off[a.n_utts]) return;
-  double* sm = reinterpret_cast<double*>(smem) + (size_t)wv * 2 * a.nmax;  // x * main window
-  double* sd = sm + a.nmax;                                                  // x * diff window
+  double2* ws = reinterpret_cast<double2*>(smem) + (size_t)wv * a.nmax;  // (x * main window, x * diff window)
   const int u = find_utt_wave(a.f_off, a.n_utts, g);
   const double* x = a.x + a.x_off[u];
   const int64_t xl = a.x_off[u + 1] - a.x_off[u];
@@ -186,111 +96,24 @@ __global__ __launch_bounds__(NT) void stonemask_wave_kernel(SmArgs a, int waves,
   const int n = 2 * half + 1;
   const int fft = 1 << (2 + ilog2(n));   // n is odd: floor(log2) is exact
   const int64_t i0 = mround((pos - (double)half / fs) * fs + 0.001);
-  {
-    const double tmp = ((double)(i0 + lane) - 1.0) / fs - pos;
-    double sn, cs, rs, rc, ds1, dc1;
-    sincospi(2.0 * tmp / wlt, &sn, &cs);
-    sincospi(2.0 * 64.0 / (fs * wlt), &rs, &rc);
-    sincospi(2.0 / (fs * wlt), &ds1, &dc1);
-    auto win = [](double c) { return 0.42 + 0.5 * c + 0.08 * (2.0 * c * c - 1.0); };
-    // four rows of 64 samples per trip, their loads in flight together
-    for (int ib = lane; ib < n; ib += 256) {
-      double xq[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        int64_t idx = i0 + (ib + 64 * q) - 1;
-        idx = idx < 0 ? 0 : (idx > xl - 1 ? xl - 1 : idx);
-        xq[q] = x[idx];
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int i = ib + 64 * q;
-        if (i < n) {
-          const double xv = xq[q];
-          const double mw = win(cs);
-          const double up = win(cs * dc1 - sn * ds1), dn = win(cs * dc1 + sn * ds1);
-          double dw;
-          if (i == 0) dw = -up / 2.0;
-          else if (i == n - 1) dw = dn / 2.0;
-          else dw = -(up - dn) / 2.0;
-          sm[i] = xv * mw;
-          sd[i] = xv * dw;
-          const double c2 = cs * rc - sn * rs;
-          sn = sn * rc + cs * rs;
-          cs = c2;
-        }
-      }
-    }
-  }
-  // spectra (main M, diff D) at `nh` harmonic bins of `base`; lanes = 2^hb harmonics x 2^(6-hb) phases
-  auto refine = [&](double base, int nh, int hb) -> double {
-    const int pbits = 6 - hb, phases = 1 << pbits;
-    const int hq = lane >> pbits, ph = lane & (phases - 1);
+  const double tmp = ((double)(i0 + lane) - 1.0) / fs - pos;
+  f0r::window_pass(2.0 * tmp / wlt, f0r::window_rotations(fs, wlt), n, lane,
+                   [&](int i) { return f0r::edge_sample(x, i0 + i - 1, xl); }, ws);
+  // spectra at `nh` harmonic bins of `base`; lanes = 2^HB harmonics x 2^(6-HB) phases
+  auto refine = [&](double base, int nh, auto hb) -> double {
+    constexpr int HB = decltype(hb)::value;
+    const int hq = lane >> (6 - HB), ph = lane & ((1 << (6 - HB)) - 1);
     const int bin = hq < nh ? mround(base * fft / fs * (hq + 1)) : 0;
-    double mr = 0.0, mi = 0.0, dr = 0.0, di = 0.0;
-    if (hq < nh) {
-      const int step = (int)(((long long)bin * phases) % fft);
-      int k = (int)(((long long)bin * ph) % fft);
-      // four samples per trip: their factors (a gather from the 128-KB master table: a trip to the L2
-      // each) and samples are requested together; the sums keep their order in i
-      int i = ph;
-      for (; i + 3 * phases < n; i += 4 * phases) {
-        double2 w[4];
-        double vm[4], vd[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          w[q] = twiddle_neg(a.g_tw, k, fft);
-          vm[q] = sm[i + q * phases];
-          vd[q] = sd[i + q * phases];
-          k += step;
-          if (k >= fft) k -= fft;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          mr += vm[q] * w[q].x;
-          mi += vm[q] * w[q].y;
-          dr += vd[q] * w[q].x;
-          di += vd[q] * w[q].y;
-        }
-      }
-      for (; i < n; i += phases) {
-        const double2 w = twiddle_neg(a.g_tw, k, fft);
-        const double vm = sm[i], vd = sd[i];
-        mr += vm * w.x;
-        mi += vm * w.y;
-        dr += vd * w.x;
-        di += vd * w.y;
-        k += step;
-        if (k >= fft) k -= fft;
-      }
-    }
-    for (int mask = 1; mask < phases; mask <<= 1) {
-      mr = sm_xor_sum(mr, mask);
-      mi = sm_xor_sum(mi, mask);
-      dr = sm_xor_sum(dr, mask);
-      di = sm_xor_sum(di, mask);
-    }
-    double num = 0.0, den = 0.0;
-    if (hq < nh) {
-      const double numer = mr * di - mi * dr;
-      const double ps = mr * mr + mi * mi;
-      const double inst = ps == 0.0 ? 0.0 : (double)bin * fs / fft + numer / ps * fs / 2.0 / kPi;
-      const double amp = sqrt(ps);
-      num = amp * inst;
-      den = amp * (hq + 1);
-    }
-    for (int mask = phases; mask < 64; mask <<= 1) {
-      num = sm_xor_sum(num, mask);
-      den = sm_xor_sum(den, mask);
-    }
-    return num / (den + kEps);
+    const SmFactor factor{a.g_tw, (int)(((long long)bin * ph) % fft), (int)(((long long)bin << (6 - HB)) % fft), fft};
+    const f0r::Spectra sp = f0r::harmonic_sums<HB>(ws, n, lane, hq < nh, factor);
+    return f0r::refined_f0<HB, false>(sp, hq < nh, bin, hq, fs, fft, base).f0;
   };
-  const double t = refine(f0, 2, 1);
+  const double t = refine(f0, 2, std::integral_constant<int, 1>());
   double mean = 0.0;
   if (!(t <= 0.0 || t > f0 * 2)) {
     int nh = (int)(fs / 2.0 / f0);
     if (nh > 6) nh = 6;
-    mean = refine(t, nh, 3);
+    mean = refine(t, nh, std::integral_constant<int, 3>());
   }
   if (lane == 0) a.f0_out[g] = fabs(mean - f0) > f0 * 0.2 ? f0 : mean;
 }
@@ -770,42 +593,36 @@ extern "C" int itts_stonemask(const double* d_x, const int64_t* h_x_off, const d
   if ((rc = upload_i64(h_f_off, n_utts + 1, &d_fo, s))) return rc;
   SmArgs a{d_x, d_xo, d_f0_in, d_fo, n_utts, fs, frame_period_ms, d_f0_out, ctx->twiddles, 0};
   a.nmax = 2 * (int)(1.5 * fs / 40.0 + 1.0) + 1 + 3;
-  const size_t per_wave = (size_t)a.nmax * 2 * 8;
-  if (per_wave <= 80 * 1024) {
-    // A wave's LDS block holds the window of its frame: 3 periods of f0.  The interface admits f0 down to 40 Hz
-    // (3 606 samples at 48 kHz: 58 KB per wave, one wave per workgroup, two per CU), DIO's floor is 71 Hz: the main
-    // launch is sized for f0 > 70 Hz (33 KB per wave at 48 kHz, 11 KB at 16 kHz: twice / 1.5 times the waves per CU)
-    // and a second launch with the long blocks takes the frames below -- none, after DIO; its waves then leave at once.
-    const double kSplit = 70.0;
-    const int64_t T = h_f_off[n_utts];
-    static std::atomic<int> lds_attr{0};
-    auto launch = [&](double from, double to) -> int {
-      SmArgs b = a;
-      b.nmax = 2 * (int)(1.5 * fs / from + 1.0) + 1 + 3;
-      const size_t pw = (size_t)b.nmax * 2 * 8;
-      // as many frames per workgroup as keep two workgroups on a CU
-      const int waves = (int)std::max<size_t>(1, std::min<size_t>(4, (80 * 1024) / pw));
-      const size_t lds = pw * waves;
-      if ((int)lds > lds_attr.load()) {
-        ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)stonemask_wave_kernel,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)(80 * 1024)));
-        lds_attr.store(80 * 1024);
-      }
-      hipLaunchKernelGGL(stonemask_wave_kernel, dim3((unsigned)((T + waves - 1) / waves)), dim3(64 * waves), lds,
-                         s, b, waves, from, to);
-      ITTS_LAUNCH_CHECK();
-      return ITTS_OK;
-    };
-    if ((rc = launch(kSplit, 1e308))) return rc;
-    if ((rc = launch(40.0, kSplit))) return rc;
-  } else {
-    const size_t lds = (size_t)a.nmax * 3 * 8 + 128 * 8;
-    ITTS_REQUIRE(lds <= 160 * 1024, "sampling rate too high for the StoneMask LDS budget");
-    ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)stonemask_kernel,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(stonemask_kernel, dim3((unsigned)h_f_off[n_utts]), dim3(NT), lds, s, a);
+  // A wave's LDS block holds the window of its frame: 3 periods of f0.  The interface admits f0 down to 40 Hz
+  // (3 606 samples at 48 kHz: 58 KB per wave, one wave per workgroup, two per CU), DIO's floor is 71 Hz: the main
+  // launch is sized for f0 > 70 Hz (33 KB per wave at 48 kHz, 11 KB at 16 kHz: twice / 1.5 times the waves per CU)
+  // and a second launch with the long blocks takes the frames below -- none, after DIO; its waves then leave at once.
+  // Where a long block is past 80 KB (from 68 214 Hz; 103 KB at 88.2 kHz) that launch has one wave per workgroup
+  // with the block as its whole LDS, up to the CU's 160 KB: sampling rates up to 136 479 Hz are accepted.
+  ITTS_REQUIRE((size_t)a.nmax * 2 * 8 <= 160 * 1024, "sampling rate too high for the StoneMask LDS budget");
+  const double kSplit = 70.0;
+  const int64_t T = h_f_off[n_utts];
+  static std::atomic<int> lds_attr{0};
+  auto launch = [&](double from, double to) -> int {
+    SmArgs b = a;
+    b.nmax = 2 * (int)(1.5 * fs / from + 1.0) + 1 + 3;
+    const size_t pw = (size_t)b.nmax * 2 * 8;
+    // as many frames per workgroup as keep two workgroups on a CU
+    const int waves = (int)std::max<size_t>(1, std::min<size_t>(4, (80 * 1024) / pw));
+    const size_t lds = pw * waves;
+    const int attr = (int)std::max<size_t>(lds, 80 * 1024);
+    if (attr > lds_attr.load()) {
+      ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)stonemask_wave_kernel,
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, attr));
+      lds_attr.store(attr);
+    }
+    hipLaunchKernelGGL(stonemask_wave_kernel, dim3((unsigned)((T + waves - 1) / waves)), dim3(64 * waves), lds,
+                       s, b, waves, from, to);
     ITTS_LAUNCH_CHECK();
-  }
+    return ITTS_OK;
+  };
+  if ((rc = launch(kSplit, 1e308))) return rc;
+  if ((rc = launch(40.0, kSplit))) return rc;
   ITTS_HIP_CHECK(itts::scratch_free(d_xo, s));
   ITTS_HIP_CHECK(itts::scratch_free(d_fo, s));
   return ITTS_OK;

@@ -253,15 +253,20 @@ def test_dio_stonemask_match_oracle(gpu, utts):
         assert np.abs(f0r[a:b] - f0_ref).max() < 1e-7
 
 
-@pytest.mark.parametrize("fs_name", ["16k", "48k"])
+@pytest.mark.parametrize("fs_name", ["16k", "48k", "88k"])
 def test_stonemask_below_dios_floor_takes_the_second_launch(gpu, utts, golden_dir, fs_name):
     """itts_stonemask sizes the LDS blocks of its main launch for f0 > 70 Hz (DIO's floor is 71 Hz) and gives the
     frames in (40 Hz, 70 Hz] -- which the interface admits and only a caller's own contour can hold -- to a second
-    launch with the long blocks: a contour with such frames (and some outside (40 Hz, fs / 12]) against the oracle."""
+    launch with the long blocks: a contour with such frames (and some outside (40 Hz, fs / 12]) against the oracle.
+    At 88.2 kHz a long block is 105 920 bytes: past the 80 KB that keep two workgroups on a CU, so that launch runs
+    one wave per workgroup with the block as its whole LDS (up to 160 KB)."""
     from idiaptts_amd import ops
     from oracle import capi
     if fs_name == "16k":
         xu, fs, _, tpu = utts[0]
+    elif fs_name == "88k":
+        fs = 88200
+        xu = _synthetic(fs, 0.6, 5)
     else:
         from scipy.io import wavfile
         fs, w = wavfile.read(os.path.join(golden_dir, "p225_001.wav"))      # the reference's own 48 kHz fixture
