@@ -254,6 +254,41 @@ class TimePoolFunction(torch.autograd.Function):
         return ops.time_pool_bwd(dy2, ctx.lens, ctx.t_max, ctx.batch_first, ctx.mode), None, None, None
 
 
+def _fa_operand(t):
+    """a [B, R, W] operand the fixed-attention kernels take as it is (unit stride on W, rows and utterances apart),
+    else a dense copy"""
+    B, R, W = t.shape
+    ok = (W <= 1 or t.stride(2) == 1) and (R <= 1 or t.stride(1) >= W) and \
+        (B <= 1 or t.stride(0) >= R * (t.stride(1) if R > 1 else W))
+    return t if ok else t.contiguous()
+
+
+class FixedAttentionFunction(torch.autograd.Function):
+    """(ctx [B, K, C], Abar [B, K, P]) of the attention matrix A [B, T, P] and the encoder output enc [B, P, C]
+    (enc_dec_dyn/attention/FixedAttention.py) on csrc/fixed_attention.hip.  A is a ground-truth input: it gets no
+    gradient, and Abar -- what the model returns as "attention" -- is not differentiable.  Saves Abar only."""
+
+    @staticmethod
+    def forward(ctx, A, enc, n_frames_per_step, partial_last):
+        context, abar = ops.fixed_attention(_fa_operand(A), _fa_operand(enc), n_frames_per_step, partial_last)
+        ctx.save_for_backward(abar)
+        ctx.mark_non_differentiable(abar)
+        return context, abar
+
+    @staticmethod
+    def backward(ctx, dctx, _dabar):
+        (abar,) = ctx.saved_tensors
+        return None, ops.fixed_attention_bwd(abar, _fa_operand(dctx)), None, None
+
+
+def fixed_attention(A, enc, n_frames_per_step=1, partial_last=False):
+    """-> (context, Abar) with the gradient of context flowing into enc; an A that requires grad is refused"""
+    if A.requires_grad:
+        raise ValueError("fixed_attention: A.requires_grad is set, but the attention matrix is a ground-truth input "
+                         "and has no gradient")
+    return FixedAttentionFunction.apply(A, enc, int(n_frames_per_step), bool(partial_last))
+
+
 def _rows2(t, width):
     """[.., width] -> [M, width] rows the kernels take (unit stride on the last extent, rows not overlapping)"""
     t2 = t.reshape(-1, width)

@@ -275,15 +275,25 @@ def _unpad_rows(x, ndir, H, Hp):
     return x.reshape(x.shape[0], ndir, Hp)[:, :, :H].reshape(x.shape[0], ndir * H)
 
 
+def _rows_share_state(h):
+    """whether all rows of the state h [layers*dirs, B, H] are one row (None: the zero state)"""
+    if h is None or h.shape[1] == 1 or h.stride(1) == 0 or getattr(h, "_itts_rows_shared", False):
+        return True
+    if getattr(h, "_itts_rows_own", False):      # (what a step returned: no comparison on the device, no wait)
+        return False
+    return bool((h == h[:, :1]).all())
+
+
 def _shared_initial_state(h):
     """The recurrence kernels take ONE initial state per layer and direction, shared by all rows
     (what RNNWrapper.init_hidden passes: a [.., 1, H] vector expanded over the batch).  Anything
-    else would silently be replaced by row 0's state, so it is refused."""
-    if h is None or h.shape[1] == 1 or h.stride(1) == 0 or getattr(h, "_itts_rows_shared", False):
-        return
-    if not bool((h == h[:, :1]).all()):
-        raise NotImplementedError("Per-sequence initial states are not implemented: all rows of "
-                                  "hx must be equal (expand one [layers*dirs, 1, H] state).")
+    else would silently be replaced by row 0's state, so it is refused.  (One frame on per-row states runs on the
+    cell kernel instead: _RNNBase._step_forward.)"""
+    if not _rows_share_state(h):
+        raise NotImplementedError("Per-sequence initial states are implemented for one time step without gradients "
+                                  "only (the step of an autoregressive decoder): all rows of hx must be equal (expand "
+                                  "one [layers*dirs, 1, H] state) for longer inputs or under autograd.  "
+                                  "Scheduled-sampling training is the follow-up.")
 
 
 class _RNNBase(nn.Module):
@@ -335,11 +345,55 @@ class _RNNBase(nn.Module):
             x = torch.nn.functional.dropout(x, self.dropout, True)
         return x
 
+    _cell_kind = None        # ops.CELL_*
+
+    def _step_forward(self, input_, h0s, lengths):
+        """One frame for every row from the row's OWN state (the step of an autoregressive decoder, which comes back
+        with the states its last call returned): per layer and direction the two products on the dense GEMM and the
+        cell on csrc/rnn_cell.hip.  No autograd.  With one frame the backward direction's output is its first step,
+        so both directions step from their [B, H] slice of the state.  -> what _recurrent_forward returns."""
+        ndir = 2 if self.bidirectional else 1
+        B, H = input_.shape[0 if self.batch_first else 1], self.hidden_size
+        if lengths is not None and not (torch.is_tensor(lengths) and lengths.is_cuda) \
+                and any(int(n) != 1 for n in lengths):
+            raise ValueError("a step on per-row states takes one frame of every row: lengths must be all 1")
+        with torch.no_grad():
+            x = input_.reshape(B, input_.shape[-1]).contiguous()
+            states = [h if h is not None else x.new_zeros(self.num_layers * ndir, B, H) for h in h0s]
+            finals = [[] for _ in h0s]
+            act = self._layer_extra[0] if self._layer_extra else ops.ACT_NONE
+            for layer in range(self.num_layers):
+                outs = []
+                for d in range(ndir):
+                    sfx = "_l{}{}".format(layer, "_reverse" if d == 1 else "")
+                    b_ih, b_hh = getattr(self, "bias_ih" + sfx), getattr(self, "bias_hh" + sfx)
+                    gru = self._cell_kind == ops.CELL_GRU
+                    gi = ops.linear_fwd(x, getattr(self, "weight_ih" + sfx).contiguous(),
+                                        b_ih if gru else b_ih + b_hh)
+                    h = states[0][layer * ndir + d].contiguous()
+                    gh = ops.linear_fwd(h, getattr(self, "weight_hh" + sfx).contiguous(), None)
+                    c = states[1][layer * ndir + d].contiguous() if len(states) > 1 else None
+                    h, c = ops.rnn_cell_step(self._cell_kind, gi, gh, h, c, b_hh if gru else None, act)
+                    outs.append(h)
+                    finals[0].append(h)
+                    if c is not None:
+                        finals[1].append(c)
+                x = self._dropout(outs[0] if ndir == 1 else torch.cat(outs, dim=1), layer)
+            out = x.reshape(input_.shape[:-1] + (ndir * H,))
+            finals = [torch.stack(f, dim=0) for f in finals]
+            for f in finals:
+                f._itts_rows_own = True
+            return out, finals
+
     def _recurrent_forward(self, input_, h0s, lengths):
         """The layers on the recurrence kernels: h0s = the initial states ((h_0, c_0) / (h_0,), each
         [num_layers*ndir, B, H] or None) -> (output, the final states, each [num_layers*ndir, B, H] in the
         caller's row order)."""
         ndir = 2 if self.bidirectional else 1
+        if input_.shape[1 if self.batch_first else 0] == 1 and not all(_rows_share_state(h) for h in h0s) \
+                and not (torch.is_grad_enabled() and (input_.requires_grad or any(
+                    t.requires_grad for t in list(self.parameters()) + [h for h in h0s if h is not None]))):
+            return self._step_forward(input_, h0s, lengths)
         pb, x = self._pack(input_, lengths, pad_cols=True)
         for h in h0s:
             _shared_initial_state(h)
@@ -376,6 +430,7 @@ class LSTM(_RNNBase):
     with output zero-padded to the input's time extent (pad_packed_sequence(total_length=...))."""
     _gates = 4
     _layer_function = LSTMLayerFunction
+    _cell_kind = ops.CELL_LSTM
 
     def forward(self, input_, hx=None, lengths=None):
         out, (hn, cn) = self._recurrent_forward(input_, hx if hx is not None else (None, None), lengths)
@@ -388,6 +443,7 @@ class GRU(_RNNBase):
         output, h_n = gru(padded, h_0, lengths)"""
     _gates = 3
     _layer_function = GRULayerFunction
+    _cell_kind = ops.CELL_GRU
 
     def forward(self, input_, hx=None, lengths=None):
         out, (hn,) = self._recurrent_forward(input_, (hx,), lengths)
@@ -403,6 +459,7 @@ class RNN(_RNNBase):
     the recurrence runs on the step kernels of csrc/rnn_step.h (one launch per time step, both directions in it) at
     the hidden size rounded up to a multiple of 16.  Unlike LSTM / GRU, a loss may use h_n."""
     _layer_function = RNNLayerFunction
+    _cell_kind = ops.CELL_RNN
     _persistent = False
 
     def __init__(self, input_size, hidden_size, num_layers=1, nonlinearity='tanh', bias=True,

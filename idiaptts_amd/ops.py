@@ -2252,3 +2252,128 @@ def wavenet_generate(weights, c, lengths, uniforms, initial_class=-1, return_log
         _c_ints(lengths), B, T, int(initial_class), _ptr(state), state.numel(), _ptr(out), _ptr(logits), _stream()),
         "itts_wavenet_generate")
     return (out, logits) if return_logits else out
+
+
+FIXED_ATTENTION_MAX_P, FIXED_ATTENTION_MAX_C, FIXED_ATTENTION_MAX_N = 2048, 4096, 64     # csrc/fixed_attention.hip
+
+
+def fixed_attention_plan(B, T, P, C, n, partial_last=False):
+    """What a fixed-attention call of that shape launches (itts_fixed_attention_plan; no device work): a dict with
+    K (chunks), fwd_grid, fwd_lds_bytes, bwd_grid (x, y) and vec_p / vec_c -- whether dense tensors on 16-byte bases
+    take 16-byte accesses on the phoneme side (A, Abar) and on the channel side (enc, ctx, d_enc).  ValueError
+    outside the envelope (P <= 2048, C <= 4096, n <= 64) or for T % n != 0 without partial_last."""
+    L = _lib.load()
+    K = ctypes.c_int64(0)
+    v = [ctypes.c_int(0) for _ in range(6)]
+    if L.itts_fixed_attention_plan(int(B), int(T), int(P), int(C), int(n), 1 if partial_last else 0, ctypes.byref(K),
+                                   *[ctypes.byref(i) for i in v]) != 0:
+        raise ValueError("no fixed-attention plan for B={}, T={}, P={}, C={}, n_frames_per_step={}, partial_last={}"
+                         .format(B, T, P, C, n, bool(partial_last)))
+    return {"K": K.value, "fwd_grid": v[0].value, "fwd_lds_bytes": v[1].value, "bwd_grid": (v[2].value, v[3].value),
+            "vec_p": bool(v[4].value), "vec_c": bool(v[5].value)}
+
+
+def _fa_steps(t, name):
+    """(row pitch, utterance step) in floats of a [B, R, W] tensor with unit stride on W"""
+    if t.dim() != 3 or (t.shape[2] > 1 and t.stride(2) != 1):
+        raise ValueError("{} must be 3-D with unit stride on the last extent".format(name))
+    B, R, W = t.shape
+    ld = t.stride(1) if R > 1 else W
+    utt = t.stride(0) if B > 1 else max(R, 1) * ld
+    if ld < W or (B > 1 and utt < R * ld):
+        raise ValueError("{}: rows or utterances overlap (strides {})".format(name, tuple(t.stride())))
+    return ld, utt
+
+
+def fixed_attention(A, enc, n_frames_per_step=1, partial_last=False, abar=None, ctx=None):
+    """A [B, T, P] (the attention matrix of the durations), enc [B, P, C] -> (ctx [B, K, C], Abar [B, K, P]): the chunk
+    means of A over n_frames_per_step frames and their product with enc, walking each row's non-zeros
+    (FixedAttention.forward_batched of the reference).  K = T / n; with `partial_last` K = ceil(T / n) and the last
+    chunk is the mean over the rows it has."""
+    L = _lib.load()
+    _need(A, torch.float32, "A")
+    _need(enc, torch.float32, "enc")
+    if A.requires_grad:
+        raise ValueError("fixed_attention: A.requires_grad is set, but the attention matrix is a ground-truth input "
+                         "and has no gradient")
+    ldA, uttA = _fa_steps(A, "A")
+    ldE, uttE = _fa_steps(enc, "enc")
+    B, T, P = A.shape
+    n = int(n_frames_per_step)
+    if enc.shape[0] != B or enc.shape[1] != P:
+        raise ValueError("enc must be [B, P, C] = [{}, {}, C], got {}".format(B, P, tuple(enc.shape)))
+    C = enc.shape[2]
+    if not 1 <= n <= FIXED_ATTENTION_MAX_N:
+        raise ValueError("n_frames_per_step = {} is outside 1 .. {}".format(n, FIXED_ATTENTION_MAX_N))
+    if not partial_last and T % n != 0:
+        raise ValueError("T = {} is not a multiple of n_frames_per_step = {} and partial_last is not set".format(T, n))
+    K = -(-T // n) if partial_last else T // n
+    if abar is None:
+        abar = torch.empty((B, K, P), dtype=torch.float32, device=A.device)
+    if ctx is None:
+        ctx = torch.empty((B, K, C), dtype=torch.float32, device=A.device)
+    _need(abar, torch.float32, "abar")
+    _need(ctx, torch.float32, "ctx")
+    if tuple(abar.shape) != (B, K, P) or tuple(ctx.shape) != (B, K, C):
+        raise ValueError("abar / ctx must be [{0}, {1}, {2}] / [{0}, {1}, {3}]".format(B, K, P, C))
+    ldM, uttM = _fa_steps(abar, "abar")
+    ldX, uttX = _fa_steps(ctx, "ctx")
+    _lib.check(L.itts_fixed_attention_fwd(_ptr(A), ldA, uttA, _ptr(enc), ldE, uttE, B, T, P, C, n,
+                                          1 if partial_last else 0, _ptr(abar), ldM, uttM, _ptr(ctx), ldX, uttX,
+                                          _stream()), "itts_fixed_attention_fwd")
+    return ctx, abar
+
+
+def fixed_attention_bwd(abar, dctx, out=None):
+    """d_enc [B, P, C] of fixed_attention for Abar [B, K, P] and dctx [B, K, C]; every position is written."""
+    L = _lib.load()
+    _need(abar, torch.float32, "abar")
+    _need(dctx, torch.float32, "dctx")
+    B, K, P = abar.shape
+    if dctx.dim() != 3 or dctx.shape[0] != B or dctx.shape[1] != K:
+        raise ValueError("dctx must be [B, K, C] = [{}, {}, C], got {}".format(B, K, tuple(dctx.shape)))
+    C = dctx.shape[2]
+    if out is None:
+        out = torch.empty((B, P, C), dtype=torch.float32, device=abar.device)
+    _need(out, torch.float32, "out")
+    if tuple(out.shape) != (B, P, C):
+        raise ValueError("out must be [{}, {}, {}]".format(B, P, C))
+    ldM, uttM = _fa_steps(abar, "abar")
+    ldX, uttX = _fa_steps(dctx, "dctx")
+    ldE, uttE = _fa_steps(out, "out")
+    _lib.check(L.itts_fixed_attention_bwd(_ptr(abar), ldM, uttM, _ptr(dctx), ldX, uttX, B, K, P, C, _ptr(out), ldE,
+                                          uttE, _stream()), "itts_fixed_attention_bwd")
+    return out
+
+
+CELL_LSTM, CELL_GRU, CELL_RNN = 0, 1, 2      # ITTS_CELL_* in include/idiaptts_amd.h
+
+
+def rnn_cell_step(kind, gi, gh, h, c=None, b_hh=None, act=ACT_TANH):
+    """One time step of an LSTM / GRU / RNN layer direction on per-row states (itts_rnn_cell_step): gi [B, G*H] =
+    x W_ih^T + b_ih (LSTM, RNN: + b_hh), gh [B, G*H] = h W_hh^T, h / c [B, H] -> (h', c') (c' None unless LSTM)."""
+    L = _lib.load()
+    for t, name in ((gi, "gi"), (gh, "gh"), (h, "h")):
+        _need(t, torch.float32, name)
+    B, H = h.shape
+    G = {CELL_LSTM: 4, CELL_GRU: 3, CELL_RNN: 1}[kind]
+    if tuple(gi.shape) != (B, G * H) or tuple(gh.shape) != (B, G * H):
+        raise ValueError("gi / gh must be [{}, {}], got {} / {}".format(B, G * H, tuple(gi.shape), tuple(gh.shape)))
+    h_out = torch.empty((B, H), dtype=torch.float32, device=h.device)
+    c_out = None
+    if kind == CELL_LSTM:
+        _need(c, torch.float32, "c")
+        if tuple(c.shape) != (B, H):
+            raise ValueError("c must be [{}, {}]".format(B, H))
+        c_out = torch.empty((B, H), dtype=torch.float32, device=h.device)
+    if kind == CELL_GRU:
+        _need(b_hh, torch.float32, "b_hh")
+        b_hh = b_hh.contiguous()
+        if b_hh.numel() != 3 * H:
+            raise ValueError("b_hh must hold 3 H = {} values".format(3 * H))
+    else:
+        b_hh = None
+    _lib.check(L.itts_rnn_cell_step(int(kind), int(act), _ptr(gi), _rows(gi, "gi"), _ptr(gh), _rows(gh, "gh"),
+                                    _ptr(b_hh), _ptr(h), _rows(h, "h"), _ptr(c), _rows(c, "c") if c is not None else 0,
+                                    B, H, _ptr(h_out), H, _ptr(c_out), H, _stream()), "itts_rnn_cell_step")
+    return h_out, c_out

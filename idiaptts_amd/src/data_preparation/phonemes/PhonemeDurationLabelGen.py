@@ -24,6 +24,22 @@ class PhonemeDurationLabelGen(ReaderBase):
         self.norm_type = None if load_as_matrix else norm_type
         self.norm_params = None
         self._configure("durations")
+        if load_as_matrix:
+            # the collation hook of the handler's prepare_batch: only a reader of matrices pads its own batch
+            self.unsorted_pad_sequence = self._pad_matrices
+
+    @staticmethod
+    def _pad_matrices(values, batch_first, lengths=None):
+        """The attention matrices [T_i, P_i] of a batch zero-padded on both axes: float32 [B, T_max, P_max], or
+        [T_max, B, P_max] when not batch_first (`lengths`, the samples' shapes, is what the handler passes; the
+        arrays say the same).  A padded frame attends to nothing, a padded phoneme is attended by nothing."""
+        values = [np.asarray(v) for v in values]
+        t_max = max(v.shape[0] for v in values)
+        p_max = max(v.shape[1] for v in values)
+        out = np.zeros((len(values), t_max, p_max), dtype=np.float32)
+        for i, v in enumerate(values):
+            out[i, :v.shape[0], :v.shape[1]] = v
+        return out if batch_first else np.ascontiguousarray(out.transpose(1, 0, 2))
 
     def load(self, id_name):
         sample = self.load_sample(id_name, self.directory)

@@ -528,7 +528,11 @@ class ModularModelHandlerPyTorch(object):
                 data[key + "_mask"] = ModularModelHandlerPyTorch.sequence_mask(
                     lengths[key], max_frames, batch_first=batch_first)
                 lengths[key + "_mask"] = lengths[key]
-            data[key] = ModularModelHandlerPyTorch.unsorted_pad_sequence(values, batch_first, pinned=pin_output)
+            pad_hook = getattr(reader, "unsorted_pad_sequence", None)
+            if callable(pad_hook):       # a reader that pads its own batch (reference :451-455): ragged matrices
+                data[key] = torch.from_numpy(pad_hook(values, batch_first, shapes)).float()
+            else:
+                data[key] = ModularModelHandlerPyTorch.unsorted_pad_sequence(values, batch_first, pinned=pin_output)
         return data, lengths
 
     def set_dataset(self, hparams, dataset_train, dataset_val, collate_fn=None):

@@ -1,7 +1,8 @@
 """enc_dec_dyn.Config with the reference's fields (models/enc_dec_dyn/Config.py), restricted to what runs here:
 named modules executed in the order of their `process_group`, each an rnn_dyn model (ModuleConfig), a pass-through
-(ModuleConfig with config=None) or a NamedForwardWrapper (WrapperConfig); all batch_first, as in the reference.
-Attention decoders, projections, combiners and splitters are separate pieces of work and refuse by name."""
+(ModuleConfig with config=None), a NamedForwardWrapper (WrapperConfig) or a fixed-attention decoder with its pre-net
+and projections (DecoderConfig, ProjectionConfig; DecoderModule.py); all batch_first, as in the reference.  Combiners
+and splitters are separate pieces of work and refuse by name."""
 from typing import List
 
 from ..NamedForwardWrapper import NamedForwardWrapper
@@ -13,7 +14,8 @@ def external_input_names(process_groups):
     written, names = set(), []
     for group in process_groups:
         for module in group:
-            for name in module.input_names or ():
+            # (a decoder also reads its attention matrix: DecoderConfig.extra_input_names)
+            for name in list(module.input_names or ()) + list(getattr(module, "extra_input_names", ())):
                 if name not in written and name not in names:
                     names.append(name)
             written.update(module.output_names or ())
@@ -48,16 +50,88 @@ class Config:
                                                 output_names=output_names)
             self.process_group = process_group
 
+    class ProjectionConfig(ModuleConfig):
+        """a projection of a decoder's output (DecoderConfig.projection_configs): it has no input names of its own;
+        `is_autoregressive_input`: its last frame is fed back to the decoder, and `out_dim` is that frame's width"""
+
+        def __init__(self, out_dim: int = None, is_autoregressive_input: bool = False, **kwargs):
+            if "input_names" in kwargs:
+                raise NotImplementedError("enc_dec_dyn.Config.ProjectionConfig(input_names={!r}): a projection with "
+                                          "inputs of its own is not implemented, it reads its decoder's output (the "
+                                          "reference takes no input_names here either)."
+                                          .format(kwargs["input_names"]))
+            if out_dim is None:
+                raise TypeError("enc_dec_dyn.Config.ProjectionConfig needs out_dim, the width of one projected frame.")
+            super().__init__(input_names=None, **kwargs)
+            Config._default_output_names(self)
+            self.is_autoregressive_input = is_autoregressive_input
+            self.out_dim = out_dim
+
+        def create_model(self):
+            from .DecoderModule import ProjectionModule
+            return ProjectionModule(self)
+
+    class DecoderConfig(ModuleConfig):
+        """a frame-rate decoder behind an attention over its phoneme-rate inputs (DecoderModule).  As in the
+        reference: `attention_config` names the mechanism (enc_dec_dyn.FIXED_ATTENTION, the only one there is: any other
+        value, the default None included, is refused here and not in the first forward) and the legacy `attention_args`
+        dict holds its arguments ({enc_dec_dyn.ATTENTION_GROUND_TRUTH: <name of the attention matrix>});
+        `teacher_forcing_input_names` makes it autoregressive; a `decoder_output_name` attribute set on the config
+        names an extra output for the decoder's own output.  A plain string for input_names / output_names means a
+        list of that one name (the reference's ModelConfig._str_to_list)."""
+
+        def __init__(self, attention_config=None, attention_args: dict = {},    # (legacy, as in the reference)
+                     teacher_forcing_input_names: List[str] = None, n_frames_per_step: int = 1,
+                     p_teacher_forcing: float = 1.0, pre_net_config=None, projection_configs=None, **kwargs):
+            from . import FIXED_ATTENTION
+            if attention_config != FIXED_ATTENTION:
+                # (the reference's DecoderModule has no attention then and fails in its first forward)
+                raise NotImplementedError("enc_dec_dyn.Config.DecoderConfig(attention_config={!r}): only {!r} is "
+                                          "implemented (learned attention is a separate piece of work)."
+                                          .format(attention_config, FIXED_ATTENTION))
+            super().__init__(**kwargs)
+            self.input_names = Config._str_to_list(self.input_names)
+            Config._default_output_names(self)
+            self.attention_config = attention_config
+            self.attention_args = attention_args
+            assert teacher_forcing_input_names is None or len(teacher_forcing_input_names) > 0, \
+                "Empty list not allowed for teacher_forcing_input_names, use None instead."
+            self.teacher_forcing_input_names = teacher_forcing_input_names
+            self.n_frames_per_step = n_frames_per_step
+            self.p_teacher_forcing = p_teacher_forcing
+            self.pre_net_config = pre_net_config
+            self.projection_configs = projection_configs
+
+        @property
+        def extra_input_names(self):
+            """what the module reads besides input_names at synthesis time: the attention matrix"""
+            from . import ATTENTION_GROUND_TRUTH
+            name = (self.attention_args or {}).get(ATTENTION_GROUND_TRUTH)
+            return [name] if name is not None else []
+
+        def create_model(self):
+            from .DecoderModule import DecoderModule
+            return DecoderModule(self)
+
+    @staticmethod
+    def _str_to_list(str_or_list):
+        if str_or_list is None or isinstance(str_or_list, (tuple, list)):
+            return str_or_list
+        return [str_or_list]
+
+    @staticmethod
+    def _default_output_names(config):
+        """the reference's ModelConfig: output_names defaults to [name], a string is a list of one"""
+        assert config.output_names is not None or config.name is not None, \
+            "Default output_names is [name], but both are None for input {}.".format(config.input_names)
+        config.output_names = Config._str_to_list(config.output_names) if config.output_names is not None \
+            else [config.name]
+
     class _NotBuilt:
         def __init__(self, *args, **kwargs):
-            raise NotImplementedError("enc_dec_dyn.Config.{} is not implemented: only ModuleConfig and WrapperConfig "
-                                      "modules run here.".format(type(self).__name__))
-
-    class ProjectionConfig(_NotBuilt):
-        pass
-
-    class DecoderConfig(_NotBuilt):
-        pass
+            raise NotImplementedError("enc_dec_dyn.Config.{} is not implemented: only ModuleConfig, WrapperConfig, "
+                                      "DecoderConfig and ProjectionConfig modules run here."
+                                      .format(type(self).__name__))
 
     class CombinerConfig(_NotBuilt):
         pass

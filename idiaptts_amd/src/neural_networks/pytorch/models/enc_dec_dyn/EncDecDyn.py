@@ -5,6 +5,10 @@ is repeated over the decoder's time axis by the wrapper's merge.  Each module is
 parameter keys are `<name>.model.<rnn_dyn keys>`.  The container also carries what the model handler reads from a
 model: `batch_first` (always True here, as in the reference) and `input_names`, the names the data readers provide.
 
+A `Config.DecoderConfig` module is a DecoderModule (DecoderModule.py): the frame-rate decoder behind the fixed attention,
+with its pre-net and projections as children (`<name>.pre_net.*`, `<name>.<name>_<projector>.model.*`); `init_hidden`
+reaches them through it.
+
 A module that reads a name an earlier module wrote is marked (`reads_module_outputs`): the handler's
 `padding_rows_identical()` context speaks for the readers' batches, not for computed tensors, so such a module works on
 every position of the padded tensor (NamedForwardWrapper.forward)."""

@@ -1113,6 +1113,42 @@ int itts_wavenet_generate(const float* d_wf, const float* d_bf, const float* d_w
                           const float* d_u, const int* h_lengths, int B, int64_t T_out, int initial_class,
                           float* d_state, int64_t state_floats, void* d_out, float* d_logits, void* stream);
 
+/* ---- Fixed (duration-derived) attention of the encoder-decoder model (csrc/fixed_attention.hip) ------------------
+ * float32; pitches (ld*) are floats from one row to the next, utterance steps (utt*) floats from one utterance to the
+ * next, last extents have unit stride.  16-byte accesses where every pitch, step and base of a side (phoneme side: A
+ * and Abar; channel side: enc, ctx / dctx, d_enc) allows, plain ones otherwise: the same lanes, the same bits.
+ *   fwd  A [B, T, P], enc [B, P, C], n = n_frames_per_step -> Abar [B, K, P], ctx [B, K, C].  K = T / n (T % n != 0
+ *        is refused), with partial_last K = ceil(T / n) and the last chunk is the mean over the rows it has.
+ *        Abar[b, k, :] = (sum of the chunk's rows of A in ascending frame order) / row count;
+ *        ctx[b, k, :] = sum over p ascending of Abar[b, k, p] * enc[b, p, :], terms with Abar == 0 skipped (so Inf or
+ *        NaN in a row of enc that no frame attends to does not reach ctx, unlike a dense product).
+ *   bwd  Abar, dctx [B, K, C] -> d_enc [B, P, C], d_enc[b, p, :] = sum over k ascending of Abar[b, k, p] * dctx[b, k, :],
+ *        zeros skipped; every position is written; no atomics.  A is ground truth: it has no gradient.
+ *   An utterance's results depend on its own rows only (not on B or its index); repeated calls give identical bits.
+ *   Envelope: P 1 .. 2048, C 1 .. 4096, n 1 .. 64; anything else is ITTS_E_INVALID with a message before any device
+ *   work.  itts_fixed_attention_plan (no device work; 0, or -1 outside the envelope): K, the forward grid and its LDS
+ *   bytes, the backward grid (x, y), and whether dense tensors on 16-byte bases take the 16-byte accesses. */
+int itts_fixed_attention_plan(int B, int64_t T, int P, int C, int n, int partial_last, int64_t* K, int* fwd_blocks,
+                              int* fwd_lds_bytes, int* bwd_blocks_x, int* bwd_blocks_y, int* vec_p, int* vec_c);
+int itts_fixed_attention_fwd(const float* d_A, int64_t ldA, int64_t uttA, const float* d_enc, int64_t ldE,
+                             int64_t uttE, int B, int64_t T, int P, int C, int n, int partial_last, float* d_abar,
+                             int64_t ldM, int64_t uttM, float* d_ctx, int64_t ldX, int64_t uttX, void* stream);
+int itts_fixed_attention_bwd(const float* d_abar, int64_t ldM, int64_t uttM, const float* d_dctx, int64_t ldX,
+                             int64_t uttX, int B, int64_t K, int P, int C, float* d_denc, int64_t ldE, int64_t uttE,
+                             void* stream);
+
+/* ---- One recurrent step on per-row states (csrc/rnn_cell.hip) -----------------------------------------------------
+ * h' (and c') of one time step of an LSTM / GRU / RNN layer direction for B rows with a state each:
+ *   d_gi [B, G*H] = x W_ih^T + b_ih (LSTM, RNN: + b_hh), d_gh [B, G*H] = h W_hh^T, both from itts_linear_fwd;
+ *   d_b_hh [3H] for the GRU (NULL otherwise); d_h / d_c [B, H] in, d_h_out / d_c_out [B, H] out (d_c* LSTM only).
+ * G = 4 / 3 / 1, torch.nn's gate order; act (RNN): ITTS_ACT_TANH or ITTS_ACT_RELU.  Any H >= 1. */
+#define ITTS_CELL_LSTM 0
+#define ITTS_CELL_GRU 1
+#define ITTS_CELL_RNN 2
+int itts_rnn_cell_step(int kind, int act, const float* d_gi, int64_t ldgi, const float* d_gh, int64_t ldgh,
+                       const float* d_b_hh, const float* d_h, int64_t ldh, const float* d_c, int64_t ldc, int B, int H,
+                       float* d_h_out, int64_t ldho, float* d_c_out, int64_t ldco, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
