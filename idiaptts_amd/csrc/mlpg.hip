@@ -12,6 +12,8 @@
 //   mlpg_stream.h   mlpg_prep / reduce / scan / solve: everything else, no wait anywhere: the backward contribution
 //                   of a chunk is accumulated while walking forward (adjoint identity), a two-level scan gives every
 //                   chunk its entry states, a second pass solves
+//   mlpg_adjoint.h  mlpg_adjoint_kernel: the gradient with respect to the means (one more solve with the shared factor,
+//                   the three windows applied inside the back-substitution), one form for every shape
 //   here            the choice of form, the override word, plans, the dispatcher and the C entry points
 // (Rounds 2 and 3 also carried a four-pass chunked solve and a single-pass kernel with cross-workgroup
 // waits; both measured slower -- DESIGN.md section 11c -- and left the library in round 4.)
@@ -29,6 +31,7 @@
 
 #include "common.h"
 #include "context.h"
+#include "mlpg_adjoint.h"
 #include "mlpg_math.h"
 #include "mlpg_ring.h"
 #include "mlpg_stream.h"
@@ -334,4 +337,76 @@ extern "C" int itts_mlpg_generation_planned(const void* plan, const void* d_feat
   return mlpg_generation_impl(feat_is_f32 ? nullptr : static_cast<const double*>(d_feat),
                               feat_is_f32 ? static_cast<const float*>(d_feat) : nullptr, ld_feat, col0, dim, d_var,
                               p->offsets.data(), p->n_utts, d_out, ld_out, ocol0, d_scratch, stream, p);
+}
+
+// ---- the adjoint (mlpg_adjoint.h) -----------------------------------------------------------------------------------
+extern "C" int64_t itts_mlpg_adjoint_scratch_bytes(int64_t t_total, int dim) {
+  if (t_total < 0 || dim <= 0) return 0;
+  // the forward's scratch (factor planes, offsets, nconv) + the forward sweep's intermediate y [Ttot, dim]
+  return itts_mlpg_scratch_bytes(t_total, dim) + t_total * (int64_t)dim * 8;
+}
+
+// The instantiations of mlpg_adjoint_kernel by (gradient in is float32, gradient out is float32).
+static const void* const kAdjointKernels[2][2] = {
+  {(const void*)mlpg_adjoint_kernel<double, double>, (const void*)mlpg_adjoint_kernel<double, float>},
+  {(const void*)mlpg_adjoint_kernel<float, double>, (const void*)mlpg_adjoint_kernel<float, float>},
+};
+
+static int mlpg_adjoint_impl(const void* d_gout, int gout_is_f32, int64_t ld_gout, int gcol0, int dim,
+                             const double* d_var, const int64_t* h_offsets, int n_utts,
+                             void* d_gfeat, int gfeat_is_f32, int64_t ld_gfeat, int col0,
+                             void* d_scratch, void* stream, const MlpgPlan* plan = nullptr) {
+  ITTS_REQUIRE(d_var && h_offsets, "null pointer");
+  ITTS_REQUIRE(dim > 0 && n_utts >= 0 && gcol0 >= 0 && col0 >= 0, "bad sizes");
+  ITTS_REQUIRE((dim + MLPG_ADJ_LANES - 1) / MLPG_ADJ_LANES <= 65535, "too many dimensions");
+  ITTS_REQUIRE(ld_gout >= gcol0 + (int64_t)dim && ld_gfeat >= col0 + 3 * (int64_t)dim,
+               "leading dimension too small");
+  if (n_utts == 0) return ITTS_OK;
+  const int64_t t_total = h_offsets[n_utts];
+  int64_t t_max = 0;
+  if (plan) {
+    t_max = plan->t_max;
+  } else {
+    const int rc = mlpg_check_offsets(h_offsets, n_utts, &t_max);
+    if (rc) return rc;
+  }
+  if (t_total == 0) return ITTS_OK;      // (a tensor without rows has no address: the pointers are looked at from here)
+  ITTS_REQUIRE(d_gout && d_gfeat && d_scratch, "null pointer");
+  ITTS_REQUIRE(t_max <= INT32_MAX, "utterance too long");
+  hipStream_t s = as_stream(stream);
+  double* scratch = reinterpret_cast<double*>(d_scratch);
+  int64_t* d_off = reinterpret_cast<int64_t*>(scratch + 3 * t_total * (int64_t)dim);
+  int* d_nconv = reinterpret_cast<int*>(d_off + (t_total + 2));
+  double* d_y = reinterpret_cast<double*>(reinterpret_cast<char*>(d_scratch) + itts_mlpg_scratch_bytes(t_total, dim));
+  MlpgArgs a{nullptr, 0, 0, dim, d_var, d_off, nullptr, 0, 0, scratch, t_total, d_nconv};
+  {
+    const int rc = itts::staged_upload(d_off, h_offsets, (size_t)(n_utts + 1) * sizeof(int64_t), s);
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL(mlpg_factor_kernel, dim3((dim + 63) / 64), dim3(64), 0, s, a, (int)t_max);
+  ITTS_LAUNCH_CHECK();
+  MlpgAdjointArgs g{a, d_gout, ld_gout, gcol0, d_gfeat, ld_gfeat, col0, d_y};
+  int t_max_arg = (int)t_max;
+  void* kernel_args[] = {&g, &t_max_arg};
+  const dim3 grid((unsigned)n_utts, (unsigned)((dim + MLPG_ADJ_LANES - 1) / MLPG_ADJ_LANES));
+  ITTS_HIP_CHECK(hipLaunchKernel(kAdjointKernels[gout_is_f32 ? 1 : 0][gfeat_is_f32 ? 1 : 0], grid, dim3(MLPG_ADJ_LANES),
+                                 kernel_args, 0, s));
+  return ITTS_OK;
+}
+
+extern "C" int itts_mlpg_adjoint(const void* d_gout, int gout_is_f32, int64_t ld_gout, int gcol0, int dim,
+                                 const double* d_var, const int64_t* h_offsets, int n_utts,
+                                 void* d_gfeat, int gfeat_is_f32, int64_t ld_gfeat, int col0,
+                                 void* d_scratch, void* stream) {
+  return mlpg_adjoint_impl(d_gout, gout_is_f32, ld_gout, gcol0, dim, d_var, h_offsets, n_utts, d_gfeat, gfeat_is_f32,
+                           ld_gfeat, col0, d_scratch, stream);
+}
+
+extern "C" int itts_mlpg_adjoint_planned(const void* plan, const void* d_gout, int gout_is_f32, int64_t ld_gout,
+                                         int gcol0, int dim, const double* d_var, void* d_gfeat, int gfeat_is_f32,
+                                         int64_t ld_gfeat, int col0, void* d_scratch, void* stream) {
+  const MlpgPlan* p = static_cast<const MlpgPlan*>(plan);
+  ITTS_REQUIRE(p, "null pointer");
+  return mlpg_adjoint_impl(d_gout, gout_is_f32, ld_gout, gcol0, dim, d_var, p->offsets.data(), p->n_utts, d_gfeat,
+                           gfeat_is_f32, ld_gfeat, col0, d_scratch, stream, p);
 }

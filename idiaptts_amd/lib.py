@@ -75,6 +75,10 @@ _SIGNATURES = {
     "itts_mlpg_set_override": (c_int, [c_int, c_int, c_int]),
     "itts_mlpg_get_override": (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "itts_mlpg_last_form": (c_int, []),
+    "itts_mlpg_adjoint_scratch_bytes": (c_int64, [c_int64, c_int]),
+    "itts_mlpg_adjoint": (c_int, [_P, c_int, c_int64, c_int, c_int, _P, POINTER(c_int64), c_int, _P, c_int, c_int64,
+                                  c_int, _P, _P]),
+    "itts_mlpg_adjoint_planned": (c_int, [_P, _P, c_int, c_int64, c_int, c_int, _P, _P, c_int, c_int64, c_int, _P, _P]),
     "itts_sqrt_inplace_f64": (c_int, [_P, c_int64, _P]),
     "itts_square_inplace_f64": (c_int, [_P, c_int64, _P]),
     "itts_stft": (c_int, [_P, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), c_int, c_int, c_int, c_int, _P,

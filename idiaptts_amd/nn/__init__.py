@@ -1,3 +1,3 @@
 from .modules import (GRU, LSTM, RNN, AllPassWarp, GradientScaling, LinearAct, MeanPooling,  # noqa: F401
-                      SelectLastPooling, VanillaVAE)
+                      MLPGLayer, SelectLastPooling, VanillaVAE)
 from .wavenet import WaveNet  # noqa: F401

@@ -223,6 +223,54 @@ class AllPassWarpFunction(torch.autograd.Function):
                 da.reshape(ctx.alpha_shape) if ctx.needs_input_grad[1] else None, None, None, None)
 
 
+class MlpgFunction(torch.autograd.Function):
+    """The MLPG trajectories of several streams of the same rows as one differentiable node: rows [N, C] (float32 or
+    float64; a pitched view is read in place), streams = [(col0, dim, variances [3 * dim] float64), ...], the
+    utterances' offsets (or an ops.MlpgPlan made from them) -> [N, sum of dims] in the rows' dtype, the streams side by
+    side in the order given.  The forward is `ops.mlpg_generation` per stream (one plan for all of them, as
+    MLPG.generation_streams); the backward one `ops.mlpg_adjoint` launch per stream into one [N, C] gradient whose
+    other columns are zero.  The trajectory is linear in the rows, so nothing but the plan is saved.  The variances
+    are statistics, not parameters: one that requires grad is refused; differentiating the backward is refused too."""
+
+    @staticmethod
+    def forward(ctx, rows, streams, offsets, plan):
+        for _, _, var in streams:
+            if var.requires_grad:
+                raise ValueError("MlpgFunction: variances that require grad are not supported (the variances are "
+                                 "statistics of the corpus, not parameters)")
+        if rows.dtype not in (torch.float32, torch.float64):
+            raise TypeError("MlpgFunction: rows must be float32 or float64, got {}".format(rows.dtype))
+        if rows.dim() != 2 or rows.stride(1) != 1:
+            rows = rows.contiguous()
+        if plan is None and len(streams) > 1:
+            plan = ops.MlpgPlan(offsets)
+        total = sum(int(dim) for _, dim, _ in streams)
+        out = torch.empty((rows.shape[0], total), dtype=torch.float64, device=rows.device)
+        o0 = 0
+        for col0, dim, var in streams:
+            ops.mlpg_generation(rows, var, int(dim), offsets, col0=int(col0), out=out, ocol0=o0, plan=plan)
+            o0 += int(dim)
+        ctx.streams, ctx.offsets, ctx.plan = streams, offsets, plan
+        ctx.width, ctx.dtype = rows.shape[1], rows.dtype
+        return out if rows.dtype == torch.float64 else out.to(rows.dtype)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        if grad.dtype != ctx.dtype:
+            grad = grad.to(ctx.dtype)
+        if grad.stride(1) != 1:
+            grad = grad.contiguous()
+        gfeat = torch.zeros((grad.shape[0], ctx.width), dtype=ctx.dtype, device=grad.device)
+        o0 = 0
+        for col0, dim, var in ctx.streams:
+            ops.mlpg_adjoint(grad, var, int(dim), ctx.offsets, gcol0=o0, out=gfeat, col0=int(col0), plan=ctx.plan)
+            o0 += int(dim)
+        return gfeat, None, None, None
+
+
 def _pitched3(x):
     """x ([B, T, D] / [T, B, D]) as the pooling kernels take it: unit stride on the features, evenly spaced
     positions; anything else is copied"""

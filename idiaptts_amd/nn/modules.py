@@ -1,15 +1,17 @@
 """nn.Modules with torch.nn-compatible parameter names on top of the HIP kernels, so that the
 reference's state dicts load unchanged (`module.0.weight`,
 `module.weight_ih_l0[_reverse]`, ...)."""
+import collections
 import math
 import os
 
+import numpy as np
 import torch
 from torch import nn
 
 from .. import ops
 from .functional import (AllPassWarpFunction, Conv1dActFunction, GRULayerFunction, LayerNormActFunction,
-                         LinearActFunction, LSTMLayerFunction, PackedBatch, RNNLayerFunction, StatesToCallerOrder,
+                         LinearActFunction, LSTMLayerFunction, MlpgFunction, PackedBatch, RNNLayerFunction, StatesToCallerOrder,
                          TimePoolFunction, VAEReparamFunction, grad_scaling)
 
 
@@ -133,6 +135,200 @@ class AllPassWarp(nn.Module):
 
     def extra_repr(self):
         return "warp_matrix_size={}".format(self.warp_matrix_size)
+
+
+def mlpg_dense(rows, dim, variances):
+    """The MLPG trajectory [T, dim] of ONE utterance's rows [T, 3 * dim] (static | delta | delta-delta) by torch ops
+    on a dense precision matrix: P = sum_w W_w^T diag(tau_w) W_w per dimension and torch.linalg.solve, differentiable
+    by autograd.  O(dim T^3): MLPGLayer's path for CPU tensors, for tests and small inputs only."""
+    T = rows.shape[0]
+    eye = torch.eye(T, dtype=rows.dtype, device=rows.device)
+    up, down = torch.diag_embed(eye.new_ones(max(T - 1, 0)), 1), torch.diag_embed(eye.new_ones(max(T - 1, 0)), -1)
+    windows = (eye, 0.5 * (up - down), up + down - 2.0 * eye)
+    edge = eye.new_ones(T, 1)
+    if T > 0:
+        edge[0] = edge[T - 1] = 0.0
+    P, b = 0.0, 0.0
+    for w, W in enumerate(windows):
+        tau = (1.0 / variances[w * dim:(w + 1) * dim]).to(rows.dtype).expand(T, dim)
+        if w > 0:      # the delta variances of the first and last frame are 1e11 (misc/mlpg.py:114-117)
+            tau = tau * edge + (1.0 - edge) * 1e-11
+        P = P + torch.einsum("ti,td,tj->dij", W, tau, W)
+        b = b + W.t() @ (tau * rows[:, w * dim:(w + 1) * dim])
+    return torch.linalg.solve(P, b.t().unsqueeze(-1)).squeeze(-1).t()
+
+
+class MLPGLayer(nn.Module):
+    """MLPG as a differentiable layer: the trajectories of the streams of a padded batch of static | delta |
+    delta-delta features, so that a loss can be taken on what the listener hears (trajectory training).
+
+    `streams` is a list of (col0, dim, variances): the stream's 3 * dim columns start at input column col0, variances
+    [3 * dim] is the diagonal of its covariance.  `passthrough` lists single input columns (V/UV) that are copied.
+    The output has sum(dim) + len(passthrough) columns, the streams' trajectories and the passthrough columns in the
+    order of their first input column -- for a WORLD reader coded_sp | lf0 | vuv | bap, the layout of a reader with
+    add_deltas=False.  With `mean` / `std_dev` ([C], both or neither) the valid frames are de-normalised (x * std_dev +
+    mean) before the solve and the output is normalised again with the entries of the columns it came from (a stream's
+    static columns).  Padding positions of the output are zero; lengths pass through unchanged.
+
+    `forward(input_, seq_lengths_input=..., max_length_inputs=..., **kwargs) -> (output, kwargs)` with input_
+    [B, T, C] (`batch_first`) or [T, B, C], float32 or float64; without lengths every frame is valid.
+    `select_only=True` solves nothing: it returns the same columns of its input unchanged (static columns instead of
+    trajectories), to cut a target down to the layout of the prediction.
+
+    Variances (`variances_0`, `variances_1`, .. in stream order, float64), `mean` and `std_dev` are buffers: they move
+    with `.to()` and are in the state dict; there are no parameters.
+
+    On the GPU the solve and its gradient are ops.mlpg_generation / ops.mlpg_adjoint (MlpgFunction).  CPU tensors go
+    through `mlpg_dense`: float64 torch ops on a dense precision matrix per utterance, cubic in the length -- for
+    tests and small inputs only."""
+
+    class Config:
+        def __init__(self, streams, passthrough=(), mean=None, std_dev=None, batch_first=True, select_only=False):
+            self.streams = streams
+            self.passthrough = passthrough
+            self.mean = mean
+            self.std_dev = std_dev
+            self.batch_first = batch_first
+            self.select_only = select_only
+
+        def create_model(self):
+            return MLPGLayer(self.streams, passthrough=self.passthrough, mean=self.mean, std_dev=self.std_dev,
+                             batch_first=self.batch_first, select_only=self.select_only)
+
+    _cache_max = 16
+
+    def __init__(self, streams, passthrough=(), mean=None, std_dev=None, batch_first=True, select_only=False):
+        super().__init__()
+        if (mean is None) != (std_dev is None):
+            raise ValueError("MLPGLayer: mean and std_dev are given together or not at all")
+        self.batch_first, self.select_only = bool(batch_first), bool(select_only)
+        self.stream_cols = []          # (col0, dim) per stream
+        taken = {}                     # input column -> who reads it
+        pieces = []                    # (first input column, static columns)
+        for i, (col0, dim, variances) in enumerate(streams):
+            col0, dim = int(col0), int(dim)
+            var = torch.as_tensor(np.asarray(variances, dtype=np.float64)).reshape(-1).clone()
+            if col0 < 0 or dim < 1 or var.numel() != 3 * dim:
+                raise ValueError("MLPGLayer: stream {} (col0 {}, dim {}) needs col0 >= 0, dim >= 1 and 3 * dim "
+                                 "variances, got {}".format(i, col0, dim, var.numel()))
+            if not bool((var > 0).all()) or not bool(torch.isfinite(var).all()):
+                raise ValueError("MLPGLayer: stream {} has non-positive variances".format(i))
+            for c in range(col0, col0 + 3 * dim):
+                if c in taken:
+                    raise ValueError("MLPGLayer: stream {} overlaps {} at column {}".format(i, taken[c], c))
+                taken[c] = "stream {}".format(i)
+            self.register_buffer("variances_{}".format(i), var)
+            self.stream_cols.append((col0, dim))
+            pieces.append((col0, list(range(col0, col0 + dim))))
+        for c in passthrough:
+            c = int(c)
+            if c < 0 or c in taken:
+                raise ValueError("MLPGLayer: passthrough column {} {}".format(
+                    c, "overlaps " + taken[c] if c in taken else "is negative"))
+            taken[c] = "passthrough column {}".format(c)
+            pieces.append((c, [c]))
+        if not pieces:
+            raise ValueError("MLPGLayer: no streams and no passthrough columns")
+        self.passthrough = [int(c) for c in passthrough]
+        self.min_width = max(taken) + 1
+        if mean is not None:
+            mean = torch.as_tensor(np.asarray(mean, dtype=np.float64)).reshape(-1).clone()
+            std_dev = torch.as_tensor(np.asarray(std_dev, dtype=np.float64)).reshape(-1).clone()
+            if mean.numel() != std_dev.numel():
+                raise ValueError("MLPGLayer: mean has {} entries, std_dev {}".format(mean.numel(), std_dev.numel()))
+            for i, (col0, dim) in enumerate(self.stream_cols):
+                if col0 + 3 * dim > mean.numel():
+                    raise ValueError("MLPGLayer: stream {} (columns {} .. {}) lies beyond the input width {}"
+                                     .format(i, col0, col0 + 3 * dim - 1, mean.numel()))
+            if self.min_width > mean.numel():
+                raise ValueError("MLPGLayer: passthrough column {} lies beyond the input width {}"
+                                 .format(max(self.passthrough), mean.numel()))
+            self.register_buffer("mean", mean)
+            self.register_buffer("std_dev", std_dev)
+        else:
+            self.mean = self.std_dev = None
+        pieces.sort(key=lambda p: p[0])
+        self.order = [p[0] for p in pieces]                  # first input column of every output piece, ascending
+        # the input column every output column comes from (a stream's static columns); not part of the state dict
+        self.register_buffer("out_cols", torch.tensor([c for _, cols in pieces for c in cols], dtype=torch.int64),
+                             persistent=False)
+        self._layouts = collections.OrderedDict()
+
+    def init_hidden(self, batch_size=1):
+        return None
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state["_layouts"] = collections.OrderedDict()          # (plans are handles of this process: made again on use)
+        return state
+
+    def extra_repr(self):
+        return "streams={}, passthrough={}, normalised={}, batch_first={}, select_only={}".format(
+            self.stream_cols, self.passthrough, self.mean is not None, self.batch_first, self.select_only)
+
+    def _layout(self, lengths, B, T, device):
+        """(flat positions of the valid frames in utterance order, the utterances' offsets, an ops.MlpgPlan on the
+        GPU) for a batch of these lengths, kept for the batches that come again"""
+        lens = np.full(B, T, dtype=np.int64) if lengths is None \
+            else np.asarray(torch.as_tensor(lengths).cpu(), dtype=np.int64).reshape(-1)
+        if len(lens) != B or (B and (lens.min() < 0 or lens.max() > T)):
+            raise ValueError("MLPGLayer: {} lengths (max {}) for a batch of {} x {} frames".format(
+                len(lens), lens.max() if len(lens) else 0, B, T))
+        key = (lens.tobytes(), T, str(device))
+        hit = self._layouts.get(key)
+        if hit is not None:
+            self._layouts.move_to_end(key)
+            return hit
+        u = np.repeat(np.arange(B, dtype=np.int64), lens)
+        offsets = np.concatenate(([0], np.cumsum(lens)))
+        t = np.arange(int(offsets[-1]), dtype=np.int64) - offsets[u]
+        idx = torch.from_numpy(u * T + t if self.batch_first else t * B + u).to(device)
+        offsets = [int(o) for o in offsets]
+        plan = ops.MlpgPlan(offsets) if device.type == "cuda" and len(self.stream_cols) > 1 else None
+        self._layouts[key] = (idx, offsets, plan)
+        while len(self._layouts) > self._cache_max:
+            self._layouts.popitem(last=False)
+        return idx, offsets, plan
+
+    def _variances(self, i):
+        var = getattr(self, "variances_{}".format(i))
+        return var if var.dtype == torch.float64 else var.double()
+
+    def forward(self, input_, seq_lengths_input=None, max_length_inputs=None, **kwargs):
+        kwargs["seq_lengths_input"], kwargs["max_length_inputs"] = seq_lengths_input, max_length_inputs
+        if input_.dim() != 3 or input_.shape[2] < self.min_width:
+            raise ValueError("MLPGLayer: input of shape {} is not a padded batch of at least {} columns"
+                             .format(tuple(input_.shape), self.min_width))
+        if self.mean is not None and input_.shape[2] != self.mean.numel():
+            raise ValueError("MLPGLayer: input width {} but {} normalisation entries"
+                             .format(input_.shape[2], self.mean.numel()))
+        if self.select_only:
+            return input_.index_select(2, self.out_cols), kwargs
+        B, T = (input_.shape[0], input_.shape[1]) if self.batch_first else (input_.shape[1], input_.shape[0])
+        idx, offsets, plan = self._layout(seq_lengths_input, B, T, input_.device)
+        rows = input_.reshape(B * T, input_.shape[2]).index_select(0, idx)
+        on_gpu = input_.is_cuda
+        if not on_gpu:
+            rows = rows.double()
+        if self.mean is not None:
+            rows = rows * self.std_dev.to(rows.dtype) + self.mean.to(rows.dtype)
+        streams = [(col0, dim, self._variances(i)) for i, (col0, dim) in enumerate(self.stream_cols)]
+        if on_gpu:
+            traj = MlpgFunction.apply(rows, streams, offsets, plan)
+            trajs, o0 = {}, 0
+            for col0, dim, _ in streams:
+                trajs[col0] = traj[:, o0:o0 + dim]
+                o0 += dim
+        else:
+            trajs = {col0: torch.cat([mlpg_dense(rows[offsets[u]:offsets[u + 1], col0:col0 + 3 * dim], dim, var)
+                                      for u in range(B) if offsets[u + 1] > offsets[u]] or [rows[:0, :dim]], dim=0)
+                     for col0, dim, var in streams}
+        out_rows = torch.cat([trajs[c] if c in trajs else rows[:, c:c + 1] for c in self.order], dim=1)
+        if self.mean is not None:
+            out_rows = (out_rows - self.mean.to(rows.dtype)[self.out_cols]) / self.std_dev.to(rows.dtype)[self.out_cols]
+        out_rows = out_rows.to(input_.dtype)
+        out = out_rows.new_zeros((B * T, out_rows.shape[1])).index_copy(0, idx, out_rows)
+        return out.reshape(input_.shape[:2] + (out_rows.shape[1],)), kwargs
 
 
 class Pooling(nn.Module):

@@ -131,6 +131,49 @@ def mlpg_generation(feat, variances, dim, offsets, col0=0, out=None, ocol0=0, pl
     return out
 
 
+def mlpg_adjoint(gout, variances, dim, offsets, gcol0=0, out=None, col0=0, plan=None):
+    """The gradient with respect to the static / delta / delta-delta means from the gradient with respect to the
+    trajectory (itts_mlpg_adjoint): gout [Ttot, >= gcol0 + dim] f32 or f64, variances [3*dim] f64, offsets / plan as
+    for `mlpg_generation`.  Writes columns col0 .. col0 + 3*dim - 1 of `out` (f32 or f64, nothing else of it is
+    touched) and returns it; without `out` a [Ttot, 3*dim] tensor of gout's dtype."""
+    L = _lib.load()
+    if gout.dtype not in (torch.float32, torch.float64):
+        raise TypeError("gout must be float32 or float64, got {}".format(gout.dtype))
+    _need(gout, gout.dtype, "gout")
+    _need(variances, torch.float64, "variances")
+    if variances.numel() != 3 * dim:
+        raise ValueError("variances must hold 3 * dim = {} values, got {}".format(3 * dim, variances.numel()))
+    ldg = _rows(gout, "gout")
+    t_total = plan.t_total if plan is not None else int(offsets[-1])
+    if gout.shape[0] != t_total:
+        raise ValueError("offsets[-1] != number of rows")
+    if gcol0 < 0 or gout.shape[1] < gcol0 + dim:
+        raise ValueError("gout has no columns {} .. {}".format(gcol0, gcol0 + dim - 1))
+    if out is None:
+        out = torch.empty((t_total, 3 * dim), dtype=gout.dtype, device=gout.device)
+    if out.dtype not in (torch.float32, torch.float64):
+        raise TypeError("out must be float32 or float64, got {}".format(out.dtype))
+    _need(out, out.dtype, "out")
+    ldo = _rows(out, "out")
+    if out.shape[0] != t_total or col0 < 0 or out.shape[1] < col0 + 3 * dim:
+        raise ValueError("out must hold {} rows and columns {} .. {}".format(t_total, col0, col0 + 3 * dim - 1))
+    nbytes = L.itts_mlpg_adjoint_scratch_bytes(t_total, dim)
+    if not variances.is_contiguous():
+        variances = variances.contiguous()
+    g32, o32 = int(gout.dtype == torch.float32), int(out.dtype == torch.float32)
+    if plan is not None:
+        scratch = plan.scratch(nbytes, gout.device)
+        _lib.check(L.itts_mlpg_adjoint_planned(plan._handle, _ptr(gout), g32, ldg, gcol0, dim, _ptr(variances),
+                                               _ptr(out), o32, ldo, col0, _ptr(scratch), _stream()),
+                   "itts_mlpg_adjoint_planned")
+        return out
+    scratch = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=gout.device)
+    offs = _lib.offsets_array(offsets)
+    _lib.check(L.itts_mlpg_adjoint(_ptr(gout), g32, ldg, gcol0, dim, _ptr(variances), offs, len(offsets) - 1,
+                                   _ptr(out), o32, ldo, col0, _ptr(scratch), _stream()), "itts_mlpg_adjoint")
+    return out
+
+
 # the form a call solves in (ITTS_MLPG_FORM_*, include/idiaptts_amd.h): one of the three solves, or-ed with flags
 MLPG_SWEEPS, MLPG_STREAM, MLPG_RING, MLPG_SOLVE_MASK = 1, 2, 3, 3
 MLPG_WIDE, MLPG_F32_ROWS, MLPG_NT_IN, MLPG_WIDENED_COPY = 4, 8, 16, 32

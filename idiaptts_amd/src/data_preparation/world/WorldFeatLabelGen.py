@@ -221,6 +221,40 @@ class WorldFeatLabelGen(ReaderBase):
                     pieces[u][slot] = traj
         return [np.concatenate(p_, axis=1) for p_ in pieces]
 
+    def mlpg_layer_config(self, normalised=True, select_only=False):
+        """The `idiaptts_amd.nn.MLPGLayer.Config` of this reader's streams, for trajectory training: the columns and
+        covariance diagonals `_postprocess_world_batch` hands to MLPG (coded sp, lf0, bap), V/UV as a passthrough
+        column, and with `normalised` the mean / std_dev of `self.norm_params`, so the layer takes the network's
+        normalised output (or, with `select_only`, cuts the normalised target down to its static columns).  Call
+        `get_normalisation_params` first."""
+        from idiaptts_amd.nn import MLPGLayer
+        if not self.add_deltas:
+            raise ValueError("mlpg_layer_config: this reader has add_deltas=False, there is nothing for MLPG to solve")
+        streams, passthrough, col = [], [], 0
+        widths = [(idx, width, idx == 2) for idx, (load, width) in enumerate(zip(
+            self.load_flags, (self.num_coded_sps, 1, 1, self.num_bap))) if load]
+        n_cols = sum(1 if is_vuv else 3 * width for _, width, is_vuv in widths)
+        for cov_idx, width, is_vuv in widths:
+            if is_vuv:
+                passthrough.append(col)
+                col += 1
+                continue
+            c0 = n_cols - width * 3 if cov_idx == 3 else col      # (bap from the end of the row, as the solve)
+            col += 3 * width
+            cov = self.covs[cov_idx]
+            if cov is None:
+                raise ValueError("mlpg_layer_config: no covariance for stream {}; call get_normalisation_params "
+                                 "first".format(cov_idx))
+            dim = cov.shape[0] // 3
+            streams.append((c0, dim, np.ascontiguousarray(np.diag(np.asarray(cov))[:3 * dim], dtype=np.float64)))
+        mean = std_dev = None
+        if normalised:
+            if self.norm_params is None:
+                raise ValueError("mlpg_layer_config: no normalisation parameters; call get_normalisation_params first")
+            mean, std_dev = (np.asarray(p, dtype=np.float64).reshape(-1) for p in self.norm_params)
+        return MLPGLayer.Config(streams, passthrough=passthrough, mean=mean, std_dev=std_dev, batch_first=True,
+                                select_only=select_only)
+
     # ------------------------------------------------------------------------------ conversions
     @staticmethod
     def convert_to_world_features(sample, contains_deltas=False, num_coded_sps=60, num_bap=1):

@@ -221,6 +221,26 @@ int itts_mlpg_get_override(int* solve, int* width, int* nt);
  * or it had nothing to solve, or failed before choosing. */
 int itts_mlpg_last_form(void);
 
+/* The adjoint of the solve: the gradient of a loss with respect to the static / delta / delta-delta means, from its
+ * gradient with respect to the trajectory.  For fixed variances the trajectory is linear in the means and P is
+ * symmetric: z = P^-1 g (the same factor, g itself as the right-hand side), then the three windows,
+ *   dL/dmu_0[t] = tau_0 z[t],  dL/dmu_1[t] = tau_1(t) 0.5 (z[t+1] - z[t-1]),  dL/dmu_2[t] = tau_2(t) (z[t-1] - 2 z[t] + z[t+1])
+ * (z outside the utterance counts as 0; tau_w(t) = 1 / var_w, or 1e-11 in the first and last frame for w = 1, 2).
+ *   d_gout      [Ttot, ld_gout] f64 (f32 if gout_is_f32): dL/dc of dimension d in column gcol0+d
+ *   d_var, h_offsets (or the plan): as for itts_mlpg_generation
+ *   d_gfeat     [Ttot, ld_gfeat] f64 (f32 if gfeat_is_f32): columns col0+d, col0+D+d, col0+2D+d of every frame are
+ *               overwritten, nothing else is touched; arithmetic in f64, an f32 destination rounded once at the store
+ *   d_scratch   >= itts_mlpg_adjoint_scratch_bytes(Ttot, D) bytes
+ * One form (mlpg_adjoint_kernel) for every shape; no atomics: repeated calls give identical bits. */
+int64_t itts_mlpg_adjoint_scratch_bytes(int64_t t_total, int dim);
+int itts_mlpg_adjoint(const void* d_gout, int gout_is_f32, int64_t ld_gout, int gcol0, int dim,
+                      const double* d_var, const int64_t* h_offsets, int n_utts,
+                      void* d_gfeat, int gfeat_is_f32, int64_t ld_gfeat, int col0,
+                      void* d_scratch, void* stream);
+int itts_mlpg_adjoint_planned(const void* plan, const void* d_gout, int gout_is_f32, int64_t ld_gout, int gcol0,
+                              int dim, const double* d_var, void* d_gfeat, int gfeat_is_f32, int64_t ld_gfeat,
+                              int col0, void* d_scratch, void* stream);
+
 /* ---- frame utilities (misc/utils.py:40-105) --------------------------------------------- */
 /* compute_deltas == np.gradient(x, axis=0) in float32 (utils.py:103-105): part of
  * itts_assemble_cmp_f32 below (static, delta, delta-delta columns of every stream in one pass). */
