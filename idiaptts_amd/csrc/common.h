@@ -113,6 +113,10 @@ class ScratchScope {
 // itts_linear_bwd_weight, queued instead of launched inside itts_defer_reductions.
 int reduce_slabs(const float* slabs, int S, int64_t n, float* out, int accumulate, hipStream_t s);
 
+// *loss = (float)(scale * sum of the nb partial sums), one launch of one workgroup in a fixed order (nn.hip): the
+// last step of every loss entry point.
+int loss_final_sum(const double* partial, int64_t nb, double scale, float* loss, hipStream_t s);
+
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 // 16-byte aligned: with a pitch that is a multiple of 4 floats, rows may be read as float4

@@ -27,6 +27,7 @@
 
 #include "common.h"
 #include "gemm_staged.h"
+#include "row4.h"
 
 namespace itts {
 namespace conv {
@@ -287,9 +288,6 @@ static bool geometry_ok(int B, int T_in, int Cin, int Cout, int Kw, int pad, int
   return sizes_positive(B, T_in, Cin, Cout, Kw, pad, dil) && out_len(T_in, Kw, pad, dil) > 0 &&
          within_2_31(B, T_in, Cin, Cout, Kw, pad, dil);
 }
-
-// 16-byte loads from rows of this pitch at this base (the VEC instantiations).
-static bool rows16(const float* p, int64_t ld) { return ld % 4 == 0 && aligned16(p); }
 
 // The plan of product 0 (forward), 1 (input gradient) or 2 (weight gradient) for a valid geometry.
 // The GEMM is M x N over K: forward B*T_out x Cout over Kw * Cinp, input gradient B*T_in x Cin over

@@ -23,6 +23,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "row4.h"
 
 namespace itts {
 namespace {
@@ -34,35 +35,8 @@ constexpr int FA_MAX_P = 2048;
 constexpr int FA_MAX_C = 4096;
 constexpr int FA_MAX_N = 64;
 
-bool rows16(const float* p, int64_t ld, int64_t utt) { return ld % 4 == 0 && utt % 4 == 0 && aligned16(p); }
-
-// columns col .. col + 3 of a row, zeros from column D on
-template <bool VEC>
-__device__ __forceinline__ void load4(const float* __restrict__ row, int col, int D, float* v) {
-  v[0] = v[1] = v[2] = v[3] = 0.f;
-  if (col >= D) return;
-  if (VEC && col + 3 < D) {
-    const float4 t = *reinterpret_cast<const float4*>(row + col);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (col + k < D) v[k] = row[col + k];
-  }
-}
-
-// .. and the store: nothing at or beyond column D is written
-template <bool VEC>
-__device__ __forceinline__ void store4(float* __restrict__ row, int col, int D, const float* v) {
-  if (col >= D) return;
-  if (VEC && col + 3 < D) {
-    *reinterpret_cast<float4*>(row + col) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (col + k < D) row[col + k] = v[k];
-  }
-}
+// .. of a batch: the utterances' rows too
+bool rows16(const float* p, int64_t ld, int64_t utt) { return utt % 4 == 0 && itts::rows16(p, ld); }
 
 struct FaArgs {
   const float* A; int64_t ldA, uttA;        // [B, T, P]: floats from one frame to the next / one utterance to the next
@@ -93,7 +67,7 @@ __global__ __launch_bounds__(FA_THREADS) void fixed_attention_fwd_kernel(FaArgs 
       float s[4] = {0.f, 0.f, 0.f, 0.f};
       for (int r = 0; r < rows; ++r) {
         float v[4];
-        load4<VEC_P>(Ab + r * a.ldA, p, a.P, v);
+        load4z<VEC_P>(Ab + r * a.ldA, p, a.P, v);
 #pragma unroll
         for (int q = 0; q < 4; ++q) s[q] += v[q];
       }
@@ -127,7 +101,7 @@ __global__ __launch_bounds__(FA_THREADS) void fixed_attention_fwd_kernel(FaArgs 
       const int2 pw = pairs[e];
       const float w = __int_as_float(pw.y);
       float v[4];
-      load4<VEC_C>(Eb + (int64_t)pw.x * a.ldE, col, a.C, v);
+      load4z<VEC_C>(Eb + (int64_t)pw.x * a.ldE, col, a.C, v);
       if (e == 0) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) acc[q] = w * v[q];
@@ -172,7 +146,7 @@ __global__ __launch_bounds__(FA_THREADS) void fixed_attention_bwd_kernel(FaBwdAr
         nz &= nz - 1ull;
         const float wk = __shfl(w[q], src, 64);
         float v[4];
-        load4<VEC_C>(Xb + (k0 + src) * a.ldX, col, a.C, v);
+        load4z<VEC_C>(Xb + (k0 + src) * a.ldX, col, a.C, v);
         if (first[q]) {
 #pragma unroll
           for (int c = 0; c < 4; ++c) acc[q][c] = wk * v[c];

@@ -17,6 +17,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "row4.h"
 
 namespace itts {
 namespace {
@@ -27,35 +28,6 @@ constexpr int PL_THREADS = PL_WAVES * kWave;
 constexpr int PL_TILE = 4 * kWave;     // columns of a workgroup's tile (four per lane)
 constexpr int64_t PL_FILL = 512;       // (utterance, tile) pairs from which one workgroup per pair fills the GPU
 constexpr int64_t PL_MAX_SEGMENTS = 65535;
-
-bool rows16(const float* p, int64_t ld) { return ld % 4 == 0 && aligned16(p); }
-
-// columns col .. col + 3 of a row, zeros from column D on
-template <bool VEC>
-__device__ __forceinline__ void load4(const float* __restrict__ row, int col, int D, float* v) {
-  v[0] = v[1] = v[2] = v[3] = 0.f;
-  if (col >= D) return;
-  if (VEC && col + 3 < D) {
-    const float4 t = *reinterpret_cast<const float4*>(row + col);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (col + k < D) v[k] = row[col + k];
-  }
-}
-
-// .. and the store: nothing at or beyond column D is written
-template <bool VEC>
-__device__ __forceinline__ void store4(float* __restrict__ row, int col, int D, const float* v) {
-  if (VEC && col + 3 < D) {
-    *reinterpret_cast<float4*>(row + col) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (col + k < D) row[col + k] = v[k];
-  }
-}
 
 struct PoolPlan {
   int tiles;         // column tiles of PL_TILE
@@ -94,7 +66,7 @@ __device__ __forceinline__ float segment_sum(const float* __restrict__ xb, int64
   for (; i + (U - 1) * PL_WAVES < n; i += U * PL_WAVES) {
     float v[U][4];
 #pragma unroll
-    for (int u = 0; u < U; ++u) load4<VEC>(xb + (t0 + i + u * PL_WAVES) * row_step, col, D, v[u]);
+    for (int u = 0; u < U; ++u) load4z<VEC>(xb + (t0 + i + u * PL_WAVES) * row_step, col, D, v[u]);
 #pragma unroll
     for (int u = 0; u < U; ++u)
 #pragma unroll
@@ -102,7 +74,7 @@ __device__ __forceinline__ float segment_sum(const float* __restrict__ xb, int64
   }
   for (; i < n; i += PL_WAVES) {
     float v[4];
-    load4<VEC>(xb + (t0 + i) * row_step, col, D, v);
+    load4z<VEC>(xb + (t0 + i) * row_step, col, D, v);
 #pragma unroll
     for (int k = 0; k < 4; ++k) s[k] += v[k];
   }
@@ -192,11 +164,11 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(PoolBwdArgs a) {
     float v[4] = {0.f, 0.f, 0.f, 0.f};
     const float sc = scale[r];
     if (a.mode == ITTS_POOL_MEAN) {
-      load4<VEC>(a.dy + utt[r] * a.lddy, col, a.D, v);
+      load4z<VEC>(a.dy + utt[r] * a.lddy, col, a.D, v);
 #pragma unroll
       for (int k = 0; k < 4; ++k) v[k] = v[k] / sc;
     } else if (sc != 0.f) {
-      load4<VEC>(a.dy + utt[r] * a.lddy, col, a.D, v);
+      load4z<VEC>(a.dy + utt[r] * a.lddy, col, a.D, v);
     }
     store4<VEC>(a.dx + (r0 + r) * a.lddx, col, a.D, v);
   }
@@ -223,9 +195,9 @@ __global__ __launch_bounds__(256) void reparam_fwd_kernel(ReparamArgs a) {
     const int64_t r = i / nq;
     const int col = 4 * (int)(i - r * nq);
     float mu[4], lv[4], e[4];
-    load4<VEC>(a.h + r * a.ldh, col, a.L, mu);
-    load4<VEC>(a.h + r * a.ldh + a.L, col, a.L, lv);
-    load4<VEC>(a.eps + r * a.lde, col, a.L, e);
+    load4z<VEC>(a.h + r * a.ldh, col, a.L, mu);
+    load4z<VEC>(a.h + r * a.ldh + a.L, col, a.L, lv);
+    load4z<VEC>(a.eps + r * a.lde, col, a.L, e);
 #pragma unroll
     for (int k = 0; k < 4; ++k) mu[k] = e[k] * expf(0.5f * lv[k]) + mu[k];
     store4<VEC>(a.z + r * a.ldz, col, a.L, mu);
@@ -240,13 +212,13 @@ __global__ __launch_bounds__(256) void reparam_bwd_kernel(ReparamArgs a) {
     const int64_t r = i / nq;
     const int col = 4 * (int)(i - r * nq);
     float g[4] = {0.f, 0.f, 0.f, 0.f}, gm[4] = {0.f, 0.f, 0.f, 0.f}, gl[4] = {0.f, 0.f, 0.f, 0.f};
-    if (a.dmu) load4<VEC>(a.dmu + r * a.lddmu, col, a.L, gm);
-    if (a.dlv) load4<VEC>(a.dlv + r * a.lddlv, col, a.L, gl);
+    if (a.dmu) load4z<VEC>(a.dmu + r * a.lddmu, col, a.L, gm);
+    if (a.dlv) load4z<VEC>(a.dlv + r * a.lddlv, col, a.L, gl);
     if (a.dz) {
       float lv[4], e[4];
-      load4<VEC>(a.dz + r * a.lddz, col, a.L, g);
-      load4<VEC>(a.h + r * a.ldh + a.L, col, a.L, lv);
-      load4<VEC>(a.eps + r * a.lde, col, a.L, e);
+      load4z<VEC>(a.dz + r * a.lddz, col, a.L, g);
+      load4z<VEC>(a.h + r * a.ldh + a.L, col, a.L, lv);
+      load4z<VEC>(a.eps + r * a.lde, col, a.L, e);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         gm[k] = g[k] + gm[k];
@@ -298,8 +270,8 @@ __global__ __launch_bounds__(KL_WAVES * kWave) void kl_kernel(KlArgs a) {
     float s = 0.f;
     for (int col = 4 * lane; col < a.L; col += 4 * kWave) {
       float m[4], l[4], gm[4], gl[4];
-      load4<VEC>(a.mu + r * a.ldmu, col, a.L, m);
-      load4<VEC>(a.lv + r * a.ldlv, col, a.L, l);
+      load4z<VEC>(a.mu + r * a.ldmu, col, a.L, m);
+      load4z<VEC>(a.lv + r * a.ldlv, col, a.L, l);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const float e = expf(l[k]);
@@ -317,15 +289,6 @@ __global__ __launch_bounds__(KL_WAVES * kWave) void kl_kernel(KlArgs a) {
   if (lane == 0) wsum[wave] = acc;
   __syncthreads();
   if (threadIdx.x == 0) a.partial[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
-}
-
-__global__ __launch_bounds__(256) void kl_final_kernel(const double* __restrict__ partial, int nb,
-                                                       float* __restrict__ loss) {
-  __shared__ double red[16];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < nb; i += 256) s += partial[i];  // fixed order: deterministic
-  s = block_sum(s, red);
-  if (threadIdx.x == 0) *loss = (float)s;
 }
 
 }  // namespace
@@ -506,7 +469,5 @@ extern "C" int itts_vae_kld(const float* d_mu, int64_t ldmu, const float* d_lv, 
   if (vec) kl_kernel<true><<<dim3(nb), KL_WAVES * kWave, 0, s>>>(a);
   else kl_kernel<false><<<dim3(nb), KL_WAVES * kWave, 0, s>>>(a);
   ITTS_LAUNCH_CHECK();
-  kl_final_kernel<<<dim3(1), 256, 0, s>>>(a.partial, nb, d_loss);
-  ITTS_LAUNCH_CHECK();
-  return ITTS_OK;
+  return loss_final_sum(a.partial, nb, 1.0, d_loss, s);
 }

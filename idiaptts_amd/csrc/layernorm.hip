@@ -23,6 +23,7 @@
 
 #include "activations.h"
 #include "common.h"
+#include "row4.h"
 
 namespace itts {
 namespace {
@@ -40,39 +41,6 @@ int64_t rows_per_block(int64_t N) {
 int64_t slab_count(int64_t N) {
   const int64_t R = rows_per_block(N);
   return (N + R - 1) / R;
-}
-
-bool rows16(const float* p, int64_t ld) { return ld % 4 == 0 && aligned16(p); }
-
-// columns col .. col + 3 of a row, zeros from column D on (what lies there -- pad floats of the pitch -- is
-// read by the 16-byte load and dropped)
-template <bool VEC>
-__device__ __forceinline__ void load4(const float* __restrict__ row, int col, int D, float* v) {
-  v[0] = v[1] = v[2] = v[3] = 0.f;
-  if (col >= D) return;
-  if (VEC) {
-    const float4 t = *reinterpret_cast<const float4*>(row + col);
-    v[0] = t.x;
-    if (col + 1 < D) v[1] = t.y;
-    if (col + 2 < D) v[2] = t.z;
-    if (col + 3 < D) v[3] = t.w;
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (col + k < D) v[k] = row[col + k];
-  }
-}
-
-// .. and the store: nothing at or beyond column D is written
-template <bool VEC>
-__device__ __forceinline__ void store4(float* __restrict__ row, int col, int D, const float* v) {
-  if (VEC && col + 3 < D) {
-    *reinterpret_cast<float4*>(row + col) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (col + k < D) row[col + k] = v[k];
-  }
 }
 
 struct LnFwdArgs {
@@ -107,7 +75,7 @@ __global__ __launch_bounds__(LN_THREADS) void ln_fwd_kernel(LnFwdArgs a) {
     float s = 0.f;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-      load4<VEC>(xr, 4 * (lane + 64 * j), D, x + 4 * j);
+      load4z_pitch<VEC>(xr, 4 * (lane + 64 * j), D, x + 4 * j);
 #pragma unroll
       for (int k = 0; k < 4; ++k) s += x[4 * j + k];
     }
@@ -192,7 +160,7 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(LnBwdArgs a) {
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       const int col = 4 * (lane + 64 * j);
-      load4<VEC>(xr, col, D, xh + 4 * j);
+      load4z_pitch<VEC>(xr, col, D, xh + 4 * j);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         xh[4 * j + k] = col + k < D ? xh[4 * j + k] - mean : 0.f;
@@ -205,8 +173,8 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(LnBwdArgs a) {
     for (int j = 0; j < NJ; ++j) {
       const int col = 4 * (lane + 64 * j);
       float y4[4];
-      load4<VEC>(dyr, col, D, g + 4 * j);
-      if (a.y) load4<VEC>(a.y + r * a.ldy, col, D, y4);
+      load4z_pitch<VEC>(dyr, col, D, g + 4 * j);
+      if (a.y) load4z_pitch<VEC>(a.y + r * a.ldy, col, D, y4);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const int i = 4 * j + k;

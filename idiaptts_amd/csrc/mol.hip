@@ -194,15 +194,6 @@ __global__ __launch_bounds__(THREADS) void mol_kernel(MolArgs a) {
   if (tid == 0) a.partial[b * gridDim.x + blockIdx.x] = tot;
 }
 
-__global__ __launch_bounds__(256) void mol_final_kernel(const double* __restrict__ partial, int64_t nb,
-                                                        float* __restrict__ loss) {
-  __shared__ double red[16];
-  double s = 0.0;
-  for (int64_t i = threadIdx.x; i < nb; i += 256) s += partial[i];      // fixed order: deterministic
-  s = block_sum(s, red);
-  if (threadIdx.x == 0) *loss = (float)s;
-}
-
 template <int THREADS>
 void launch_mol(const MolArgs& a, int B, hipStream_t s) {
   const size_t lds = (size_t)3 * a.K * THREADS * sizeof(float);
@@ -368,9 +359,7 @@ extern "C" int itts_mol_loss(const float* d_x, const float* d_y, const float* d_
   else if (threads == 128) launch_mol<128>(a, B, s);
   else launch_mol<64>(a, B, s);
   ITTS_LAUNCH_CHECK();
-  mol_final_kernel<<<dim3(1), 256, 0, s>>>(a.partial, mol_chunks(T, threads) * B, d_loss);
-  ITTS_LAUNCH_CHECK();
-  return ITTS_OK;
+  return loss_final_sum(a.partial, mol_chunks(T, threads) * B, 1.0, d_loss, s);
 }
 
 extern "C" int itts_mulaw_encode_f64(const double* d_x, const int64_t* h_offsets, int n_signals, int mu,

@@ -558,6 +558,22 @@ int reduce_slabs(const float* slabs, int S, int64_t n, float* out, int accumulat
   return launch_reduce_slabs(slabs, S, n, out, accumulate, s);
 }
 
+// The last step of every loss entry point: the workgroups' partial sums, added in a fixed order.
+__global__ __launch_bounds__(256) void loss_final_kernel(const double* __restrict__ partial, int64_t nb,
+                                                         double scale, float* __restrict__ loss) {
+  __shared__ double red[16];
+  double s = 0.0;
+  for (int64_t i = threadIdx.x; i < nb; i += 256) s += partial[i];  // fixed order: deterministic
+  s = block_sum(s, red);
+  if (threadIdx.x == 0) *loss = (float)(s * scale);
+}
+
+int loss_final_sum(const double* partial, int64_t nb, double scale, float* loss, hipStream_t s) {
+  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, s, partial, nb, scale, loss);
+  ITTS_LAUNCH_CHECK();
+  return ITTS_OK;
+}
+
 extern "C" int itts_defer_reductions(int on) {
   ITTS_REQUIRE(on || t_pending.nseg == 0,
                "queued reductions must be run (itts_reduce_deferred) before deferral is switched off");
@@ -607,27 +623,14 @@ __global__ __launch_bounds__(256) void masked_mse_kernel(
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
-__global__ __launch_bounds__(256) void masked_mse_final_kernel(const double* __restrict__ partial,
-                                                               int nb, double scale,
-                                                               float* __restrict__ loss) {
-  __shared__ double red[16];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < nb; i += 256) s += partial[i];  // fixed order: deterministic
-  s = block_sum(s, red);
-  if (threadIdx.x == 0) *loss = (float)(s * scale);
-}
-
 static int launch_mse_final(const double* partial, int nb, double scale, float* loss, hipStream_t s) {
   if (t_defer) {
     ReduceSeg g{};
     g.src = partial; g.out = loss; g.n = nb; g.scale = scale; g.S = 1; g.kind = 2;
     return queue_deferred(g, s);
   }
-  hipLaunchKernelGGL(masked_mse_final_kernel, dim3(1), dim3(256), 0, s, partial, nb, scale, loss);
-  ITTS_LAUNCH_CHECK();
-  return ITTS_OK;
+  return loss_final_sum(partial, nb, scale, loss, s);
 }
-
 
 // ---- row-weighted elementwise losses (the other NamedLoss types / reductions) ------------------
 // loss = sum_r w[r] sum_c e(pred - target), e = squared (kind 0, MSELoss) or absolute (kind 1,
@@ -1136,10 +1139,7 @@ extern "C" int itts_weighted_loss(const float* d_pred, int64_t ldp, const float*
                      d_row_weight, M, D, kind, d_grad, ldg, d_elem, lde,
                      reinterpret_cast<double*>(d_workspace));
   ITTS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(masked_mse_final_kernel, dim3(1), dim3(256), 0, s,
-                     reinterpret_cast<const double*>(d_workspace), nb, 1.0, d_loss);
-  ITTS_LAUNCH_CHECK();
-  return ITTS_OK;
+  return loss_final_sum(reinterpret_cast<const double*>(d_workspace), nb, 1.0, d_loss, s);
 }
 
 extern "C" int itts_adam_step(float* d_param, const float* d_grad, float* d_exp_avg,

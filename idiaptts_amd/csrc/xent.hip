@@ -33,6 +33,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "row4.h"
 
 namespace itts {
 namespace {
@@ -42,34 +43,6 @@ constexpr int XE_THREADS = XE_WAVES * kWave;
 constexpr int64_t XE_MAX_BLOCKS = 4096;
 constexpr int XE_MAX_C = 4096;
 constexpr int XE_CONF_MAX_C = 1024;    // largest confusion matrix: 1024 x 1024 int64 = 8 MiB
-
-bool rows16(const float* p, int64_t ld) { return ld % 4 == 0 && aligned16(p); }
-
-// columns col .. col + 3 of a row; what lies at or beyond column C stays as it is
-template <bool VEC>
-__device__ __forceinline__ void load4(const float* __restrict__ row, int col, int C, float* v) {
-  if (col >= C) return;
-  if (VEC && col + 3 < C) {
-    const float4 t = *reinterpret_cast<const float4*>(row + col);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (col + k < C) v[k] = row[col + k];
-  }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void store4(float* __restrict__ row, int col, int C, const float* v) {
-  if (col >= C) return;
-  if (VEC && col + 3 < C) {
-    *reinterpret_cast<float4*>(row + col) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (col + k < C) row[col + k] = v[k];
-  }
-}
 
 // lanes of a row and steps of 4 * lanes columns
 struct RowsPlan {
@@ -342,15 +315,6 @@ __global__ __launch_bounds__(XS_THREADS) void xent_strided_kernel(XentStridedArg
   if (threadIdx.x == 0) a.partial[b * gridDim.x + blockIdx.x] = tot;
 }
 
-__global__ __launch_bounds__(256) void xent_final_kernel(const double* __restrict__ partial, int64_t nb,
-                                                         float* __restrict__ loss) {
-  __shared__ double red[16];
-  double s = 0.0;
-  for (int64_t i = threadIdx.x; i < nb; i += 256) s += partial[i];      // fixed order: deterministic
-  s = block_sum(s, red);
-  if (threadIdx.x == 0) *loss = (float)s;
-}
-
 template <int G, int S>
 void launch_rows(const XentArgs& a, bool vec, int nb, hipStream_t s) {
   if (vec) xent_rows_kernel<G, S, true><<<dim3(nb), XE_THREADS, 0, s>>>(a);
@@ -464,9 +428,7 @@ extern "C" int itts_softmax_xent(const float* d_x, int64_t ld, const int64_t* d_
     default: ITTS_REQUIRE(false, "no width class for C = " + std::to_string(C));
   }
   ITTS_LAUNCH_CHECK();
-  xent_final_kernel<<<dim3(1), 256, 0, s>>>(a.partial, nb, d_loss);
-  ITTS_LAUNCH_CHECK();
-  return ITTS_OK;
+  return loss_final_sum(a.partial, nb, 1.0, d_loss, s);
 }
 
 extern "C" int itts_softmax_xent_strided(const float* d_x, const float* d_onehot, const float* d_cw,
@@ -498,9 +460,7 @@ extern "C" int itts_softmax_xent_strided(const float* d_x, const float* d_onehot
   else
     xent_strided_kernel<false><<<dim3((unsigned)chunks, (unsigned)B), XS_THREADS, 0, s>>>(a);
   ITTS_LAUNCH_CHECK();
-  xent_final_kernel<<<dim3(1), 256, 0, s>>>(a.partial, chunks * B, d_loss);
-  ITTS_LAUNCH_CHECK();
-  return ITTS_OK;
+  return loss_final_sum(a.partial, chunks * B, 1.0, d_loss, s);
 }
 
 template <int G>

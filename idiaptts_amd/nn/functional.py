@@ -372,6 +372,69 @@ class VAEReparamFunction(torch.autograd.Function):
         return ops.vae_reparam_bwd(grads[0], grads[1], grads[2], h2, e2).reshape(ctx.in_shape), None
 
 
+# ---- the loss Functions: one launch gives the loss and its gradient(s); backward only scales what forward saved ----
+def _scale_saved(grad, dloss, lift=None):
+    """d loss / d input from the gradient the forward saved and the gradient of the Function's output.  A summed loss
+    (lift None) has a 0-dim dloss: the training loop's `unit_gradient` gives the saved tensor itself, no launch, any
+    other factor one product.  An element-wise loss (reduction 'none') passes `lift`, which brings dloss to the saved
+    gradient's shape."""
+    if lift is not None:
+        return grad * lift(dloss)
+    return grad if is_unit_gradient(dloss) else grad * dloss
+
+
+def _as_is(dloss):
+    return dloss
+
+
+def _over_classes(dloss):
+    """[..] per-row values -> [.., 1] against logits [.., C]"""
+    return dloss.unsqueeze(-1)
+
+
+def _over_channels(shift):
+    """[B, T - shift] per-frame values -> [B, 1, T] against [B, C, T]: the last `shift` frames have no loss"""
+    return lambda dloss: (torch.nn.functional.pad(dloss, (0, shift)) if shift else dloss).unsqueeze(1)
+
+
+# When the gradient is computed: MaskedMSEFunction and WeightedLossFunction always ask the kernel for it, the four
+# others follow needs_input_grad (none under no_grad); making them one is a speed change for validation, not done here.
+class MaskedMSEFunction(torch.autograd.Function):
+    """sum over the valid rows of (pred - target)^2 / (n_valid * D): MSELoss under 'mean_per_frame'"""
+
+    @staticmethod
+    def forward(ctx, pred, target, row_valid, n_valid):
+        D = pred.shape[-1]
+        loss, grad = ops.masked_mse(_rows2(pred, D), _rows2(target, D), row_valid, n_valid, want_grad=True)
+        ctx.save_for_backward(grad)
+        ctx.shape = pred.shape
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        (grad,) = ctx.saved_tensors
+        return _scale_saved(grad, dloss).reshape(ctx.shape), None, None, None
+
+
+class WeightedLossFunction(torch.autograd.Function):
+    """sum_r w[r] sum_c e(pred - target) (e: squared / absolute error) or, with `elementwise`, the
+    weighted element-wise values themselves (reduction 'none')."""
+
+    @staticmethod
+    def forward(ctx, pred, target, row_weight, kind, elementwise):
+        D = pred.shape[-1]
+        loss, grad, elem = ops.weighted_loss(_rows2(pred, D), _rows2(target, D), row_weight, kind, want_grad=True,
+                                             want_elem=elementwise)
+        ctx.save_for_backward(grad)
+        ctx.shape, ctx.elementwise = pred.shape, elementwise
+        return elem.reshape(pred.shape) if elementwise else loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        (grad,) = ctx.saved_tensors
+        return _scale_saved(grad.reshape(ctx.shape), dloss, _as_is if ctx.elementwise else None), None, None, None, None
+
+
 class VAEKLDFunction(torch.autograd.Function):
     """sum_r w[r] * 0.5 * sum_c (exp(log_var) + mu^2 - 1 - log_var), or with `elementwise` the weighted per-row
     values [.., 1] (reduction 'none'); loss/VAEKLDLoss.py:56-58 with the mask and the reduction folded into w as in
@@ -391,10 +454,8 @@ class VAEKLDFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dloss):
-        dmu, dlv = ctx.saved_tensors
-        dmu, dlv = dmu.reshape(ctx.shape), dlv.reshape(ctx.shape)
-        if not is_unit_gradient(dloss):
-            dmu, dlv = dmu * dloss, dlv * dloss       # (elementwise: [.., 1] broadcasts over the latent axis)
+        lift = _as_is if ctx.elementwise else None        # ([.., 1] broadcasts over the latent axis)
+        dmu, dlv = (_scale_saved(g.reshape(ctx.shape), dloss, lift) for g in ctx.saved_tensors)
         return dmu, dlv, None, None
 
 
@@ -418,12 +479,8 @@ class SoftmaxXentFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dloss):
         (grad,) = ctx.saved_tensors
-        grad = grad.reshape(ctx.shape)
-        if ctx.elementwise:
-            grad = grad * dloss.unsqueeze(-1)
-        elif not is_unit_gradient(dloss):
-            grad = grad * dloss
-        return grad, None, None, None, None, None
+        lift = _over_classes if ctx.elementwise else None
+        return _scale_saved(grad.reshape(ctx.shape), dloss, lift), None, None, None, None, None
 
 
 class SoftmaxXentStridedFunction(torch.autograd.Function):
@@ -438,19 +495,13 @@ class SoftmaxXentStridedFunction(torch.autograd.Function):
                                                     want_grad=want_grad, want_elem=elementwise)
         if want_grad:
             ctx.save_for_backward(grad)
-        ctx.elementwise, ctx.shift = elementwise, int(shift or 0)
+        ctx.lift = _over_channels(int(shift or 0)) if elementwise else None
         return elem if elementwise else loss.reshape(())
 
     @staticmethod
     def backward(ctx, dloss):
         (grad,) = ctx.saved_tensors
-        if ctx.elementwise:
-            if ctx.shift:                            # [B, T - shift] -> [B, 1, T]: the last frames have no loss
-                dloss = torch.nn.functional.pad(dloss, (0, ctx.shift))
-            grad = grad * dloss.unsqueeze(1)
-        elif not is_unit_gradient(dloss):
-            grad = grad * dloss
-        return grad, None, None, None, None, None, None
+        return _scale_saved(grad, dloss, ctx.lift), None, None, None, None, None, None
 
 
 class MolLossFunction(torch.autograd.Function):
@@ -465,19 +516,13 @@ class MolLossFunction(torch.autograd.Function):
                                         want_grad=want_grad, want_elem=elementwise)
         if want_grad:
             ctx.save_for_backward(grad)
-        ctx.elementwise, ctx.shift = elementwise, int(shift or 0)
+        ctx.lift = _over_channels(int(shift or 0)) if elementwise else None
         return elem if elementwise else loss.reshape(())
 
     @staticmethod
     def backward(ctx, dloss):
         (grad,) = ctx.saved_tensors
-        if ctx.elementwise:
-            if ctx.shift:                            # [B, T - shift] -> [B, 1, T]: the last frames have no loss
-                dloss = torch.nn.functional.pad(dloss, (0, ctx.shift))
-            grad = grad * dloss.unsqueeze(1)
-        elif not is_unit_gradient(dloss):
-            grad = grad * dloss
-        return grad, None, None, None, None, None, None, None
+        return _scale_saved(grad, dloss, ctx.lift), None, None, None, None, None, None, None
 
 
 class GluGateFunction(torch.autograd.Function):

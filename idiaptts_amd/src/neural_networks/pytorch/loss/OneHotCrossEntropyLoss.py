@@ -25,12 +25,19 @@ class OneHotCrossEntropyLoss(torch.nn.CrossEntropyLoss):
         self.shift = shift
         super().__init__(weight=weight, ignore_index=ignore_index, reduction='none')
 
+    def _check(self, input, target, need_frames=True):
+        if input.dim() != 3 or target.shape != input.shape:
+            raise ValueError("OneHotCrossEntropyLoss takes logits and a one-hot target of one shape [B, C, T], got {} "
+                             "and {}.".format(tuple(input.shape), tuple(target.shape)))
+        shift = self.shift or 0
+        if need_frames and shift >= input.shape[2]:
+            raise ValueError("shift = {} leaves no frame of T = {}.".format(shift, input.shape[2]))
+        return shift
+
     def frame_losses(self, input, target, row_weight=None, elementwise=True):
         """The kernel call NamedLoss shares: per-frame values [B, T - shift] times `row_weight`, or their sum."""
+        shift = self._check(input, target)
         B, _, T = input.shape
-        shift = self.shift or 0
-        if shift >= T:
-            raise ValueError("shift = {} leaves no frame of T = {}.".format(shift, T))
         if row_weight is None:
             row_weight = torch.ones(B * (T - shift), dtype=torch.float32, device=input.device)
         weight = self.weight.float() if self.weight is not None else None
@@ -38,9 +45,7 @@ class OneHotCrossEntropyLoss(torch.nn.CrossEntropyLoss):
                                                 shift, elementwise)
 
     def forward(self, input, target):
-        if input.dim() != 3 or target.shape != input.shape:
-            raise ValueError("OneHotCrossEntropyLoss takes logits and a one-hot target of one shape [B, C, T], got {} "
-                             "and {}.".format(tuple(input.shape), tuple(target.shape)))
+        self._check(input, target, need_frames=input.is_cuda)     # (on the CPU no frames give an empty loss, as torch)
         if not input.is_cuda:
             _, targets = target.max(dim=1)
             if self.shift is not None:

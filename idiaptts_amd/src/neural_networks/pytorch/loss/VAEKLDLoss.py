@@ -13,7 +13,7 @@ from torch import nn
 
 from idiaptts_amd.nn.functional import VAEKLDFunction
 
-from .NamedLoss import _total
+from .row_weight import effective_reduction, mask_lengths, row_weight, weighted_output
 
 
 class VAEKLDLoss(nn.Module):
@@ -29,11 +29,7 @@ class VAEKLDLoss(nn.Module):
             self.seq_mask = seq_mask
             self.batch_first = batch_first
             self.input_merge_type = input_merge_type
-            # reference NamedLoss.Config :39-43: nothing to divide by without a mask
-            if seq_mask is None and reduction in ('mean_per_frame', 'mean_per_sample'):
-                self.reduction = 'mean'
-            else:
-                self.reduction = reduction
+            self.reduction = effective_reduction(reduction, seq_mask)
             self.loss_weight = loss_weight
             self.start_step = start_step
             self.kwargs = kwargs
@@ -88,16 +84,8 @@ class VAEKLDLoss(nn.Module):
             else:
                 raise ValueError("Sequence mask {} of {} frames cannot be applied to {} of {} frames."
                                  .format(self.seq_mask, Tm, self.input_names, T))
-        if self.reduction == "mean_per_frame":
-            w = w / _total(length_dict[self.seq_mask])
-        elif self.reduction == "mean_per_sample":
-            lens = torch.as_tensor(length_dict[self.seq_mask], dtype=torch.float32, device=mu.device)
-            shape = [1, 1]
-            shape[1 - time_dim] = lens.numel()
-            w = w / (lens.reshape(shape) * lens.numel())
-        elif self.reduction == "mean":
-            w = w / float(n_pos)
-        return w.reshape(-1).contiguous()
+        return row_weight(w, self.reduction, mask_lengths(self.reduction, length_dict, self.seq_mask), 1 - time_dim,
+                          n_pos=n_pos)
 
     def forward(self, data, length_dict, step):
         mu, log_var = (data[n] for n in self.input_names)
@@ -115,10 +103,8 @@ class VAEKLDLoss(nn.Module):
         else:
             w = self._row_weight(mu, mask, length_dict)
             loss = VAEKLDFunction.apply(mu, log_var, w, self.reduction == "none")
-        weight = 0. if step < self.start_step else self.loss_weight
-        out = {self.name: self._anneal(loss if weight == 1.0 else loss * weight, step)}
-        data.update(out)
-        return out
+        return weighted_output(data, self.name, loss, step, self.start_step, self.loss_weight,
+                               then=lambda weighted: self._anneal(weighted, step))
 
     def annealing_factor(self, step):
         """reference _anneal (:60-67), literally: non-zero only on a multiple of annealing_steps past the first
