@@ -7,6 +7,8 @@
 //     broadcasts, the slab address, a ds_read_b128, two packed fmaf and its share of the loads and loop), and the
 //     walk runs to the longest of four lists; the LDS reads themselves (nnz x N x 4 bytes at 256 B/clk/CU) take
 //     under a fifth of the kernel's time.
+//   * what does not depend on the density: the slab fill (w read along k, 16 bytes a lane where w's rows allow it),
+//     the store of y and the activation.
 #include <algorithm>
 #include <atomic>
 #include <utility>
@@ -22,6 +24,7 @@ constexpr int kFwdWaves = 16;         // one workgroup per CU (LDS), four waves 
 constexpr int kRowsPerWave = 4;       // a quarter wave per row: 16 lanes x 4 columns
 constexpr int kStep = 8;              // list slots per trip of the walk; the build pads every list to whole trips
 constexpr int kFetch = 16;            // list entries per load: one per lane of a quarter wave
+constexpr int kFillTrips = kSparseMaxK / 4 / kFwdWaves;   // 16-byte loads of a lane in the slab fill
 
 static std::atomic<int64_t> g_sparse_path[3];
 
@@ -113,7 +116,7 @@ template <int AF>
 __global__ __launch_bounds__(kFwdWaves * 64) void sparse_linear_fwd_kernel(
     const int* __restrict__ counts, const int2* __restrict__ entries, int64_t pitch, const float* __restrict__ w,
     const float* __restrict__ bias, float* __restrict__ y, int64_t ldy, int64_t M, int N, int K, int act, int ranges,
-    int store_cols, int wide_out) {
+    int store_cols, int wide_out, int wide_w) {
   extern __shared__ float4 slab4[];   // [K + 1][16] float4
   float* slab = reinterpret_cast<float*>(slab4);
   const int lane = threadIdx.x & 63;
@@ -125,11 +128,33 @@ __global__ __launch_bounds__(kFwdWaves * 64) void sparse_linear_fwd_kernel(
   const int q = lane >> 4, c4 = (lane & 15) * 4;   // this lane's row of the group and its first column in the slab
 
   // slab[k][c] = w[n0 + c][k]: a lane per column, the waves take turns at k (each lane walks along its own row of w,
-  // whose cache lines the other waves' turns reuse)
+  // whose cache lines the other waves' turns reuse).  A wave load touches 64 lines, one per lane, whatever its
+  // width, so with 16-byte rows of w a lane takes four k at a time: a quarter of the line requests, all of a wave's
+  // loads in flight together, and four ds_write_b32 into consecutive slab rows (the lanes stay consecutive in a row:
+  // conflict free).  Rows of w that are not 16-byte aligned keep the dword loop; the slab is the same either way.
   {
     const bool col_ok = n0 + lane < N;
     const float* wr = w + (int64_t)(col_ok ? n0 + lane : 0) * K;
-    for (int k = wave; k < K; k += kFwdWaves) slab[k * kSlabCols + lane] = col_ok ? wr[k] : 0.f;
+    if (wide_w) {
+      const float4* wr4 = reinterpret_cast<const float4*>(wr);
+      const int K4 = K >> 2;
+      float4 v[kFillTrips];
+#pragma unroll
+      for (int u = 0; u < kFillTrips; ++u) {
+        const int j = wave + u * kFwdWaves;
+        v[u] = (col_ok && j < K4) ? wr4[j] : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+#pragma unroll
+      for (int u = 0; u < kFillTrips; ++u) {
+        const int j = wave + u * kFwdWaves;
+        if (j < K4) {
+          float* row = slab + 4 * j * kSlabCols + lane;
+          row[0] = v[u].x; row[kSlabCols] = v[u].y; row[2 * kSlabCols] = v[u].z; row[3 * kSlabCols] = v[u].w;
+        }
+      }
+    } else {
+      for (int k = wave; k < K; k += kFwdWaves) slab[k * kSlabCols + lane] = col_ok ? wr[k] : 0.f;
+    }
     if (wave == 0) slab[K * kSlabCols + lane] = 0.f;
   }
 
@@ -252,7 +277,7 @@ static int launch_sparse_fwd(const void* d_lists, const float* d_w, const float*
   hipLaunchKernelGGL(sparse_linear_fwd_kernel<AF>, dim3((unsigned)(slabs * ranges)), dim3(kFwdWaves * 64),
                      (size_t)(K + 1) * kSlabCols * 4, s, reinterpret_cast<const int*>(base + l.counts_off),
                      reinterpret_cast<const int2*>(base + l.entries_off), l.pitch, d_w, d_b, d_y, ldy, M, N, K, act,
-                     (int)ranges, store_cols, wide_out ? 1 : 0);
+                     (int)ranges, store_cols, wide_out ? 1 : 0, (K % 4 == 0 && aligned16(d_w)) ? 1 : 0);
   ITTS_LAUNCH_CHECK();
   return ITTS_OK;
 }

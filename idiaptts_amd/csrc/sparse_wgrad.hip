@@ -173,8 +173,9 @@ __device__ __forceinline__ void col_group(const char* buf, int lane_off, int2 e,
 //   heavy: waves 0..7 take dz columns 0..31, waves 8..15 columns 32..63, each 32 rows of the tile: 16 MFMAs
 //     32x32x2 with A = dz^T from LDS (lane = column: conflict free) and B = the strip rows straight from memory.
 // Order of the sums: a light column's fmaf chain runs over the range's rows in ascending m from +0; a heavy
-// column's (and the bias's) over the rows of a wave's share, tile after tile, then the shares in wave order; the
-// ranges are the slabs of the usual split-K workspace and are added in slab order by the usual reduction.
+// column's (and the bias's) over the rows of a wave's share, tile after tile, then the shares in wave order (parked
+// in LDS by every wave at once and summed by one thread per cell: one barrier, not a round per wave); the ranges are
+// the slabs of the usual split-K workspace and are added in slab order by the usual reduction.
 __global__ __launch_bounds__(kWgWaves * 64) void sparse_wgrad_kernel(
     const float* __restrict__ dz, int64_t lddz, const float* __restrict__ strip, const char* __restrict__ streams,
     const int* __restrict__ plan, float* __restrict__ slabs, int64_t slab_stride, int lddw,
@@ -294,6 +295,25 @@ __global__ __launch_bounds__(kWgWaves * 64) void sparse_wgrad_kernel(
     __syncthreads();
   }
 
+  // The heavy shares, merged in wave order: the dz buffers are free, so every wave parks its 16 accumulators in 4 KB
+  // of its own, [wave][r][lane]; behind one barrier thread (wave, lane) sums, for two r of its half's 16, the eight
+  // shares of lane `lane` from +0 in wave order (a sum of -0 shares stays +0, as a zeroed cell that is added to).
+  float hsum[2];
+  {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) smemf[(wave * 16 + r) * 64 + lane] = hacc[r];
+    __syncthreads();
+#pragma unroll
+    for (int rr = 0; rr < 2; ++rr) {
+      const int r = 2 * (wave & 7) + rr;
+      float s = 0.f;
+#pragma unroll
+      for (int w = 0; w < 8; ++w) s += smemf[((hb * 8 + w) * 16 + r) * 64 + lane];
+      hsum[rr] = s;
+    }
+    __syncthreads();
+  }
+
   // the partial dw^T slab, transposed through LDS: out[n][k], pad columns zero, the bias sums behind it
   for (int i = tid; i < kBiasFloat + kSlab; i += kWgWaves * 64) smemf[i] = 0.f;
   __syncthreads();
@@ -307,22 +327,18 @@ __global__ __launch_bounds__(kWgWaves * 64) void sparse_wgrad_kernel(
       smemf[(4 * i16 + 3) * kTPitch + col] = acc[c].w;
     }
   }
-  __syncthreads();
-  {
+  {   // a heavy column is nobody's light column: these cells are written once
     const int h = lane & 31;
     const int hc = h < kStrip - 1 ? plan[h] : -1;
-    for (int w = 0; w < kWgWaves; ++w) {   // the waves' shares in wave order
-      if (wave == w) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int nl = hb * 32 + 8 * (r / 4) + 4 * (lane >> 5) + (r % 4);
-          if (h == kStrip - 1) smemf[kBiasFloat + nl] += hacc[r];
-          else if (hc >= 0 && hc < K) smemf[nl * kTPitch + hc] += hacc[r];
-        }
-      }
-      __syncthreads();
+    for (int rr = 0; rr < 2; ++rr) {
+      const int r = 2 * (wave & 7) + rr;
+      const int nl = hb * 32 + 8 * (r / 4) + 4 * (lane >> 5) + (r % 4);
+      if (h == kStrip - 1) smemf[kBiasFloat + nl] = hsum[rr];
+      else if (hc >= 0 && hc < K) smemf[nl * kTPitch + hc] = hsum[rr];
     }
   }
+  __syncthreads();
   for (int nn = wave; nn < kSlab; nn += kWgWaves) {
     if (n0 + nn < N) {
       float* dst = slabs + range * slab_stride + (int64_t)(n0 + nn) * lddw;
