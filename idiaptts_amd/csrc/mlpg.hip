@@ -12,8 +12,9 @@
 //   mlpg_stream.h   mlpg_prep / reduce / scan / solve: everything else, no wait anywhere: the backward contribution
 //                   of a chunk is accumulated while walking forward (adjoint identity), a two-level scan gives every
 //                   chunk its entry states, a second pass solves
-//   mlpg_adjoint.h  mlpg_adjoint_kernel: the gradient with respect to the means (one more solve with the shared factor,
-//                   the three windows applied inside the back-substitution), one form for every shape
+//   mlpg_adjoint.h  the gradient with respect to the means (one more solve with the shared factor, then the three
+//                   windows): mlpg_adjoint_kernel for short utterances (sequential, the windows inside the
+//                   back-substitution), the stream form's solve + mlpg_adjoint_window_kernel for everything else
 //   here            the choice of form, the override word, plans, the dispatcher and the C entry points
 // (Rounds 2 and 3 also carried a four-pass chunked solve and a single-pass kernel with cross-workgroup
 // waits; both measured slower -- DESIGN.md section 11c -- and left the library in round 4.)
@@ -342,7 +343,8 @@ extern "C" int itts_mlpg_generation_planned(const void* plan, const void* d_feat
 // ---- the adjoint (mlpg_adjoint.h) -----------------------------------------------------------------------------------
 extern "C" int64_t itts_mlpg_adjoint_scratch_bytes(int64_t t_total, int dim) {
   if (t_total < 0 || dim <= 0) return 0;
-  // the forward's scratch (factor planes, offsets, nconv) + the forward sweep's intermediate y [Ttot, dim]
+  // the forward's scratch (factor planes, offsets, nconv) + one [Ttot, dim] plane: the forward sweep's intermediate y
+  // (sweeps) or z (stream)
   return itts_mlpg_scratch_bytes(t_total, dim) + t_total * (int64_t)dim * 8;
 }
 
@@ -352,10 +354,40 @@ static const void* const kAdjointKernels[2][2] = {
   {(const void*)mlpg_adjoint_kernel<float, double>, (const void*)mlpg_adjoint_kernel<float, float>},
 };
 
+// The adjoint's own choice of form and override word (the forward's are not touched): sweeps under MLPG_SEQ_BELOW
+// frames, the stream form from there; no ring form.  The override forces one of the two for any length.
+static std::atomic<int> g_mlpg_adjoint_override{0};
+static thread_local int t_mlpg_adjoint_last_form = 0;
+
+static int mlpg_adjoint_choose(int64_t t_max, int ovr) {
+  if (ovr) return ovr;
+  return t_max < MLPG_SEQ_BELOW ? ITTS_MLPG_FORM_SWEEPS : ITTS_MLPG_FORM_STREAM;
+}
+
+extern "C" int itts_mlpg_adjoint_choose_form(int n_utts, int dim, int64_t t_max, int64_t t_total) {
+  ITTS_REQUIRE(n_utts >= 0 && dim > 0 && t_max >= 0 && t_total >= t_max, "bad sizes");
+  return mlpg_adjoint_choose(t_max, g_mlpg_adjoint_override.load(std::memory_order_relaxed));
+}
+
+extern "C" int itts_mlpg_adjoint_set_override(int form) {
+  ITTS_REQUIRE(form == 0 || form == ITTS_MLPG_FORM_SWEEPS || form == ITTS_MLPG_FORM_STREAM, "form: 0, sweeps or stream");
+  g_mlpg_adjoint_override.store(form, std::memory_order_relaxed);
+  return ITTS_OK;
+}
+
+extern "C" int itts_mlpg_adjoint_get_override(void) {
+  return g_mlpg_adjoint_override.load(std::memory_order_relaxed);
+}
+
+extern "C" int itts_mlpg_adjoint_last_form(void) {
+  return t_mlpg_adjoint_last_form;
+}
+
 static int mlpg_adjoint_impl(const void* d_gout, int gout_is_f32, int64_t ld_gout, int gcol0, int dim,
                              const double* d_var, const int64_t* h_offsets, int n_utts,
                              void* d_gfeat, int gfeat_is_f32, int64_t ld_gfeat, int col0,
                              void* d_scratch, void* stream, const MlpgPlan* plan = nullptr) {
+  t_mlpg_adjoint_last_form = 0;
   ITTS_REQUIRE(d_var && h_offsets, "null pointer");
   ITTS_REQUIRE(dim > 0 && n_utts >= 0 && gcol0 >= 0 && col0 >= 0, "bad sizes");
   ITTS_REQUIRE((dim + MLPG_ADJ_LANES - 1) / MLPG_ADJ_LANES <= 65535, "too many dimensions");
@@ -379,13 +411,19 @@ static int mlpg_adjoint_impl(const void* d_gout, int gout_is_f32, int64_t ld_gou
   int* d_nconv = reinterpret_cast<int*>(d_off + (t_total + 2));
   double* d_y = reinterpret_cast<double*>(reinterpret_cast<char*>(d_scratch) + itts_mlpg_scratch_bytes(t_total, dim));
   MlpgArgs a{nullptr, 0, 0, dim, d_var, d_off, nullptr, 0, 0, scratch, t_total, d_nconv};
+  MlpgAdjointArgs g{a, d_gout, ld_gout, gcol0, d_gfeat, ld_gfeat, col0, d_y};
+  const int form = mlpg_adjoint_choose(t_max, g_mlpg_adjoint_override.load(std::memory_order_relaxed));
+  t_mlpg_adjoint_last_form = form;
+  if (form == ITTS_MLPG_FORM_STREAM) {
+    itts::ScratchScope scratch_scope(s);
+    return mlpg_adjoint_stream_launch(g, gout_is_f32 != 0, gfeat_is_f32 != 0, h_offsets, n_utts, t_max, s);
+  }
   {
     const int rc = itts::staged_upload(d_off, h_offsets, (size_t)(n_utts + 1) * sizeof(int64_t), s);
     if (rc) return rc;
   }
   hipLaunchKernelGGL(mlpg_factor_kernel, dim3((dim + 63) / 64), dim3(64), 0, s, a, (int)t_max);
   ITTS_LAUNCH_CHECK();
-  MlpgAdjointArgs g{a, d_gout, ld_gout, gcol0, d_gfeat, ld_gfeat, col0, d_y};
   int t_max_arg = (int)t_max;
   void* kernel_args[] = {&g, &t_max_arg};
   const dim3 grid((unsigned)n_utts, (unsigned)((dim + MLPG_ADJ_LANES - 1) / MLPG_ADJ_LANES));

@@ -6,10 +6,17 @@
 //   dL/dmu_1[t] = tau_1(t)  0.5 (z[t+1] - z[t-1])
 //   dL/dmu_2[t] = tau_2(t)  (z[t-1] - 2 z[t] + z[t+1])          (z outside the utterance counts as 0)
 // with tau_w(t) = mlpg_rvar: 1 / var_w, or 1 / kBigVar in the first and last frame for w = 1, 2.
-// One form for every shape, modelled on the sequential form (mlpg_kernel, mlpg_sweeps.h): the shared factor planes of
-// mlpg_factor_kernel, the last two frames re-derived (MlpgTail).  Included by mlpg.hip only.
+// Two forms, chosen as the forward chooses (mlpg.hip):
+//   sweeps  mlpg_adjoint_kernel, modelled on the sequential form (mlpg_kernel, mlpg_sweeps.h): the shared factor planes
+//           of mlpg_factor_kernel, the last two frames re-derived (MlpgTail), the windows inside the back-substitution;
+//           batches whose longest utterance is under MLPG_SEQ_BELOW frames
+//   stream  the forward's prep -> reduce -> scan -> solve (mlpg_stream.h) with the reduce kernel in its adjoint mode
+//           (b = g), z left in the plane the sweeps keep y in, then mlpg_adjoint_window_kernel: one pointwise launch
+//           that reads rows t-1, t, t+1 of z and stores the three columns of row t
+// Included by mlpg.hip only.
 #pragma once
 #include "mlpg_math.h"
+#include "mlpg_stream.h"
 
 namespace itts {
 
@@ -21,7 +28,7 @@ struct MlpgAdjointArgs {
   void* gfeat;            // [Ttot, ld_gfeat] TO: dL/dmu_w of dimension d in column col0 + w dim + d
   int64_t ld_gfeat;
   int col0;
-  double* y;              // [Ttot, dim]: the forward sweep's intermediate
+  double* y;              // [Ttot, dim]: the forward sweep's intermediate (sweeps); z (stream)
 };
 
 // As latency-bound as mlpg_kernel (two first-order chains of ~3 dependent FMAs a frame), so the same geometry: 16
@@ -151,6 +158,61 @@ __global__ __launch_bounds__(MLPG_ADJ_LANES) void mlpg_adjoint_kernel(MlpgAdjoin
       rd[i] = pd[i]; r1[i] = p1[i]; r2[i] = p2[i]; ry[i] = py[i];
     }
   }
+}
+
+// ---- the stream form ------------------------------------------------------------------------------------------------
+// The three windows over the z plane (g.a.out, pitch g.a.ld_out) the solve kernel left.  Same grid as the solve kernel:
+// one workgroup per (group of ST_GS chunks, 64 dimensions), g.rec its records; a wave takes the 16 frames
+// [(k0 + w) 16, ..) of its utterance (the pointwise pass has no use for the last chunk's borrowed frame), reads them
+// and one row on either side -- 0 outside the utterance -- and stores 3 values a frame in the destination type.
+template <typename TO>
+__global__ __launch_bounds__(ST_GS * 64) void mlpg_adjoint_window_kernel(StreamArgs g, void* gfeat, int64_t ld_gfeat,
+                                                                         int col0) {
+  constexpr int FL = ST_FL;
+  const MlpgArgs& a = g.a;
+  const int grp = (int)(blockIdx.x / (unsigned)g.nblk), db = (int)(blockIdx.x % (unsigned)g.nblk);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int D = a.dim, d = db * 64 + lane;
+  if (d >= D) return;
+  const StRecord rec = g.rec[grp];
+  const int64_t T = rec.T;
+  const int64_t j0 = (int64_t)(rec.k0 + w) * FL;
+  if (j0 >= T) return;
+  const int n = T - j0 < FL ? (int)(T - j0) : FL;
+  const double rv0 = 1.0 / a.var[d], rv1 = 1.0 / a.var[D + d], rv2 = 1.0 / a.var[2 * D + d];
+  const double* z = a.out + (rec.t0 + j0) * a.ld_out + a.ocol0 + d;
+  double zz[FL + 2];      // z of rows j0-1 .. j0+FL
+#pragma unroll
+  for (int i = -1; i <= FL; ++i) {
+    const int64_t r = j0 + i;
+    zz[i + 1] = (i <= n && r >= 0 && r < T) ? z[(int64_t)i * a.ld_out] : 0.0;
+  }
+  TO* o = static_cast<TO*>(gfeat) + (rec.t0 + j0) * ld_gfeat + col0 + d;
+#pragma unroll
+  for (int i = 0; i < FL; ++i) {
+    if (i < n) {
+      const int64_t r = j0 + i;
+      TO* row = o + (int64_t)i * ld_gfeat;
+      row[0] = (TO)(rv0 * zz[i + 1]);
+      row[D] = (TO)(mlpg_rvar(r, T, rv1) * (0.5 * (zz[i + 2] - zz[i])));
+      row[2 * D] = (TO)(mlpg_rvar(r, T, rv2) * (zz[i] - 2.0 * zz[i + 1] + zz[i + 2]));
+    }
+  }
+}
+
+// g.a: var, scratch (factor planes), nconv, dim as for the sweeps; the offsets travel with the stream form's own tables
+static int mlpg_adjoint_stream_launch(const MlpgAdjointArgs& g, bool gout_f32, bool gfeat_f32, const int64_t* h_offsets,
+                                      int n_utts, int64_t t_max, hipStream_t s) {
+  MlpgArgs a = g.a;
+  a.out = g.y;      // b, then z
+  a.ld_out = a.dim;
+  a.ocol0 = 0;
+  const StGrad grad{g.gout, gout_f32, g.ld_gout, g.gcol0};
+  return mlpg_stream_launch(a, h_offsets, n_utts, a.dim, t_max, s, &grad, [&](const StreamArgs& sg) {
+    const dim3 grid((unsigned)((size_t)sg.n_groups * sg.nblk)), block(ST_GS * 64);
+    if (gfeat_f32) hipLaunchKernelGGL(mlpg_adjoint_window_kernel<float>, grid, block, 0, s, sg, g.gfeat, g.ld_gfeat, g.col0);
+    else hipLaunchKernelGGL(mlpg_adjoint_window_kernel<double>, grid, block, 0, s, sg, g.gfeat, g.ld_gfeat, g.col0);
+  });
 }
 
 }  // namespace itts

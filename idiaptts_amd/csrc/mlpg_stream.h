@@ -1,6 +1,7 @@
 // MLPG, the stream form: prep -> reduce -> scan -> solve, no wait anywhere.  Included by mlpg.hip only.
 #pragma once
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -200,7 +201,14 @@ struct StreamArgs {
   int n_groups, nblk;
   double* agg;           // [n_chunks][4][Dp]: e_f (2), e_b0 (2)
   double* st;            // [n_chunks][4][Dp]: forward entry state (2), backward entry state (2)
+  // the adjoint's mode of the reduce kernel only: b is the incoming gradient itself, dimension d in column gcol0 + d
+  const void* gout;      // [Ttot, ld_gout] float32 or float64
+  int64_t ld_gout;
+  int gcol0;
 };
+
+// the incoming gradient of the adjoint's mode, as mlpg_stream_launch takes it (nullptr: the forward solve)
+struct StGrad { const void* gout; bool f32; int64_t ld_gout; int gcol0; };
 
 struct FuMats { double Mf[4], Mb[4], C[4]; };
 
@@ -437,26 +445,39 @@ __device__ __forceinline__ void st_group_rows(const StRecord& rec, int64_t& jlo,
 constexpr int ST_TILE_ROWS = ST_GW * ST_FL + 2;
 static_assert(ST_TILE_ROWS * ST_W * sizeof(double) <= 64 * 1024, "the staged tile fits the default dynamic-LDS limit");
 
+// TG = void: the forward solve, b formed from the three staged column blocks.  TG = float / double: the adjoint's
+// mode, z = P^-1 g -- b is the incoming gradient itself (g.gout, widened in the load): a gradient row is D contiguous
+// values, a wave's load of a frame is one segment already, so nothing is staged and no LDS is asked for.
+template <typename TG>
 __global__ __launch_bounds__(ST_GW * 64) void mlpg_reduce_kernel(StreamArgs g) {
   constexpr int FU_FL = ST_FL;
-  extern __shared__ __attribute__((aligned(16))) double st_tile[];
+  constexpr bool ADJ = !std::is_void<TG>::value;
   const MlpgArgs& a = g.a;
-  int64_t jlo = 0;
   StChunk<FU_FL> q;
   const bool active = q.open(g);      // its loads (constants, factor) fly together with the staging loads
-  {
-    const int grp = (int)(blockIdx.x / (unsigned)g.nblk), db = (int)(blockIdx.x % (unsigned)g.nblk);
-    const StRecord rec = g.rec[grp];
-    int rows;
-    st_group_rows<FU_FL, ST_GW>(rec, jlo, rows);
-    st_stage_rows<ST_GW * 64, ST_TILE_ROWS>(a, db, rec.t0, jlo, rows, st_tile);
-    __syncthreads();
-  }
-  if (!active) return;
   double b[FU_FL];
-  const double* f = st_tile - jlo * ST_W + (threadIdx.x & 63);      // b from the staged rows: the tile's pitch and piece offsets
-  if (q.cst) fu_form_b<FU_FL, true>(f, ST_W, 64, q.j0, q.n, q.T, q.v0, q.v1, q.v2, b);
-  else fu_form_b<FU_FL, false>(f, ST_W, 64, q.j0, q.n, q.T, q.v0, q.v1, q.v2, b);
+  if constexpr (ADJ) {
+    if (!active) return;
+    using TL = typename std::conditional<ADJ, TG, double>::type;
+    const TL* gin = static_cast<const TL*>(g.gout) + q.t0 * g.ld_gout + g.gcol0 + q.d;
+#pragma unroll
+    for (int i = 0; i < FU_FL; ++i) b[i] = (q.cst || i < q.n) ? (double)gin[(q.j0 + i) * g.ld_gout] : 0.0;
+  } else {
+    extern __shared__ __attribute__((aligned(16))) double st_tile[];
+    int64_t jlo = 0;
+    {
+      const int grp = (int)(blockIdx.x / (unsigned)g.nblk), db = (int)(blockIdx.x % (unsigned)g.nblk);
+      const StRecord rec = g.rec[grp];
+      int rows;
+      st_group_rows<FU_FL, ST_GW>(rec, jlo, rows);
+      st_stage_rows<ST_GW * 64, ST_TILE_ROWS>(a, db, rec.t0, jlo, rows, st_tile);
+      __syncthreads();
+    }
+    if (!active) return;
+    const double* f = st_tile - jlo * ST_W + (threadIdx.x & 63);      // b from the staged rows: the tile's pitch and piece offsets
+    if (q.cst) fu_form_b<FU_FL, true>(f, ST_W, 64, q.j0, q.n, q.T, q.v0, q.v1, q.v2, b);
+    else fu_form_b<FU_FL, false>(f, ST_W, 64, q.j0, q.n, q.T, q.v0, q.v1, q.v2, b);
+  }
   // b goes to the output rows: the solve kernel reads 496 B per frame from there instead of forming
   // b again from 1 488 B of input (and overwrites it with x, chunk by chunk, in place)
   if (q.dok) {
@@ -748,9 +769,12 @@ __global__ __launch_bounds__(ST_GS * 64) void mlpg_solve_kernel(StreamArgs g) {
   }
 }
 
-// reduce -> scan -> solve (see above)
+// reduce -> scan -> solve (see above).  grad: the adjoint's mode (the reduce kernel takes b from it, a.feat is not read;
+// a.out is then the z plane).  after(g): queued behind the solve, while the records (g.rec: the solve kernel's groups of
+// ST_GS chunks) and the offsets are still there.
+template <typename After>
 static int mlpg_stream_launch(MlpgArgs a, const int64_t* h_offsets, int n_utts, int dim, int64_t t_max,
-                              hipStream_t s) {
+                              hipStream_t s, const StGrad* grad, After after) {
   // per utterance: first chunk and first group (batch-wide indices); the per-group records are
   // expanded from them on the device (at 4 096 utterances the host would otherwise build and
   // upload 2.4 - 4.9 MB of records per call)
@@ -804,17 +828,28 @@ static int mlpg_stream_launch(MlpgArgs a, const int64_t* h_offsets, int n_utts, 
   g.nblk = nblk;
   g.agg = reinterpret_cast<double*>(blk + rec_bytes + c0_bytes);
   g.st = g.agg + plane_bytes / sizeof(double);
+  g.gout = grad ? grad->gout : nullptr;
+  g.ld_gout = grad ? grad->ld_gout : 0;
+  g.gcol0 = grad ? grad->gcol0 : 0;
   const dim3 grid((unsigned)((size_t)n_groups * nblk));
   const size_t tile_bytes = (size_t)ST_TILE_ROWS * ST_W * sizeof(double);
-  hipLaunchKernelGGL(mlpg_reduce_kernel, grid, dim3(GW * 64), tile_bytes, s, g);
+  if (!grad) hipLaunchKernelGGL(mlpg_reduce_kernel<void>, grid, dim3(GW * 64), tile_bytes, s, g);
+  else if (grad->f32) hipLaunchKernelGGL(mlpg_reduce_kernel<float>, grid, dim3(GW * 64), 0, s, g);
+  else hipLaunchKernelGGL(mlpg_reduce_kernel<double>, grid, dim3(GW * 64), 0, s, g);
   hipLaunchKernelGGL(mlpg_scan_kernel, dim3((unsigned)(n_utts * nblk)), dim3(ST_SW * 64), 0, s, g);
   g.rec = reinterpret_cast<const StRecord*>(blk + rrec_bytes);
   g.n_groups = n_sgroups;
   hipLaunchKernelGGL(mlpg_solve_kernel, dim3((unsigned)((size_t)n_sgroups * nblk)), dim3(GS * 64), 0, s,
                      g);
+  after(g);
   ITTS_LAUNCH_CHECK();
   ITTS_HIP_CHECK(itts::scratch_free(blk, s));
   return ITTS_OK;
+}
+
+static int mlpg_stream_launch(MlpgArgs a, const int64_t* h_offsets, int n_utts, int dim, int64_t t_max,
+                              hipStream_t s) {
+  return mlpg_stream_launch(a, h_offsets, n_utts, dim, t_max, s, nullptr, [](const StreamArgs&) {});
 }
 
 }  // namespace itts

@@ -79,6 +79,10 @@ _SIGNATURES = {
     "itts_mlpg_adjoint": (c_int, [_P, c_int, c_int64, c_int, c_int, _P, POINTER(c_int64), c_int, _P, c_int, c_int64,
                                   c_int, _P, _P]),
     "itts_mlpg_adjoint_planned": (c_int, [_P, _P, c_int, c_int64, c_int, c_int, _P, _P, c_int, c_int64, c_int, _P, _P]),
+    "itts_mlpg_adjoint_choose_form": (c_int, [c_int, c_int, c_int64, c_int64]),
+    "itts_mlpg_adjoint_set_override": (c_int, [c_int]),
+    "itts_mlpg_adjoint_get_override": (c_int, []),
+    "itts_mlpg_adjoint_last_form": (c_int, []),
     "itts_sqrt_inplace_f64": (c_int, [_P, c_int64, _P]),
     "itts_square_inplace_f64": (c_int, [_P, c_int64, _P]),
     "itts_stft": (c_int, [_P, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), c_int, c_int, c_int, c_int, _P,

@@ -227,6 +227,37 @@ def mlpg_forced(solve=None, width=None, nt=None):
         _lib.check(L.itts_mlpg_set_override(*[p.value for p in prev]), "itts_mlpg_set_override")
 
 
+def mlpg_adjoint_choose_form(n_utts, dim, t_max, t_total):
+    """The form `mlpg_adjoint` takes for such a batch under the adjoint's override: MLPG_SWEEPS or MLPG_STREAM
+    (itts_mlpg_adjoint_choose_form)."""
+    form = _lib.load().itts_mlpg_adjoint_choose_form(n_utts, dim, t_max, t_total)
+    if form < 0:
+        _lib.check(form, "itts_mlpg_adjoint_choose_form")
+    return form
+
+
+def mlpg_adjoint_last_form():
+    """The form of this thread's last `mlpg_adjoint` call (0: none, or nothing to solve)."""
+    return _lib.load().itts_mlpg_adjoint_last_form()
+
+
+@contextlib.contextmanager
+def mlpg_adjoint_forced(form):
+    """Forces the form of the `mlpg_adjoint` calls inside, whatever their lengths (process-wide; the forward's override
+    is another word); the previous value comes back on exit.  form: None / 0 / "auto", MLPG_SWEEPS / "sweeps",
+    MLPG_STREAM / "stream"."""
+    L = _lib.load()
+    code = {None: 0, "auto": 0, "sweeps": MLPG_SWEEPS, "stream": MLPG_STREAM}.get(form, form)
+    if isinstance(code, bool) or code not in (0, MLPG_SWEEPS, MLPG_STREAM):
+        raise ValueError("mlpg_adjoint_forced({!r})".format(form))
+    prev = L.itts_mlpg_adjoint_get_override()
+    _lib.check(L.itts_mlpg_adjoint_set_override(code), "itts_mlpg_adjoint_set_override")
+    try:
+        yield
+    finally:
+        _lib.check(L.itts_mlpg_adjoint_set_override(prev), "itts_mlpg_adjoint_set_override")
+
+
 def lf0_vuv(f0, offsets, f0_silence_threshold=30.0, lf0_zero=0.0):
     """f0 [Ttot] f64 -> (lf0 [Ttot] f32 interpolated, vuv [Ttot] f32): WorldFeatLabelGen.py:798-802
     (float32 log, threshold, interpolate_lin) per utterance."""

@@ -221,11 +221,12 @@ class WorldFeatLabelGen(ReaderBase):
                     pieces[u][slot] = traj
         return [np.concatenate(p_, axis=1) for p_ in pieces]
 
-    def mlpg_layer_config(self, normalised=True, select_only=False):
+    def mlpg_layer_config(self, normalised=True, select_only=False, batch_first=True):
         """The `idiaptts_amd.nn.MLPGLayer.Config` of this reader's streams, for trajectory training: the columns and
         covariance diagonals `_postprocess_world_batch` hands to MLPG (coded sp, lf0, bap), V/UV as a passthrough
         column, and with `normalised` the mean / std_dev of `self.norm_params`, so the layer takes the network's
-        normalised output (or, with `select_only`, cuts the normalised target down to its static columns).  Call
+        normalised output (or, with `select_only`, cuts the normalised target down to its static columns).
+        `batch_first`: the layout of the padded batches the layer will see ([B, T, C], or [T, B, C]).  Call
         `get_normalisation_params` first."""
         from idiaptts_amd.nn import MLPGLayer
         if not self.add_deltas:
@@ -252,7 +253,7 @@ class WorldFeatLabelGen(ReaderBase):
             if self.norm_params is None:
                 raise ValueError("mlpg_layer_config: no normalisation parameters; call get_normalisation_params first")
             mean, std_dev = (np.asarray(p, dtype=np.float64).reshape(-1) for p in self.norm_params)
-        return MLPGLayer.Config(streams, passthrough=passthrough, mean=mean, std_dev=std_dev, batch_first=True,
+        return MLPGLayer.Config(streams, passthrough=passthrough, mean=mean, std_dev=std_dev, batch_first=batch_first,
                                 select_only=select_only)
 
     # ------------------------------------------------------------------------------ conversions

@@ -19,6 +19,7 @@ from idiaptts_amd.src.neural_networks.pytorch.loss.NamedLoss import NamedLoss
 from idiaptts_amd.src.neural_networks.pytorch.models import rnn_dyn
 from idiaptts_amd.src.neural_networks.pytorch.models.NamedForwardWrapper import \
     NamedForwardWrapper
+from idiaptts_amd.src.neural_networks.pytorch.models.TrajectoryHead import TrajectoryHead
 
 
 class AcousticModelTrainer(ModularTrainer):
@@ -60,18 +61,29 @@ class AcousticModelTrainer(ModularTrainer):
             load_lf0=True, load_vuv=True, load_bap=True, sp_type="mcep", add_deltas=True,
             synth_load_org_sp=False, synth_load_org_lf0=False, synth_load_org_vuv=False,
             synth_load_org_bap=False,
+            # the loss on the MLPG trajectory of the prediction instead of its static / delta / delta-delta columns
+            trajectory_training=False,
             metrics=[Metrics.MCD, Metrics.F0_RMSE, Metrics.VDE, Metrics.BAP_distortion])
         if verbose:
             logging.info(hparams.get_debug_string())
         return hparams
 
     def init(self, hparams, data_reader_configs=None, model_config=None, loss_configs=None):
+        trajectory = bool(hparams.get_value("trajectory_training", False))
+        if trajectory:
+            self._check_trajectory_training(hparams, model_config, loss_configs)
+        self._trajectory_head = None
         if model_config is None and hparams.has_value("model_type"):
             model_config = NamedForwardWrapper.Config(
                 wrapped_model_config=rnn_dyn.convert_legacy_to_config(
                     (hparams.num_questions,), hparams),
                 input_names=["questions"], batch_first=hparams.batch_first,
                 name="AcousticModel", output_names=["pred_acoustic_features"])
+        if loss_configs is None and trajectory:
+            loss_configs = [NamedLoss.Config(
+                "MSELoss_trajectory", "MSELoss", seq_mask="acoustic_features_mask",
+                input_names=["acoustic_static", "pred_trajectory"],
+                batch_first=hparams.batch_first)]
         if loss_configs is None:
             loss_configs = [NamedLoss.Config(
                 name="MSELoss_acoustic_features", type_="MSELoss",
@@ -80,7 +92,43 @@ class AcousticModelTrainer(ModularTrainer):
                 batch_first=hparams.batch_first)]
         super().init(data_reader_configs=data_reader_configs, hparams=hparams,
                      model_config=model_config, loss_configs=loss_configs)
+        if trajectory:
+            # behind whichever model init() ended with: a new one, or one read from a checkpoint
+            if hparams.use_gpu:
+                self._trajectory_head.cuda()
+            self._trajectory_head.attach(self.model_handler.model)
         self.logger.info("AcousticModelTrainer ready.")
+
+    @staticmethod
+    def _check_trajectory_training(hparams, model_config, loss_configs):
+        if model_config is not None or loss_configs is not None:
+            raise ValueError("trajectory_training=True builds the model and the loss itself; a caller who passes "
+                             "model_config or loss_configs builds the chain (MLPGLayer, NamedLoss) there and "
+                             "leaves the switch off.")
+        if not hparams.add_deltas:
+            raise ValueError("trajectory_training=True needs add_deltas=True: without delta features there is "
+                             "nothing for MLPG to solve.")
+        if hparams.get_value("resident_dataset", False):
+            raise NotImplementedError("trajectory_training=True with resident_dataset=True is not implemented: "
+                                      "the trajectory loss trains through the module path.")
+
+    def _setup_datareaders(self, data_reader_configs, hparams):
+        """The trajectory head takes its statistics from the trainer's own `cmp_features` reader, so it is built
+        here: behind the readers (whose normalisation parameters DataReaderConfig.create_reader has loaded) and in
+        front of everything init() does with the model -- a reader that cannot supply them stops init() before a
+        model or a checkpoint exists."""
+        super()._setup_datareaders(data_reader_configs, hparams)
+        if not hparams.get_value("trajectory_training", False):
+            return
+        reader = next((r for r in self._readers if getattr(r, "name", None) == "cmp_features"),
+                      self.datareaders.get("acoustic_features"))
+        if not callable(getattr(reader, "mlpg_layer_config", None)):
+            raise ValueError("trajectory_training=True needs a WorldFeatLabelGen reader named cmp_features "
+                             "(output acoustic_features).")
+        self._trajectory_head = TrajectoryHead(
+            reader.mlpg_layer_config(batch_first=hparams.batch_first),
+            reader.mlpg_layer_config(select_only=True, batch_first=hparams.batch_first),
+            batch_first=hparams.batch_first)
 
     def benchmark(self, hparams, post_processing_mapping=None, ids_input=None):
         if post_processing_mapping is None:

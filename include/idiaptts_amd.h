@@ -14,7 +14,8 @@
  *     asynchronous with respect to the host unless stated otherwise.
  *   - return value: 0 = ok, negative = error (ITTS_E_*); itts_last_error() gives a message.
  *   - no hidden global state besides read-only tables cached per device (and the MLPG form override and
- *     last-form record, itts_mlpg_set_override / itts_mlpg_last_form); HIP is not
+ *     last-form record, itts_mlpg_set_override / itts_mlpg_last_form, and the adjoint's own pair,
+ *     itts_mlpg_adjoint_set_override / itts_mlpg_adjoint_last_form); HIP is not
  *     initialised before the first GPU entry point is called (fork-safe for DataLoader workers,
  *     src/neural_networks/pytorch/ModularModelHandlerPyTorch.py:528-548).
  */
@@ -231,7 +232,15 @@ int itts_mlpg_last_form(void);
  *   d_gfeat     [Ttot, ld_gfeat] f64 (f32 if gfeat_is_f32): columns col0+d, col0+D+d, col0+2D+d of every frame are
  *               overwritten, nothing else is touched; arithmetic in f64, an f32 destination rounded once at the store
  *   d_scratch   >= itts_mlpg_adjoint_scratch_bytes(Ttot, D) bytes
- * One form (mlpg_adjoint_kernel) for every shape; no atomics: repeated calls give identical bits. */
+ * Two forms, chosen per call as the forward chooses (no ring form):
+ *   ITTS_MLPG_FORM_SWEEPS   longest utterance under 194 frames: mlpg_adjoint_kernel, one sequential sweep per
+ *                           (utterance, dimension), the windows inside the back-substitution
+ *   ITTS_MLPG_FORM_STREAM   from 194 frames: the forward's reduce -> scan -> solve over 16-frame chunks with the
+ *                           gradient as the right-hand side, then one pointwise launch for the windows
+ *                           (mlpg_adjoint_window_kernel); what it needs beyond d_scratch is the library's own
+ *                           stream-ordered scratch
+ * No atomics in either: repeated calls, planned or not, give identical bits (the two forms agree to rounding, not
+ * bit for bit). */
 int64_t itts_mlpg_adjoint_scratch_bytes(int64_t t_total, int dim);
 int itts_mlpg_adjoint(const void* d_gout, int gout_is_f32, int64_t ld_gout, int gcol0, int dim,
                       const double* d_var, const int64_t* h_offsets, int n_utts,
@@ -240,6 +249,18 @@ int itts_mlpg_adjoint(const void* d_gout, int gout_is_f32, int64_t ld_gout, int 
 int itts_mlpg_adjoint_planned(const void* plan, const void* d_gout, int gout_is_f32, int64_t ld_gout, int gcol0,
                               int dim, const double* d_var, void* d_gfeat, int gfeat_is_f32, int64_t ld_gfeat,
                               int col0, void* d_scratch, void* stream);
+/* The form (ITTS_MLPG_FORM_SWEEPS or ITTS_MLPG_FORM_STREAM) itts_mlpg_adjoint* would take for such a batch under the
+ * adjoint's override.  No device work; -1 for bad sizes. */
+int itts_mlpg_adjoint_choose_form(int n_utts, int dim, int64_t t_max, int64_t t_total);
+/* Forces one form for every later adjoint call of the process, whatever the lengths: ITTS_MLPG_FORM_SWEEPS,
+ * ITTS_MLPG_FORM_STREAM, or 0 for the library's choice; ITTS_E_INVALID for any other value.  A word of its own: the
+ * forward's override (itts_mlpg_set_override) and itts_mlpg_last_form are not touched.  _get_override: the value in
+ * force. */
+int itts_mlpg_adjoint_set_override(int form);
+int itts_mlpg_adjoint_get_override(void);
+/* The form of the last itts_mlpg_adjoint* call on the calling thread; 0 when there was none, or it had nothing to
+ * solve, or failed before choosing. */
+int itts_mlpg_adjoint_last_form(void);
 
 /* ---- frame utilities (misc/utils.py:40-105) --------------------------------------------- */
 /* compute_deltas == np.gradient(x, axis=0) in float32 (utils.py:103-105): part of

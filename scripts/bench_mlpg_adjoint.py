@@ -1,12 +1,14 @@
 """Times the MLPG adjoint (csrc/mlpg_adjoint.h) on a training-sized batch: 64 utterances of 600 .. 1 600 frames (seeded
 lengths), the three streams of a WORLD reader with deltas (60 + 1 + 1 dimensions in rows of 187 columns), float32.
 
-  adjoint      (a) ops.mlpg_adjoint, one launch per stream into one [N, 187] gradient -- MlpgFunction's backward
+  adjoint      (a) ops.mlpg_adjoint, one call per stream into one [N, 187] gradient -- MlpgFunction's backward -- in the
+               form the library chooses (recorded per call: `adjoint_forms`), and the same under each form forced
+               with ops.mlpg_adjoint_forced: `adjoint_stream`, `adjoint_sweeps`
   forward      (b) ops.mlpg_generation on the same batch in the form the library chooses -- MlpgFunction's forward
   composition  (c) the same gradient without a new kernel: ops.mlpg_generation on rows (g * var_0, 0, 0), whose
                right-hand side is g itself, followed by the three windows and the edge precisions in torch ops
 
-All three use one ops.MlpgPlan and preallocated outputs.  The three are measured alternately, HIP events around every
+All of them use one ops.MlpgPlan and preallocated outputs.  They are measured alternately, HIP events around every
 call, `--iters` calls per process; a process reports its medians, and the parent starts `--processes` (six) fresh
 processes one after the other and reports the median over their medians and the spread (smallest, largest).  (a) is
 also given as a fraction of its byte floor -- dim * 4 bytes read and 3 * dim * 4 written per frame at the 8.0 TB/s
@@ -46,11 +48,23 @@ def measure(iters, warmup):
     traj = torch.empty(N, total, dtype=torch.float64, device=dev)
     gfeat = torch.zeros(N, WIDTH, device=dev)
 
+    adjoint_forms = []
+
     def adjoint():
+        del adjoint_forms[:]
         o0 = 0
         for (c0, d), var in zip(STREAMS, variances):
             ops.mlpg_adjoint(gout, var, d, offsets, gcol0=o0, out=gfeat, col0=c0, plan=plan)
+            adjoint_forms.append(ops.mlpg_form_name(ops.mlpg_adjoint_last_form()))
             o0 += d
+
+    def adjoint_stream():
+        with ops.mlpg_adjoint_forced(ops.MLPG_STREAM):
+            adjoint()
+
+    def adjoint_sweeps():
+        with ops.mlpg_adjoint_forced(ops.MLPG_SWEEPS):
+            adjoint()
 
     forms = []
 
@@ -93,14 +107,19 @@ def measure(iters, warmup):
             gfeat_c[:, c0 + 2 * d:c0 + 3 * d] = t2 * (zps - 2.0 * zs + zns)
             o0 += d
 
-    fns = (adjoint, forward, composition)
+    fns = (adjoint, forward, composition, adjoint_stream, adjoint_sweeps)
     for _ in range(warmup):
         for fn in fns:
             fn()
     forward()
     forms.append(ops.mlpg_form_name(ops.mlpg_last_form()))
+    adjoint_sweeps()
+    swept = gfeat.clone()
+    adjoint()                                  # (last: gfeat holds the chosen form's gradient, adjoint_forms its forms)
+    chosen_forms = list(adjoint_forms)
     torch.cuda.synchronize()
     diff = float((gfeat - gfeat_c).abs().max())
+    forms_diff = float((gfeat - swept).abs().max())
     scale = float(gfeat.abs().max())
     times = [[] for _ in fns]
     for _ in range(iters):
@@ -113,9 +132,11 @@ def measure(iters, warmup):
             times[i].append(a.elapsed_time(b))
     torch.cuda.synchronize()
     plan.close()
-    return dict(frames=N, longest=int(lengths.max()), forward_form=forms[0], composition_max_abs_diff=diff,
+    return dict(frames=N, longest=int(lengths.max()), forward_form=forms[0], adjoint_forms=chosen_forms,
+                composition_max_abs_diff=diff, stream_sweeps_max_abs_diff=forms_diff,
                 gradient_max_abs=scale, adjoint_ms=float(np.median(times[0])), forward_ms=float(np.median(times[1])),
-                composition_ms=float(np.median(times[2])))
+                composition_ms=float(np.median(times[2])), adjoint_stream_ms=float(np.median(times[3])),
+                adjoint_sweeps_ms=float(np.median(times[4])))
 
 
 def main():
@@ -141,9 +162,10 @@ def main():
         runs.append(json.loads(res.stdout.strip().splitlines()[-1]))
     out = dict(kernel="mlpg_adjoint", utterances=UTTERANCES, streams=[d for _, d in STREAMS], dtype="float32",
                processes=args.processes, iters=args.iters)
-    for key in ("frames", "longest", "forward_form", "composition_max_abs_diff", "gradient_max_abs"):
+    for key in ("frames", "longest", "forward_form", "adjoint_forms", "composition_max_abs_diff",
+                "stream_sweeps_max_abs_diff", "gradient_max_abs"):
         out[key] = runs[0][key]
-    for name in ("adjoint", "forward", "composition"):
+    for name in ("adjoint", "forward", "composition", "adjoint_stream", "adjoint_sweeps"):
         vals = [r[name + "_ms"] for r in runs]
         out[name + "_ms"] = round(float(np.median(vals)), 4)
         out[name + "_ms_spread"] = [round(min(vals), 4), round(max(vals), 4)]
