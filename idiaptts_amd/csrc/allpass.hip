@@ -208,8 +208,7 @@ size_t ap_lds_bytes(int N, int nbg, bool bwd) {
 
 template <typename K>
 hipError_t ap_launch(K kernel, const AllpassArgs& a, size_t lds, hipStream_t s) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipError_t e = itts::allow_dynamic_lds(reinterpret_cast<const void*>(kernel), lds);
   if (e != hipSuccess) return e;
   kernel<<<dim3((unsigned)((a.M + 63) / 64)), kWave, lds, s>>>(a);
   return hipGetLastError();

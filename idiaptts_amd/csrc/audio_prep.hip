@@ -357,9 +357,9 @@ extern "C" int itts_fir_filtfilt_batch(const double* d_x, const int64_t* h_offse
   AP_REQUIRE_GRID((longest + L + FIR_TILE - 1) / FIR_TILE, "the longest signal");
   ITTS_REQUIRE(d_x && d_taps && d_y && d_workspace, "null pointer with n_signals = " + std::to_string(n_signals));
   hipStream_t s = as_stream(stream);
-  ScratchScope scratch_scope(s);
+  ScratchScope scratch(s);
   int64_t* d_off = nullptr;
-  if (int rc = upload_i64(h_offsets, n_signals + 1, &d_off, s)) return rc;
+  if (int rc = upload_i64(h_offsets, n_signals + 1, &d_off, scratch)) return rc;
   FirArgs a{};
   a.x = d_x; a.ws = reinterpret_cast<double*>(d_workspace); a.y = d_y; a.off = d_off; a.taps = d_taps;
   a.numtaps = numtaps; a.nk = (numtaps + FIR_R - 1) / FIR_R; a.L = (int)L; a.W = fir_columns(a.nk);
@@ -372,7 +372,6 @@ extern "C" int itts_fir_filtfilt_batch(const double* d_x, const int64_t* h_offse
     fir_unit_kernel<2><<<dim3((unsigned)((longest + FIR_TILE - 1) / FIR_TILE), ny), AP_THREADS, lds, s>>>(a);
     ITTS_LAUNCH_CHECK();
   }
-  ITTS_HIP_CHECK(scratch_free(d_off, s));
   return ITTS_OK;
 }
 
@@ -400,12 +399,12 @@ extern "C" int itts_resample_poly_batch(const double* d_x, const int64_t* h_offs
   AP_REQUIRE_GRID((longest_out + resample_tile(up, down) - 1) / resample_tile(up, down), "the longest output");
   ITTS_REQUIRE(d_x && d_taps && d_y, "null pointer with n_signals = " + std::to_string(n_signals));
   hipStream_t s = as_stream(stream);
-  ScratchScope scratch_scope(s);
+  ScratchScope scratch(s);
   std::vector<int64_t> h(2 * (size_t)n_signals + 2);
   std::copy(h_offsets, h_offsets + n_signals + 1, h.begin());
   std::copy(h_out_offsets, h_out_offsets + n_signals + 1, h.begin() + n_signals + 1);
   int64_t* d_off = nullptr;
-  if (int rc = upload_i64(h.data(), (int)h.size(), &d_off, s)) return rc;
+  if (int rc = upload_i64(h.data(), (int)h.size(), &d_off, scratch)) return rc;
   ResampleArgs a{};
   a.x = d_x; a.off = d_off; a.out_off = d_off + n_signals + 1; a.taps = d_taps; a.y = d_y;
   a.numtaps = numtaps; a.up = up; a.down = down; a.T = resample_tile(up, down);
@@ -415,7 +414,6 @@ extern "C" int itts_resample_poly_batch(const double* d_x, const int64_t* h_offs
     resample_kernel<<<dim3((unsigned)((longest_out + a.T - 1) / a.T), ny), AP_THREADS, 0, s>>>(a);
     ITTS_LAUNCH_CHECK();
   }
-  ITTS_HIP_CHECK(scratch_free(d_off, s));
   return ITTS_OK;
 }
 
@@ -431,13 +429,13 @@ extern "C" int itts_loudness_normalise_batch(const double* d_x, const int64_t* h
   AP_REQUIRE_GRID(n_signals, "n_signals = " + std::to_string(n_signals));
   ITTS_REQUIRE(d_x && d_y, "null pointer with n_signals = " + std::to_string(n_signals));
   hipStream_t s = as_stream(stream);
-  ScratchScope scratch_scope(s);
+  ScratchScope scratch(s);
   int64_t* d_off = nullptr;
-  if (int rc = upload_i64(h_offsets, n_signals + 1, &d_off, s)) return rc;
+  if (int rc = upload_i64(h_offsets, n_signals + 1, &d_off, scratch)) return rc;
   LoudArgs a{};
   a.x = d_x; a.y = d_y; a.off = d_off; a.n_signals = n_signals; a.ref_rms = ref_rms;
   a.pitch = (longest + LD_CHUNK - 1) / LD_CHUNK;
-  ITTS_HIP_CHECK(scratch_malloc((void**)&a.partial, (size_t)(a.pitch + 3) * n_signals * sizeof(double), s));
+  ITTS_HIP_CHECK(scratch.take(&a.partial, (size_t)(a.pitch + 3) * n_signals));
   a.stat = a.partial + a.pitch * n_signals;
   const unsigned nx = (unsigned)a.pitch;
   for (int pass = 0; pass < 3; ++pass) {
@@ -460,8 +458,6 @@ extern "C" int itts_loudness_normalise_batch(const double* d_x, const int64_t* h
     loud_apply_kernel<<<dim3(nx, (unsigned)std::min(AP_MAX_GRID_Y, n_signals - s0)), AP_THREADS, 0, s>>>(a);
     ITTS_LAUNCH_CHECK();
   }
-  ITTS_HIP_CHECK(scratch_free(a.partial, s));
-  ITTS_HIP_CHECK(scratch_free(d_off, s));
   return ITTS_OK;
 }
 
@@ -492,12 +488,12 @@ extern "C" int itts_frame_rms_batch(const double* d_x, const int64_t* h_offsets,
                                                  std::to_string(AP_MAX_GRID_X));
   ITTS_REQUIRE(d_x && d_rms, "null pointer with n_signals = " + std::to_string(n_signals));
   hipStream_t s = as_stream(stream);
-  ScratchScope scratch_scope(s);
+  ScratchScope scratch(s);
   std::vector<int64_t> h(2 * (size_t)n_signals + 2);
   std::copy(h_offsets, h_offsets + n_signals + 1, h.begin());
   std::copy(h_frame_offsets, h_frame_offsets + n_signals + 1, h.begin() + n_signals + 1);
   int64_t* d_off = nullptr;
-  if (int rc = upload_i64(h.data(), (int)h.size(), &d_off, s)) return rc;
+  if (int rc = upload_i64(h.data(), (int)h.size(), &d_off, scratch)) return rc;
   RmsArgs a{};
   a.x = d_x; a.off = d_off; a.f_off = d_off + n_signals + 1; a.out = d_rms;
   a.frame_length = frame_length; a.hop = hop; a.pad_mode = pad_mode;
@@ -507,6 +503,5 @@ extern "C" int itts_frame_rms_batch(const double* d_x, const int64_t* h_offsets,
                        s>>>(a);
     ITTS_LAUNCH_CHECK();
   }
-  ITTS_HIP_CHECK(scratch_free(d_off, s));
   return ITTS_OK;
 }

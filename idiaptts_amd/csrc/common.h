@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
+#include <vector>
 
 #include "../../include/idiaptts_amd.h"
 
@@ -80,34 +81,42 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
 // device allocation occasionally takes hundreds of milliseconds to seconds on this platform
 // (measured: an analysis pass of 65 ms took 2.3 s right after the pool had been emptied; a whole
 // bench process ran its analysis section at 330 ms per pass).  So the library keeps its own
-// blocks: scratch_malloc returns a cached block of the request's size class (plain hipMalloc the
-// first time), scratch_free marks it free behind an event on the caller's stream; a block that
+// blocks (context.hip): a request gets a cached block of its size class (plain hipMalloc the first
+// time), a release marks the block free behind an event on the releasing stream, and a block that
 // moves to another stream waits for that event first (stream-ordered like hipMallocAsync /
 // hipFreeAsync).  At most ITTS_POOL_KEEP_GB (default 64) stay cached; itts_release_scratch() frees
 // everything that is not in use.
-hipError_t scratch_malloc(void** out, size_t bytes, hipStream_t s);
-hipError_t scratch_free(void* p, hipStream_t s);
-
-// Every entry point that takes scratch opens a ScratchScope first: blocks obtained (on this thread)
-// while it is alive and not handed back by scratch_free -- the early returns of ITTS_REQUIRE /
-// ITTS_HIP_CHECK / ITTS_LAUNCH_CHECK between a scratch_malloc and its scratch_free -- are released
-// by its destructor, behind the work already queued on the stream.  Scopes nest (an entry point
-// calling another one).
+//
+// A ScratchScope is the only way to the pool, and it owns what is taken through it: take() hands out
+// `count` elements of T, and the destructor releases every block the scope took, behind the work
+// already queued on its stream -- at the end of the entry point and at every early return of
+// ITTS_REQUIRE / ITTS_HIP_CHECK / ITTS_LAUNCH_CHECK alike.  There is no separate free.  Blocks that
+// must go back before a later request of the same call (so that the request can reuse them) live in
+// a nested scope in a C++ block of their own.  A helper that allocates for its caller takes the
+// caller's ScratchScope&.
 class ScratchScope {
  public:
-  explicit ScratchScope(hipStream_t s);
+  explicit ScratchScope(hipStream_t s) : stream_(s) {}
   ~ScratchScope();
   ScratchScope(const ScratchScope&) = delete;
   ScratchScope& operator=(const ScratchScope&) = delete;
-  void track(void* p);
-  void untrack(void* p);
+
+  template <typename T>
+  hipError_t take(T** out, size_t count) {
+    return take_bytes(reinterpret_cast<void**>(out), count * sizeof(T));
+  }
+  hipStream_t stream() const { return stream_; }
 
  private:
+  hipError_t take_bytes(void** out, size_t bytes);
   hipStream_t stream_;
-  ScratchScope* prev_;
-  void* live_[64];
-  int n_live_ = 0;
+  std::vector<void*> blocks_;
 };
+
+// Raises the dynamic-LDS limit of `kernel` on the current device to at least `bytes` (launches above
+// 64 KB need it).  Grow-only and thread-safe; the runtime is asked only when this (device, kernel)
+// pair has not been granted that much yet.
+hipError_t allow_dynamic_lds(const void* kernel, size_t bytes);
 
 // Sum of S split-K slabs of n floats (slab s at slabs + s * n) into out (nn.hip): the reduction of
 // itts_linear_bwd_weight, queued instead of launched inside itts_defer_reductions.

@@ -124,8 +124,7 @@ struct PinnedTable {
 int pinned_table_begin(const void* src, size_t bytes, PinnedTable* t);
 int pinned_table_end(PinnedTable* t, hipStream_t s);
 
-// Small stream-ordered device copy of a host int64 array (offsets). Caller frees with
-// scratch_free on the same stream.
-int upload_i64(const int64_t* h, int n, int64_t** d_out, hipStream_t s);
+// Small stream-ordered device copy of a host int64 array (offsets), owned by `scratch`.
+int upload_i64(const int64_t* h, int n, int64_t** d_out, ScratchScope& scratch);
 
 }  // namespace itts

@@ -96,35 +96,7 @@ static void scratch_evict(ScratchCache& c, size_t limit) {
   }
 }
 
-static thread_local ScratchScope* t_scope = nullptr;
-
-ScratchScope::ScratchScope(hipStream_t s) : stream_(s), prev_(t_scope) { t_scope = this; }
-ScratchScope::~ScratchScope() {
-  t_scope = prev_;   // first: the frees below must not come back to this scope
-  for (int i = 0; i < n_live_; ++i)
-    if (live_[i]) (void)scratch_free(live_[i], stream_);
-}
-void ScratchScope::track(void* p) {
-  if (n_live_ < 64) live_[n_live_++] = p;   // beyond 64 live blocks: as before (explicit frees only)
-}
-void ScratchScope::untrack(void* p) {
-  for (int i = n_live_ - 1; i >= 0; --i)
-    if (live_[i] == p) {
-      live_[i] = nullptr;
-      while (n_live_ > 0 && live_[n_live_ - 1] == nullptr) --n_live_;
-      return;
-    }
-  if (prev_) prev_->untrack(p);   // obtained under an outer scope
-}
-
-static hipError_t scratch_malloc_impl(void** out, size_t bytes, hipStream_t s);
-hipError_t scratch_malloc(void** out, size_t bytes, hipStream_t s) {
-  const hipError_t e = scratch_malloc_impl(out, bytes, s);
-  if (e == hipSuccess && *out && t_scope) t_scope->track(*out);
-  return e;
-}
-
-static hipError_t scratch_malloc_impl(void** out, size_t bytes, hipStream_t s) {
+static hipError_t scratch_malloc(void** out, size_t bytes, hipStream_t s) {
   *out = nullptr;
   int dev = -1;
   hipError_t e = hipGetDevice(&dev);
@@ -165,9 +137,7 @@ static hipError_t scratch_malloc_impl(void** out, size_t bytes, hipStream_t s) {
   return hipSuccess;
 }
 
-hipError_t scratch_free(void* p, hipStream_t s) {
-  if (!p) return hipSuccess;
-  if (t_scope) t_scope->untrack(p);
+static hipError_t scratch_free(void* p, hipStream_t s) {
   std::lock_guard<std::mutex> lock(g_scratch_mutex);
   for (auto& kv : g_scratch)
     for (ScratchBlock& b : kv.second.blocks)
@@ -178,6 +148,30 @@ hipError_t scratch_free(void* p, hipStream_t s) {
         return e;
       }
   return hipErrorInvalidValue;
+}
+
+hipError_t ScratchScope::take_bytes(void** out, size_t bytes) {
+  const hipError_t e = scratch_malloc(out, bytes, stream_);
+  if (e == hipSuccess) blocks_.push_back(*out);
+  return e;
+}
+ScratchScope::~ScratchScope() {
+  for (void* p : blocks_) (void)scratch_free(p, stream_);
+}
+
+// ---- dynamic LDS above 64 KB --------------------------------------------------------------------------
+hipError_t allow_dynamic_lds(const void* kernel, size_t bytes) {
+  int dev = -1;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  static std::mutex mutex;
+  static std::map<std::pair<int, const void*>, size_t> granted;
+  std::lock_guard<std::mutex> lock(mutex);
+  size_t& have = granted[{dev, kernel}];
+  if (bytes <= have) return hipSuccess;
+  e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e == hipSuccess) have = bytes;
+  return e;
 }
 
 }  // namespace itts
@@ -719,9 +713,9 @@ int pinned_table_end(PinnedTable* t, hipStream_t s) {
   return stage_release(sl, true, s, "pinned_table");
 }
 
-int upload_i64(const int64_t* h, int n, int64_t** d_out, hipStream_t s) {
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)d_out, (size_t)n * sizeof(int64_t), s));
-  return staged_upload(*d_out, h, (size_t)n * sizeof(int64_t), s);
+int upload_i64(const int64_t* h, int n, int64_t** d_out, ScratchScope& scratch) {
+  ITTS_HIP_CHECK(scratch.take(d_out, (size_t)n));
+  return staged_upload(*d_out, h, (size_t)n * sizeof(int64_t), scratch.stream());
 }
 
 }  // namespace itts

@@ -350,9 +350,9 @@ extern "C" int itts_conv1d_fwd(const float* d_x, int64_t ldx, const float* d_w, 
   hipStream_t s = as_stream(stream);
   const int T_out = (int)out_len(T_in, Kw, pad, dil);
   const int Cp = (Cin + 3) & ~3, Kp = Kw * Cp;
-  ScratchScope scope(s);
+  ScratchScope scratch(s);
   float* wt = nullptr;
-  ITTS_HIP_CHECK(scratch_malloc((void**)&wt, (size_t)Cout * Kp * 4, s));
+  ITTS_HIP_CHECK(scratch.take(&wt, (size_t)Cout * Kp));
   int rc = launch_pack(d_w, wt, Cout, Cin, Kw, 0, s);
   if (rc) return rc;
   ConvArgs a{};
@@ -364,7 +364,6 @@ extern "C" int itts_conv1d_fwd(const float* d_x, int64_t ldx, const float* d_w, 
   a.kchunk = p.kchunk;
   rc = launch<MODE_FWD, EPI_BIAS_ACT>(a, p, vec, s);
   if (rc) return rc;
-  ITTS_HIP_CHECK(scratch_free(wt, s));
   return ITTS_OK;
 }
 
@@ -380,9 +379,9 @@ extern "C" int itts_conv1d_bwd_input(const float* d_dz, int64_t lddz, const floa
   // dx = the forward correlation on dz: Cout -> Cin channels, T_out -> T_in steps, flipped taps,
   // pad' = dil (Kw - 1) - pad (negative when pad exceeds the kernel span: the range check covers it)
   const int Cp = (Cout + 3) & ~3, Kp = Kw * Cp;
-  ScratchScope scope(s);
+  ScratchScope scratch(s);
   float* wf = nullptr;
-  ITTS_HIP_CHECK(scratch_malloc((void**)&wf, (size_t)Cin * Kp * 4, s));
+  ITTS_HIP_CHECK(scratch.take(&wf, (size_t)Cin * Kp));
   int rc = launch_pack(d_w, wf, Cout, Cin, Kw, 1, s);
   if (rc) return rc;
   ConvArgs a{};
@@ -394,7 +393,6 @@ extern "C" int itts_conv1d_bwd_input(const float* d_dz, int64_t lddz, const floa
   a.kchunk = p.kchunk;
   rc = d_yprev ? launch<MODE_FWD, EPI_DACT>(a, p, vec, s) : launch<MODE_FWD, EPI_STORE>(a, p, vec, s);
   if (rc) return rc;
-  ITTS_HIP_CHECK(scratch_free(wf, s));
   return ITTS_OK;
 }
 

@@ -582,7 +582,7 @@ extern "C" int itts_dio(const double* d_x, const int64_t* h_x_off, const int64_t
   ITTS_REQUIRE(f0_floor > 0 && f0_ceil > f0_floor && channels_in_octave > 0, "bad f0 range");
   if (n_utts == 0) return ITTS_OK;
   hipStream_t s = as_stream(stream);
-  itts::ScratchScope scratch_scope(s);
+  itts::ScratchScope scratch(s);
   DioParams p{};
   p.fs = fs; p.frame_period = frame_period_ms; p.f0_floor = f0_floor; p.f0_ceil = f0_ceil;
   p.allowed_range = allowed_range;
@@ -619,9 +619,9 @@ extern "C" int itts_dio(const double* d_x, const int64_t* h_x_off, const int64_t
   }
   double *d_taps = nullptr, *d_lpf = nullptr;
   int* d_lpf_off = nullptr;
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_taps, taps.size() * 8, s));
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_lpf, lpf.size() * 8, s));
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_lpf_off, lpf_off.size() * 4, s));
+  ITTS_HIP_CHECK(scratch.take(&d_taps, taps.size()));
+  ITTS_HIP_CHECK(scratch.take(&d_lpf, lpf.size()));
+  ITTS_HIP_CHECK(scratch.take(&d_lpf_off, lpf_off.size()));
   // (through the page-locked staging ring: the host vectors may go at once, and nothing waits for the stream)
   if (int rc = itts::staged_upload(d_taps, taps.data(), taps.size() * 8, s)) return rc;
   if (int rc = itts::staged_upload(d_lpf, lpf.data(), lpf.size() * 8, s)) return rc;
@@ -660,15 +660,16 @@ extern "C" int itts_dio(const double* d_x, const int64_t* h_x_off, const int64_t
     double *d_mean = nullptr, *d_ylc = nullptr, *d_sig = nullptr, *d_fine = nullptr, *d_cand = nullptr,
            *d_score = nullptr, *d_tmp = nullptr;
     int* d_cnt = nullptr;
-    ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_utts, U * sizeof(DioUtt), s));
-    ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_mean, U * 8, s));
-    ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_ylc, ylc_n * 8, s));
-    ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_sig, sig_n * 8, s));
-    ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_fine, fine_n * 8, s));
-    ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_cand, cand_n * 8, s));
-    ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_score, cand_n * 8, s));
-    ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_tmp, tmp_n * 8, s));
-    ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_cnt, cnt_n * 4, s));
+    itts::ScratchScope chunk(s);
+    ITTS_HIP_CHECK(chunk.take(&d_utts, U));
+    ITTS_HIP_CHECK(chunk.take(&d_mean, U));
+    ITTS_HIP_CHECK(chunk.take(&d_ylc, ylc_n));
+    ITTS_HIP_CHECK(chunk.take(&d_sig, sig_n));
+    ITTS_HIP_CHECK(chunk.take(&d_fine, fine_n));
+    ITTS_HIP_CHECK(chunk.take(&d_cand, cand_n));
+    ITTS_HIP_CHECK(chunk.take(&d_score, cand_n));
+    ITTS_HIP_CHECK(chunk.take(&d_tmp, tmp_n));
+    ITTS_HIP_CHECK(chunk.take(&d_cnt, cnt_n));
     if (int rc = itts::staged_upload(d_utts, utts.data(), U * sizeof(DioUtt), s)) return rc;
 
     hipLaunchKernelGGL(dio_mean_kernel, dim3(U), dim3(NT), 0, s, d_x, d_utts, d_mean);
@@ -677,8 +678,7 @@ extern "C" int itts_dio(const double* d_x, const int64_t* h_x_off, const int64_t
       const int total = max_yl + 2 * p.pad;
       const size_t lds = fir_lds_bytes(fir_pad_taps(p.lowcut_n));
       ITTS_REQUIRE(lds <= 160 * 1024, "sampling rate too high for the DIO low-cut tile");
-      ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)dio_lowcut_kernel,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      ITTS_HIP_CHECK(itts::allow_dynamic_lds((const void*)dio_lowcut_kernel, lds));
       hipLaunchKernelGGL(dio_lowcut_kernel, dim3((total + TILE - 1) / TILE, U), dim3(NT), lds, s, d_x,
                          d_utts, d_mean, d_taps, p, d_ylc);
       ITTS_LAUNCH_CHECK();
@@ -686,26 +686,24 @@ extern "C" int itts_dio(const double* d_x, const int64_t* h_x_off, const int64_t
     {
       const size_t lds = fir_lds_bytes(fir_pad_taps(4 * p.hal[0]));
       ITTS_REQUIRE(lds <= 160 * 1024, "sampling rate too high for the DIO band tile");
-      ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)dio_band_kernel,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      ITTS_HIP_CHECK(itts::allow_dynamic_lds((const void*)dio_band_kernel, lds));
       hipLaunchKernelGGL(dio_band_kernel, dim3((max_yl + TILE - 1) / TILE, U, p.nb), dim3(NT), lds, s,
                          d_utts, d_lpf, d_lpf_off, p, d_ylc, d_sig);
       ITTS_LAUNCH_CHECK();
     }
     {
       const int nch = (max_yl - 1 + ECH - 1) / ECH;        // chunks of the longest signal
+      itts::ScratchScope edges(s);
       unsigned long long* d_cc = nullptr;
-      ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_cc, (size_t)U * p.nb * nch * sizeof(unsigned long long), s));
+      ITTS_HIP_CHECK(edges.take(&d_cc, (size_t)U * p.nb * nch));
       int4* d_bases = nullptr;
-      ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_bases, (size_t)U * p.nb * nch * sizeof(int4), s));
+      ITTS_HIP_CHECK(edges.take(&d_bases, (size_t)U * p.nb * nch));
       hipLaunchKernelGGL(dio_edge_count_kernel, dim3(nch, p.nb, U), dim3(ET), 0, s, d_utts, nch, d_sig, d_cc);
       ITTS_LAUNCH_CHECK();
       hipLaunchKernelGGL(dio_edge_scan_kernel, dim3(U * p.nb), dim3(64), 0, s, d_utts, p.nb, nch, d_cc, d_bases, d_cnt);
       ITTS_LAUNCH_CHECK();
       hipLaunchKernelGGL(dio_edge_emit_kernel, dim3(nch, p.nb, U), dim3(ET), 0, s, d_utts, nch, d_sig, d_bases, d_fine);
       ITTS_LAUNCH_CHECK();
-      ITTS_HIP_CHECK(itts::scratch_free(d_cc, s));
-      ITTS_HIP_CHECK(itts::scratch_free(d_bases, s));
     }
     hipLaunchKernelGGL(dio_candidates_kernel, dim3((max_T + NT - 1) / NT, p.nb, U), dim3(NT), 0, s, d_utts,
                        p, d_fine, d_cnt, d_cand, d_score);
@@ -713,25 +711,12 @@ extern "C" int itts_dio(const double* d_x, const int64_t* h_x_off, const int64_t
     {
       size_t lds = std::min<size_t>((size_t)(p.nb + 2) * max_T * 8, 150 * 1024);
       p.contour_lds = (unsigned)lds;
-      ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)dio_contour_kernel,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      ITTS_HIP_CHECK(itts::allow_dynamic_lds((const void*)dio_contour_kernel, lds));
       hipLaunchKernelGGL(dio_contour_kernel, dim3(U), dim3(NT), lds, s, d_utts, p, d_cand, d_score, d_tmp,
                          d_f0);
     }
     ITTS_LAUNCH_CHECK();
-    ITTS_HIP_CHECK(itts::scratch_free(d_utts, s));
-    ITTS_HIP_CHECK(itts::scratch_free(d_mean, s));
-    ITTS_HIP_CHECK(itts::scratch_free(d_ylc, s));
-    ITTS_HIP_CHECK(itts::scratch_free(d_sig, s));
-    ITTS_HIP_CHECK(itts::scratch_free(d_fine, s));
-    ITTS_HIP_CHECK(itts::scratch_free(d_cand, s));
-    ITTS_HIP_CHECK(itts::scratch_free(d_score, s));
-    ITTS_HIP_CHECK(itts::scratch_free(d_tmp, s));
-    ITTS_HIP_CHECK(itts::scratch_free(d_cnt, s));
     u0 = u1;
   }
-  ITTS_HIP_CHECK(itts::scratch_free(d_taps, s));
-  ITTS_HIP_CHECK(itts::scratch_free(d_lpf, s));
-  ITTS_HIP_CHECK(itts::scratch_free(d_lpf_off, s));
   return ITTS_OK;
 }

@@ -294,14 +294,15 @@ __global__ void xtx_reduce_kernel(const double* __restrict__ part, int width,
 using namespace itts;
 
 static int interpolate_launch(const double* d_f0, const float* d_in, const int64_t* h_off, int n_utts,
-                              double thr, float lf0_zero, float* d_ip, float* d_vuv, hipStream_t s) {
+                              double thr, float lf0_zero, float* d_ip, float* d_vuv, ScratchScope& scratch) {
   if (n_utts == 0 || h_off[n_utts] == 0) return ITTS_OK;
+  hipStream_t s = scratch.stream();
   const int64_t total = h_off[n_utts];
   int64_t* d_off = nullptr;
-  int rc = upload_i64(h_off, n_utts + 1, &d_off, s);
+  int rc = upload_i64(h_off, n_utts + 1, &d_off, scratch);
   if (rc != ITTS_OK) return rc;
   int* d_prev = nullptr;
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_prev, total * sizeof(int), s));
+  ITTS_HIP_CHECK(scratch.take(&d_prev, total));
   if (d_f0)
     hipLaunchKernelGGL(interpolate_lin_kernel<true>, dim3(n_utts), dim3(IL_THREADS), 0, s, d_f0,
                        nullptr, d_off, (float)std::log(thr), lf0_zero, d_ip, d_vuv, d_prev);
@@ -309,8 +310,6 @@ static int interpolate_launch(const double* d_f0, const float* d_in, const int64
     hipLaunchKernelGGL(interpolate_lin_kernel<false>, dim3(n_utts), dim3(IL_THREADS), 0, s, nullptr,
                        d_in, d_off, 0.f, 0.f, d_ip, d_vuv, d_prev);
   ITTS_LAUNCH_CHECK();
-  ITTS_HIP_CHECK(itts::scratch_free(d_prev, s));
-  ITTS_HIP_CHECK(itts::scratch_free(d_off, s));
   return ITTS_OK;
 }
 
@@ -323,8 +322,9 @@ extern "C" int itts_lf0_vuv(const double* d_f0, const int64_t* h_f_off, int n_ut
   for (int u = 0; u < n_utts; ++u)
     ITTS_REQUIRE(h_f_off[u + 1] >= h_f_off[u] && h_f_off[u + 1] - h_f_off[u] < (1ll << 24),
                  "utterance lengths must be in [0, 2^24)");
+  ScratchScope scratch(as_stream(stream));
   return interpolate_launch(d_f0, nullptr, h_f_off, n_utts, f0_silence_threshold, lf0_zero, d_lf0,
-                            d_vuv, as_stream(stream));
+                            d_vuv, scratch);
 }
 
 // amp_sp = sqrt(sp) in place (WorldFeatLabelGen.py:795, `np.sqrt` of pyworld's power envelope): IEEE square
@@ -369,7 +369,8 @@ extern "C" int itts_interpolate_lin_f32(const float* d_in, const int64_t* h_off,
   for (int u = 0; u < n_utts; ++u)
     ITTS_REQUIRE(h_off[u + 1] >= h_off[u] && h_off[u + 1] - h_off[u] < (1ll << 24),
                  "utterance lengths must be in [0, 2^24)");
-  return interpolate_launch(nullptr, d_in, h_off, n_utts, 1.0, 0.f, d_ip, d_vuv, as_stream(stream));
+  ScratchScope scratch(as_stream(stream));
+  return interpolate_launch(nullptr, d_in, h_off, n_utts, 1.0, 0.f, d_ip, d_vuv, scratch);
 }
 
 extern "C" int itts_assemble_cmp_f32(const float* d_sp, int64_t ld_sp, int n_sp, const float* d_lf0,
@@ -384,9 +385,9 @@ extern "C" int itts_assemble_cmp_f32(const float* d_sp, int64_t ld_sp, int n_sp,
   ITTS_REQUIRE(d_lf0 && d_vuv && d_out && (n_sp == 0 || d_sp) && (n_bap == 0 || d_bap),
                "null pointer");
   hipStream_t s = as_stream(stream);
-  itts::ScratchScope scratch_scope(s);
+  itts::ScratchScope scratch(s);
   int64_t* d_off = nullptr;
-  int rc = upload_i64(h_f_off, n_utts + 1, &d_off, s);
+  int rc = upload_i64(h_f_off, n_utts + 1, &d_off, scratch);
   if (rc != ITTS_OK) return rc;
   CmpArgs a{d_sp, ld_sp, n_sp, d_lf0, d_vuv, d_bap, ld_bap, n_bap, d_off, n_utts, d_out, ld_out,
             h_f_off[n_utts]};
@@ -397,7 +398,6 @@ extern "C" int itts_assemble_cmp_f32(const float* d_sp, int64_t ld_sp, int n_sp,
   else
     hipLaunchKernelGGL(assemble_cmp_kernel<false>, dim3(blocks), dim3(256), 0, s, a);
   ITTS_LAUNCH_CHECK();
-  ITTS_HIP_CHECK(itts::scratch_free(d_off, s));
   return ITTS_OK;
 }
 
@@ -414,7 +414,6 @@ extern "C" int itts_feature_stats(const float* d_x, int64_t ld_x, int64_t n_rows
   ITTS_REQUIRE(width > 0 && col0 >= 0 && ld_x >= col0 + width && n_rows >= 0, "bad sizes");
   ITTS_REQUIRE(d_sum && d_second && d_workspace && (n_rows == 0 || d_x), "null pointer");
   hipStream_t s = as_stream(stream);
-  itts::ScratchScope scratch_scope(s);
   if (n_rows == 0) {
     if (!accumulate) {
       ITTS_HIP_CHECK(hipMemsetAsync(d_sum, 0, width * sizeof(double), s));

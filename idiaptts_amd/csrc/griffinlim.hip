@@ -232,8 +232,7 @@ template <int R, int TH, bool F64>
 int launch_gl(const GlArgs& a, int n_tiles, hipStream_t s) {
   const size_t lds = wf::table_bytes<R>() + (size_t)(TH / 64) * wf::lds_bytes<R>() + (size_t)a.seg_cap * 8;
   ITTS_REQUIRE(lds <= GL_LDS_BUDGET, "LDS budget exceeded");
-  ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)griffinlim_kernel<R, TH, F64>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  ITTS_HIP_CHECK(itts::allow_dynamic_lds((const void*)griffinlim_kernel<R, TH, F64>, lds));
   hipLaunchKernelGGL((griffinlim_kernel<R, TH, F64>), dim3((unsigned)n_tiles), dim3(TH), lds, s, a);
   ITTS_LAUNCH_CHECK();
   return ITTS_OK;
@@ -303,11 +302,11 @@ extern "C" int itts_griffinlim(const void* d_S, void* d_ang_a, void* d_ang_b, vo
   DeviceContext* ctx = get_context();
   if (!ctx) return ITTS_E_HIP;
   hipStream_t s = as_stream(stream);
-  itts::ScratchScope scratch_scope(s);
+  itts::ScratchScope scratch(s);
   const int n_tiles = (int)(tiles.size() / 3);
   h.insert(h.end(), tiles.begin(), tiles.end());
   int64_t* d_off = nullptr;
-  int rc = upload_i64(h.data(), (int)h.size(), &d_off, s);
+  int rc = upload_i64(h.data(), (int)h.size(), &d_off, scratch);
   if (rc != ITTS_OK) return rc;
   const int64_t K = n_fft / 2 + 1, rows = h_f_off[n_utts];
   ITTS_HIP_CHECK(hipMemsetAsync(d_tprev, 0, (size_t)rows * K * (is_f64 ? 16 : 8), s));
@@ -326,6 +325,5 @@ extern "C" int itts_griffinlim(const void* d_S, void* d_ang_a, void* d_ang_b, vo
       rc = is_f64 ? launch_gl<16, 384, true>(a, n_tiles, s) : launch_gl<16, 384, false>(a, n_tiles, s);
     if (rc) return rc;
   }
-  ITTS_HIP_CHECK(itts::scratch_free(d_off, s));
   return ITTS_OK;
 }

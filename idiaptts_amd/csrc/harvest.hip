@@ -1117,7 +1117,7 @@ extern "C" int itts_harvest(const double* d_x, const int64_t* h_x_off, const int
   ITTS_REQUIRE(!(d_dbg_raw || d_dbg_cand || d_dbg_score || d_dbg_best) || n_utts == 1,
                "the per-stage outputs are for a single utterance");
   hipStream_t s = as_stream(stream);
-  itts::ScratchScope scratch_scope(s);
+  itts::ScratchScope scratch(s);
   DeviceContext* ctx = get_context();
   if (!ctx) return ITTS_E_HIP;
 
@@ -1199,9 +1199,9 @@ extern "C" int itts_harvest(const double* d_x, const int64_t* h_x_off, const int
   HvTables* d_tab = nullptr;
   double* d_wt = nullptr;
   int* d_err = nullptr;
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_tab, sizeof(HvTables), s));
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_wt, wts.size() * 8, s));
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_err, 4, s));
+  ITTS_HIP_CHECK(scratch.take(&d_tab, 1));
+  ITTS_HIP_CHECK(scratch.take(&d_wt, wts.size()));
+  ITTS_HIP_CHECK(scratch.take(&d_err, 1));
   ITTS_HIP_CHECK(hipMemcpyAsync(d_tab, &tab, sizeof(HvTables), hipMemcpyHostToDevice, s));
   ITTS_HIP_CHECK(hipMemcpyAsync(d_wt, wts.data(), wts.size() * 8, hipMemcpyHostToDevice, s));
   ITTS_HIP_CHECK(hipMemsetAsync(d_err, 0, 4, s));
@@ -1257,21 +1257,22 @@ extern "C" int itts_harvest(const double* d_x, const int64_t* h_x_off, const int
     int *d_cnt = nullptr, *d_nc = nullptr;
     double* d_coef = nullptr;
     double4* d_rot = nullptr;
-    ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_rot, (size_t)(p.bl_max / 2 + 1) * sizeof(double4), s));
-    ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_coef, (size_t)U * p.nch * 3 * 8, s));
-    ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_utts, U * sizeof(HvUtt), s));
-    ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_y, y_n * 8, s));
-    ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_dec, std::max<int64_t>(dec_n, 1) * 8, s));
-    ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_sig, sig_n * 8, s));
-    ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_ev, ev_n * 8, s));
-    ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_raw, raw_n * 8, s));
-    ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_base, base_n * 8, s));
-    ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_cand, 4 * cand_n * 8, s));
-    ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_ctr, ctr_n * 8, s));
-    ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_mc, mc_n * 8, s));
-    ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_sm, sm_n * 8, s));
-    ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_cnt, cnt_n * 4, s));
-    ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_nc, U * 4, s));
+    itts::ScratchScope chunk(s);
+    ITTS_HIP_CHECK(chunk.take(&d_rot, (size_t)(p.bl_max / 2 + 1)));
+    ITTS_HIP_CHECK(chunk.take(&d_coef, (size_t)U * p.nch * 3));
+    ITTS_HIP_CHECK(chunk.take(&d_utts, U));
+    ITTS_HIP_CHECK(chunk.take(&d_y, y_n));
+    ITTS_HIP_CHECK(chunk.take(&d_dec, std::max<int64_t>(dec_n, 1)));
+    ITTS_HIP_CHECK(chunk.take(&d_sig, sig_n));
+    ITTS_HIP_CHECK(chunk.take(&d_ev, ev_n));
+    ITTS_HIP_CHECK(chunk.take(&d_raw, raw_n));
+    ITTS_HIP_CHECK(chunk.take(&d_base, base_n));
+    ITTS_HIP_CHECK(chunk.take(&d_cand, 4 * cand_n));
+    ITTS_HIP_CHECK(chunk.take(&d_ctr, ctr_n));
+    ITTS_HIP_CHECK(chunk.take(&d_mc, mc_n));
+    ITTS_HIP_CHECK(chunk.take(&d_sm, sm_n));
+    ITTS_HIP_CHECK(chunk.take(&d_cnt, cnt_n));
+    ITTS_HIP_CHECK(chunk.take(&d_nc, U));
     ITTS_HIP_CHECK(hipMemcpyAsync(d_utts, utts.data(), U * sizeof(HvUtt), hipMemcpyHostToDevice, s));
     ITTS_HIP_CHECK(hipMemsetAsync(d_nc, 0, U * 4, s));
     ITTS_HIP_CHECK(hipMemsetAsync(d_mc, 0, mc_n * 8, s));
@@ -1306,8 +1307,7 @@ extern "C" int itts_harvest(const double* d_x, const int64_t* h_x_off, const int
       ITTS_LAUNCH_CHECK();
       const size_t lds = (size_t)p.fft_max * 16 + (size_t)HV_REFINE_FRAMES * (p.bl_max + 2) * 16;
       ITTS_REQUIRE(lds <= 160 * 1024, "refinement window does not fit the LDS");
-      ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)hv_refine_kernel,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      ITTS_HIP_CHECK(itts::allow_dynamic_lds((const void*)hv_refine_kernel, lds));
       hipLaunchKernelGGL(hv_refine_kernel, dim3((max_T1 + HV_REFINE_FRAMES - 1) / HV_REFINE_FRAMES, U),
                          dim3(NT), lds, s, d_utts, p, ctx->tw_compact[p.log_fft_max], d_rot, d_y, d_base, d_nc,
                          d_cand, d_score);
@@ -1315,8 +1315,7 @@ extern "C" int itts_harvest(const double* d_x, const int64_t* h_x_off, const int
     }
     {
       const size_t lds = (size_t)(HV_RM_FRAMES + 2) * p.maxc * 8;
-      ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)hv_remove_kernel,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      ITTS_HIP_CHECK(itts::allow_dynamic_lds((const void*)hv_remove_kernel, lds));
       hipLaunchKernelGGL(hv_remove_kernel, dim3((max_T1 + HV_RM_FRAMES - 1) / HV_RM_FRAMES, U), dim3(NT),
                          lds, s, d_utts, p, d_nc, d_cand, d_score, d_cand2, d_score2);
       ITTS_LAUNCH_CHECK();
@@ -1340,21 +1339,6 @@ extern "C" int itts_harvest(const double* d_x, const int64_t* h_x_off, const int
       ITTS_HIP_CHECK(hipMemcpyAsync(d_dbg_cand, d_cand2, cand_n * 8, hipMemcpyDeviceToDevice, s));
     if (d_dbg_score)
       ITTS_HIP_CHECK(hipMemcpyAsync(d_dbg_score, d_score2, cand_n * 8, hipMemcpyDeviceToDevice, s));
-    ITTS_HIP_CHECK(itts::scratch_free(d_utts, s));
-    ITTS_HIP_CHECK(itts::scratch_free(d_y, s));
-    ITTS_HIP_CHECK(itts::scratch_free(d_dec, s));
-    ITTS_HIP_CHECK(itts::scratch_free(d_sig, s));
-    ITTS_HIP_CHECK(itts::scratch_free(d_ev, s));
-    ITTS_HIP_CHECK(itts::scratch_free(d_raw, s));
-    ITTS_HIP_CHECK(itts::scratch_free(d_base, s));
-    ITTS_HIP_CHECK(itts::scratch_free(d_cand, s));
-    ITTS_HIP_CHECK(itts::scratch_free(d_ctr, s));
-    ITTS_HIP_CHECK(itts::scratch_free(d_mc, s));
-    ITTS_HIP_CHECK(itts::scratch_free(d_sm, s));
-    ITTS_HIP_CHECK(itts::scratch_free(d_cnt, s));
-    ITTS_HIP_CHECK(itts::scratch_free(d_nc, s));
-    ITTS_HIP_CHECK(itts::scratch_free(d_coef, s));
-    ITTS_HIP_CHECK(itts::scratch_free(d_rot, s));
     u0 = u1;
   }
   int64_t* slot = pinned_slot(ctx);
@@ -1362,9 +1346,6 @@ extern "C" int itts_harvest(const double* d_x, const int64_t* h_x_off, const int
   ITTS_HIP_CHECK(hipMemcpyAsync(slot, d_err, 4, hipMemcpyDeviceToHost, s));
   ITTS_HIP_CHECK(itts_spin_sync(s));
   const bool overflow = *reinterpret_cast<int*>(slot) != 0;
-  ITTS_HIP_CHECK(itts::scratch_free(d_tab, s));
-  ITTS_HIP_CHECK(itts::scratch_free(d_wt, s));
-  ITTS_HIP_CHECK(itts::scratch_free(d_err, s));
   if (overflow) {
     set_error("itts_harvest: a band produced more zero crossings than its event list holds");
     return ITTS_E_INVALID;

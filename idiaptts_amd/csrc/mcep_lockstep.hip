@@ -14,7 +14,6 @@
 // round 2 made the warping steps products, rounds 2-4 kept two transforms per frame and iteration in a
 // kernel of their own (7.7 ms per analysis, 3.4 ms on wave_fft.h) until round 4 folded them away.
 #include <algorithm>
-#include <atomic>
 #include <chrono>
 #include <cstdlib>
 #include <utility>
@@ -1156,22 +1155,13 @@ int launch_gemm_f64(const double* A, int64_t lda, const double* B, int64_t ldb, 
   // unless K is a multiple of 4 or the caller's buffer has that slack
   const bool vec = lda % 2 == 0 && (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (a_has_slack || K % 4 == 0);
   if (K > 64 && T >= 1024) {      // long K, enough rows to fill the chip: the staged kernel
-    static bool attr_set = false;
-    if (!attr_set) {
-      ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_f64_staged_kernel,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
-      attr_set = true;
-    }
     if (vec) {
-      static bool attr2 = false;
-      if (!attr2) {
-        ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_f64_lds_kernel,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES));
-        attr2 = true;
-      }
+      ITTS_HIP_CHECK(allow_dynamic_lds((const void*)gemm_f64_lds_kernel, GEMM_LDS_BYTES));
       hipLaunchKernelGGL(gemm_f64_lds_kernel, dim3(grid.x * grid.y), dim3(256), GEMM_LDS_BYTES, s, A, lda, B, ldb, C, ldc, T, N, K, rows);
-    } else
+    } else {
+      ITTS_HIP_CHECK(allow_dynamic_lds((const void*)gemm_f64_staged_kernel, 65536));
       hipLaunchKernelGGL(gemm_f64_staged_kernel, grid, dim3(256), 65536, s, A, lda, B, ldb, C, ldc, T, N, K, rows);
+    }
   } else if (vec)
     hipLaunchKernelGGL(gemm_f64_kernel<true>, dim3(gemm_f64_grid(T, N)), dim3(256), 0, s, A, lda, B, ldb, C, ldc, T, N, K, rows);
   else
@@ -1183,7 +1173,8 @@ int launch_gemm_f64(const double* A, int64_t lda, const double* B, int64_t ldb, 
 // d_in: amplitude or power spectra [T, K]; results as in itts_mcep.
 int mcep_lockstep(DeviceContext* ctx, const double* d_in, int in_is_power, int64_t T, int K, int order,
                   double alpha, double eps, int miniter, int maxiter, double threshold, float* d_mc_f32,
-                  int64_t ld_mc, double* d_mc_f64, int* d_iters, hipStream_t s) {
+                  int64_t ld_mc, double* d_mc_f64, int* d_iters, ScratchScope& scratch) {
+  hipStream_t s = scratch.stream();
   const int flng = (K - 1) * 2, f2 = flng / 2, m1 = order + 1, m2 = 2 * order;
   const FreqtTables* ft = get_freqt(ctx, order, f2, alpha, true);
   if (!ft) return ITTS_E_HIP;
@@ -1195,22 +1186,22 @@ int mcep_lockstep(DeviceContext* ctx, const double* d_in, int in_is_power, int64
   // the vector loads may run up to 3 doubles past a row's end; the fused kernel's operand loads of the last
   // mel-cepstrum row up to 64 values (they meet zero rows of specP / crP: the slack is cleared, an Inf or NaN
   // would survive the zero)
-  const size_t slack = 512;
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&xp, (size_t)T * Kp * 8 + slack, s));
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&cbuf, (size_t)T * Kp * 8 + slack, s));
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&mc, (size_t)T * m1 * 8 + slack, s));
+  const size_t slack = 512;         // bytes: 64 doubles
+  ITTS_HIP_CHECK(scratch.take(&xp, (size_t)T * Kp + slack / 8));
+  ITTS_HIP_CHECK(scratch.take(&cbuf, (size_t)T * Kp + slack / 8));
+  ITTS_HIP_CHECK(scratch.take(&mc, (size_t)T * m1 + slack / 8));
   ITTS_HIP_CHECK(hipMemsetAsync(reinterpret_cast<char*>(xp) + (size_t)T * Kp * 8, 0, slack, s));
   ITTS_HIP_CHECK(hipMemsetAsync(reinterpret_cast<char*>(mc) + (size_t)T * m1 * 8, 0, slack, s));
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&cr, (size_t)T * (m2 + 1) * 8, s));
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&sprev, (size_t)T * 8, s));
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&done, (size_t)T * 4, s));
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&iters, (size_t)T * 4, s));
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&rows, (size_t)T * 4, s));
+  ITTS_HIP_CHECK(scratch.take(&cr, (size_t)T * (m2 + 1)));
+  ITTS_HIP_CHECK(scratch.take(&sprev, (size_t)T));
+  ITTS_HIP_CHECK(scratch.take(&done, (size_t)T));
+  ITTS_HIP_CHECK(scratch.take(&iters, (size_t)T));
+  ITTS_HIP_CHECK(scratch.take(&rows, (size_t)T));
   // [MCLS_COUNTERS x 32] frames done, then [0] frames still iterating (mcls_remaining_kernel), [1] list cursor
   constexpr size_t kCountInts = (size_t)MCLS_COUNTERS * 32;
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&n_active, (kCountInts + 2) * 4, s));
+  ITTS_HIP_CHECK(scratch.take(&n_active, kCountInts + 2));
   double* apow = nullptr;
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&apow, (size_t)m1 * 8, s));
+  ITTS_HIP_CHECK(scratch.take(&apow, (size_t)m1));
   hipLaunchKernelGGL(mcls_alpha_pow_kernel, dim3((m1 + 63) / 64), dim3(64), 0, s, alpha, m1, apow);
   ITTS_LAUNCH_CHECK();
   ITTS_HIP_CHECK(hipMemsetAsync(n_active, 0, (kCountInts + 2) * 4, s));
@@ -1221,21 +1212,14 @@ int mcep_lockstep(DeviceContext* ctx, const double* d_in, int in_is_power, int64
   a.cbuf = cbuf; a.mc = mc; a.cr = cr; a.sprev = sprev; a.done = done; a.iters = iters;
   a.n_active = n_active; a.ldk = Kp; a.rows = nullptr; a.n_rows = T; a.apow = apow;
   const size_t lds_solve = (size_t)(m2 + 2 + (size_t)m1 * (order + 2) + m1 + 2) * 8;
-  ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)mcls_solve_kernel,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_solve));
+  ITTS_HIP_CHECK(allow_dynamic_lds((const void*)mcls_solve_kernel, lds_solve));
   // both products of a round in one kernel where its accumulators fit (order <= 63), and the start of the loop in
   // one kernel likewise; ITTS_MCEP_FUSED=0: the separate launches
   const char* fenv = getenv("ITTS_MCEP_FUSED");
   const bool fused = m1 <= 64 && m2 + 1 <= 128 && ft->specP && ft->crP && ft->initP && !(fenv && fenv[0] == '0');
   int rc = ITTS_OK;
   if (fused) {
-    static std::atomic<uint64_t> iattr{0};
-    int dev = 0;
-    ITTS_HIP_CHECK(hipGetDevice(&dev));
-    if (dev >= 64 || !((iattr.load() >> dev) & 1)) {
-      ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)mcls_init_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, FI_LDS_BYTES));
-      if (dev < 64) iattr.fetch_or(uint64_t(1) << dev);
-    }
+    ITTS_HIP_CHECK(allow_dynamic_lds((const void*)mcls_init_fused_kernel, FI_LDS_BYTES));
     hipLaunchKernelGGL(mcls_init_fused_kernel, dim3((unsigned)((T + 16 * FI_WAVES - 1) / (16 * FI_WAVES))), dim3(64 * FI_WAVES),
                        FI_LDS_BYTES, s, a, ft->initP, ft->kpad);
     ITTS_LAUNCH_CHECK();
@@ -1246,19 +1230,13 @@ int mcep_lockstep(DeviceContext* ctx, const double* d_in, int in_is_power, int64
   }
   int* rows_all = nullptr;          // the identity list the fused kernel walks while no frame has converged yet
   if (fused) {
-    ITTS_HIP_CHECK(itts::scratch_malloc((void**)&rows_all, (size_t)T * 4, s));
+    ITTS_HIP_CHECK(scratch.take(&rows_all, (size_t)T));
     hipLaunchKernelGGL(mcls_iota_kernel, dim3((unsigned)std::min<int64_t>((T + 255) / 256, 2048)), dim3(256), 0, s, rows_all, T);
     ITTS_LAUNCH_CHECK();
   }
   if (fused) {
-    static std::atomic<uint64_t> attr_done{0};
-    int dev = 0;
-    ITTS_HIP_CHECK(hipGetDevice(&dev));
-    if (dev >= 64 || !((attr_done.load() >> dev) & 1)) {
-      ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)mcls_fused3_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, F3_LDS_BYTES));
-      ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)mcls_fused3_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, F3_LDS_BYTES));
-      if (dev < 64) attr_done.fetch_or(uint64_t(1) << dev);
-    }
+    const void* f3 = m2 + 1 <= 64 ? (const void*)mcls_fused3_kernel<4> : (const void*)mcls_fused3_kernel<8>;
+    ITTS_HIP_CHECK(allow_dynamic_lds(f3, F3_LDS_BYTES));
   }
   for (int it = 1; it <= maxiter; ++it) {
     a.iter = it;
@@ -1327,17 +1305,6 @@ int mcep_lockstep(DeviceContext* ctx, const double* d_in, int in_is_power, int64
   hipLaunchKernelGGL(mcls_finalize_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256),
                      0, s, mc, T, m1, d_mc_f32, ld_mc, d_mc_f64, iters, d_iters);
   ITTS_LAUNCH_CHECK();
-  ITTS_HIP_CHECK(itts::scratch_free(xp, s));
-  ITTS_HIP_CHECK(itts::scratch_free(cbuf, s));
-  ITTS_HIP_CHECK(itts::scratch_free(mc, s));
-  ITTS_HIP_CHECK(itts::scratch_free(cr, s));
-  ITTS_HIP_CHECK(itts::scratch_free(sprev, s));
-  ITTS_HIP_CHECK(itts::scratch_free(done, s));
-  ITTS_HIP_CHECK(itts::scratch_free(iters, s));
-  ITTS_HIP_CHECK(itts::scratch_free(n_active, s));
-  ITTS_HIP_CHECK(itts::scratch_free(apow, s));
-  ITTS_HIP_CHECK(itts::scratch_free(rows, s));
-  if (rows_all) ITTS_HIP_CHECK(itts::scratch_free(rows_all, s));
   return ITTS_OK;
 }
 

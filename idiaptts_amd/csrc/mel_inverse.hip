@@ -194,8 +194,7 @@ __global__ __launch_bounds__(64 * MI_WAVES) void mel_inverse_kernel(MiArgs a) {
 template <int C>
 int launch_mi(const MiArgs& a, hipStream_t s) {
   const size_t lds = (size_t)MI_WAVES * (C * 64 * 16 + MI_RS * 8);
-  ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)mel_inverse_kernel<C>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  ITTS_HIP_CHECK(itts::allow_dynamic_lds((const void*)mel_inverse_kernel<C>, lds));
   const int64_t blocks = (a.F + MI_WAVES - 1) / MI_WAVES;
   hipLaunchKernelGGL(mel_inverse_kernel<C>, dim3((unsigned)blocks), dim3(64 * MI_WAVES), lds, s, a);
   ITTS_LAUNCH_CHECK();

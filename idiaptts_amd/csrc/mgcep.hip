@@ -425,8 +425,7 @@ extern "C" int itts_mgcep(const double* d_amp_sp, int input_is_power, int64_t T,
                      (size_t)(m2 + 2) * 8 + (size_t)(m2 + 4) * 8 + (size_t)12 * (m2 + 1) * 8 +
                      (size_t)m * (m + 2) * 8 + 64;
   ITTS_REQUIRE(lds <= 160 * 1024, "LDS budget exceeded");
-  ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)mgcep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds));
+  ITTS_HIP_CHECK(itts::allow_dynamic_lds((const void*)mgcep_kernel, lds));
   hipLaunchKernelGGL(mgcep_kernel, dim3((unsigned)T), dim3(NT), lds, as_stream(stream), a);
   ITTS_LAUNCH_CHECK();
   return ITTS_OK;
@@ -447,18 +446,17 @@ extern "C" int itts_mgc2sp_gamma(const double* d_mgc, int64_t T, int order, doub
   const FreqtTables* ft = get_freqt(ctx, order, fftlen / 2, alpha, false);
   if (!ft) return ITTS_E_HIP;
   hipStream_t s = as_stream(stream);
-  itts::ScratchScope scratch_scope(s);
+  itts::ScratchScope scratch(s);
   const int K = fftlen / 2 + 1;
   const int64_t ld_cep = (K + 1) & ~1;
   double* d_cep = nullptr;
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_cep, (size_t)T * ld_cep * 8, s));
+  ITTS_HIP_CHECK(scratch.take(&d_cep, (size_t)T * ld_cep));
   // freqt(mgc, m -> f2, -alpha) of all frames: one fp64-MFMA GEMM against the cached warping matrix
   int rc = launch_gemm_f64(d_mgc, order + 1, ft->invT, K, d_cep, ld_cep, T, K, order + 1, nullptr, s,
                            /*a_has_slack=*/false);
   if (rc) return rc;
   const size_t lds1 = (size_t)4 * 2 * K * 8;
-  ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)mg_gc2gc_rows_kernel,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
+  ITTS_HIP_CHECK(itts::allow_dynamic_lds((const void*)mg_gc2gc_rows_kernel, lds1));
   hipLaunchKernelGGL(mg_gc2gc_rows_kernel, dim3((unsigned)((T + 3) / 4)), dim3(256), lds1, s, d_cep, ld_cep,
                      T, fftlen / 2, gamma);
   ITTS_LAUNCH_CHECK();
@@ -467,6 +465,5 @@ extern "C" int itts_mgc2sp_gamma(const double* d_mgc, int64_t T, int order, doub
   const size_t lds2 = (size_t)(fftlen / 2 + 1) * 16;
   hipLaunchKernelGGL(mg_c2sp_kernel, dim3((unsigned)T), dim3(NT), lds2, s, a);
   ITTS_LAUNCH_CHECK();
-  ITTS_HIP_CHECK(itts::scratch_free(d_cep, s));
   return ITTS_OK;
 }

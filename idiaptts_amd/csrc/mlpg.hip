@@ -170,22 +170,7 @@ extern "C" int itts_mlpg_last_form(void) {
   return t_mlpg_last_form;
 }
 
-// Kernels that ask for more dynamic LDS than the default limit need the attribute raised once per device: for every
-// entry's .kernel of a table.  `done`: one bit per device (any thread may get here first; setting the attribute twice
-// is harmless; devices past the 64th set it on every call).
-template <typename Table>
-static int raise_dynamic_lds(std::atomic<uint64_t>& done, const Table& table, int bytes) {
-  int dev = 0;
-  ITTS_HIP_CHECK(hipGetDevice(&dev));
-  if (dev < 64 && ((done.load(std::memory_order_acquire) >> dev) & 1)) return ITTS_OK;
-  for (const auto& entry : table)
-    ITTS_HIP_CHECK(hipFuncSetAttribute(entry.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-  if (dev < 64) done.fetch_or(uint64_t(1) << dev, std::memory_order_release);
-  return ITTS_OK;
-}
-
-// The instantiations of mlpg_ring_kernel, by the form bits that select them: the launch and the LDS attribute both
-// go through this table.
+// The instantiations of mlpg_ring_kernel, by the form bits that select them.
 struct RingVariant { int bits; const void* kernel; };
 static const RingVariant kRingVariants[] = {
   {ITTS_MLPG_FORM_F32_ROWS | ITTS_MLPG_FORM_WIDE, (const void*)mlpg_ring_kernel<float, true, false>},
@@ -214,7 +199,6 @@ static int mlpg_generation_impl(const double* d_feat, const float* d_feat32, int
   }
   if (t_total == 0) return ITTS_OK;
   hipStream_t s = as_stream(stream);
-  itts::ScratchScope scratch_scope(s);
   double* scratch = reinterpret_cast<double*>(d_scratch);
   int64_t* d_off = reinterpret_cast<int64_t*>(scratch + 3 * t_total * (int64_t)dim);
   int* d_nconv = reinterpret_cast<int*>(d_off + (t_total + 2));
@@ -232,16 +216,16 @@ static int mlpg_generation_impl(const double* d_feat, const float* d_feat32, int
     a.ld_feat = cols;
     a.col0 = 0;
   }
-  if ((form & ITTS_MLPG_FORM_SOLVE_MASK) == ITTS_MLPG_FORM_STREAM)
-    return mlpg_stream_launch(a, h_offsets, n_utts, dim, t_max, s);
+  if ((form & ITTS_MLPG_FORM_SOLVE_MASK) == ITTS_MLPG_FORM_STREAM) {
+    itts::ScratchScope scope(s);
+    return mlpg_stream_launch(a, h_offsets, n_utts, dim, t_max, scope);
+  }
   if ((form & ITTS_MLPG_FORM_SOLVE_MASK) == ITTS_MLPG_FORM_RING) {
     const RingVariant* variant = nullptr;
     for (const RingVariant& v : kRingVariants)
       if (v.bits == (form & (ITTS_MLPG_FORM_WIDE | ITTS_MLPG_FORM_F32_ROWS | ITTS_MLPG_FORM_NT_IN))) variant = &v;
     ITTS_REQUIRE(variant, "no one-pass kernel for this form");
-    static std::atomic<uint64_t> attr_done{0};
-    const int rc_attr = raise_dynamic_lds(attr_done, kRingVariants, RING_LDS_BYTES);
-    if (rc_attr) return rc_attr;
+    ITTS_HIP_CHECK(itts::allow_dynamic_lds(variant->kernel, RING_LDS_BYTES));
     itts::PinnedTable table;          // (nothing between here and the launch returns early: the slot goes back after it)
     const int64_t* bounds = plan ? plan->table : nullptr;
     if (!bounds) {
@@ -415,8 +399,8 @@ static int mlpg_adjoint_impl(const void* d_gout, int gout_is_f32, int64_t ld_gou
   const int form = mlpg_adjoint_choose(t_max, g_mlpg_adjoint_override.load(std::memory_order_relaxed));
   t_mlpg_adjoint_last_form = form;
   if (form == ITTS_MLPG_FORM_STREAM) {
-    itts::ScratchScope scratch_scope(s);
-    return mlpg_adjoint_stream_launch(g, gout_is_f32 != 0, gfeat_is_f32 != 0, h_offsets, n_utts, t_max, s);
+    itts::ScratchScope scope(s);
+    return mlpg_adjoint_stream_launch(g, gout_is_f32 != 0, gfeat_is_f32 != 0, h_offsets, n_utts, t_max, scope);
   }
   {
     const int rc = itts::staged_upload(d_off, h_offsets, (size_t)(n_utts + 1) * sizeof(int64_t), s);

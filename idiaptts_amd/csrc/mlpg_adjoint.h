@@ -202,13 +202,14 @@ __global__ __launch_bounds__(ST_GS * 64) void mlpg_adjoint_window_kernel(StreamA
 
 // g.a: var, scratch (factor planes), nconv, dim as for the sweeps; the offsets travel with the stream form's own tables
 static int mlpg_adjoint_stream_launch(const MlpgAdjointArgs& g, bool gout_f32, bool gfeat_f32, const int64_t* h_offsets,
-                                      int n_utts, int64_t t_max, hipStream_t s) {
+                                      int n_utts, int64_t t_max, ScratchScope& scratch) {
+  hipStream_t s = scratch.stream();
   MlpgArgs a = g.a;
   a.out = g.y;      // b, then z
   a.ld_out = a.dim;
   a.ocol0 = 0;
   const StGrad grad{g.gout, gout_f32, g.ld_gout, g.gcol0};
-  return mlpg_stream_launch(a, h_offsets, n_utts, a.dim, t_max, s, &grad, [&](const StreamArgs& sg) {
+  return mlpg_stream_launch(a, h_offsets, n_utts, a.dim, t_max, scratch, &grad, [&](const StreamArgs& sg) {
     const dim3 grid((unsigned)((size_t)sg.n_groups * sg.nblk)), block(ST_GS * 64);
     if (gfeat_f32) hipLaunchKernelGGL(mlpg_adjoint_window_kernel<float>, grid, block, 0, s, sg, g.gfeat, g.ld_gfeat, g.col0);
     else hipLaunchKernelGGL(mlpg_adjoint_window_kernel<double>, grid, block, 0, s, sg, g.gfeat, g.ld_gfeat, g.col0);

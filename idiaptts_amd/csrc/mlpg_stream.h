@@ -774,7 +774,8 @@ __global__ __launch_bounds__(ST_GS * 64) void mlpg_solve_kernel(StreamArgs g) {
 // ST_GS chunks) and the offsets are still there.
 template <typename After>
 static int mlpg_stream_launch(MlpgArgs a, const int64_t* h_offsets, int n_utts, int dim, int64_t t_max,
-                              hipStream_t s, const StGrad* grad, After after) {
+                              ScratchScope& scratch, const StGrad* grad, After after) {
+  hipStream_t s = scratch.stream();
   // per utterance: first chunk and first group (batch-wide indices); the per-group records are
   // expanded from them on the device (at 4 096 utterances the host would otherwise build and
   // upload 2.4 - 4.9 MB of records per call)
@@ -806,7 +807,7 @@ static int mlpg_stream_launch(MlpgArgs a, const int64_t* h_offsets, int n_utts, 
   const size_t c0_bytes = off_bytes + (tab.size() * sizeof(int) + 31) / 32 * 32;
   const size_t plane_bytes = (size_t)n_chunks * 4 * nblk * 64 * sizeof(double);
   char* blk = nullptr;
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&blk, rec_bytes + c0_bytes + 2 * plane_bytes, s));
+  ITTS_HIP_CHECK(scratch.take(&blk, rec_bytes + c0_bytes + 2 * plane_bytes));
   {
     std::vector<char> host(off_bytes + tab.size() * sizeof(int), 0);
     std::memcpy(host.data(), h_offsets, (size_t)(n_utts + 1) * sizeof(int64_t));
@@ -843,13 +844,12 @@ static int mlpg_stream_launch(MlpgArgs a, const int64_t* h_offsets, int n_utts, 
                      g);
   after(g);
   ITTS_LAUNCH_CHECK();
-  ITTS_HIP_CHECK(itts::scratch_free(blk, s));
   return ITTS_OK;
 }
 
 static int mlpg_stream_launch(MlpgArgs a, const int64_t* h_offsets, int n_utts, int dim, int64_t t_max,
-                              hipStream_t s) {
-  return mlpg_stream_launch(a, h_offsets, n_utts, dim, t_max, s, nullptr, [](const StreamArgs&) {});
+                              ScratchScope& scratch) {
+  return mlpg_stream_launch(a, h_offsets, n_utts, dim, t_max, scratch, nullptr, [](const StreamArgs&) {});
 }
 
 }  // namespace itts

@@ -413,12 +413,12 @@ extern "C" int itts_mulaw_onehot(const double* d_x, const int64_t* h_begin, cons
   RW_REQUIRE_GRID((longest + OH_ROWS - 1) / OH_ROWS, "the longest signal");
   ITTS_REQUIRE(d_x && d_onehot, "null pointer with n_signals = " + std::to_string(n_signals));
   hipStream_t s = as_stream(stream);
-  ScratchScope scratch_scope(s);
+  ScratchScope scratch(s);
   std::vector<int64_t> h((size_t)2 * n_signals + 1);
   std::copy(h_begin, h_begin + n_signals, h.begin());
   std::copy(h_out_offsets, h_out_offsets + n_signals + 1, h.begin() + n_signals);
   int64_t* d_off = nullptr;
-  if (int rc = upload_i64(h.data(), (int)h.size(), &d_off, s)) return rc;
+  if (int rc = upload_i64(h.data(), (int)h.size(), &d_off, scratch)) return rc;
   OnehotArgs a{};
   a.x = d_x; a.begin = d_off; a.out_off = d_off + n_signals; a.out = d_onehot;
   a.mu = (double)mu; a.log1pmu = log(1.0 + mu); a.W = mu + 1;
@@ -428,7 +428,6 @@ extern "C" int itts_mulaw_onehot(const double* d_x, const int64_t* h_begin, cons
     mulaw_onehot_kernel<<<dim3((unsigned)((longest + OH_ROWS - 1) / OH_ROWS), ny), RW_THREADS, 0, s>>>(a);
     ITTS_LAUNCH_CHECK();
   }
-  ITTS_HIP_CHECK(scratch_free(d_off, s));
   return ITTS_OK;
 }
 
@@ -450,9 +449,9 @@ extern "C" int itts_sample_linearly(const void* d_x, int in_f64, const int64_t* 
   RW_REQUIRE_GRID(blocks, "the longest signal");
   ITTS_REQUIRE(d_x && d_y, "null pointer with n_signals = " + std::to_string(n_signals));
   hipStream_t s = as_stream(stream);
-  ScratchScope scratch_scope(s);
+  ScratchScope scratch(s);
   int64_t* d_off = nullptr;
-  if (int rc = upload_i64(h_offsets, n_signals + 1, &d_off, s)) return rc;
+  if (int rc = upload_i64(h_offsets, n_signals + 1, &d_off, scratch)) return rc;
   LinArgs a{};
   a.x = d_x; a.y = d_y; a.off = d_off; a.D = D; a.m = m;
   for (int s0 = 0; s0 < n_signals; s0 += RW_MAX_GRID_Y) {
@@ -464,6 +463,5 @@ extern "C" int itts_sample_linearly(const void* d_x, int in_f64, const int64_t* 
     else sample_linearly_kernel<float, float><<<grid, RW_THREADS, 0, s>>>(a);
     ITTS_LAUNCH_CHECK();
   }
-  ITTS_HIP_CHECK(scratch_free(d_off, s));
   return ITTS_OK;
 }

@@ -339,7 +339,6 @@ static int persist_read_flag(int64_t* slot, const int* d_flag, hipStream_t s) {
 constexpr int kPersistCooldown = 64, kPersistCooldownCap = 1 << 16;
 struct PersistDevice {
   int n_cu = 0;
-  bool attr_set = false;
   int cooldown = 0;
   int next_cooldown = kPersistCooldown;
   int give_ups = 0;       // in a row
@@ -361,12 +360,9 @@ static int persist_device_ready(const void* kernel, int lds_bytes, PersistDevice
   }
   if (d.n_cu != 256) return 0;
   if (d.cooldown > 0) { --d.cooldown; return 0; }
-  if (!d.attr_set) {
-    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      return 0;
-    }
-    d.attr_set = true;
+  if (itts::allow_dynamic_lds(kernel, lds_bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return 0;
   }
   return 1;
 }
@@ -412,8 +408,8 @@ static int persist_run(void (*kernel)(Args), int lds_bytes, size_t xbytes, Args 
   if (!ctx) return declined();
   const size_t lbytes = h_lengths ? ((size_t)p.B * sizeof(int) + 63) / 64 * 64 : 0;
   char* blk = nullptr;
-  itts::ScratchScope scope(s);
-  if (itts::scratch_malloc((void**)&blk, xbytes + 64 + lbytes, s) != hipSuccess) return -1;
+  itts::ScratchScope scratch(s);
+  if (scratch.take(&blk, xbytes + 64 + lbytes) != hipSuccess) return -1;
   if (hipMemsetAsync(blk, 0, xbytes + 64, s) != hipSuccess) return -1;
   if (h_lengths) {
     if (staged_upload(blk + xbytes + 64, h_lengths, (size_t)p.B * sizeof(int), s) != ITTS_OK) return -1;
@@ -439,7 +435,6 @@ static int persist_run(void (*kernel)(Args), int lds_bytes, size_t xbytes, Args 
   }
   const int gave_up = persist_read_flag(pinned_slot(ctx), p.abort_flag, s);
   if (gave_up < 0) return -1;
-  if (itts::scratch_free(blk, s) != hipSuccess) return -1;
   if (gave_up == 0) {
     persist_ran(devices, dev);
     counts.ran.fetch_add(1, std::memory_order_relaxed);

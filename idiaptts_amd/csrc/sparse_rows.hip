@@ -259,13 +259,7 @@ static int fwd_compute_units() {
 template <int AF>
 static int launch_sparse_fwd(const void* d_lists, const float* d_w, const float* d_b, float* d_y, int64_t ldy, int64_t M,
                              int N, int K, int act, hipStream_t s) {
-  static bool lds_set = false;
-  if (!lds_set) {
-    ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)sparse_linear_fwd_kernel<AF>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (kSparseMaxK + 1) * kSlabCols * 4));
-    lds_set = true;
-  }
+  ITTS_HIP_CHECK(itts::allow_dynamic_lds((const void*)sparse_linear_fwd_kernel<AF>, (kSparseMaxK + 1) * kSlabCols * 4));
   const ListLayout l = list_layout(M, K);
   const char* base = static_cast<const char*>(d_lists);
   const int slabs = (N + kSlabCols - 1) / kSlabCols;

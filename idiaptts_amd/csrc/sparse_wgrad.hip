@@ -428,12 +428,7 @@ extern "C" int itts_linear_bwd_weight_sparse(const float* d_dz, int64_t lddz, co
     return itts_linear_bwd_weight(d_dz, lddz, d_x, ldx, d_dw, d_db, M, N, (int)lddw, d_workspace, accumulate, stream);
   }
   hipStream_t s = as_stream(stream);
-  static bool lds_set = false;
-  if (!lds_set) {
-    ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)sparse_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       kWgLdsBytes));
-    lds_set = true;
-  }
+  ITTS_HIP_CHECK(itts::allow_dynamic_lds((const void*)sparse_wgrad_kernel, kWgLdsBytes));
   const ColsLayout l = cols_layout(M);
   int per, ranges;
   wgrad_ranges(M, N, &per, &ranges);

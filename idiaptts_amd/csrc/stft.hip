@@ -156,8 +156,7 @@ int launch_stft(const StftArgs& a, hipStream_t s) {
   constexpr int NW = TH / 64;
   const size_t lds = wf::table_bytes<R>() + (size_t)NW * wf::lds_bytes<R>();
   ITTS_REQUIRE(lds <= 160 * 1024, "LDS budget exceeded");
-  ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)stft_wave_kernel<R, TH>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  ITTS_HIP_CHECK(itts::allow_dynamic_lds((const void*)stft_wave_kernel<R, TH>, lds));
   const dim3 grid((unsigned)std::min<int64_t>((a.t_total + NW - 1) / NW, n_cu));
   hipLaunchKernelGGL((stft_wave_kernel<R, TH>), grid, dim3(TH), lds, s, a);
   ITTS_LAUNCH_CHECK();
@@ -186,14 +185,14 @@ int run_stft(StftArgs a, const int64_t* h_x_off, const int64_t* h_f_off, const i
              hipStream_t s) {
   DeviceContext* ctx = get_context();
   if (!ctx) return ITTS_E_HIP;
-  itts::ScratchScope scratch_scope(s);
+  itts::ScratchScope scratch(s);
   const int U = a.n_utts;
   std::vector<int64_t> h(3 * (size_t)U + 2);
   std::copy(h_x_off, h_x_off + U + 1, h.begin());
   std::copy(h_f_off, h_f_off + U + 1, h.begin() + U + 1);
   std::copy(h_first, h_first + U, h.begin() + 2 * (size_t)U + 2);
   int64_t* d_off = nullptr;
-  int rc = upload_i64(h.data(), (int)h.size(), &d_off, s);
+  int rc = upload_i64(h.data(), (int)h.size(), &d_off, scratch);
   if (rc != ITTS_OK) return rc;
   a.x_off = d_off;
   a.f_off = d_off + U + 1;
@@ -201,7 +200,6 @@ int run_stft(StftArgs a, const int64_t* h_x_off, const int64_t* h_f_off, const i
   a.tw = ctx->tw_compact[n_fft == 1024 ? 10 : 11];
   rc = n_fft == 1024 ? launch_stft<8, 768>(a, s) : launch_stft<16, 512>(a, s);
   if (rc) return rc;
-  ITTS_HIP_CHECK(itts::scratch_free(d_off, s));
   return ITTS_OK;
 }
 

@@ -15,7 +15,6 @@
 //      (4 real FFTs for the two minimum-phase spectra, 1 for the noise, 2 inverse) and
 //      overlap-adds them with f64 atomics.
 // PARITY: the reference has no golden waveform; checked against oracle/c/synth.c.
-#include <atomic>
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -1134,8 +1133,7 @@ static int launch_pulse_kernel(const PulseArgs& a, int64_t n_pulses, hipStream_t
   if (n_pulses == 0) return ITTS_OK;
   const size_t lds = syn_pulse_lds_bytes(a.p.fft / 2, UNV);
   ITTS_REQUIRE(lds <= 160 * 1024, "LDS budget exceeded");
-  ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)syn_pulse_kernel<CFFT, UNV>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds));
+  ITTS_HIP_CHECK(itts::allow_dynamic_lds((const void*)syn_pulse_kernel<CFFT, UNV>, lds));
   hipLaunchKernelGGL((syn_pulse_kernel<CFFT, UNV>), dim3((unsigned)n_pulses), dim3(NT), lds, s, a);
   ITTS_LAUNCH_CHECK();
   return ITTS_OK;
@@ -1157,7 +1155,7 @@ static int world_synthesize_impl(const double* d_f0, const double* d_sp, const d
                "fft_size must be 2^k in [256, 4096]");
   if (n_utts == 0) return ITTS_OK;
   hipStream_t s = as_stream(stream);
-  itts::ScratchScope scratch_scope(s);
+  itts::ScratchScope scratch(s);
   DeviceContext* ctx = get_context();
   if (!ctx) return ITTS_E_HIP;
   const JumpTable* jt = get_jump_table(ctx);
@@ -1193,15 +1191,15 @@ static int world_synthesize_impl(const double* d_f0, const double* d_sp, const d
   uint8_t* d_vuv = nullptr;
   int* d_pidx = nullptr;
   int64_t* d_gpoff = nullptr;
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_utts, n_utts * sizeof(SynUtt), s));
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_wrap, s_n * 8, s));
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_R, s_n * 8, s));
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_vuv, s_n, s));
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_pidx, s_n * 4, s));
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_pc, b_n * 8, s));
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_ptot, n_utts * 8, s));
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_gpoff, (n_utts + 1) * 8, s));
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_y, y_total * 8, s));
+  ITTS_HIP_CHECK(scratch.take(&d_utts, n_utts));
+  ITTS_HIP_CHECK(scratch.take(&d_wrap, s_n));
+  ITTS_HIP_CHECK(scratch.take(&d_R, s_n));
+  ITTS_HIP_CHECK(scratch.take(&d_vuv, s_n));
+  ITTS_HIP_CHECK(scratch.take(&d_pidx, s_n));
+  ITTS_HIP_CHECK(scratch.take(&d_pc, b_n));
+  ITTS_HIP_CHECK(scratch.take(&d_ptot, n_utts));
+  ITTS_HIP_CHECK(scratch.take(&d_gpoff, n_utts + 1));
+  ITTS_HIP_CHECK(scratch.take(&d_y, y_total));
   if (int rc = itts::staged_upload(d_utts, utts.data(), n_utts * sizeof(SynUtt), s)) return rc;
 
   const dim3 gblk(max_nblk, n_utts);
@@ -1224,15 +1222,15 @@ static int world_synthesize_impl(const double* d_f0, const double* d_sp, const d
   ITTS_LAUNCH_CHECK();
   const int h = fft_size / 2;
   double* d_dcr = nullptr;
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_dcr, (size_t)(h + 1) * 8, s));
+  ITTS_HIP_CHECK(scratch.take(&d_dcr, (size_t)(h + 1)));
   // the pulses by kind (a pulse kernel per kind: the unvoiced ones without what only a periodic response needs)
   int *d_kq = nullptr, *d_kcnt = nullptr;
   int64_t* d_kgp = nullptr;
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_kq, s_n * 4, s));
+  ITTS_HIP_CHECK(scratch.take(&d_kq, s_n));
   // (+ the two pulse kernels' counters; a multiple of 256 bytes: one fill instead of two)
   const size_t kcnt_bytes = (((size_t)(2 * n_utts + 2) * 4 + 255) / 256) * 256;
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_kcnt, kcnt_bytes, s));
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_kgp, (size_t)2 * (n_utts + 1) * 8, s));
+  ITTS_HIP_CHECK(scratch.take(&d_kcnt, kcnt_bytes / 4));
+  ITTS_HIP_CHECK(scratch.take(&d_kgp, (size_t)2 * (n_utts + 1)));
   hipLaunchKernelGGL(syn_pulse_offsets_kernel, dim3(2), dim3(NT), 0, s, d_ptot, n_utts, d_gpoff, d_kcnt,
                      (int)(kcnt_bytes / 4), fft_size, d_dcr);
   ITTS_LAUNCH_CHECK();
@@ -1270,17 +1268,9 @@ static int world_synthesize_impl(const double* d_f0, const double* d_sp, const d
     ITTS_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
     constexpr size_t lds_v = syn_wave_lds_bytes(false), lds_u = syn_wave_lds_bytes(true);
     static_assert(SYN_WAVE_OCC * lds_v <= 160 * 1024 && 3 * lds_u <= 160 * 1024, "LDS budget exceeded");
-    {
-      // more than 64 KB of dynamic LDS: the attribute once per device (runtimes that enforce it fail the launch otherwise)
-      static std::atomic<uint64_t> attr_done{0};
-      if (dev >= 64 || !((attr_done.load() >> dev) & 1)) {
-        ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)syn_pulse_wave_kernel<false>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_v));
-        ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)syn_pulse_wave_kernel<true>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_u));
-        if (dev < 64) attr_done.fetch_or(uint64_t(1) << dev);
-      }
-    }
+    // more than 64 KB of dynamic LDS (runtimes that enforce the limit fail the launch otherwise)
+    ITTS_HIP_CHECK(itts::allow_dynamic_lds((const void*)syn_pulse_wave_kernel<false>, lds_v));
+    ITTS_HIP_CHECK(itts::allow_dynamic_lds((const void*)syn_pulse_wave_kernel<true>, lds_u));
     // a kernel per kind: the unvoiced pulses at three waves per SIMD, the voiced ones at two
     // (the unvoiced pulses read the envelope only: the aperiodicity may still be on its way while their kernel runs)
     if (spectra_ready) ITTS_HIP_CHECK(hipStreamWaitEvent(s, spectra_ready, 0));
@@ -1309,10 +1299,6 @@ static int world_synthesize_impl(const double* d_f0, const double* d_sp, const d
     a.kgpoff = d_kgp + (n_utts + 1);
     if (int rc = sized ? launch_pulse_kernel<11, false>(a, n_voi, s) : launch_pulse_kernel<0, false>(a, n_voi, s)) return rc;
   }
-  ITTS_HIP_CHECK(itts::scratch_free(d_dcr, s));
-  ITTS_HIP_CHECK(itts::scratch_free(d_kq, s));
-  ITTS_HIP_CHECK(itts::scratch_free(d_kcnt, s));
-  ITTS_HIP_CHECK(itts::scratch_free(d_kgp, s));
   if (preemphasis == 0.0) {
     hipLaunchKernelGGL(syn_cast_kernel, dim3((unsigned)std::min<int64_t>((y_total + 255) / 256, 8192)), dim3(256),
                        0, s, d_y, y_total, d_y_f32, d_y_f64);
@@ -1328,15 +1314,6 @@ static int world_synthesize_impl(const double* d_f0, const double* d_sp, const d
                        d_utts, preemphasis, (int)seg, (int)warm, d_y_f32, d_y_f64);
   }
   ITTS_LAUNCH_CHECK();
-  ITTS_HIP_CHECK(itts::scratch_free(d_utts, s));
-  ITTS_HIP_CHECK(itts::scratch_free(d_wrap, s));
-  ITTS_HIP_CHECK(itts::scratch_free(d_R, s));
-  ITTS_HIP_CHECK(itts::scratch_free(d_vuv, s));
-  ITTS_HIP_CHECK(itts::scratch_free(d_pidx, s));
-  ITTS_HIP_CHECK(itts::scratch_free(d_pc, s));
-  ITTS_HIP_CHECK(itts::scratch_free(d_ptot, s));
-  ITTS_HIP_CHECK(itts::scratch_free(d_gpoff, s));
-  ITTS_HIP_CHECK(itts::scratch_free(d_y, s));
   return ITTS_OK;
 }
 

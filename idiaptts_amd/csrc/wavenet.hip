@@ -641,15 +641,13 @@ extern "C" int itts_wavenet_generate(const float* d_wf, const float* d_bf, const
   ITTS_REQUIRE(lds + 256 <= WN_MAX_LDS, "the tile needs " + std::to_string(lds) + " bytes of LDS");
 
   hipStream_t s = as_stream(stream);
-  ScratchScope scratch_scope(s);
+  ScratchScope scratch(s);
   int* d_len = nullptr;
-  ITTS_HIP_CHECK(scratch_malloc(reinterpret_cast<void**>(&d_len), (size_t)B * sizeof(int), s));
+  ITTS_HIP_CHECK(scratch.take(&d_len, (size_t)B));
   if (int rc = staged_upload(d_len, h_lengths, (size_t)B * sizeof(int), s)) return rc;
   a.len = d_len;
-  ITTS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(wavenet_generate_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  ITTS_HIP_CHECK(itts::allow_dynamic_lds(reinterpret_cast<const void*>(wavenet_generate_kernel), lds));
   wavenet_generate_kernel<<<dim3((unsigned)tiles), WN_THREADS, lds, s>>>(a);
   ITTS_LAUNCH_CHECK();
-  ITTS_HIP_CHECK(scratch_free(d_len, s));
   return ITTS_OK;
 }

@@ -10,7 +10,6 @@
 // master table) -- no LDS FFT buffer, any f0-dependent FFT size.  The refinement math (GetRefinedF0) is
 // f0_refine.h, shared with Harvest.  D4C: one 256-thread workgroup per frame, every spectrum in LDS.
 #include <algorithm>
-#include <atomic>
 #include <cstdlib>
 #include <cmath>
 #include <type_traits>
@@ -585,12 +584,12 @@ extern "C" int itts_stonemask(const double* d_x, const int64_t* h_x_off, const d
   int rc = check_offsets(h_x_off, h_f_off, n_utts, fs, frame_period_ms);
   if (rc) return rc;
   hipStream_t s = as_stream(stream);
-  itts::ScratchScope scratch_scope(s);
+  itts::ScratchScope scratch(s);
   DeviceContext* ctx = get_context();
   if (!ctx) return ITTS_E_HIP;
   int64_t *d_xo = nullptr, *d_fo = nullptr;
-  if ((rc = upload_i64(h_x_off, n_utts + 1, &d_xo, s))) return rc;
-  if ((rc = upload_i64(h_f_off, n_utts + 1, &d_fo, s))) return rc;
+  if ((rc = upload_i64(h_x_off, n_utts + 1, &d_xo, scratch))) return rc;
+  if ((rc = upload_i64(h_f_off, n_utts + 1, &d_fo, scratch))) return rc;
   SmArgs a{d_x, d_xo, d_f0_in, d_fo, n_utts, fs, frame_period_ms, d_f0_out, ctx->twiddles, 0};
   a.nmax = 2 * (int)(1.5 * fs / 40.0 + 1.0) + 1 + 3;
   // A wave's LDS block holds the window of its frame: 3 periods of f0.  The interface admits f0 down to 40 Hz
@@ -602,7 +601,6 @@ extern "C" int itts_stonemask(const double* d_x, const int64_t* h_x_off, const d
   ITTS_REQUIRE((size_t)a.nmax * 2 * 8 <= 160 * 1024, "sampling rate too high for the StoneMask LDS budget");
   const double kSplit = 70.0;
   const int64_t T = h_f_off[n_utts];
-  static std::atomic<int> lds_attr{0};
   auto launch = [&](double from, double to) -> int {
     SmArgs b = a;
     b.nmax = 2 * (int)(1.5 * fs / from + 1.0) + 1 + 3;
@@ -610,12 +608,7 @@ extern "C" int itts_stonemask(const double* d_x, const int64_t* h_x_off, const d
     // as many frames per workgroup as keep two workgroups on a CU
     const int waves = (int)std::max<size_t>(1, std::min<size_t>(4, (80 * 1024) / pw));
     const size_t lds = pw * waves;
-    const int attr = (int)std::max<size_t>(lds, 80 * 1024);
-    if (attr > lds_attr.load()) {
-      ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)stonemask_wave_kernel,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, attr));
-      lds_attr.store(attr);
-    }
+    ITTS_HIP_CHECK(itts::allow_dynamic_lds((const void*)stonemask_wave_kernel, lds));
     hipLaunchKernelGGL(stonemask_wave_kernel, dim3((unsigned)((T + waves - 1) / waves)), dim3(64 * waves), lds,
                        s, b, waves, from, to);
     ITTS_LAUNCH_CHECK();
@@ -623,8 +616,6 @@ extern "C" int itts_stonemask(const double* d_x, const int64_t* h_x_off, const d
   };
   if ((rc = launch(kSplit, 1e308))) return rc;
   if ((rc = launch(40.0, kSplit))) return rc;
-  ITTS_HIP_CHECK(itts::scratch_free(d_xo, s));
-  ITTS_HIP_CHECK(itts::scratch_free(d_fo, s));
   return ITTS_OK;
 }
 
@@ -643,7 +634,7 @@ extern "C" int itts_d4c(const double* d_x, const int64_t* h_x_off, const double*
   int rc = check_offsets(h_x_off, h_f_off, n_utts, fs, frame_period_ms);
   if (rc) return rc;
   hipStream_t s = as_stream(stream);
-  itts::ScratchScope scratch_scope(s);
+  itts::ScratchScope scratch(s);
   DeviceContext* ctx = get_context();
   if (!ctx) return ITTS_E_HIP;
   D4cArgs a{};
@@ -653,8 +644,8 @@ extern "C" int itts_d4c(const double* d_x, const int64_t* h_x_off, const double*
   a.logfftd = ilog2h(a.fftd);
   a.logfftl = ilog2h(a.fftl);
   int64_t *d_xo = nullptr, *d_fo = nullptr;
-  if ((rc = upload_i64(h_x_off, n_utts + 1, &d_xo, s))) return rc;
-  if ((rc = upload_i64(h_f_off, n_utts + 1, &d_fo, s))) return rc;
+  if ((rc = upload_i64(h_x_off, n_utts + 1, &d_xo, scratch))) return rc;
+  if ((rc = upload_i64(h_f_off, n_utts + 1, &d_fo, scratch))) return rc;
   a.x = d_x; a.x_off = d_xo; a.f0 = d_f0; a.f_off = d_fo; a.n_utts = n_utts; a.fs = fs;
   a.frame_period = frame_period_ms; a.fft_size = fft_size; a.threshold = threshold; a.nap = nap;
   a.ap = d_ap; a.bap_f64 = d_bap_f64; a.bap_f32 = d_bap_f32; a.ld_bap = ld_bap;
@@ -672,11 +663,11 @@ extern "C" int itts_d4c(const double* d_x, const int64_t* h_x_off, const double*
   const bool sized = a.fftd == a.fftl && a.logfftd == (areg ? 12 : 11) && !getenv("ITTS_D4C_GENERIC");
   const void* kern = areg ? (sized ? (const void*)d4c_kernel<true, 12> : (const void*)d4c_kernel<true>)
                           : (sized ? (const void*)d4c_kernel<false, 11> : (const void*)d4c_kernel<false>);
-  ITTS_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  ITTS_HIP_CHECK(itts::allow_dynamic_lds(kern, lds));
   const int64_t t_total = h_f_off[n_utts];
   ITTS_REQUIRE(t_total < ((int64_t)1 << 31), "too many frames in one call");
   int* d_order = nullptr;
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_order, (size_t)(t_total + 2) * sizeof(int), s));
+  ITTS_HIP_CHECK(scratch.take(&d_order, (size_t)(t_total + 2)));
   ITTS_HIP_CHECK(hipMemsetAsync(d_order + t_total, 0, 2 * sizeof(int), s));
   hipLaunchKernelGGL(d4c_order_kernel, dim3((unsigned)std::min<int64_t>((t_total + 255) / 256, 1024)), dim3(256),
                      0, s, d_f0, t_total, d_order, d_order + t_total);
@@ -684,7 +675,7 @@ extern "C" int itts_d4c(const double* d_x, const int64_t* h_x_off, const double*
   a.order = d_order;
   const int wl = (int)(3000.0 * a.fftd / fs) * 2 + 1;
   double* d_nwin = nullptr;
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_nwin, (size_t)wl * 8, s));
+  ITTS_HIP_CHECK(scratch.take(&d_nwin, (size_t)wl));
   hipLaunchKernelGGL(d4c_nuttall_kernel, dim3((wl + 255) / 256), dim3(256), 0, s, wl, d_nwin);
   ITTS_LAUNCH_CHECK();
   a.nwin = d_nwin;
@@ -719,9 +710,5 @@ extern "C" int itts_d4c(const double* d_x, const int64_t* h_x_off, const double*
       hipLaunchKernelGGL(d4c_kernel<false>, dim3((unsigned)n_active), dim3(NT), lds, s, a);
     ITTS_LAUNCH_CHECK();
   }
-  ITTS_HIP_CHECK(itts::scratch_free(d_nwin, s));
-  ITTS_HIP_CHECK(itts::scratch_free(d_order, s));
-  ITTS_HIP_CHECK(itts::scratch_free(d_xo, s));
-  ITTS_HIP_CHECK(itts::scratch_free(d_fo, s));
   return ITTS_OK;
 }

@@ -608,7 +608,7 @@ __global__ __launch_bounds__(256) void decode_aperiodicity_kernel(const double* 
 // mcep_lockstep.hip
 int mcep_lockstep(DeviceContext* ctx, const double* d_in, int in_is_power, int64_t T, int K, int order,
                   double alpha, double eps, int miniter, int maxiter, double threshold, float* d_mc_f32,
-                  int64_t ld_mc, double* d_mc_f64, int* d_iters, hipStream_t s);
+                  int64_t ld_mc, double* d_mc_f64, int* d_iters, ScratchScope& scratch);
 
 static int smoothing_bmax(int fs, int fft, double max_width) { return (int)(max_width * fft / fs) + 2; }
 
@@ -649,88 +649,81 @@ extern "C" int itts_cheaptrick_mcep(const double* d_x, const int64_t* h_x_off, c
                  "frame offsets do not match int(1000*n/fs/frame_period)+1");
   }
   hipStream_t s = as_stream(stream);
-  itts::ScratchScope scratch_scope(s);
+  itts::ScratchScope scratch(s);
   DeviceContext* ctx = get_context();
   if (!ctx) return ITTS_E_HIP;
   FrameArgs a{};
   // lockstep mcep needs the envelope in memory: use the caller's buffer or a temporary
   double* sp_buf = d_sp;
   if (do_mcep && !sp_buf)
-    ITTS_HIP_CHECK(itts::scratch_malloc((void**)&sp_buf, (size_t)t_total * (fft_size / 2 + 1) * 8, s));
-  int64_t *d_xo = nullptr, *d_fo = nullptr;
-  int rc = upload_i64(h_x_off, n_utts + 1, &d_xo, s);
-  if (rc) return rc;
-  rc = upload_i64(h_f_off, n_utts + 1, &d_fo, s);
-  if (rc) return rc;
-  a.x = d_x; a.x_off = d_xo; a.f0 = d_f0; a.f_off = d_fo; a.n_utts = n_utts; a.fs = fs;
-  a.frame_period = frame_period_ms; a.fft = fft_size; a.logfft = ilog2_host(fft_size); a.q1 = q1;
-  a.sp = sp_buf; a.do_mcep = 0; a.m = order; a.alpha = alpha; a.eps = eps;
-  a.itr1 = miniter; a.itr2 = maxiter; a.dd = threshold; a.mc_f32 = d_mc_f32; a.mc_f64 = d_mc_f64;
-  a.ld_mc = ld_mc; a.iters = d_iters; a.g_tw = ctx->twiddles;
-  a.g_tw_compact = ctx->tw_compact[a.logfft];
-  a.bmax = smoothing_bmax(fs, fft_size, 1000.0);
-  // safeguard-noise streams: positions (scan over the frames' window lengths), then the normals
-  const int K = fft_size / 2 + 1;
-  const int64_t rn_pitch = 2 * (int64_t)std::lround((fft_size - 3.0) / 2.0) + 1 + K;
-  int64_t t_max = 0;
-  for (int u = 0; u < n_utts; ++u) t_max = std::max<int64_t>(t_max, h_f_off[u + 1] - h_f_off[u]);
-  int64_t* d_rpos = nullptr;   // [t_total] + r_off [U] + r_len [U]
-  uint32_t* d_rn = nullptr;
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_rpos, (size_t)(t_total + 2 * n_utts + 1) * sizeof(int64_t), s));
-  int* d_next = reinterpret_cast<int*>(d_rpos + t_total + 2 * n_utts);      // the wave kernel's frame counter
-  ITTS_HIP_CHECK(hipMemsetAsync(d_next, 0, sizeof(int64_t), s));
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_rn, (size_t)t_total * rn_pitch * sizeof(uint32_t), s));
-  int64_t* d_roff = d_rpos + t_total;
-  int64_t* d_rlen = d_roff + n_utts;
-  hipLaunchKernelGGL(ct_noise_pos_kernel, dim3(n_utts), dim3(256), 0, s, d_f0, d_fo, fs, fft_size,
-                     rn_pitch, d_rpos, d_roff, d_rlen);
-  ITTS_LAUNCH_CHECK();
-  rc = launch_randn_u32(ctx, d_roff, d_rlen, n_utts, t_max * rn_pitch, d_rn, s);
-  if (rc) return rc;
-  a.rn = d_rn; a.rn_pos = d_rpos; a.rn_pitch = rn_pitch; a.t_total = t_total; a.far_only = 0;
-  // the smoothing boundary of the wave kernel is bounded by its scratch: 513 + 2 b <= 1088 doubles
-  const int wave_r = fft_size == 1024 ? 8 : (fft_size == 2048 ? 16 : 0);
-  if (wave_r != 0 && fft_size / 2 + 1 + 2 * ((int)(1000.0 * 2.0 / 3.0 * fft_size / fs) + 1) <=
-                         64 * (wave_r == 8 ? ctw_scan<8>() : ctw_scan<16>())) {
-    int dev = 0, n_cu = 256;
-    ITTS_HIP_CHECK(hipGetDevice(&dev));
-    ITTS_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-    constexpr int TH16 = CTW_THREADS;          // (R = 16 at one wave per SIMD -- 256 threads, no scratch -- took 3.48 ms against 3.05)
-    const int NW = (wave_r == 8 ? CTW_THREADS : TH16) / 64;
-    const dim3 grid((unsigned)std::min<int64_t>((t_total + NW - 1) / NW, n_cu));
-    if (wave_r == 8) {
-      const size_t lds = wf::table_bytes<8>() + (size_t)NW * wf::lds_bytes<8>();
-      ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)cheaptrick_wave_kernel<8>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(cheaptrick_wave_kernel<8>, grid, dim3(CTW_THREADS), lds, s, a, t_total, d_next);
-    } else {
-      const size_t lds = wf::table_bytes<16>() + (size_t)NW * wf::lds_bytes<16>();
-      ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)cheaptrick_wave_kernel<16, TH16>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL((cheaptrick_wave_kernel<16, TH16>), grid, dim3(TH16), lds, s, a, t_total, d_next);
+    ITTS_HIP_CHECK(scratch.take(&sp_buf, (size_t)t_total * (fft_size / 2 + 1)));
+  {
+    itts::ScratchScope frames(s);   // back in the pool before mcep_lockstep takes its blocks
+    int64_t *d_xo = nullptr, *d_fo = nullptr;
+    int rc = upload_i64(h_x_off, n_utts + 1, &d_xo, frames);
+    if (rc) return rc;
+    rc = upload_i64(h_f_off, n_utts + 1, &d_fo, frames);
+    if (rc) return rc;
+    a.x = d_x; a.x_off = d_xo; a.f0 = d_f0; a.f_off = d_fo; a.n_utts = n_utts; a.fs = fs;
+    a.frame_period = frame_period_ms; a.fft = fft_size; a.logfft = ilog2_host(fft_size); a.q1 = q1;
+    a.sp = sp_buf; a.do_mcep = 0; a.m = order; a.alpha = alpha; a.eps = eps;
+    a.itr1 = miniter; a.itr2 = maxiter; a.dd = threshold; a.mc_f32 = d_mc_f32; a.mc_f64 = d_mc_f64;
+    a.ld_mc = ld_mc; a.iters = d_iters; a.g_tw = ctx->twiddles;
+    a.g_tw_compact = ctx->tw_compact[a.logfft];
+    a.bmax = smoothing_bmax(fs, fft_size, 1000.0);
+    // safeguard-noise streams: positions (scan over the frames' window lengths), then the normals
+    const int K = fft_size / 2 + 1;
+    const int64_t rn_pitch = 2 * (int64_t)std::lround((fft_size - 3.0) / 2.0) + 1 + K;
+    int64_t t_max = 0;
+    for (int u = 0; u < n_utts; ++u) t_max = std::max<int64_t>(t_max, h_f_off[u + 1] - h_f_off[u]);
+    int64_t* d_rpos = nullptr;   // [t_total] + r_off [U] + r_len [U]
+    uint32_t* d_rn = nullptr;
+    ITTS_HIP_CHECK(frames.take(&d_rpos, (size_t)(t_total + 2 * n_utts + 1)));
+    int* d_next = reinterpret_cast<int*>(d_rpos + t_total + 2 * n_utts);      // the wave kernel's frame counter
+    ITTS_HIP_CHECK(hipMemsetAsync(d_next, 0, sizeof(int64_t), s));
+    ITTS_HIP_CHECK(frames.take(&d_rn, (size_t)t_total * rn_pitch));
+    int64_t* d_roff = d_rpos + t_total;
+    int64_t* d_rlen = d_roff + n_utts;
+    hipLaunchKernelGGL(ct_noise_pos_kernel, dim3(n_utts), dim3(256), 0, s, d_f0, d_fo, fs, fft_size,
+                       rn_pitch, d_rpos, d_roff, d_rlen);
+    ITTS_LAUNCH_CHECK();
+    rc = launch_randn_u32(ctx, d_roff, d_rlen, n_utts, t_max * rn_pitch, d_rn, s);
+    if (rc) return rc;
+    a.rn = d_rn; a.rn_pos = d_rpos; a.rn_pitch = rn_pitch; a.t_total = t_total; a.far_only = 0;
+    // the smoothing boundary of the wave kernel is bounded by its scratch: 513 + 2 b <= 1088 doubles
+    const int wave_r = fft_size == 1024 ? 8 : (fft_size == 2048 ? 16 : 0);
+    if (wave_r != 0 && fft_size / 2 + 1 + 2 * ((int)(1000.0 * 2.0 / 3.0 * fft_size / fs) + 1) <=
+                           64 * (wave_r == 8 ? ctw_scan<8>() : ctw_scan<16>())) {
+      int dev = 0, n_cu = 256;
+      ITTS_HIP_CHECK(hipGetDevice(&dev));
+      ITTS_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+      constexpr int TH16 = CTW_THREADS;          // (R = 16 at one wave per SIMD -- 256 threads, no scratch -- took 3.48 ms against 3.05)
+      const int NW = (wave_r == 8 ? CTW_THREADS : TH16) / 64;
+      const dim3 grid((unsigned)std::min<int64_t>((t_total + NW - 1) / NW, n_cu));
+      if (wave_r == 8) {
+        const size_t lds = wf::table_bytes<8>() + (size_t)NW * wf::lds_bytes<8>();
+        ITTS_HIP_CHECK(itts::allow_dynamic_lds((const void*)cheaptrick_wave_kernel<8>, lds));
+        hipLaunchKernelGGL(cheaptrick_wave_kernel<8>, grid, dim3(CTW_THREADS), lds, s, a, t_total, d_next);
+      } else {
+        const size_t lds = wf::table_bytes<16>() + (size_t)NW * wf::lds_bytes<16>();
+        ITTS_HIP_CHECK(itts::allow_dynamic_lds((const void*)cheaptrick_wave_kernel<16, TH16>, lds));
+        hipLaunchKernelGGL((cheaptrick_wave_kernel<16, TH16>), grid, dim3(TH16), lds, s, a, t_total, d_next);
+      }
+      ITTS_LAUNCH_CHECK();
+      a.far_only = 1;     // frames with an F0 at or beyond fs / 2: a pass that reads the F0 values and normally finds none
+    }
+    {
+      size_t lds = ct_lds_bytes(fft_size, a.bmax, false);
+      ITTS_REQUIRE(lds <= 160 * 1024, "LDS budget exceeded");
+      ITTS_HIP_CHECK(itts::allow_dynamic_lds((const void*)cheaptrick_kernel, lds));
+      hipLaunchKernelGGL(cheaptrick_kernel, dim3((unsigned)(a.far_only ? std::min<int64_t>(t_total, 256) : t_total)),
+                         dim3(NT), lds, s, a);
     }
     ITTS_LAUNCH_CHECK();
-    a.far_only = 1;     // frames with an F0 at or beyond fs / 2: a pass that reads the F0 values and normally finds none
   }
-  {
-    size_t lds = ct_lds_bytes(fft_size, a.bmax, false);
-    ITTS_REQUIRE(lds <= 160 * 1024, "LDS budget exceeded");
-    ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)cheaptrick_kernel,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(cheaptrick_kernel, dim3((unsigned)(a.far_only ? std::min<int64_t>(t_total, 256) : t_total)),
-                       dim3(NT), lds, s, a);
-  }
-  ITTS_LAUNCH_CHECK();
-  ITTS_HIP_CHECK(itts::scratch_free(d_xo, s));
-  ITTS_HIP_CHECK(itts::scratch_free(d_fo, s));
-  ITTS_HIP_CHECK(itts::scratch_free(d_rpos, s));
-  ITTS_HIP_CHECK(itts::scratch_free(d_rn, s));
-  if (do_mcep) {
-    rc = mcep_lockstep(ctx, sp_buf, 1, t_total, fft_size / 2 + 1, order, alpha, eps, miniter, maxiter,
-                       threshold, d_mc_f32, ld_mc, d_mc_f64, d_iters, s);
-    if (sp_buf != d_sp) ITTS_HIP_CHECK(itts::scratch_free(sp_buf, s));
-    if (rc) return rc;
-  }
+  if (do_mcep)
+    return mcep_lockstep(ctx, sp_buf, 1, t_total, fft_size / 2 + 1, order, alpha, eps, miniter, maxiter,
+                         threshold, d_mc_f32, ld_mc, d_mc_f64, d_iters, scratch);
   return ITTS_OK;
 }
 
@@ -745,8 +738,9 @@ extern "C" int itts_mcep(const double* d_amp_sp, int64_t T, int K, int order, do
   if (T == 0) return ITTS_OK;
   DeviceContext* ctx = get_context();
   if (!ctx) return ITTS_E_HIP;
+  itts::ScratchScope scratch(as_stream(stream));
   return mcep_lockstep(ctx, d_amp_sp, 0, T, K, order, alpha, eps, miniter, maxiter, threshold,
-                       d_mc_f32, ld_mc, d_mc_f64, d_iters, as_stream(stream));
+                       d_mc_f32, ld_mc, d_mc_f64, d_iters, scratch);
 }
 
 extern "C" int itts_mgc2sp(const double* d_mc, int64_t T, int order, double alpha, int fftlen,
@@ -758,7 +752,7 @@ extern "C" int itts_mgc2sp(const double* d_mc, int64_t T, int order, double alph
   DeviceContext* ctx = get_context();
   if (!ctx) return ITTS_E_HIP;
   hipStream_t s = as_stream(stream);
-  itts::ScratchScope scratch_scope(s);
+  itts::ScratchScope scratch(s);
   const int K = fftlen / 2 + 1;
   // Orders up to 63 at transform sizes up to 2048: de-warping, transform and real part are ONE linear map
   // (FreqtTables::specT), so the log amplitude is one fp64-MFMA product and exp / square ride in its
@@ -774,7 +768,7 @@ extern "C" int itts_mgc2sp(const double* d_mc, int64_t T, int order, double alph
   if (!ft) return ITTS_E_HIP;
   const int64_t ld_cep = (K + 1) & ~1;
   double* d_cep = nullptr;
-  ITTS_HIP_CHECK(itts::scratch_malloc((void**)&d_cep, (size_t)T * ld_cep * 8, s));
+  ITTS_HIP_CHECK(scratch.take(&d_cep, (size_t)T * ld_cep));
   int rc = launch_gemm_f64(d_mc, order + 1, ft->invT, K, d_cep, ld_cep, T, K, order + 1, nullptr, s,
                            /*a_has_slack=*/false);
   if (rc) return rc;
@@ -782,12 +776,10 @@ extern "C" int itts_mgc2sp(const double* d_mc, int64_t T, int order, double alph
                ctx->twiddles};
   {
     size_t lds = (size_t)(fftlen / 2) * 16 + (size_t)(fftlen / 2 + 1) * 16;
-    ITTS_HIP_CHECK(hipFuncSetAttribute((const void*)mgc2sp_kernel,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    ITTS_HIP_CHECK(itts::allow_dynamic_lds((const void*)mgc2sp_kernel, lds));
     hipLaunchKernelGGL(mgc2sp_kernel, dim3((unsigned)T), dim3(NT), lds, s, a);
   }
   ITTS_LAUNCH_CHECK();
-  ITTS_HIP_CHECK(itts::scratch_free(d_cep, s));
   return ITTS_OK;
 }
 
