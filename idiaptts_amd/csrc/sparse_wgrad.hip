@@ -1,7 +1,8 @@
 // Weight gradient of the first dense layer on a sparse input for gfx950: dw = dz^T x without the products by x's
 // exact zeros (sparse_rows.hip is the forward's side of the same input).  The accumulators stay in registers, so
 // the non-zeros are walked by column: once per batch sparse_cols_build_kernel cuts x into tiles of 256 rows and
-// writes, per tile, the (row, value) lists of the light columns and a compact strip of the heavy ones; the plan
+// writes, per tile, the (row, value) lists of the light columns and a compact strip of the heavy ones
+// (sparse_cols_from_rows_kernel writes the same from the forward's row lists, without reading x); the plan
 // (itts_sparse_cols_* in the header) says which column is which and who owns it.
 //   * light columns: a quarter wave owns up to 8 of them and keeps a float4 accumulator per column and lane (four
 //     adjacent dz columns); per list entry one DPP row broadcast, one 16-byte LDS read of the dz row, four fmaf.
@@ -140,6 +141,176 @@ __global__ __launch_bounds__(256) void sparse_cols_build_kernel(const uint32_t* 
     const int end = (total + kBlock - 1) / kBlock * kBlock;
     for (int e = total; e < end; ++e) *entry_of(streams, tiles, pair, e) = make_int2(kTile * kRowBytes, 0);
     reinterpret_cast<uint16_t*>(streams + ((int64_t)tile * kOwners + owner) * kHeaderBytes)[slot] = (uint16_t)total;
+  }
+}
+
+// The same column block from the row lists of x (sparse_rows.hip) instead of x itself: the lists already name every
+// non-zero, so nothing dense is read or compacted.  Workgroup = tile of 256 rows, wave = 16 consecutive rows, half
+// wave = row, lane = two adjacent list entries (one 16-byte load); block 0 of the tile's 512 lists and its strip
+// tile are put together in LDS and leave as whole lines.
+//   fill:   mask words and strip zeros (column 31: ones in front of M), every list of `first` neutral entries, the
+//           plan's inverse; meanwhile the first 64 slots of the wave's 16 rows and their counts are on their way
+//           into registers (together: what lies behind a row's count is read and masked out)
+//   mark:   word[wave][list of the entry's column] |= 1 << row of the wave (an integer OR in LDS: no order changes
+//           the word); entries of columns >= K are nobody's
+//   prefix: lane = list: the upper half of each of the list's 16 words becomes the number of entries in the waves
+//           before it, the total the header
+//   place:  position = entries before the wave + marked rows of the wave before this one: ascending rows inside
+//           every list, without a counter.  A position < 16 lands in `first`, a later one goes straight to its
+//           overflow block (8-byte stores, as the build from x); a heavy column's value lands in the strip tile
+//   out:    64 KB of first blocks and 32 KB of strip, 16 bytes a lane; then the neutral tails of the lists that
+//           end beyond block 0
+// A row of more than 64 entries takes further trips, read again in both sweeps.
+constexpr int kFromRowsWaves = 16;
+constexpr int kFromRowsPairs = kTile / kFromRowsWaves / 2;   // row pairs of a wave
+constexpr int kLists = kOwners * kSlots;
+constexpr int kFromRowsLdsBytes = kLists * kFirstBytes + kTile * kStrip * 4 + kFromRowsWaves * kLists * 4 + kWgMaxK * 4;
+
+__global__ __launch_bounds__(kFromRowsWaves * 64) void sparse_cols_from_rows_kernel(
+    const int* __restrict__ counts, const int4* __restrict__ entries2, int64_t pitch2, int64_t M, int K, int tiles,
+    const int* __restrict__ plan, uint32_t* __restrict__ strip, char* __restrict__ streams) {
+  constexpr int T = kFromRowsWaves * 64;
+  extern __shared__ uint4 from_rows_lds[];
+  int2* first = reinterpret_cast<int2*>(from_rows_lds);                          // [512 lists][16]
+  uint32_t* tile_strip = reinterpret_cast<uint32_t*>(first + kLists * kBlock);   // [256][32]
+  uint32_t* words = tile_strip + kTile * kStrip;                                 // [16 waves][512 lists]
+  int* inverse = reinterpret_cast<int*>(words + kFromRowsWaves * kLists);        // [512 columns]
+  const int tid = threadIdx.x, lane = tid & 63, l32 = lane & 31;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int tile = (int)blockIdx.x;
+  const int64_t m0 = (int64_t)tile * kTile;
+  const int row0 = wave * 2 * kFromRowsPairs + (lane >> 5);   // this lane's row of pair q: row0 + 2 q
+
+  int code_of_tid = -1;   // light: the list; heavy: as in the plan; else nobody's
+  if (tid < K) {
+    const int code = plan[kPlanInv + tid];
+    if ((code >= 0 && code < kLists) || (code >= kHeavyCode && code < kHeavyCode + kStrip - 1)) code_of_tid = code;
+  }
+  int cnt[kFromRowsPairs];
+  int4 head[kFromRowsPairs];   // {column, value} of entries 2 l32 and 2 l32 + 1, later {code, value}
+#pragma unroll
+  for (int q = 0; q < kFromRowsPairs; ++q) {
+    const int64_t m = m0 + row0 + 2 * q;
+    const bool in = m < M && l32 < pitch2;
+    cnt[q] = in ? std::min(counts[m], (int)(2 * pitch2)) : 0;
+    head[q] = in ? entries2[m * pitch2 + l32] : make_int4(-1, 0, -1, 0);
+  }
+
+  {
+    const uint4 neutral = make_uint4((uint32_t)(kTile * kRowBytes), 0u, (uint32_t)(kTile * kRowBytes), 0u);
+    uint4* first4 = reinterpret_cast<uint4*>(first);
+    for (int i = tid; i < kLists * kFirstBytes / 16; i += T) first4[i] = neutral;
+    uint4* strip4 = reinterpret_cast<uint4*>(tile_strip);
+    for (int i = tid; i < kTile * kStrip / 4; i += T) {
+      const bool ones = (i & 7) == 7 && m0 + (i >> 3) < M;   // the last four columns of row i / 8
+      strip4[i] = make_uint4(0u, 0u, 0u, ones ? 0x3f800000u : 0u);
+    }
+    uint4* words4 = reinterpret_cast<uint4*>(words);
+    for (int i = tid; i < kFromRowsWaves * kLists / 4; i += T) words4[i] = make_uint4(0u, 0u, 0u, 0u);
+    if (tid < kWgMaxK) inverse[tid] = code_of_tid;
+  }
+  int most = 0;
+#pragma unroll
+  for (int q = 0; q < kFromRowsPairs; ++q) {
+    if (2 * l32 >= cnt[q]) head[q].x = -1;
+    if (2 * l32 + 1 >= cnt[q]) head[q].z = -1;
+    most = std::max(most, cnt[q]);
+  }
+  const bool further = std::max(most, __shfl_xor(most, 32, 64)) > 64;   // uniform in the wave
+  __syncthreads();
+
+  uint32_t* my_words = words + wave * kLists;
+  auto code_of = [&](int k) { return (unsigned)k < (unsigned)K ? inverse[k] : -1; };
+  auto again = [&](int q, int j0) {   // entries j0 + 2 l32 and the next of the lane's row
+    int4 e = j0 + 2 * l32 < cnt[q] ? entries2[(m0 + row0 + 2 * q) * pitch2 + j0 / 2 + l32] : make_int4(-1, 0, -1, 0);
+    if (j0 + 2 * l32 + 1 >= cnt[q]) e.z = -1;
+    e.x = code_of(e.x);
+    e.z = code_of(e.z);
+    return e;
+  };
+  auto mark = [&](int q, int code) {
+    if (code >= 0 && code < kLists) atomicOr(&my_words[code], 1u << (2 * q + (lane >> 5)));
+  };
+  auto place = [&](int q, int code, int value) {
+    const int row = 2 * q + (lane >> 5);   // of the wave
+    if (code >= 0 && code < kLists) {
+      const uint32_t word = my_words[code];
+      const int pos = (int)(word >> 16) + __popc(word & ((1u << row) - 1u));
+      const int2 out = make_int2((row0 + 2 * q) * kRowBytes, value);
+      if (pos < kBlock) first[code * kBlock + pos] = out;
+      else if (pos < kTile) *entry_of(streams, tiles, (int64_t)tile * kLists + code, pos) = out;
+    } else if (code >= kHeavyCode) {
+      tile_strip[(row0 + 2 * q) * kStrip + (code - kHeavyCode)] = (uint32_t)value;
+    }
+  };
+
+#pragma unroll
+  for (int q = 0; q < kFromRowsPairs; ++q) {
+    head[q].x = code_of(head[q].x);
+    head[q].z = code_of(head[q].z);
+  }
+#pragma unroll
+  for (int q = 0; q < kFromRowsPairs; ++q) {
+    mark(q, head[q].x);
+    mark(q, head[q].z);
+  }
+  if (further) {
+#pragma unroll
+    for (int q = 0; q < kFromRowsPairs; ++q)
+      for (int j0 = 64; j0 < cnt[q]; j0 += 64) {
+        const int4 e = again(q, j0);
+        mark(q, e.x);
+        mark(q, e.z);
+      }
+  }
+  __syncthreads();
+
+  if (tid < kLists) {
+    int run = 0;
+#pragma unroll
+    for (int w = 0; w < kFromRowsWaves; ++w) {
+      const uint32_t rows_of_wave = words[w * kLists + tid];
+      words[w * kLists + tid] = rows_of_wave | ((uint32_t)run << 16);
+      run += __popc(rows_of_wave);
+    }
+    reinterpret_cast<uint16_t*>(streams)[(int64_t)tile * kLists + tid] = (uint16_t)run;
+  }
+  __syncthreads();
+
+#pragma unroll
+  for (int q = 0; q < kFromRowsPairs; ++q) {
+    place(q, head[q].x, head[q].y);
+    place(q, head[q].z, head[q].w);
+  }
+  if (further) {
+#pragma unroll
+    for (int q = 0; q < kFromRowsPairs; ++q)
+      for (int j0 = 64; j0 < cnt[q]; j0 += 64) {
+        const int4 e = again(q, j0);
+        place(q, e.x, e.y);
+        place(q, e.z, e.w);
+      }
+  }
+  __syncthreads();
+
+  {
+    const uint4* first4 = reinterpret_cast<const uint4*>(first);
+    uint4* dst = reinterpret_cast<uint4*>(const_cast<char*>(firsts_of(streams, tiles)) +
+                                          (int64_t)tile * kLists * kFirstBytes);
+    for (int i = tid; i < kLists * kFirstBytes / 16; i += T) dst[i] = first4[i];
+    const uint4* strip4 = reinterpret_cast<const uint4*>(tile_strip);
+    uint4* sdst = reinterpret_cast<uint4*>(strip + m0 * kStrip);
+    for (int i = tid; i < kTile * kStrip / 4; i += T) sdst[i] = strip4[i];
+  }
+  {   // two threads a list: the neutral entries behind its last one, up to a whole block
+    const int list = tid & (kLists - 1);
+    const uint32_t last = words[(kFromRowsWaves - 1) * kLists + list];
+    const int total = (int)(last >> 16) + __popc(last & 0xffffu);
+    if (total > kBlock) {
+      const int end = (total + kBlock - 1) / kBlock * kBlock;
+      for (int e = total + (tid >> 9); e < end; e += T / kLists)
+        *entry_of(streams, tiles, (int64_t)tile * kLists + list, e) = make_int2(kTile * kRowBytes, 0);
+    }
   }
 }
 
@@ -399,6 +570,30 @@ extern "C" int itts_sparse_cols_build(const float* d_x, int64_t ldx, int64_t M, 
   char* base = static_cast<char*>(d_cols);
   hipLaunchKernelGGL(sparse_cols_build_kernel, dim3((unsigned)(l.tiles * (parts + 1))), dim3(256), 0,
                      as_stream(stream), reinterpret_cast<const uint32_t*>(d_x), ldx, M, K, parts, (int)l.tiles, d_plan,
+                     reinterpret_cast<uint32_t*>(base + l.strip_off), base + l.streams_off);
+  ITTS_LAUNCH_CHECK();
+  g_wgrad_path[0].fetch_add(1, std::memory_order_relaxed);
+  return ITTS_OK;
+}
+
+extern "C" int itts_sparse_cols_build_from_rows(const void* d_lists, int64_t M, int K_lists, int K, const int* d_plan,
+                                                void* d_cols, void* stream) {
+  ITTS_REQUIRE(d_plan && d_cols && (M == 0 || d_lists), "null pointer");
+  ITTS_REQUIRE(M >= 0 && K > 0 && K <= kWgMaxK && K_lists >= K && K_lists <= 65535,
+               "bad sizes (K <= 512, K <= K_lists <= 65535)");
+  ITTS_REQUIRE(aligned16(d_cols) && aligned16(d_lists), "the column and list blocks must be 16-byte aligned");
+  if (M == 0) return ITTS_OK;
+  int64_t rows[4];   // counts, entries, pitch, bytes of the list block
+  if (int rc = itts_sparse_rows_layout(M, K_lists, rows)) return rc;
+  const ColsLayout l = cols_layout(M);
+  ITTS_REQUIRE(l.tiles < ((int64_t)1 << 31), "too many rows");
+  ITTS_HIP_CHECK(itts::allow_dynamic_lds((const void*)sparse_cols_from_rows_kernel, kFromRowsLdsBytes));
+  const char* lists = static_cast<const char*>(d_lists);
+  char* base = static_cast<char*>(d_cols);
+  // the kernel reads two entries a lane: the pitch is a multiple of 16 entries, the entries start 16-byte aligned
+  hipLaunchKernelGGL(sparse_cols_from_rows_kernel, dim3((unsigned)l.tiles), dim3(kFromRowsWaves * 64),
+                     kFromRowsLdsBytes, as_stream(stream), reinterpret_cast<const int*>(lists + rows[0]),
+                     reinterpret_cast<const int4*>(lists + rows[1]), rows[2] / 2, M, K, (int)l.tiles, d_plan,
                      reinterpret_cast<uint32_t*>(base + l.strip_off), base + l.streams_off);
   ITTS_LAUNCH_CHECK();
   g_wgrad_path[0].fetch_add(1, std::memory_order_relaxed);

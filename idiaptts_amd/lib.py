@@ -113,6 +113,7 @@ _SIGNATURES = {
     "itts_sparse_cols_plan_ints": (c_int, []),
     "itts_sparse_cols_layout": (c_int, [c_int64, c_int, POINTER(c_int64)]),
     "itts_sparse_cols_build": (c_int, [_P, c_int64, c_int64, c_int, _P, _P, _P]),
+    "itts_sparse_cols_build_from_rows": (c_int, [_P, c_int64, c_int, c_int, _P, _P, _P]),
     "itts_linear_bwd_weight_sparse_workspace_bytes": (c_int64, [c_int64, c_int, c_int, c_int64]),
     "itts_linear_bwd_weight_sparse": (c_int, [_P, c_int64, _P, _P, _P, c_int64, _P, c_int64, _P, c_int64, c_int,
                                               c_int, _P, c_int, _P]),

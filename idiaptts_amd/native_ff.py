@@ -51,7 +51,13 @@ class FlatFFModel:
     (ops.sparse_cols_build + ops.linear_bwd_weight_sparse) / through the dense product; None takes the lists where
     sparse_input does and the first batch's density is at most SPARSE_WGRAD_MAX_DENSITY.  The column plan is made
     once, from the column counts of the first batch (read where the density decision is made), and is a hint for
-    speed only."""
+    speed only.
+
+    cols_from_lists: the column data of a step are made from the row lists that the step's sparse forward built from
+    the same input (the same block as from the input itself, without a second pass over it); False restores the
+    build from the input."""
+
+    cols_from_lists = True
 
     def __init__(self, dims=(425, 512, 512, 187), acts=("tanh", "tanh", None), device="cuda",
                  seed=0, state_dict=None, sparse_input=None, sparse_wgrad=None):
@@ -266,7 +272,10 @@ class FlatFFModel:
             elif self._wgrad_sparse_now:
                 # without a plan (dims[0] > 512) the entry point runs the dense product and counts it
                 if self._col_plan is not None:
-                    self._cols = ops.sparse_cols_build(x, self._col_plan, K=self.dims[0], cols=self._cols)
+                    # the forward above listed the non-zeros of this x when it took the sparse path
+                    lists = self._lists if self.cols_from_lists and self.sparse_input else None
+                    self._cols = ops.sparse_cols_build(x, self._col_plan, K=self.dims[0], cols=self._cols,
+                                                       lists=lists)
                 ops.linear_bwd_weight_sparse(dz, x, self._cols if self._col_plan is not None else None,
                                              self._col_plan, dw=self.weight_padded(i, self.grads),
                                              db=self.bias(i, self.grads), K=self.dims[0])

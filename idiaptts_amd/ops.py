@@ -876,9 +876,10 @@ class SparseCols(object):
         return self.block[self._strip_off:self._streams_off].view(torch.float32).view(-1, 32)
 
 
-def sparse_cols_build(x, plan, K=None, cols=None):
+def sparse_cols_build(x, plan, K=None, cols=None, lists=None):
     """Column data of the first K (default: all) columns of x [M, >= K] fp32 under `plan`; `cols`: a SparseCols whose
-    block is reused when it is large enough."""
+    block is reused when it is large enough.  `lists`: the SparseRows of the same x (over at least K columns): the
+    block is then built from them (itts_sparse_cols_build_from_rows) and x is not read."""
     _need(x, torch.float32, "x")
     ldx = _rows(x, "x")
     M = x.shape[0]
@@ -888,6 +889,13 @@ def sparse_cols_build(x, plan, K=None, cols=None):
     if plan.K != K:
         raise ValueError("the plan was made for {} columns, not {}".format(plan.K, K))
     out = SparseCols(M, K, x.device, cols.block if cols is not None else None)
+    if lists is not None:
+        if lists.M != M or lists.K < K:
+            raise ValueError("the row lists were built for another shape")
+        _lib.check(_lib.load().itts_sparse_cols_build_from_rows(_ptr(lists.block), M, lists.K, K, _ptr(plan.table),
+                                                                _ptr(out.block), _stream()),
+                   "itts_sparse_cols_build_from_rows")
+        return out
     _lib.check(_lib.load().itts_sparse_cols_build(_ptr(x), ldx, M, K, _ptr(plan.table), _ptr(out.block), _stream()),
                "itts_sparse_cols_build")
     return out

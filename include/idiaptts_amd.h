@@ -519,18 +519,24 @@ int itts_sparse_path_counts(int64_t out[3]);
  * byte offset of the row in a [257][64] float tile, float value}, rows ascending, the last block of a list filled
  * up with {row 256, +0.0}.  -0.0 / NaN / denormals as in
  * itts_sparse_rows_build; a column of 256 non-zeros gives 256 entries: nothing is capped.
+ * itts_sparse_cols_build_from_rows writes the same block from the row lists d_lists of the same x
+ * (itts_sparse_rows_build over K_lists >= K columns; listed columns >= K are left out) without reading x: the same
+ * counts, the same entries in the same order, the same strip -- but for a -0.0 in a heavy column, which the lists do
+ * not hold: its strip cell is +0.0 where the build from x copies the sign bit (no sum depends on it).
  * itts_linear_bwd_weight_sparse: the result goes through the split-K slab workspace and the reduction of
  * itts_linear_bwd_weight (itts_defer_reductions applies, accumulate likewise; workspace size from the _sparse query);
  * dw's pad columns K..lddw-1 become zeros.  Deterministic, no float atomics: a light column's fmaf chain runs in
  * ascending m per row range, a heavy column's per wave share, the shares in wave order, the ranges in slab order.
  * What the kernel does not serve -- K or lddw > 512, lddz % 4 != 0, dz or d_cols not 16-byte aligned, d_plan or
  * d_cols NULL -- runs itts_linear_bwd_weight on d_x over lddw columns instead (decided on the host; then lddw == K,
- * or ldx >= lddw with x's pad columns zero).  itts_sparse_wgrad_counts: out = {itts_sparse_cols_build launches,
+ * or ldx >= lddw with x's pad columns zero).  itts_sparse_wgrad_counts: out = {column build launches (either entry),
  * calls that ran the sparse kernel, calls that ran the dense product}; process-wide, no device call. */
 int itts_sparse_cols_plan_ints(void);
 int itts_sparse_cols_layout(int64_t M, int K, int64_t out[3]);
 int itts_sparse_cols_build(const float* d_x, int64_t ldx, int64_t M, int K, const int* d_plan, void* d_cols,
                            void* stream);
+int itts_sparse_cols_build_from_rows(const void* d_lists, int64_t M, int K_lists, int K, const int* d_plan,
+                                     void* d_cols, void* stream);
 int64_t itts_linear_bwd_weight_sparse_workspace_bytes(int64_t M, int N, int K, int64_t lddw);
 int itts_linear_bwd_weight_sparse(const float* d_dz, int64_t lddz, const void* d_cols, const int* d_plan,
                                   const float* d_x, int64_t ldx, float* d_dw, int64_t lddw, float* d_db, int64_t M,
