@@ -47,6 +47,7 @@
 #include <stdint.h>
 
 #include "activations.h"
+#include "dropout.h"
 
 #ifndef RING_DBG
 #define RING_DBG 0   // lab only: 1 no DMA, 2 no step barrier, 4 no MFMA, 8 no epilogue, 16 no fragment reads,
@@ -457,10 +458,30 @@ __device__ __forceinline__ void fetch_epilogue_operands(const Args& g, const Til
   }
 }
 
-template <int EPI, int ACT>
+// DR: the dropout rule (dropout.h) of the EPI_BIAS_ACT / EPI_DACT epilogue, or NoDrop; one Philox call per float4
+// row segment, all eight ahead of the arithmetic.
+// The keep bits of a lane's eight float4 row segments of tile pc (segment s = 4 i + rg of the epilogue: bits 4 s ..
+// 4 s + 3), worked out before the epilogue and outside its dispatch over the activations: one Philox call at a time,
+// none of its temporaries alive under an activation's (together they go beyond a wave's 128 registers).
+template <class DR>
+__device__ __forceinline__ uint32_t tile_keep_bits(const Tile& pc, int wm, int wn, int lane, const DR& dr) {
+  uint32_t keep = 0;
+  if constexpr (DR::on) {
+    const int col = pc.n0 + wn * 32 + 4 * ((lane & 31) >> 2);
+    const int64_t row = (int64_t)pc.m0 + wm * 64 + 4 * (lane >> 5) + (lane & 3);
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      keep |= dr.keep_bits(row + (s >> 2) * 32 + 8 * (s & 3), col) << (4 * s);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  return keep;
+}
+
+template <int EPI, int ACT, class DR = NoDrop>
 __device__ __forceinline__ void epilogue(const Args& g, const Tile& pc, const f32x16& acc0, const f32x16& acc1,
                                          int wm, int wn, int lane, const float4& bv, double& lsum,
-                                         const EpiOperands<EPI>& eo) {
+                                         const EpiOperands<EPI>& eo, const DR& dr = DR(), uint32_t keep = 0) {
   const int quad = (lane & 31) >> 2, j = lane & 3, h = lane >> 5;
   const int col = pc.n0 + wn * 32 + 4 * quad;
   const int rloc = wm * 64 + 4 * h + j;          // + 32 i + 8 rg
@@ -503,8 +524,22 @@ __device__ __forceinline__ void epilogue(const Args& g, const Tile& pc, const f3
       if (EPI == EPI_BIAS_ACT) {
         v.x = act1<ACT>(v.x + bv.x); v.y = act1<ACT>(v.y + bv.y);
         v.z = act1<ACT>(v.z + bv.z); v.w = act1<ACT>(v.w + bv.w);
+        if constexpr (DR::on) {   // d = act(z) * m * scale
+          const uint32_t kb = keep >> (4 * (4 * i + rg));
+          v.x = dr.apply_bit(v.x, kb & 1u); v.y = dr.apply_bit(v.y, kb & 2u);
+          v.z = dr.apply_bit(v.z, kb & 4u); v.w = dr.apply_bit(v.w, kb & 8u);
+        }
       }
-      if constexpr (EPI == EPI_DACT) {
+      if constexpr (EPI == EPI_DACT && DR::on) {
+        // the previous layer's output d carries dropout: dx = v * m * scale * act'(y), y = d * (1 - p) where m = 1
+        const f32x4 d = eo.y[4 * i + rg];
+        const uint32_t kb = keep >> (4 * (4 * i + rg));
+        v.x = (kb & 1u) ? v.x * (dr.scale * dact1<ACT>(d[0] * dr.keep)) : 0.f;
+        v.y = (kb & 2u) ? v.y * (dr.scale * dact1<ACT>(d[1] * dr.keep)) : 0.f;
+        v.z = (kb & 4u) ? v.z * (dr.scale * dact1<ACT>(d[2] * dr.keep)) : 0.f;
+        v.w = (kb & 8u) ? v.w * (dr.scale * dact1<ACT>(d[3] * dr.keep)) : 0.f;
+      }
+      if constexpr (EPI == EPI_DACT && !DR::on) {
         const f32x4 y = eo.y[4 * i + rg];   // fetched at the tile's first K-step
         v.x *= dact1<ACT>(y[0]); v.y *= dact1<ACT>(y[1]);
         v.z *= dact1<ACT>(y[2]); v.w *= dact1<ACT>(y[3]);
@@ -540,8 +575,8 @@ __device__ __forceinline__ void epilogue(const Args& g, const Tile& pc, const f3
   }
 }
 
-template <bool A_ROW, bool B_ROW, int EPI, int BMT, int BNT, bool GROUPED = false, int AF = AF_BASE>
-__device__ __forceinline__ void compute_waves(const Args& g, char* lds, int wid, int lane) {
+template <bool A_ROW, bool B_ROW, int EPI, int BMT, int BNT, bool GROUPED = false, int AF = AF_BASE, class DR = NoDrop>
+__device__ __forceinline__ void compute_waves(const Args& g, char* lds, int wid, int lane, const DR& dr = DR()) {
   constexpr int WN = BNT / 32;
   constexpr int A_BYTES = BMT * 128;
   const int wm = wid / WN, wn = wid % WN;
@@ -590,17 +625,18 @@ __device__ __forceinline__ void compute_waves(const Args& g, char* lds, int wid,
         for (int r = 0; r < 16; ++r) t += acc0[r] + acc1[r];
         if (t == 1.2345f) g.C[0] = t;
       } else {
+        const uint32_t keep = tile_keep_bits(pc, wm, wn, lane, dr);
         float4 bv;
         if constexpr (EPI == EPI_MSE) bv = eo.bv;
         else bv = load_bias<EPI>(g, pc.n0, wn, lane);
         if (AF == AF_EXT && (EPI == EPI_BIAS_ACT || EPI == EPI_DACT)) {
           with_ext_act(g.act, [&](auto act) {
-            epilogue<EPI, decltype(act)::value>(g, pc, acc0, acc1, wm, wn, lane, bv, lsum, eo);
+            epilogue<EPI, decltype(act)::value, DR>(g, pc, acc0, acc1, wm, wn, lane, bv, lsum, eo, dr, keep);
           });
           // (EPI_MSE has no activation: one copy of its epilogue whatever g.act holds, not three identical ones)
-        } else if (EPI == EPI_STORE || EPI == EPI_MSE || g.act == ITTS_ACT_NONE) epilogue<EPI, ITTS_ACT_NONE>(g, pc, acc0, acc1, wm, wn, lane, bv, lsum, eo);
-        else if (g.act == ITTS_ACT_TANH) epilogue<EPI, ITTS_ACT_TANH>(g, pc, acc0, acc1, wm, wn, lane, bv, lsum, eo);
-        else epilogue<EPI, ITTS_ACT_RELU>(g, pc, acc0, acc1, wm, wn, lane, bv, lsum, eo);
+        } else if (EPI == EPI_STORE || EPI == EPI_MSE || g.act == ITTS_ACT_NONE) epilogue<EPI, ITTS_ACT_NONE, DR>(g, pc, acc0, acc1, wm, wn, lane, bv, lsum, eo, dr, keep);
+        else if (g.act == ITTS_ACT_TANH) epilogue<EPI, ITTS_ACT_TANH, DR>(g, pc, acc0, acc1, wm, wn, lane, bv, lsum, eo, dr, keep);
+        else epilogue<EPI, ITTS_ACT_RELU, DR>(g, pc, acc0, acc1, wm, wn, lane, bv, lsum, eo, dr, keep);
       }
       pending = false;
       // the operands of the epilogue of the tile that starts now, a whole K loop ahead of their use:
@@ -711,6 +747,22 @@ __global__ __launch_bounds__(THREADS, (2 * THREADS + 255) / 256) void gemm_ring_
   }
 }
 
+// The same with a dropout rule in the EPI_BIAS_ACT / EPI_DACT epilogue (plain tile order): kernels of their own, so
+// that the ones above keep their arguments and their code.
+template <bool A_ROW, bool B_ROW, int EPI, int WM, int AF = AF_BASE>
+__global__ __launch_bounds__(THREADS, (2 * THREADS + 255) / 256) void gemm_ring_drop_kernel(Args g, DropRule dr) {
+  constexpr int BMT = 64 * WM, BNT = 32 * (4 / WM);
+  __shared__ __attribute__((aligned(1024))) char lds[LDS_BYTES];
+  const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_char_p)lds;
+  const int lane = threadIdx.x & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (wid >= 4) {
+    loader_wave<A_ROW, B_ROW, BMT, BNT, false>(g, lds, lds0, lane, false, wid - 4);
+  } else {
+    compute_waves<A_ROW, B_ROW, EPI, BMT, BNT, false, AF, DropRule>(g, lds, wid, lane, dr);
+  }
+}
+
 // Two independent GEMMs in one launch (the weight-gradient and the input-gradient product of a
 // layer both start from dz): every persistent workgroup walks its tiles of the first problem, then
 // its tiles of the second.  One launch boundary less per layer (ramp, drain and the end-of-kernel
@@ -729,6 +781,24 @@ __global__ __launch_bounds__(THREADS, (2 * THREADS + 255) / 256) void gemm_ring_
   } else {
     compute_waves<A1, B1, E1, 64 * W1, 32 * (4 / W1)>(g1, lds, wid, lane);
     compute_waves<A2, B2, E2, 64 * W2, 32 * (4 / W2), false, AF2>(g2, lds, wid, lane);
+  }
+}
+
+// The pair of a layer whose input carries dropout: weight gradient (col x col, EPI_STORE) and input gradient (row x
+// col, EPI_DACT with the rule of the previous layer's output).
+template <int W1, int AF2 = AF_BASE>
+__global__ __launch_bounds__(THREADS, (2 * THREADS + 255) / 256) void gemm_ring_pair_drop_kernel(Args g1, Args g2,
+                                                                                               DropRule dr) {
+  __shared__ __attribute__((aligned(1024))) char lds[LDS_BYTES];
+  const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_char_p)lds;
+  const int lane = threadIdx.x & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (wid >= 4) {
+    loader_wave<false, false, 64 * W1, 32 * (4 / W1)>(g1, lds, lds0, lane, false, wid - 4);
+    loader_wave<true, false, 128, 64>(g2, lds, lds0, lane, false, wid - 4);
+  } else {
+    compute_waves<false, false, EPI_STORE, 64 * W1, 32 * (4 / W1)>(g1, lds, wid, lane);
+    compute_waves<true, false, EPI_DACT, 128, 64, false, AF2, DropRule>(g2, lds, wid, lane, dr);
   }
 }
 

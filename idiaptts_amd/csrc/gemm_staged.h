@@ -22,6 +22,7 @@
 
 #include "activations.h"
 #include "common.h"
+#include "dropout.h"
 
 namespace itts {
 
@@ -206,9 +207,11 @@ __device__ __forceinline__ StagedTile staged_gemm_tile(const GemmArgs& g, const 
 // in slab blockIdx.z; bias + activation of family AF (EPI_BIAS_ACT), times the activation
 // derivative through aux (EPI_DACT), or the plain sum (EPI_STORE).
 // C/D map of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5).
-template <int EPI, int TN, int AF, class RowOf>
+// DR: the dropout rule of the dense layers (dropout.h) on the output (EPI_BIAS_ACT) or on the previous layer's
+// output in aux (EPI_DACT); a lane holds one column here, so it takes one word of a Philox call per element.
+template <int EPI, int TN, int AF, class RowOf, class DR = NoDrop>
 __device__ __forceinline__ void staged_epilogue(const GemmArgs& g, const StagedTile& t, const f32x16 (&acc)[2][TN],
-                                                const RowOf& row_of) {
+                                                const RowOf& row_of, const DR& dr = DR()) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int wm = wid >> 1, wn = wid & 1;
   float* C = g.C + (int64_t)blockIdx.z * g.slab_stride;
@@ -221,6 +224,15 @@ __device__ __forceinline__ void staged_epilogue(const GemmArgs& g, const StagedT
       if (col >= g.N) continue;
       float bv = 0.f;
       if (EPI == EPI_BIAS_ACT && g.bias) bv = g.bias[col];
+      uint32_t keep = 0;   // bit r: element r of the block is kept (worked out ahead of the arithmetic: registers)
+      if constexpr (DR::on) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int64_t m = t.m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * rh;
+          if (m < g.M) keep |= ((dr.keep_bits(row_of(m), col) >> (col & 3)) & 1u) << r;
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int64_t m = t.m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * rh;
@@ -228,7 +240,14 @@ __device__ __forceinline__ void staged_epilogue(const GemmArgs& g, const StagedT
         const int64_t row = row_of(m);
         float v = acc[i][j][r];
         if (EPI == EPI_BIAS_ACT) v = act_fwd_af<AF>(v + bv, g.act);
-        if (EPI == EPI_DACT) v *= act_grad_af<AF>(g.aux[row * g.ldaux + col], g.act);
+        if constexpr (DR::on) {
+          const uint32_t bit = (keep >> r) & 1u;
+          if (EPI == EPI_BIAS_ACT) v = dr.apply_bit(v, bit);
+          if (EPI == EPI_DACT)
+            v = bit ? v * (dr.scale * act_grad_af<AF>(g.aux[row * g.ldaux + col] * dr.keep, g.act)) : 0.f;
+        } else {
+          if (EPI == EPI_DACT) v *= act_grad_af<AF>(g.aux[row * g.ldaux + col], g.act);
+        }
         C[row * g.ldc + col] = v;
       }
     }

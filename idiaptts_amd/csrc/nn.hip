@@ -82,9 +82,9 @@ struct DenseLoader {
 
 // TN = MFMA tiles per wave along N: output tile 128 x (64*TN). TN = 1 halves the tile so that
 // narrow outputs (N = 187) and awkward tile counts waste fewer workgroup slots.  AF: activation family.
-template <bool A_ROW, bool B_ROW, int EPI, bool VEC_A, bool VEC_B, int TN, int STAGES = 2, int AF = AF_BASE>
-__global__ __launch_bounds__(256, STAGES == 1 ? 4 : 2) void gemm_f32_kernel(GemmArgs g) {
-  __shared__ __attribute__((aligned(16))) float lds[staged_lds_floats<B_ROW, TN, STAGES>()];
+// DR: the dropout rule of the EPI_BIAS_ACT / EPI_DACT epilogue (dropout.h), or NoDrop.
+template <bool A_ROW, bool B_ROW, int EPI, bool VEC_A, bool VEC_B, int TN, int STAGES, int AF, class DR>
+__device__ __forceinline__ void gemm_f32_body(const GemmArgs& g, float* lds, const DR& dr) {
   f32x16 acc[2][TN];
   const StagedTile t =
       staged_gemm_tile<A_ROW, B_ROW, TN, STAGES>(g, DenseLoader<A_ROW, B_ROW, VEC_A, VEC_B>{g}, lds, acc);
@@ -168,18 +168,38 @@ __global__ __launch_bounds__(256, STAGES == 1 ? 4 : 2) void gemm_f32_kernel(Gemm
       float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
       const bool full = col + 3 < g.N;
       if (EPI == EPI_BIAS_ACT && g.bias && full) bv = *reinterpret_cast<const float4*>(g.bias + col);
+      uint32_t keep = 0;   // the keep bits of the lane's four float4, ahead of the arithmetic (registers)
+      if constexpr (DR::on) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          keep |= dr.keep_bits(m0 + wm * 64 + i * 32 + rq + 8 * q, col) << (4 * q);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int rl = rq + 8 * q;
         const int64_t row = m0 + wm * 64 + i * 32 + rl;
         float4 v = *reinterpret_cast<const float4*>(stage + rl * 36 + c4);
         if (row >= g.M || col >= g.N) continue;
+        const uint32_t kb = keep >> (4 * q);
         if (full) {
           if (EPI == EPI_BIAS_ACT) {
             v.x = act_fwd_af<AF>(v.x + bv.x, g.act); v.y = act_fwd_af<AF>(v.y + bv.y, g.act);
             v.z = act_fwd_af<AF>(v.z + bv.z, g.act); v.w = act_fwd_af<AF>(v.w + bv.w, g.act);
+            if constexpr (DR::on) {
+              v.x = dr.apply_bit(v.x, kb & 1u); v.y = dr.apply_bit(v.y, kb & 2u);
+              v.z = dr.apply_bit(v.z, kb & 4u); v.w = dr.apply_bit(v.w, kb & 8u);
+            }
           }
-          if (EPI == EPI_DACT) {
+          if constexpr (EPI == EPI_DACT && DR::on) {
+            const float4 a = *reinterpret_cast<const float4*>(g.aux + row * g.ldaux + col);
+            v.x = (kb & 1u) ? v.x * (dr.scale * act_grad_af<AF>(a.x * dr.keep, g.act)) : 0.f;
+            v.y = (kb & 2u) ? v.y * (dr.scale * act_grad_af<AF>(a.y * dr.keep, g.act)) : 0.f;
+            v.z = (kb & 4u) ? v.z * (dr.scale * act_grad_af<AF>(a.z * dr.keep, g.act)) : 0.f;
+            v.w = (kb & 8u) ? v.w * (dr.scale * act_grad_af<AF>(a.w * dr.keep, g.act)) : 0.f;
+          }
+          if (EPI == EPI_DACT && !DR::on) {
             const float4 a = *reinterpret_cast<const float4*>(g.aux + row * g.ldaux + col);
             v.x *= act_grad_af<AF>(a.x, g.act); v.y *= act_grad_af<AF>(a.y, g.act);
             v.z *= act_grad_af<AF>(a.z, g.act); v.w *= act_grad_af<AF>(a.w, g.act);
@@ -190,7 +210,15 @@ __global__ __launch_bounds__(256, STAGES == 1 ? 4 : 2) void gemm_f32_kernel(Gemm
           for (int e = 0; e < 4 && col + e < g.N; ++e) {
             float o = vv[e];
             if (EPI == EPI_BIAS_ACT) o = act_fwd_af<AF>(o + (g.bias ? g.bias[col + e] : 0.f), g.act);
-            if (EPI == EPI_DACT) o *= act_grad_af<AF>(g.aux[row * g.ldaux + col + e], g.act);
+            if constexpr (DR::on) {
+              if (EPI == EPI_BIAS_ACT) o = dr.apply_bit(o, (kb >> e) & 1u);
+              if (EPI == EPI_DACT)
+                o = ((kb >> e) & 1u)
+                        ? o * (dr.scale * act_grad_af<AF>(g.aux[row * g.ldaux + col + e] * dr.keep, g.act))
+                        : 0.f;
+            } else {
+              if (EPI == EPI_DACT) o *= act_grad_af<AF>(g.aux[row * g.ldaux + col + e], g.act);
+            }
             C[row * g.ldc + col + e] = o;
           }
         }
@@ -198,7 +226,21 @@ __global__ __launch_bounds__(256, STAGES == 1 ? 4 : 2) void gemm_f32_kernel(Gemm
     }
     return;
   }
-  staged_epilogue<EPI, TN, AF>(g, t, acc, [](int64_t m) { return m; });
+  staged_epilogue<EPI, TN, AF>(g, t, acc, [](int64_t m) { return m; }, dr);
+}
+
+template <bool A_ROW, bool B_ROW, int EPI, bool VEC_A, bool VEC_B, int TN, int STAGES = 2, int AF = AF_BASE>
+__global__ __launch_bounds__(256, STAGES == 1 ? 4 : 2) void gemm_f32_kernel(GemmArgs g) {
+  __shared__ __attribute__((aligned(16))) float lds[staged_lds_floats<B_ROW, TN, STAGES>()];
+  gemm_f32_body<A_ROW, B_ROW, EPI, VEC_A, VEC_B, TN, STAGES, AF>(g, lds, NoDrop{});
+}
+
+// The single-stage row-form kernel with a dropout rule in its epilogue: a kernel of its own, so that the one above
+// keeps its arguments and its code.
+template <bool B_ROW, int EPI, bool VEC_A, bool VEC_B, int AF>
+__global__ __launch_bounds__(256, 4) void gemm_f32_drop_kernel(GemmArgs g, DropRule dr) {
+  __shared__ __attribute__((aligned(16))) float lds[staged_lds_floats<B_ROW, 1, 1>()];
+  gemm_f32_body<true, B_ROW, EPI, VEC_A, VEC_B, 1, 1, AF>(g, lds, dr);
 }
 
 // Which kernel the dense-layer products of this process ran on, per epilogue kind (itts_gemm_path_counts): [0][epi] the
@@ -223,11 +265,11 @@ struct PlanScope {
 };
 
 static void plan_gemm(int kernel, bool a_row, bool b_row, int epi, int tn, int stages, int wm, bool va, bool vb,
-                      bool wide, bool grouped, int splitk, int af, int64_t tiles, int64_t grid) {
+                      bool wide, bool grouped, int splitk, int af, int64_t tiles, int64_t grid, bool drop = false) {
   if (t_plan.depth == 0) return;
   if (t_plan.n < kPlanMax) {
     const int32_t v[kPlanInts] = {kernel, a_row, b_row, epi, tn, stages, wm, va, vb, wide, grouped, splitk, af,
-                                  (int32_t)std::min<int64_t>(tiles, INT32_MAX), (int32_t)grid, 0};
+                                  (int32_t)std::min<int64_t>(tiles, INT32_MAX), (int32_t)grid, drop};
     std::copy(v, v + kPlanInts, t_plan.e[t_plan.n]);
   }
   ++t_plan.n;
@@ -242,15 +284,28 @@ static void plan_reduce(bool vec, bool merged, bool deferred, int S) {
   ++t_plan.n;
 }
 
-template <bool A_ROW, bool B_ROW, int EPI, int TN, int STAGES, int AF = AF_BASE>
-static int launch_gemm_tn(const GemmArgs& g, int splitk, hipStream_t s) {
+template <bool A_ROW, bool B_ROW, int EPI, int TN, int STAGES, int AF = AF_BASE, class DR = NoDrop>
+static int launch_gemm_tn(const GemmArgs& g, int splitk, hipStream_t s, const DR& dr = DR()) {
   g_gemm_path[1][EPI].fetch_add(1, std::memory_order_relaxed);
   const int64_t tiles = ((g.M + BM - 1) / BM) * ((g.N + 64 * TN - 1) / (64 * TN));
   dim3 grid((unsigned)tiles, 1, (unsigned)splitk);
   const bool va = g.vecA, vb = g.vecB;   // pitch and alignment allow 16-byte loads (see load_tile)
   // (the wide-store branch of gemm_f32_kernel: behind the EPI_MSE epilogue, single-stage 128 x 64 tiles only)
   plan_gemm(PLAN_STAGED, A_ROW, B_ROW, EPI, TN, STAGES, 0, va, vb, EPI != EPI_MSE && STAGES == 1 && TN == 1 && g.wide_out,
-            false, splitk, AF, tiles * splitk, tiles * splitk);
+            false, splitk, AF, tiles * splitk, tiles * splitk, DR::on);
+  if constexpr (DR::on) {
+    static_assert(A_ROW && TN == 1 && STAGES == 1, "the dropout epilogue exists on the single-stage row-form kernel");
+    if (va && vb)
+      hipLaunchKernelGGL((gemm_f32_drop_kernel<B_ROW, EPI, true, true, AF>), grid, dim3(256), 0, s, g, dr);
+    else if (va)
+      hipLaunchKernelGGL((gemm_f32_drop_kernel<B_ROW, EPI, true, false, AF>), grid, dim3(256), 0, s, g, dr);
+    else if (vb)
+      hipLaunchKernelGGL((gemm_f32_drop_kernel<B_ROW, EPI, false, true, AF>), grid, dim3(256), 0, s, g, dr);
+    else
+      hipLaunchKernelGGL((gemm_f32_drop_kernel<B_ROW, EPI, false, false, AF>), grid, dim3(256), 0, s, g, dr);
+    ITTS_LAUNCH_CHECK();
+    return ITTS_OK;
+  }
   if (va && vb)
     hipLaunchKernelGGL((gemm_f32_kernel<A_ROW, B_ROW, EPI, true, true, TN, STAGES, AF>), grid, dim3(256), 0, s, g);
   else if (va)
@@ -318,8 +373,8 @@ static ring::Args ring_args(const GemmArgs& g, int splitk) {
   return r;
 }
 
-template <bool A_ROW, bool B_ROW, int EPI, int WM, int AF = AF_BASE>
-static int launch_ring_wm(const GemmArgs& g, int splitk, hipStream_t s) {
+template <bool A_ROW, bool B_ROW, int EPI, int WM, int AF = AF_BASE, class DR = NoDrop>
+static int launch_ring_wm(const GemmArgs& g, int splitk, hipStream_t s, const DR& dr = DR()) {
   constexpr int BNT = 32 * (4 / WM);
   g_gemm_path[0][EPI].fetch_add(1, std::memory_order_relaxed);
   ring::Args r = ring_args<WM>(g, splitk);
@@ -327,8 +382,16 @@ static int launch_ring_wm(const GemmArgs& g, int splitk, hipStream_t s) {
   const int64_t ntiles = (int64_t)r.tiles_m * r.tiles_n * splitk;
   ITTS_REQUIRE(ntiles < ((int64_t)1 << 31), "too many tiles");
   const int grid = (int)std::min<int64_t>(kRingGrid, (ntiles + 7) / 8 * 8);
-  const bool grouped = A_ROW && B_ROW && EPI == ring::EPI_BIAS_ACT && r.gn < r.tiles_n;
-  plan_gemm(PLAN_RING, A_ROW, B_ROW, EPI, 0, 0, WM, true, true, false, grouped, splitk, AF, ntiles, grid);
+  // (the dropout kernels walk the plain order: the products that gain from groups, the recurrent layers' input
+  // projections, carry no dropout of this kind)
+  const bool grouped = !DR::on && A_ROW && B_ROW && EPI == ring::EPI_BIAS_ACT && r.gn < r.tiles_n;
+  plan_gemm(PLAN_RING, A_ROW, B_ROW, EPI, 0, 0, WM, true, true, false, grouped, splitk, AF, ntiles, grid, DR::on);
+  if constexpr (DR::on) {
+    hipLaunchKernelGGL((ring::gemm_ring_drop_kernel<A_ROW, B_ROW, EPI, WM, AF>), dim3(grid), dim3(ring::THREADS), 0, s, r,
+                       dr);
+    ITTS_LAUNCH_CHECK();
+    return ITTS_OK;
+  }
   if (grouped)
     hipLaunchKernelGGL((ring::gemm_ring_kernel<A_ROW, B_ROW, EPI, WM, A_ROW && B_ROW && EPI == ring::EPI_BIAS_ACT, AF>),
                        dim3(grid), dim3(ring::THREADS), 0, s, r);
@@ -356,33 +419,41 @@ static int ring_wm(int64_t M, int N) {
   return w1 < w2 ? 1 : 2;
 }
 
-template <bool A_ROW, bool B_ROW, int EPI, int AF>
-static int launch_ring(const GemmArgs& g, int splitk, hipStream_t s) {
-  if (ring_wm(g.M, g.N) == 1) return launch_ring_wm<A_ROW, B_ROW, EPI, 1, AF>(g, splitk, s);
-  return launch_ring_wm<A_ROW, B_ROW, EPI, 2, AF>(g, splitk, s);
+template <bool A_ROW, bool B_ROW, int EPI, int AF, class DR = NoDrop>
+static int launch_ring(const GemmArgs& g, int splitk, hipStream_t s, const DR& dr = DR()) {
+  if (ring_wm(g.M, g.N) == 1) return launch_ring_wm<A_ROW, B_ROW, EPI, 1, AF, DR>(g, splitk, s, dr);
+  return launch_ring_wm<A_ROW, B_ROW, EPI, 2, AF, DR>(g, splitk, s, dr);
 }
 
 // weight-gradient GEMM (col x col, split-K slabs) and input-gradient GEMM (row x col, activation
 // derivative in the epilogue) of one layer in ONE launch
-template <int WM_W, int EPI_X, int AF_X = AF_BASE>
-static int launch_ring_bwd_pair(const GemmArgs& gw, int splitk, const GemmArgs& gx, hipStream_t s) {
+template <int WM_W, int EPI_X, int AF_X = AF_BASE, class DR = NoDrop>
+static int launch_ring_bwd_pair(const GemmArgs& gw, int splitk, const GemmArgs& gx, hipStream_t s, const DR& dr = DR()) {
   g_gemm_path[0][EPI_STORE].fetch_add(1, std::memory_order_relaxed);
   g_gemm_path[0][EPI_X].fetch_add(1, std::memory_order_relaxed);
   const ring::Args rw = ring_args<WM_W>(gw, splitk), rx = ring_args<2>(gx, 1);
   plan_gemm(PLAN_RING_PAIR, false, false, EPI_STORE, 0, 0, WM_W, true, true, false, false, splitk, AF_BASE,
             (int64_t)rw.tiles_m * rw.tiles_n * splitk, kRingGrid);
   plan_gemm(PLAN_RING_PAIR, true, false, EPI_X, 0, 0, 2, true, true, false, false, 1, AF_X,
-            (int64_t)rx.tiles_m * rx.tiles_n, kRingGrid);
+            (int64_t)rx.tiles_m * rx.tiles_n, kRingGrid, DR::on);
+  if constexpr (DR::on) {
+    static_assert(EPI_X == EPI_DACT, "the dropout pair is the one with the activation derivative");
+    hipLaunchKernelGGL((ring::gemm_ring_pair_drop_kernel<WM_W, AF_X>), dim3(kRingGrid), dim3(ring::THREADS), 0, s, rw, rx,
+                       dr);
+    ITTS_LAUNCH_CHECK();
+    return ITTS_OK;
+  }
   hipLaunchKernelGGL((ring::gemm_ring_pair_kernel<false, false, EPI_STORE, WM_W, true, false, EPI_X, 2, AF_X>),
                      dim3(kRingGrid), dim3(ring::THREADS), 0, s, rw, rx);
   ITTS_LAUNCH_CHECK();
   return ITTS_OK;
 }
 
-template <bool A_ROW, bool B_ROW, int EPI, int AF = AF_BASE>
-static int launch_gemm(GemmArgs g, int splitk, hipStream_t s) {
+template <bool A_ROW, bool B_ROW, int EPI, int AF = AF_BASE, class DR = NoDrop>
+static int launch_gemm(GemmArgs g, int splitk, hipStream_t s, const DR& dr = DR()) {
   if (g.M <= 0 || g.N <= 0) return ITTS_OK;
-  if (ring_ok<A_ROW, B_ROW>(g, splitk, EPI)) return launch_ring<A_ROW, B_ROW, EPI, AF>(g, splitk, s);
+  if (ring_ok<A_ROW, B_ROW>(g, splitk, EPI)) return launch_ring<A_ROW, B_ROW, EPI, AF, DR>(g, splitk, s, dr);
+  if constexpr (DR::on) return launch_gemm_tn<A_ROW, B_ROW, EPI, 1, 1, AF, DR>(g, splitk, s, dr);
   if (A_ROW) return launch_gemm_tn<A_ROW, B_ROW, EPI, 1, 1, AF>(g, splitk, s);
   const double e2 = tile_efficiency(g.M, g.N, splitk, 2, 1.0);
   const double e1 = tile_efficiency(g.M, g.N, splitk, 1, 0.90);
@@ -1090,6 +1161,200 @@ extern "C" int itts_linear_bwd(const float* d_dz, int64_t lddz, const float* d_x
   rc = launch_reduce_slabs(slabs, S_eff, merged ? n + N : n, d_dw, accumulate, s, merged);
   if (rc || merged || !d_db) return rc;
   return launch_reduce_slabs(slabs + (int64_t)S_eff * n, S_eff, (int64_t)N, d_db, accumulate, s);
+}
+
+// ---- dropout fused into the dense products (the rule: dropout.h) ---------------------------------
+// Each entry point is its plain counterpart with p == 0 (the same launches), and otherwise the same product with the
+// rule in the epilogue: on the output of the forward, on the previous layer's output in the input gradient.
+extern "C" int itts_linear_fwd_dropout(const float* d_x, int64_t ldx, const float* d_w, const float* d_b, float* d_y,
+                                       int64_t ldy, int64_t M, int N, int K, int act, double p, uint64_t seed,
+                                       uint32_t salt, int64_t row_offset, void* stream) {
+  ITTS_REQUIRE_DROP_P(p);
+  if (p == 0.0) return itts_linear_fwd(d_x, ldx, d_w, d_b, d_y, ldy, M, N, K, act, stream);
+  const PlanScope plan_scope;
+  ITTS_REQUIRE(d_w && (M == 0 || (d_x && d_y)), "null pointer");
+  ITTS_REQUIRE(M >= 0 && N > 0 && K > 0 && ldx >= K && ldy >= N, "bad sizes");
+  ITTS_REQUIRE(act >= ITTS_ACT_NONE && act <= ITTS_ACT_HARDSIGMOID, "unknown activation");
+  if (M == 0) return ITTS_OK;
+  GemmArgs g{};
+  g.A = d_x; g.lda = ldx; g.B = d_w; g.ldb = K; g.C = d_y; g.ldc = ldy;
+  g.M = M; g.N = N; g.K = K; g.bias = d_b; g.act = act;
+  g.kchunk = ((K + BK - 1) / BK) * BK; g.slab_stride = 0;
+  g.vecA = (ldx % 4 == 0) && aligned16(d_x);
+  g.vecB = (K % 4 == 0) && aligned16(d_w);
+  g.wide_out = (ldy % 4 == 0) && aligned16(d_y) && (!d_b || aligned16(d_b));
+  const DropRule dr = make_drop_rule(p, seed, salt, row_offset);
+  if (act_family(act) == AF_EXT)
+    return launch_gemm<true, true, EPI_BIAS_ACT, AF_EXT, DropRule>(g, 1, as_stream(stream), dr);
+  return launch_gemm<true, true, EPI_BIAS_ACT, AF_BASE, DropRule>(g, 1, as_stream(stream), dr);
+}
+
+extern "C" int itts_linear_bwd_input_dropout(const float* d_dz, int64_t lddz, const float* d_w, float* d_dx,
+                                             int64_t lddx, const float* d_yprev, int64_t ldyp, int act_prev, int64_t M,
+                                             int N, int K, double p, uint64_t seed, uint32_t salt, int64_t row_offset,
+                                             void* stream) {
+  ITTS_REQUIRE_DROP_P(p);
+  if (p == 0.0) return itts_linear_bwd_input(d_dz, lddz, d_w, d_dx, lddx, d_yprev, ldyp, act_prev, M, N, K, stream);
+  const PlanScope plan_scope;
+  ITTS_REQUIRE(d_w && (M == 0 || (d_dz && d_dx)), "null pointer");
+  ITTS_REQUIRE(d_yprev, "the previous layer's output is needed where it carries dropout");
+  ITTS_REQUIRE(M >= 0 && N > 0 && K > 0 && lddz >= N && lddx >= K && ldyp >= K, "bad sizes");
+  ITTS_REQUIRE(act_prev >= ITTS_ACT_NONE && act_prev <= ITTS_ACT_HARDSIGMOID, "unknown activation");
+  if (M == 0) return ITTS_OK;
+  GemmArgs g{};
+  g.A = d_dz; g.lda = lddz; g.B = d_w; g.ldb = K; g.C = d_dx; g.ldc = lddx;
+  g.M = M; g.N = K; g.K = N; g.aux = d_yprev; g.ldaux = ldyp; g.act = act_prev;
+  g.kchunk = ((N + BK - 1) / BK) * BK; g.slab_stride = 0;
+  g.vecA = (lddz % 4 == 0) && aligned16(d_dz);
+  g.vecB = (K % 4 == 0) && aligned16(d_w);
+  g.wide_out = (lddx % 4 == 0) && aligned16(d_dx) && (ldyp % 4 == 0) && aligned16(d_yprev);
+  const DropRule dr = make_drop_rule(p, seed, salt, row_offset);
+  if (act_family(act_prev) == AF_EXT)
+    return launch_gemm<true, false, EPI_DACT, AF_EXT, DropRule>(g, 1, as_stream(stream), dr);
+  return launch_gemm<true, false, EPI_DACT, AF_BASE, DropRule>(g, 1, as_stream(stream), dr);
+}
+
+// dw / db as itts_linear_bwd_weight (their operands dz and x are already the dropped values), dx as
+// itts_linear_bwd_input_dropout; one launch for both where itts_linear_bwd has one, with the same tiles and chunks.
+extern "C" int itts_linear_bwd_dropout(const float* d_dz, int64_t lddz, const float* d_x, int64_t ldx, const float* d_w,
+                                       float* d_dw, float* d_db, float* d_dx, int64_t lddx, const float* d_yprev,
+                                       int64_t ldyp, int act_prev, int64_t M, int N, int K, void* d_workspace,
+                                       int accumulate, double p, uint64_t seed, uint32_t salt, int64_t row_offset,
+                                       void* stream) {
+  ITTS_REQUIRE_DROP_P(p);
+  if (p == 0.0)
+    return itts_linear_bwd(d_dz, lddz, d_x, ldx, d_w, d_dw, d_db, d_dx, lddx, d_yprev, ldyp, act_prev, M, N, K,
+                           d_workspace, accumulate, stream);
+  const PlanScope plan_scope;
+  ITTS_REQUIRE(d_w && d_dw && d_workspace && (M == 0 || (d_dz && d_x && d_dx)), "null pointer");
+  ITTS_REQUIRE(d_yprev, "the previous layer's output is needed where it carries dropout");
+  ITTS_REQUIRE(M >= 0 && N > 0 && K > 0 && lddz >= N && ldx >= K && lddx >= K && ldyp >= K, "bad sizes");
+  ITTS_REQUIRE(act_prev >= ITTS_ACT_NONE && act_prev <= ITTS_ACT_HARDSIGMOID, "unknown activation");
+  hipStream_t s = as_stream(stream);
+  const bool vec_ok = (lddz % 4 == 0) && aligned16(d_dz) && (ldx % 4 == 0) && aligned16(d_x) && (K % 4 == 0) &&
+                      aligned16(d_w);
+  const int64_t n = (int64_t)N * K;
+  const bool merged = d_db && d_db == d_dw + n && N % 4 == 0 && n % 4 == 0;
+  bool fused = vec_ok && M > 0 && (lddx % 4 == 0) && aligned16(d_dx) && (ldyp % 4 == 0) && aligned16(d_yprev);
+  GemmArgs gw{}, gx{};
+  int S_eff = 1;
+  if (fused) {   // the operands of itts_linear_bwd's pair, item for item
+    const int S = choose_splitk_ring(M, N, K);
+    int64_t kchunk = (M + S - 1) / S;
+    kchunk = ((kchunk + BK - 1) / BK) * BK;
+    S_eff = (int)((M + kchunk - 1) / kchunk);
+    float* slabs = reinterpret_cast<float*>(d_workspace);
+    gw.A = d_dz; gw.lda = lddz; gw.B = d_x; gw.ldb = ldx; gw.C = slabs; gw.ldc = K;
+    gw.M = N; gw.N = K; gw.K = M; gw.kchunk = kchunk; gw.vecA = gw.vecB = 1;
+    const int64_t stride = merged ? n + N : n;
+    gw.slab_stride = stride;
+    if (merged) { gw.bias_part = slabs + n; gw.bias_part_stride = stride; }
+    else if (d_db) { gw.bias_part = slabs + (int64_t)S_eff * n; gw.bias_part_stride = N; }
+    gx.A = d_dz; gx.lda = lddz; gx.B = d_w; gx.ldb = K; gx.C = d_dx; gx.ldc = lddx;
+    gx.M = M; gx.N = K; gx.K = N; gx.aux = d_yprev; gx.ldaux = ldyp; gx.act = act_prev;
+    gx.kchunk = ((N + BK - 1) / BK) * BK; gx.vecA = gx.vecB = 1;
+    fused = ring_ok<false, false>(gw, S_eff, EPI_STORE) && ring_ok<true, false>(gx, 1, EPI_DACT);
+  }
+  if (!fused) {
+    int rc = itts_linear_bwd_weight(d_dz, lddz, d_x, ldx, d_dw, d_db, M, N, K, d_workspace, accumulate, stream);
+    if (rc) return rc;
+    return itts_linear_bwd_input_dropout(d_dz, lddz, d_w, d_dx, lddx, d_yprev, ldyp, act_prev, M, N, K, p, seed, salt,
+                                         row_offset, stream);
+  }
+  const DropRule dr = make_drop_rule(p, seed, salt, row_offset);
+  int rc;
+  const int wm = ring_wm(gw.M, gw.N);
+  if (act_family(act_prev) == AF_EXT)
+    rc = wm == 1 ? launch_ring_bwd_pair<1, EPI_DACT, AF_EXT, DropRule>(gw, S_eff, gx, s, dr)
+                 : launch_ring_bwd_pair<2, EPI_DACT, AF_EXT, DropRule>(gw, S_eff, gx, s, dr);
+  else
+    rc = wm == 1 ? launch_ring_bwd_pair<1, EPI_DACT, AF_BASE, DropRule>(gw, S_eff, gx, s, dr)
+                 : launch_ring_bwd_pair<2, EPI_DACT, AF_BASE, DropRule>(gw, S_eff, gx, s, dr);
+  if (rc) return rc;
+  float* slabs = reinterpret_cast<float*>(d_workspace);
+  rc = launch_reduce_slabs(slabs, S_eff, merged ? n + N : n, d_dw, accumulate, s, merged);
+  if (rc || merged || !d_db) return rc;
+  return launch_reduce_slabs(slabs + (int64_t)S_eff * n, S_eff, (int64_t)N, d_db, accumulate, s);
+}
+
+// ---- elementwise dropout: out = in * m * scale (forward and backward alike), or the mask itself ----
+// A thread takes four consecutive columns of a row: one Philox call.  Rows may have a pitch; in-place is allowed.
+__global__ __launch_bounds__(256) void dropout_apply_kernel(const float* in, int64_t ldi, float* out,
+                                                            int64_t ldo, uint8_t* mask, int64_t ldm, int64_t M, int N,
+                                                            DropRule dr) {
+  const int n4 = (N + 3) >> 2;
+  const int64_t total = M * n4;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t row = i / n4;
+    const int col = (int)(i - row * n4) << 2;
+    const uint4x w = dr.words(row, col);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (col + e >= N) break;
+      if (mask) mask[row * ldm + col + e] = dr.keeps(w.w[e]) ? 1 : 0;
+      else out[row * ldo + col + e] = dr.apply(in[row * ldi + col + e], w.w[e]);
+    }
+  }
+}
+
+extern "C" int itts_dropout_apply(const float* d_in, int64_t ldi, void* d_out, int64_t ldo, int64_t M, int N,
+                                  int mask_only, double p, uint64_t seed, uint32_t salt, int64_t row_offset,
+                                  void* stream) {
+  ITTS_REQUIRE_DROP_P(p);
+  ITTS_REQUIRE(M >= 0 && N > 0 && ldo >= N && (mask_only || ldi >= N), "bad sizes");
+  ITTS_REQUIRE(M == 0 || (d_out && (mask_only || d_in)), "null pointer");
+  if (M == 0) return ITTS_OK;
+  const int64_t total = M * (int64_t)((N + 3) / 4);
+  const int blocks = (int)std::min<int64_t>((total + 255) / 256, 4096);
+  const DropRule dr = make_drop_rule(p, seed, salt, row_offset);
+  hipLaunchKernelGGL(dropout_apply_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), d_in, ldi,
+                     mask_only ? nullptr : static_cast<float*>(d_out), ldo,
+                     mask_only ? static_cast<uint8_t*>(d_out) : nullptr, ldo, M, N, dr);
+  ITTS_LAUNCH_CHECK();
+  return ITTS_OK;
+}
+
+// dz = dy * m * scale * act'(y), y = d * (1 - p): the way back through the dropout and the activation of a layer whose
+// dropped output d nothing multiplies after it (the last layer of a chain).  dz may be dy.
+template <int AF>
+__global__ __launch_bounds__(256) void dropout_act_bwd_kernel(const float* dy, int64_t lddy, const float* __restrict__ d,
+                                                              int64_t ldd, float* dz, int64_t lddz, int64_t M, int N,
+                                                              int act, DropRule dr) {
+  const int n4 = (N + 3) >> 2;
+  const int64_t total = M * n4;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t row = i / n4;
+    const int col = (int)(i - row * n4) << 2;
+    const uint4x w = dr.words(row, col);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (col + e >= N) break;
+      const float g = dy[row * lddy + col + e];
+      dz[row * lddz + col + e] =
+          dr.keeps(w.w[e]) ? g * (dr.scale * act_grad_af<AF>(d[row * ldd + col + e] * dr.keep, act)) : 0.f;
+    }
+  }
+}
+
+extern "C" int itts_dropout_act_bwd(const float* d_dy, int64_t lddy, const float* d_d, int64_t ldd, float* d_dz,
+                                    int64_t lddz, int64_t M, int N, int act, double p, uint64_t seed, uint32_t salt,
+                                    int64_t row_offset, void* stream) {
+  ITTS_REQUIRE_DROP_P(p);
+  ITTS_REQUIRE(M >= 0 && N > 0 && lddy >= N && ldd >= N && lddz >= N, "bad sizes");
+  ITTS_REQUIRE(M == 0 || (d_dy && d_d && d_dz), "null pointer");
+  ITTS_REQUIRE(act >= ITTS_ACT_NONE && act <= ITTS_ACT_HARDSIGMOID, "unknown activation");
+  if (M == 0) return ITTS_OK;
+  const int64_t total = M * (int64_t)((N + 3) / 4);
+  const int blocks = (int)std::min<int64_t>((total + 255) / 256, 4096);
+  const DropRule dr = make_drop_rule(p, seed, salt, row_offset);
+  if (act_family(act) == AF_EXT)
+    hipLaunchKernelGGL(dropout_act_bwd_kernel<AF_EXT>, dim3(blocks), dim3(256), 0, as_stream(stream), d_dy, lddy, d_d,
+                       ldd, d_dz, lddz, M, N, act, dr);
+  else
+    hipLaunchKernelGGL(dropout_act_bwd_kernel<AF_BASE>, dim3(blocks), dim3(256), 0, as_stream(stream), d_dy, lddy, d_d,
+                       ldd, d_dz, lddz, M, N, act, dr);
+  ITTS_LAUNCH_CHECK();
+  return ITTS_OK;
 }
 
 static int mse_blocks(int64_t M, int D) {

@@ -15,6 +15,7 @@
 
 #include "activations.h"
 #include "common.h"
+#include "dropout.h"
 
 namespace itts {
 
@@ -112,11 +113,13 @@ __device__ __forceinline__ void walk_trip(const float4* slab4, int i16, int2 e, 
 // counts of the next four rows are requested before the current rows are walked.  One fmaf chain per output, in
 // ascending k, from +0; the bias is added last.
 // (A list entry with k > K would read LDS out of range, which returns zeros; the lists come from the build.)
-template <int AF>
+// DR: the dropout rule of the dense layers on the output (dropout.h: a lane's four columns are one Philox call), or
+// NoDrop, which carries nothing.
+template <int AF, class DR = NoDrop>
 __global__ __launch_bounds__(kFwdWaves * 64) void sparse_linear_fwd_kernel(
     const int* __restrict__ counts, const int2* __restrict__ entries, int64_t pitch, const float* __restrict__ w,
     const float* __restrict__ bias, float* __restrict__ y, int64_t ldy, int64_t M, int N, int K, int act, int ranges,
-    int store_cols, int wide_out, int wide_w) {
+    int store_cols, int wide_out, int wide_w, DR dr) {
   extern __shared__ float4 slab4[];   // [K + 1][16] float4
   float* slab = reinterpret_cast<float*>(slab4);
   const int lane = threadIdx.x & 63;
@@ -200,6 +203,11 @@ __global__ __launch_bounds__(kFwdWaves * 64) void sparse_linear_fwd_kernel(
       o.y = n + 1 < N ? act_fwd_af<AF>(acc.y + bv.y, act) : 0.f;
       o.z = n + 2 < N ? act_fwd_af<AF>(acc.z + bv.z, act) : 0.f;
       o.w = n + 3 < N ? act_fwd_af<AF>(acc.w + bv.w, act) : 0.f;
+      if constexpr (DR::on) {
+        const uint4x dw = dr.words(m, n);
+        o.x = dr.apply(o.x, dw.w[0]); o.y = dr.apply(o.y, dw.w[1]);
+        o.z = dr.apply(o.z, dw.w[2]); o.w = dr.apply(o.w, dw.w[3]);
+      }
       float* yr = y + m * ldy + n;
       if (vec_store) {
         *reinterpret_cast<float4*>(yr) = o;
@@ -256,10 +264,10 @@ static int fwd_compute_units() {
   return cus;
 }
 
-template <int AF>
+template <int AF, class DR = NoDrop>
 static int launch_sparse_fwd(const void* d_lists, const float* d_w, const float* d_b, float* d_y, int64_t ldy, int64_t M,
-                             int N, int K, int act, hipStream_t s) {
-  ITTS_HIP_CHECK(itts::allow_dynamic_lds((const void*)sparse_linear_fwd_kernel<AF>, (kSparseMaxK + 1) * kSlabCols * 4));
+                             int N, int K, int act, hipStream_t s, const DR& dr = DR()) {
+  ITTS_HIP_CHECK(itts::allow_dynamic_lds((const void*)sparse_linear_fwd_kernel<AF, DR>, (kSparseMaxK + 1) * kSlabCols * 4));
   const ListLayout l = list_layout(M, K);
   const char* base = static_cast<const char*>(d_lists);
   const int slabs = (N + kSlabCols - 1) / kSlabCols;
@@ -268,10 +276,10 @@ static int launch_sparse_fwd(const void* d_lists, const float* d_w, const float*
   // the pad columns inside a 16-byte row pitch are written as zeros, as the dense epilogue does
   const bool wide_out = (ldy % 4 == 0) && aligned16(d_y);
   const int store_cols = wide_out ? (int)std::min<int64_t>((N + 3) / 4 * 4, ldy) : N;
-  hipLaunchKernelGGL(sparse_linear_fwd_kernel<AF>, dim3((unsigned)(slabs * ranges)), dim3(kFwdWaves * 64),
+  hipLaunchKernelGGL((sparse_linear_fwd_kernel<AF, DR>), dim3((unsigned)(slabs * ranges)), dim3(kFwdWaves * 64),
                      (size_t)(K + 1) * kSlabCols * 4, s, reinterpret_cast<const int*>(base + l.counts_off),
                      reinterpret_cast<const int2*>(base + l.entries_off), l.pitch, d_w, d_b, d_y, ldy, M, N, K, act,
-                     (int)ranges, store_cols, wide_out ? 1 : 0, (K % 4 == 0 && aligned16(d_w)) ? 1 : 0);
+                     (int)ranges, store_cols, wide_out ? 1 : 0, (K % 4 == 0 && aligned16(d_w)) ? 1 : 0, dr);
   ITTS_LAUNCH_CHECK();
   return ITTS_OK;
 }
@@ -290,6 +298,28 @@ extern "C" int itts_linear_fwd_sparse(const void* d_lists, const float* d_x, int
   g_sparse_path[1].fetch_add(1, std::memory_order_relaxed);
   if (act_family(act) == AF_EXT) return launch_sparse_fwd<AF_EXT>(d_lists, d_w, d_b, d_y, ldy, M, N, K, act, as_stream(stream));
   return launch_sparse_fwd<AF_BASE>(d_lists, d_w, d_b, d_y, ldy, M, N, K, act, as_stream(stream));
+}
+
+// itts_linear_fwd_sparse with the dropout rule of the dense layers on the output; p == 0 is the plain call.
+extern "C" int itts_linear_fwd_sparse_dropout(const void* d_lists, const float* d_x, int64_t ldx, const float* d_w,
+                                              const float* d_b, float* d_y, int64_t ldy, int64_t M, int N, int K,
+                                              int act, double p, uint64_t seed, uint32_t salt, int64_t row_offset,
+                                              void* stream) {
+  ITTS_REQUIRE_DROP_P(p);
+  if (p == 0.0) return itts_linear_fwd_sparse(d_lists, d_x, ldx, d_w, d_b, d_y, ldy, M, N, K, act, stream);
+  ITTS_REQUIRE(d_w && (M == 0 || (d_lists && d_x && d_y)), "null pointer");
+  ITTS_REQUIRE(M >= 0 && N > 0 && K > 0 && K <= 65535 && ldx >= K && ldy >= N, "bad sizes");
+  ITTS_REQUIRE(act >= ITTS_ACT_NONE && act <= ITTS_ACT_HARDSIGMOID, "unknown activation");
+  if (M == 0) return ITTS_OK;
+  if (K > kSparseMaxK) {   // the slab does not fit: the dense product, decided from the shape alone
+    g_sparse_path[2].fetch_add(1, std::memory_order_relaxed);
+    return itts_linear_fwd_dropout(d_x, ldx, d_w, d_b, d_y, ldy, M, N, K, act, p, seed, salt, row_offset, stream);
+  }
+  g_sparse_path[1].fetch_add(1, std::memory_order_relaxed);
+  const DropRule dr = make_drop_rule(p, seed, salt, row_offset);
+  if (act_family(act) == AF_EXT)
+    return launch_sparse_fwd<AF_EXT, DropRule>(d_lists, d_w, d_b, d_y, ldy, M, N, K, act, as_stream(stream), dr);
+  return launch_sparse_fwd<AF_BASE, DropRule>(d_lists, d_w, d_b, d_y, ldy, M, N, K, act, as_stream(stream), dr);
 }
 
 extern "C" int itts_sparse_path_counts(int64_t out[3]) {

@@ -5,7 +5,7 @@ raises.  (cffi is not available in the target image, hence ctypes.)
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_uint8, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_uint8, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "_lib", "libidiaptts_amd.so")
@@ -126,6 +126,18 @@ _SIGNATURES = {
                                        _P, c_int, _P]),
     "itts_linear_bwd": (c_int, [_P, c_int64, _P, c_int64, _P, _P, _P, _P, c_int64, _P, c_int64, c_int,
                                 c_int64, c_int, c_int, _P, c_int, _P]),
+    "itts_dropout_apply": (c_int, [_P, c_int64, _P, c_int64, c_int64, c_int, c_int, c_double, c_uint64, c_uint32,
+                                   c_int64, _P]),
+    "itts_dropout_act_bwd": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, c_int64, c_int, c_int, c_double, c_uint64,
+                                     c_uint32, c_int64, _P]),
+    "itts_linear_fwd_dropout": (c_int, [_P, c_int64, _P, _P, _P, c_int64, c_int64, c_int, c_int, c_int, c_double,
+                                        c_uint64, c_uint32, c_int64, _P]),
+    "itts_linear_bwd_input_dropout": (c_int, [_P, c_int64, _P, _P, c_int64, _P, c_int64, c_int, c_int64, c_int, c_int,
+                                              c_double, c_uint64, c_uint32, c_int64, _P]),
+    "itts_linear_bwd_dropout": (c_int, [_P, c_int64, _P, c_int64, _P, _P, _P, _P, c_int64, _P, c_int64, c_int,
+                                        c_int64, c_int, c_int, _P, c_int, c_double, c_uint64, c_uint32, c_int64, _P]),
+    "itts_linear_fwd_sparse_dropout": (c_int, [_P, _P, c_int64, _P, _P, _P, c_int64, c_int64, c_int, c_int, c_int,
+                                               c_double, c_uint64, c_uint32, c_int64, _P]),
     "itts_conv1d_fwd": (c_int, [_P, c_int64, _P, _P, _P, c_int64, c_int, c_int, c_int, c_int, c_int,
                                 c_int, c_int, c_int, c_int, _P]),
     "itts_conv1d_bwd_input": (c_int, [_P, c_int64, _P, _P, c_int64, _P, c_int64, c_int, c_int, c_int,

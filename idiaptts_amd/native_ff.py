@@ -55,13 +55,22 @@ class FlatFFModel:
 
     cols_from_lists: the column data of a step are made from the row lists that the step's sparse forward built from
     the same input (the same block as from the input itself, without a second pass over it); False restores the
-    build from the input."""
+    build from the input.
+
+    dropouts: one probability in [0, 1) per layer (default: none) of the dropout behind the layer's activation, as
+    `LayerConfig(dropout=...)` puts an nn.Dropout behind every layer of a Linear group.  A training step applies it
+    in the epilogues of the products (csrc/dropout.h: the mask of an element follows from the step's seed, the layer
+    and the element's position, so the backward recomputes it and none is stored); forward() without training=True,
+    the validation and inference forward, is the model without dropout."""
 
     cols_from_lists = True
 
     def __init__(self, dims=(425, 512, 512, 187), acts=("tanh", "tanh", None), device="cuda",
-                 seed=0, state_dict=None, sparse_input=None, sparse_wgrad=None):
+                 seed=0, state_dict=None, sparse_input=None, sparse_wgrad=None, dropouts=None):
         assert len(acts) == len(dims) - 1
+        self.dropouts = [0.0] * len(acts) if dropouts is None else [float(p) for p in dropouts]
+        if len(self.dropouts) != len(acts) or not all(0.0 <= p < 1.0 for p in self.dropouts):
+            raise ValueError("dropouts: one probability in [0, 1) per layer, got {!r}".format(dropouts))
         self.dims = tuple(int(d) for d in dims)
         self.acts = [ops.act_code(a) for a in acts]
         self.device = torch.device(device)
@@ -110,10 +119,12 @@ class FlatFFModel:
     def from_module(model, device=None):
         """Mirror of a drop-in module stack (NamedForwardWrapper / RNNDyn) that consists of Linear
         groups only: same weights, flat buffers.  Returns None when the model has anything else
-        (recurrent groups, Conv1d groups, LayerNorm groups, dropout) -- those train through the module path."""
+        (recurrent groups, Conv1d groups, LayerNorm groups, a dropout with p = 1 or in front of the first layer) --
+        those train through the module path.  The nn.Dropout behind a layer becomes that layer's entry of
+        `dropouts`."""
         from .nn.modules import LinearAct
         inner = getattr(model, "model", model)
-        layers, acts = [], []
+        layers, acts, drops = [], [], []
         for group in getattr(inner, "layer_groups", []):
             seq = getattr(group, "module", None)
             if not isinstance(seq, torch.nn.Sequential):
@@ -122,7 +133,12 @@ class FlatFFModel:
                 if isinstance(m, LinearAct):
                     layers.append((m.weight.detach(), m.bias.detach()))
                     acts.append(ops.ACT_TORCH_NAME.get(m.act))
-                elif isinstance(m, (torch.nn.Dropout, torch.nn.Conv1d)):
+                    drops.append(0.0)
+                elif isinstance(m, torch.nn.Dropout):
+                    if type(m).__name__ != "Dropout" or not layers or drops[-1] != 0.0 or not 0.0 <= m.p < 1.0:
+                        return None
+                    drops[-1] = float(m.p)
+                elif isinstance(m, torch.nn.Conv1d):
                     return None
                 elif type(m).__name__ != "FusedActivation":
                     return None
@@ -130,7 +146,7 @@ class FlatFFModel:
             return None
         dims = [layers[0][0].shape[1]] + [w.shape[0] for w, _ in layers]
         device = device if device is not None else layers[0][0].device
-        return FlatFFModel(dims, acts, device=device, state_dict=layers)
+        return FlatFFModel(dims, acts, device=device, state_dict=layers, dropouts=drops)
 
     def store_to_module(self, model, buf=None):
         """Writes the flat parameters (or another buffer of the same layout, e.g. the EMA shadow)
@@ -187,17 +203,32 @@ class FlatFFModel:
             self._buffers[name] = buf
         return buf[:M, :width]
 
-    def forward(self, x, n_layers=None, sparse=False):
+    def has_dropout(self):
+        return any(p > 0.0 for p in self.dropouts)
+
+    def forward(self, x, n_layers=None, sparse=False, training=False, seed=None):
         """x [M, dims[0]] fp32 packed frames -> list of layer outputs (of the first n_layers).  sparse: layer 0
-        walks the row lists of x, built here, instead of the dense product."""
+        walks the row lists of x, built here, instead of the dense product.  training=True applies the layers'
+        dropout with the masks of `seed` (an integer; layer i's salt is i): the outputs are the dropped ones."""
         acts = []
         h = self.pack_input(x)
         M = h.shape[0]
+        if training and seed is None and self.has_dropout():
+            raise ValueError("a training forward of a model with dropout needs a seed")
         for i in range(len(self.layout) if n_layers is None else n_layers):
             out = self._rows_buffer("h%d" % i, M, self.layout[i][2])
+            p = self.dropouts[i] if training else 0.0
             if i == 0 and sparse:
                 self._lists = ops.sparse_rows_build(h, lists=self._lists, want_record=False)
-                h = ops.linear_fwd_sparse(self._lists, h, self.weight_padded(i), self.bias(i), self.acts[i], out=out)
+                if p > 0.0:
+                    h = ops.linear_fwd_sparse_dropout(self._lists, h, self.weight_padded(i), self.bias(i), self.acts[i],
+                                                      p=p, seed=seed, salt=i, out=out)
+                else:
+                    h = ops.linear_fwd_sparse(self._lists, h, self.weight_padded(i), self.bias(i), self.acts[i],
+                                              out=out)
+            elif p > 0.0:
+                h = ops.linear_fwd_dropout(h, self.weight_padded(i), self.bias(i), self.acts[i], p=p, seed=seed, salt=i,
+                                           out=out)
             else:
                 h = ops.linear_fwd(h, self.weight_padded(i), self.bias(i), self.acts[i], out=out)
             acts.append(h)
@@ -224,13 +255,23 @@ class FlatFFModel:
             self._col_plan = ops.sparse_cols_plan(x, K=self.dims[0])
         return True
 
-    def loss_and_backward(self, x, target, row_valid, n_valid_global, reduce_group=None, reduce=False):
+    def loss_and_backward(self, x, target, row_valid, n_valid_global, reduce_group=None, reduce=False, seed=None):
         """Fills self.grads with d(loss)/d(params) of this rank's frames; returns loss tensor
         (this rank's contribution, already divided by the global frame count).  reduce=True (data
         parallel): the sum all-reduce of a layer's gradient segment is issued as soon as its weight
         gradient is queued -- it runs on the collective's own stream under the remaining GEMMs --
-        and the handles are left in self._pending for train_step to wait on before Adam."""
+        and the handles are left in self._pending for train_step to wait on before Adam.  seed: of this step's
+        dropout masks (a model with dropouts); None draws one from the process's stream (nn.functional.DropoutStream:
+        every rank of a data-parallel run its own)."""
         self._pending = []
+        self._seed = 0
+        if self.has_dropout():
+            # (a training step captured into a graph would replay this seed, and with it one mask, on every replay;
+            # nothing captures training steps)
+            if seed is None:
+                from .nn.functional import default_dropout_stream
+                seed = default_dropout_stream().next()
+            self._seed = int(seed)
         x = self.pack_input(x)
         if self.sparse_input is None:
             self._decide_sparse_input(x)
@@ -246,16 +287,28 @@ class FlatFFModel:
     def _loss_and_backward(self, x, target, row_valid, n_valid_global, reduce_group, reduce):
         M = x.shape[0]
         n = len(self.layout)
-        if self.acts[-1] in (None, ops.ACT_NONE) and n > 1:
+        drops, seed = self.dropouts, self._seed
+        if drops[-1] > 0.0:
+            # the output layer itself carries dropout: the fused output-layer + loss epilogue has no registers left
+            # for the rule, so the layer stores its (dropped) output, the loss reads it, and its gradient goes back
+            # through the dropout and the activation in one elementwise pass
+            hs = self.forward(x, sparse=bool(self.sparse_input), training=True, seed=seed)
+            loss, dz = ops.masked_mse(hs[-1], target, row_valid, n_valid_global,
+                                      grad=self._rows_buffer("dz_out", M, self.dims[-1]))
+            if self.acts[-1] in (None, ops.ACT_NONE):
+                dz = ops.dropout_apply(dz, drops[-1], seed, n - 1, out=dz)
+            else:
+                dz = ops.dropout_act_bwd(dz, hs[-1], self.acts[-1], drops[-1], seed, n - 1, out=dz)
+        elif self.acts[-1] in (None, ops.ACT_NONE) and n > 1:
             # the output layer never materialises: its GEMM epilogue forms the masked difference
             # to the target, the loss partial sums and d loss / d output
-            hs = self.forward(x, n_layers=n - 1, sparse=bool(self.sparse_input))
+            hs = self.forward(x, n_layers=n - 1, sparse=bool(self.sparse_input), training=True, seed=seed)
             loss, dz = ops.linear_fwd_mse(hs[-1], self.weight_padded(n - 1), self.bias(n - 1), target,
                                           row_valid, n_valid_global,
                                           grad=self._rows_buffer("dz_out", M, self.dims[-1]))
             hs.append(None)
         else:
-            hs = self.forward(x, sparse=bool(self.sparse_input))
+            hs = self.forward(x, sparse=bool(self.sparse_input), training=True, seed=seed)
             loss, dz = ops.masked_mse(hs[-1], target, row_valid, n_valid_global,
                                       grad=self._rows_buffer("dz_out", M, self.dims[-1]))
             if self.acts[-1] != ops.ACT_NONE:
@@ -267,8 +320,13 @@ class FlatFFModel:
             if i > 0:
                 # dW, db and the input gradient of the layer in one call (one launch)
                 dz_in = self._rows_buffer("dz%d" % (i & 1), M, self.layout[i][3])
-                ops.linear_bwd(dz, inp, self.weight_padded(i), self.weight_padded(i, self.grads),
-                               self.bias(i, self.grads), dz_in, yprev=hs[i - 1], act_prev=self.acts[i - 1])
+                if drops[i - 1] > 0.0:
+                    ops.linear_bwd_dropout(dz, inp, self.weight_padded(i), self.weight_padded(i, self.grads),
+                                           self.bias(i, self.grads), dz_in, yprev=hs[i - 1], act_prev=self.acts[i - 1],
+                                           p=drops[i - 1], seed=seed, salt=i - 1)
+                else:
+                    ops.linear_bwd(dz, inp, self.weight_padded(i), self.weight_padded(i, self.grads),
+                                   self.bias(i, self.grads), dz_in, yprev=hs[i - 1], act_prev=self.acts[i - 1])
             elif self._wgrad_sparse_now:
                 # without a plan (dims[0] > 512) the entry point runs the dense product and counts it
                 if self._col_plan is not None:
@@ -295,7 +353,7 @@ class FlatFFModel:
     def train_step(self, x, target, row_valid, n_valid_global, lr=1e-3, betas=(0.9, 0.999),
                    eps=1e-8, weight_decay=0.0, process_group=None, world_size=1,
                    clip_norm_kind=None, clip_max_norm=0.0, clip_value=None, ema_shadow=None,
-                   ema_decay=0.0):
+                   ema_decay=0.0, seed=None):
         """forward + masked MSE + backward + [all-reduce] + optimiser tail.  clip_norm_kind 2 / 0
         (infinity) clips the gradient norm to clip_max_norm, clip_value clamps the elements,
         ema_shadow (flat, this model's layout) is updated with ema_decay -- all inside the one
@@ -303,7 +361,7 @@ class FlatFFModel:
         from . import parallel
         dist_on = world_size > 1 or parallel._active(process_group)
         loss = self.loss_and_backward(x, target, row_valid, n_valid_global, reduce_group=process_group,
-                                      reduce=dist_on)
+                                      reduce=dist_on, seed=seed)
         for work in self._pending:   # the optimiser's stream waits for the collectives
             work.wait()
         self._pending = []

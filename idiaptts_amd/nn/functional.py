@@ -569,6 +569,70 @@ def _rows_padded(M, N, device):
     return full[:, :N]
 
 
+class DropoutStream(object):
+    """Seeds of the fused dropout (csrc/dropout.h): next() is a 63-bit integer from a host generator private to the
+    package.  It is seeded lazily from torch.initial_seed() plus the process's distributed rank (every rank draws its
+    own masks) and seeded again when torch.initial_seed() has changed (a torch.manual_seed between two runs makes the
+    runs repeat); reseed(value) sets it to a known state, restart() makes the next draw seed it from torch's seed
+    again (the handler's seed() does, so that a second run with the same seed repeats the first).  No public torch
+    generator is consumed and nothing touches the device."""
+
+    def __init__(self):
+        self._gen = torch.Generator(device="cpu")
+        self._torch_seed = None
+
+    def reseed(self, value):
+        self._gen.manual_seed(int(value) & 0x7FFFFFFFFFFFFFFF)
+        self._torch_seed = torch.initial_seed()
+
+    def restart(self):
+        self._torch_seed = None
+
+    def next(self):
+        seed = torch.initial_seed()
+        if seed != self._torch_seed:
+            rank = 0
+            if torch.distributed.is_available() and torch.distributed.is_initialized():
+                rank = torch.distributed.get_rank()
+            self._gen.manual_seed((seed + rank) & 0x7FFFFFFFFFFFFFFF)
+            self._torch_seed = seed
+        return int(torch.randint(0, 0x7FFFFFFFFFFFFFFF, (1,), generator=self._gen, dtype=torch.int64).item())
+
+
+_default_dropout_stream = DropoutStream()
+
+
+def default_dropout_stream():
+    """the process's one stream of dropout seeds"""
+    return _default_dropout_stream
+
+
+# `acts` of a LinearChainFunction whose layers carry dropout: drops[i] = (p, salt) of layer i, one seed per call
+ChainDropout = collections.namedtuple("ChainDropout", "acts drops seed")
+
+
+class DropoutFunction(torch.autograd.Function):
+    """y = x * m / (1 - p) on rows of any leading shape, mask from (seed, salt, position): the backward is the same
+    launch on the gradient and no mask is stored (dropout behind a LayerNorm or pooling group)."""
+
+    @staticmethod
+    def forward(ctx, x, p, seed, salt):
+        ctx.rule = (float(p), int(seed), int(salt))
+        x2 = x.reshape(-1, x.shape[-1])
+        if x2.stride(-1) != 1:
+            x2 = x2.contiguous()
+        y = torch.empty((x2.shape[0], x2.shape[1]), dtype=torch.float32, device=x.device)
+        return ops.dropout_apply(x2, *ctx.rule, out=y).view(x.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        d2 = dy.reshape(-1, dy.shape[-1])
+        if d2.stride(-1) != 1:
+            d2 = d2.contiguous()
+        dx = torch.empty((d2.shape[0], d2.shape[1]), dtype=torch.float32, device=dy.device)
+        return ops.dropout_apply(d2, *ctx.rule, out=dx).view(dy.shape), None, None, None
+
+
 class LinearChainFunction(torch.autograd.Function):
     """A run of Linear (+ activation) layers on rows -- the layers of consecutive FFWrapper groups
     (rnn_dyn/FFWrapper.py:63-73) -- as ONE autograd node: forward the same `itts_linear_fwd` launches as the layers
@@ -576,10 +640,17 @@ class LinearChainFunction(torch.autograd.Function):
     gradient, bias gradient and input gradient (`itts_linear_bwd`), the previous layer's activation derivative in its
     epilogue -- no `act_bwd` pass over the rows, no second launch per layer, one node instead of one per layer.
     x: [M, K0] rows, or [M, K0 rounded up to 4] with zeroed pad columns (LinearActFunction's convention);
-    acts: tuple of ops.ACT_*; wb: weight0, bias0, weight1, bias1, ..."""
+    acts: tuple of ops.ACT_*, or ChainDropout(acts, drops, seed) for layers with a dropout behind them (drops[i] =
+    (p, salt) of layer i; the masks come from the position, so the backward recomputes them and none is saved; with
+    every p == 0 the launches are those of the plain tuple); wb: weight0, bias0, weight1, bias1, ..."""
 
     @staticmethod
     def forward(ctx, x, acts, *wb):
+        drops, seed = None, 0
+        if isinstance(acts, ChainDropout):
+            acts, drops, seed = acts
+            if not any(p > 0 for p, _ in drops):
+                drops = None
         n = len(acts)
         if x.stride(-1) != 1:
             x = x.contiguous()
@@ -590,11 +661,16 @@ class LinearChainFunction(torch.autograd.Function):
             w = w.contiguous()
             if i == 0 and h.shape[1] != K and h.shape[1] == (K + 3) // 4 * 4:
                 w = torch.nn.functional.pad(w, (0, h.shape[1] - K))
-            h = ops.linear_fwd(h, w, b, acts[i], out=_rows_padded(h.shape[0], N, h.device))
+            if drops is not None and drops[i][0] > 0:
+                h = ops.linear_fwd_dropout(h, w, b, acts[i], p=drops[i][0], seed=seed, salt=drops[i][1],
+                                           out=_rows_padded(h.shape[0], N, h.device))
+            else:
+                h = ops.linear_fwd(h, w, b, acts[i], out=_rows_padded(h.shape[0], N, h.device))
             ws.append(w)
             hs.append(h)
         ctx.save_for_backward(x, *hs, *ws)
         ctx.acts, ctx.n = tuple(acts), n
+        ctx.drops, ctx.seed = (None if drops is None else tuple((float(p), int(s)) for p, s in drops)), int(seed)
         ctx.k0 = wb[0].shape[1]
         return hs[-1]
 
@@ -609,7 +685,11 @@ class LinearChainFunction(torch.autograd.Function):
             buf = _rows_padded(M, dy.shape[1], dy.device)
             buf.copy_(dy)
             dz = buf
-        if ctx.acts[-1] != ops.ACT_NONE:
+        drops, seed = ctx.drops, ctx.seed
+        if drops is not None and drops[-1][0] > 0:
+            # back through the last layer's dropout and activation in one pass (its output is the dropped one)
+            dz = ops.dropout_act_bwd(dz, hs[-1], ctx.acts[-1], drops[-1][0], seed, drops[-1][1])
+        elif ctx.acts[-1] != ops.ACT_NONE:
             dz = ops.act_bwd(dz, hs[-1], ctx.acts[-1])
         grads = [None] * (2 * n)
         dx = None
@@ -620,7 +700,11 @@ class LinearChainFunction(torch.autograd.Function):
             db = torch.empty((N,), dtype=torch.float32, device=x.device)
             if i > 0:
                 dz_in = _rows_padded(M, K, x.device)
-                ops.linear_bwd(dz, hs[i - 1], w, dw, db, dz_in, yprev=hs[i - 1], act_prev=ctx.acts[i - 1])
+                if drops is not None and drops[i - 1][0] > 0:
+                    ops.linear_bwd_dropout(dz, hs[i - 1], w, dw, db, dz_in, yprev=hs[i - 1], act_prev=ctx.acts[i - 1],
+                                           p=drops[i - 1][0], seed=seed, salt=drops[i - 1][1])
+                else:
+                    ops.linear_bwd(dz, hs[i - 1], w, dw, db, dz_in, yprev=hs[i - 1], act_prev=ctx.acts[i - 1])
                 grads[2 * i], grads[2 * i + 1] = dw, db
                 dz = dz_in
             else:

@@ -1122,6 +1122,149 @@ def linear_bwd(dz, x, w, dw, db, dx, yprev=None, act_prev=ACT_NONE, accumulate=F
     return dw, db, dx
 
 
+# ------------------------------------------------------------------------------ dropout (csrc/dropout.h)
+# The mask of element (row, col) is a function of (seed, salt, row + row_offset, col): the backward recomputes it,
+# none is stored.  p in [0, 1); seed a 64-bit integer, salt a 32-bit one (the layer).
+def _drop_args(p, seed, salt, row_offset):
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError("dropout p must be in [0, 1), got {}".format(p))
+    return (p, ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), ctypes.c_uint32(int(salt) & 0xFFFFFFFF),
+            ctypes.c_int64(int(row_offset)))
+
+
+def _like_rows(t):
+    """[M, N] view of fresh rows whose pitch is N rounded up to four floats, pad columns zero (the GEMMs behind it
+    keep their 16-byte rows)"""
+    M, N = t.shape
+    Np = (N + 3) // 4 * 4
+    full = torch.empty((M, Np), dtype=torch.float32, device=t.device)
+    if Np != N:
+        full[:, N:] = 0
+    return full[:, :N]
+
+
+def dropout_apply(x, p, seed, salt, row_offset=0, out=None):
+    """out = x * m * (1 / (1 - p)) on [M, N] rows (any pitch), the forward and the backward of a dropout alike;
+    out may be x (in place)."""
+    L = _lib.load()
+    _need(x, torch.float32, "x")
+    if out is None:
+        out = _like_rows(x)
+    _need(out, torch.float32, "out")
+    if out.shape != x.shape:
+        raise ValueError("out must have the shape of x")
+    M, N = x.shape
+    if N == 0:
+        return out
+    _lib.check(L.itts_dropout_apply(_ptr(x), _rows(x, "x"), _ptr(out), _rows(out, "out"), M, N, 0,
+                                    *_drop_args(p, seed, salt, row_offset), _stream()), "itts_dropout_apply")
+    return out
+
+
+def dropout_mask(M, N, p, seed, salt, row_offset=0, device="cuda"):
+    """bool [M, N]: True where the rule keeps the element"""
+    L = _lib.load()
+    out = torch.empty((int(M), int(N)), dtype=torch.uint8, device=device)
+    if M and N:
+        _lib.check(L.itts_dropout_apply(None, 0, _ptr(out), int(N), int(M), int(N), 1,
+                                        *_drop_args(p, seed, salt, row_offset), _stream()), "itts_dropout_apply")
+    return out.bool()
+
+
+def dropout_act_bwd(dy, d, act, p, seed, salt, row_offset=0, out=None):
+    """dz = dy * m * scale * act'(y) from the dropped output d = y * m * scale of a layer (act_bwd for a layer with
+    dropout); out may be dy"""
+    L = _lib.load()
+    _need(dy, torch.float32, "dy")
+    _need(d, torch.float32, "d")
+    if dy.shape != d.shape:
+        raise ValueError("dy and d must have one shape")
+    if out is None:
+        out = _like_rows(dy)
+    M, N = dy.shape
+    if N == 0:
+        return out
+    _lib.check(L.itts_dropout_act_bwd(_ptr(dy), _rows(dy, "dy"), _ptr(d), _rows(d, "d"), _ptr(out), _rows(out, "out"),
+                                      M, N, int(act if act is not None else ACT_NONE),
+                                      *_drop_args(p, seed, salt, row_offset), _stream()), "itts_dropout_act_bwd")
+    return out
+
+
+def linear_fwd_dropout(x, w, b, act=ACT_NONE, p=0.0, seed=0, salt=0, row_offset=0, out=None):
+    """linear_fwd with dropout on the output, applied in the product's epilogue"""
+    L = _lib.load()
+    _need(x, torch.float32, "x")
+    _need(w, torch.float32, "w")
+    M, K = x.shape
+    N = w.shape[0]
+    if w.shape[1] != K or not w.is_contiguous():
+        raise ValueError("w must be contiguous [N, K]")
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=x.device)
+    _lib.check(L.itts_linear_fwd_dropout(_ptr(x), _rows(x, "x"), _ptr(w), _ptr(b), _ptr(out), _rows(out, "out"), M, N,
+                                         K, act, *_drop_args(p, seed, salt, row_offset), _stream()),
+               "itts_linear_fwd_dropout")
+    return out
+
+
+def linear_fwd_sparse_dropout(rows, x, w, b, act=ACT_NONE, p=0.0, seed=0, salt=0, row_offset=0, out=None):
+    """linear_fwd_sparse with dropout on the output"""
+    L = _lib.load()
+    _need(x, torch.float32, "x")
+    _need(w, torch.float32, "w")
+    M, K = x.shape
+    N = w.shape[0]
+    if w.shape[1] != K or not w.is_contiguous():
+        raise ValueError("w must be contiguous [N, K]")
+    if rows.M != M or rows.K != K:
+        raise ValueError("the row lists were built for another shape")
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=x.device)
+    _lib.check(L.itts_linear_fwd_sparse_dropout(_ptr(rows.block), _ptr(x), _rows(x, "x"), _ptr(w), _ptr(b), _ptr(out),
+                                                _rows(out, "out"), M, N, K, act,
+                                                *_drop_args(p, seed, salt, row_offset), _stream()),
+               "itts_linear_fwd_sparse_dropout")
+    return out
+
+
+def linear_bwd_input_dropout(dz, w, yprev, act_prev=ACT_NONE, p=0.0, seed=0, salt=0, row_offset=0, out=None):
+    """linear_bwd_input where yprev, the previous layer's output, carries the dropout (p, seed, salt, row_offset)"""
+    L = _lib.load()
+    _need(dz, torch.float32, "dz")
+    M, N = dz.shape
+    K = w.shape[1]
+    if out is None:
+        out = torch.empty((M, K), dtype=torch.float32, device=dz.device)
+    _lib.check(L.itts_linear_bwd_input_dropout(_ptr(dz), _rows(dz, "dz"), _ptr(w), _ptr(out), _rows(out, "out"),
+                                               _ptr(yprev), _rows(yprev, "yprev") if yprev is not None else 0,
+                                               int(act_prev if act_prev is not None else ACT_NONE), M, N, K,
+                                               *_drop_args(p, seed, salt, row_offset), _stream()),
+               "itts_linear_bwd_input_dropout")
+    return out
+
+
+def linear_bwd_dropout(dz, x, w, dw, db, dx, yprev, act_prev=ACT_NONE, p=0.0, seed=0, salt=0, row_offset=0,
+                       accumulate=False):
+    """linear_bwd where yprev, the previous layer's output, carries the dropout (p, seed, salt, row_offset)"""
+    L = _lib.load()
+    _need(dz, torch.float32, "dz")
+    _need(x, torch.float32, "x")
+    _need(w, torch.float32, "w")
+    M, N = dz.shape
+    K = x.shape[1]
+    if w.shape != (N, K) or not w.is_contiguous() or not dw.is_contiguous() or dw.shape != (N, K):
+        raise ValueError("w and dw must be contiguous [N, K]")
+    ws = _workspace(L.itts_linear_bwd_weight_workspace_bytes(M, N, K), dz.device)
+    _lib.check(L.itts_linear_bwd_dropout(_ptr(dz), _rows(dz, "dz"), _ptr(x), _rows(x, "x"), _ptr(w), _ptr(dw),
+                                         _ptr(db), _ptr(dx), _rows(dx, "dx"), _ptr(yprev),
+                                         _rows(yprev, "yprev") if yprev is not None else 0,
+                                         int(act_prev if act_prev is not None else ACT_NONE), M, N, K, _ptr(ws),
+                                         1 if accumulate else 0, *_drop_args(p, seed, salt, row_offset), _stream()),
+               "itts_linear_bwd_dropout")
+    return dw, db, dx
+
+
 def masked_mse(pred, target, row_valid, n_valid, loss_weight=1.0, want_grad=True, grad=None):
     """NamedLoss(MSELoss, 'mean_per_frame') (loss/NamedLoss.py:70-117) on [M, D] rows."""
     L = _lib.load()
@@ -1630,7 +1773,7 @@ def gemm_path_counts():
 GEMM_KERNELS = {1: "staged", 2: "ring", 3: "ring_pair"}
 GEMM_EPILOGUES = {0: "store", 1: "bias_act", 2: "dact", 3: "mse"}
 GemmLaunch = collections.namedtuple("GemmLaunch", "kernel a_row b_row epi tn stages wm vec_a vec_b wide grouped splitk "
-                                                  "family tiles grid")
+                                                  "family tiles grid dropout")
 SlabReduction = collections.namedtuple("SlabReduction", "vec merged deferred slabs")
 GEMM_PLAN_MAX = 8                # kPlanMax of csrc/nn.hip
 
@@ -1640,7 +1783,8 @@ def gemm_last_plan():
     linear_bwd_weight, linear_bwd; itts_gemm_last_plan, no device call): a list, in launch order, of
     GemmLaunch(kernel "staged" / "ring" / "ring_pair", a_row, b_row, epi "store" / "bias_act" / "dact" / "mse", tn and
     stages (staged; 0 otherwise), wm (ring; 0 otherwise), vec_a, vec_b, wide (the wide-store epilogue), grouped (tile
-    order), splitk, family (0 base, 1 extended activations), tiles, grid) -- a pair launch gives two, the weight and
+    order), splitk, family (0 base, 1 extended activations), tiles, grid, dropout (the epilogue applied it)) -- a pair
+    launch gives two, the weight and
     the input product -- and SlabReduction(vec: float4 or scalar columns, merged with the bias, deferred, slabs)."""
     L = _lib.load()
     out = (ctypes.c_int32 * (16 * GEMM_PLAN_MAX))()
@@ -1654,7 +1798,7 @@ def gemm_last_plan():
             plan.append(SlabReduction(bool(v[1]), bool(v[2]), bool(v[3]), v[4]))
         else:
             plan.append(GemmLaunch(GEMM_KERNELS[v[0]], bool(v[1]), bool(v[2]), GEMM_EPILOGUES[v[3]], v[4], v[5], v[6],
-                                   bool(v[7]), bool(v[8]), bool(v[9]), bool(v[10]), v[11], v[12], v[13], v[14]))
+                                   bool(v[7]), bool(v[8]), bool(v[9]), bool(v[10]), v[11], v[12], v[13], v[14], bool(v[15])))
     return plan
 
 

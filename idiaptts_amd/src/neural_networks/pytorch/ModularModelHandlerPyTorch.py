@@ -439,6 +439,9 @@ class ModularModelHandlerPyTorch(object):
     @staticmethod
     def seed(seed):
         torch.manual_seed(seed)
+        # the fused dropout's own seeds start over as well (also when the value is the one of the run before)
+        from idiaptts_amd.nn.functional import default_dropout_stream
+        default_dropout_stream().restart()
 
     # ----------------------------------------------------------------------------- batching
     @staticmethod
@@ -655,7 +658,8 @@ class ModularModelHandlerPyTorch(object):
         loaders then only draw utterance indices -- same batch sizes, same shuffling and the same
         RNG consumption as the per-item loaders -- and every mini-batch is gathered on the device
         as packed valid frames for the flat feed-forward step (idiaptts_amd.native_ff).  That step
-        covers Linear groups without dropout, one input and one target stream, Adam, one unweighted
+        covers Linear groups (with or without dropout: the step draws its masks from the package's seed stream,
+        validation runs without them), one input and one target stream, Adam, one unweighted
         masked MSE; any other model, optimiser or loss trains on the module path with the device
         batch cache instead (data_preparation/DeviceBatchCache.py), which holds the same rows."""
         from idiaptts_amd.native_ff import FlatFFModel
@@ -665,7 +669,7 @@ class ModularModelHandlerPyTorch(object):
         flat = FlatFFModel.from_module(self.model, self._device())
         reason = None
         if flat is None:
-            reason = "the model is not a stack of Linear groups without dropout"
+            reason = "the model is not a stack of Linear groups"
         else:
             try:
                 for ds in (dataset_train, dataset_val):

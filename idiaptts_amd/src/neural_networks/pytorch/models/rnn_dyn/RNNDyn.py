@@ -14,7 +14,8 @@ import torch
 from torch import nn
 
 from idiaptts_amd import ops
-from idiaptts_amd.nn.functional import LinearChainFunction, ValidRows, padding_is_identical, padding_rows_identical
+from idiaptts_amd.nn.functional import (ChainDropout, DropoutFunction, LinearChainFunction, ValidRows,
+                                        default_dropout_stream, padding_is_identical, padding_rows_identical)
 from idiaptts_amd.nn.modules import (GRU, LSTM, RNN, Conv1dAct, LayerNormAct, LinearAct, MeanPooling, SelectLastPooling,
                                      VanillaVAE)
 
@@ -38,12 +39,36 @@ class FusedActivation(nn.Identity):
         return "{} (fused into the previous layer)".format(self.name)
 
 
-def run_linear_chain(rows, layers):
-    """rows -> the layers' output rows through one autograd node (nn/functional.py: LinearChainFunction)"""
+class Dropout(nn.Dropout):
+    """The nn.Dropout slot of the reference's nn.Sequential (same state-dict layout: no parameters).  In training, on
+    float32 device tensors and for 0 < p < 1, the mask comes from the counter rule of csrc/dropout.h -- (seed, salt,
+    position) -- instead of torch's generator: the same distribution and scaling, other masks.  `salt` is the index
+    in the model of the layer in front (RNNDyn numbers them); the seed of a forward is handed over by the group
+    (FFWrapper.forward_dropout) or drawn from the package's stream.  Everything else is torch's module."""
+
+    salt = 0
+    seed = None          # of the group's current forward
+
+    def fused(self, x):
+        return self.training and 0.0 < self.p < 1.0 and x.is_cuda and x.dtype == torch.float32 and not self.inplace
+
+    def forward(self, x):
+        if not self.fused(x) or x.dim() < 2:
+            return super().forward(x)
+        seed = self.seed if self.seed is not None else default_dropout_stream().next()
+        return DropoutFunction.apply(x, self.p, seed, self.salt)
+
+
+def run_linear_chain(rows, layers, drops=None, seed=0):
+    """rows -> the layers' output rows through one autograd node (nn/functional.py: LinearChainFunction); drops: per
+    layer (p, salt) of the dropout behind it, with one seed for the call"""
     flat = []
     for m in layers:
         flat += [m.weight, m.bias]
-    return LinearChainFunction.apply(rows, tuple(m.act for m in layers), *flat)
+    acts = tuple(m.act for m in layers)
+    if drops is not None:
+        acts = ChainDropout(acts, tuple(drops), seed)
+    return LinearChainFunction.apply(rows, acts, *flat)
 
 
 class FFWrapper(nn.Module):
@@ -83,9 +108,21 @@ class FFWrapper(nn.Module):
             if nonlin is not None:
                 layers.append(FusedActivation(nonlin))
             if layer_config.dropout > 0.0:
-                layers.append(nn.Dropout(layer_config.dropout))
+                layers.append(Dropout(layer_config.dropout))
         self.module = nn.Sequential(*layers)
         self.out_dim = in_dim
+        self.number_layers(0)
+
+    def number_layers(self, first):
+        """Gives every dropout of the group the index of the layer in front of it as its salt, counting the group's
+        layers from `first` (RNNDyn passes the number of layers in the groups before); returns the next index."""
+        idx = first - 1
+        for m in self.module:
+            if isinstance(m, Dropout):
+                m.salt = max(idx, 0)
+            elif not isinstance(m, FusedActivation):
+                idx += 1
+        return idx + 1
 
     def _create_latent_module(self, in_dim, layer_config, nonlin):
         """PoolLast / PoolMean and VAE / VanillaVAE groups.  What fails in the reference at the first forward, with
@@ -102,7 +139,7 @@ class FFWrapper(nn.Module):
                 raise ValueError("{} group batch_first={} in a model with batch_first={}."
                                  .format(layer_config.type, layers[0].batch_first, self.batch_first))
             if layer_config.dropout > 0.0:
-                layers.append(nn.Dropout(layer_config.dropout))
+                layers.append(Dropout(layer_config.dropout))
             self.out_dim = in_dim
         else:
             if layer_config.num_layers != 1 or nonlin is not None or layer_config.dropout > 0.0:
@@ -115,6 +152,7 @@ class FFWrapper(nn.Module):
             layers = [VanillaVAE(in_dim, layer_config.out_dim)]
             self.out_dim = layer_config.out_dim          # the width of z (the reference leaves in_dim here)
         self.module = nn.Sequential(*layers)
+        self.number_layers(0)
 
     @property
     def returns_tuple(self):
@@ -164,6 +202,42 @@ class FFWrapper(nn.Module):
             return self.module(rows)
         return run_linear_chain(rows, layers)
 
+    def chain_dropouts(self):
+        """[(p, salt)] per LinearAct of a group that is nothing but Linear (+ activation) (+ dropout), (0, 0) where
+        none follows; None when a dropout does not stand behind a layer or cannot be fused (p = 1)"""
+        drops, last = [], None
+        for m in self.module:
+            if isinstance(m, LinearAct):
+                drops.append((0.0, 0))
+                last = len(drops) - 1
+            elif isinstance(m, nn.Dropout):
+                if last is None or not isinstance(m, Dropout) or not 0.0 <= m.p < 1.0 or m.inplace:
+                    return None
+                drops[last], last = (float(m.p), m.salt), None
+        return drops
+
+    def forward_dropout(self, input_):
+        """Training with dropout (every position of the padded tensor): one seed for the whole group.  A group of
+        Linear (+ activation) + dropout layers runs as ONE chain node over the flattened positions, the masks applied
+        in the products' epilogues; in any other group the dropout modules take the seed and run the elementwise
+        kernel.  (A training step captured into a graph would replay this seed, and with it one mask, on every
+        replay; nothing captures training steps.)"""
+        seed = default_dropout_stream().next()
+        layers = self.linear_layers()
+        drops = self.chain_dropouts() if layers is not None else None
+        if drops is not None and input_.dim() >= 2:
+            rows = input_.reshape(-1, input_.shape[-1])
+            out = run_linear_chain(rows, layers, drops, seed)
+            return out.reshape(input_.shape[:-1] + (out.shape[-1],))
+        mods = [m for m in self.module if isinstance(m, Dropout)]
+        for m in mods:
+            m.seed = seed
+        try:
+            return self.module(input_)
+        finally:
+            for m in mods:
+                m.seed = None
+
     def forward(self, input_, **kwargs):
         """reference FFWrapper.py:63-73: the Sequential on every position of the padded tensor.  Inside a
         `padding_rows_identical()` context (the handler's training / validation loops over stock batches) the
@@ -179,6 +253,9 @@ class FFWrapper(nn.Module):
         vr = self.valid_rows_for(input_, kwargs)
         if vr is not None:
             return vr.unpack(self.forward_rows(vr.pack(input_))), kwargs
+        if (self.training and input_.is_cuda and input_.dtype == torch.float32
+                and any(isinstance(m, Dropout) for m in self.module)):
+            return self.forward_dropout(input_), kwargs
         return self.module(input_), kwargs
 
 
@@ -314,6 +391,7 @@ class RNNDyn(nn.ModuleList):
             emb.name = emb_config.name
             self.emb_groups[emb_config.name] = emb
         self.layer_groups = []
+        n_layers = 0
         in_dim = config.in_dim
         for group_idx, layer_config in enumerate(config.layer_configs):
             in_dim += self._get_embeddings_dim(group_idx)
@@ -333,6 +411,11 @@ class RNNDyn(nn.ModuleList):
                                                  len(config.layer_configs)))
             self.append(layer)
             self.layer_groups.append(layer)
+            # the salt of a dropout is the index in the model of the layer in front of it
+            if isinstance(layer, FFWrapper):
+                n_layers = layer.number_layers(n_layers)
+            else:
+                n_layers += layer_config.num_layers
 
     def forward(self, input_, *emb_inputs, **kwargs):
         """reference :88-121.  Embedding indices come as extra arguments (one [T, B, 1] tensor

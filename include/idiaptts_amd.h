@@ -481,6 +481,45 @@ int itts_linear_bwd(const float* d_dz, int64_t lddz, const float* d_x, int64_t l
                     int64_t ldyp, int act_prev, int64_t M, int N, int K, void* d_workspace,
                     int accumulate, void* stream);
 
+/* ---- dropout fused into the dense layers (csrc/dropout.h; replaces the nn.Dropout behind every layer of a Linear
+ * group, rnn_dyn/FFWrapper.py:40-61) ---------------------------------------------------------------------------
+ * The mask is a function of the element's position, not of a generator's state, so a backward recomputes it and
+ * none is stored.  Element (row, col) of a matrix, with a 64-bit seed, a 32-bit salt, a probability p in [0, 1) and
+ * an int64 row_offset: Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter (r & 0xffffffff, r >> 32,
+ * col >> 2, salt), r = row + row_offset; output word col & 3 keeps the element iff word >= min(2^32 - 1,
+ * round(p * 2^32)).  Kept elements are multiplied by scale = 1 / (1 - p) (float32 of 1 - p, float32 division);
+ * dropped elements are +0.0.  Every entry point below with p == 0 launches exactly what its counterpart without the
+ * suffix launches.
+ *
+ * out = in * m * scale on [M, N] rows with pitches ldi / ldo (floats), forward and backward alike; d_out may be d_in.
+ * mask_only != 0: d_out is uint8 [M, ldo] and receives m itself (1 kept, 0 dropped); d_in is not read. */
+int itts_dropout_apply(const float* d_in, int64_t ldi, void* d_out, int64_t ldo, int64_t M, int N, int mask_only,
+                       double p, uint64_t seed, uint32_t salt, int64_t row_offset, void* stream);
+/* dz = dy * m * scale * act'(y), y = d * (1 - p): back through the dropout and the activation of a layer from its
+ * dropped output d [M, ldd] (itts_act_bwd for such a layer); d_dz may be d_dy. */
+int itts_dropout_act_bwd(const float* d_dy, int64_t lddy, const float* d_d, int64_t ldd, float* d_dz, int64_t lddz,
+                         int64_t M, int N, int act, double p, uint64_t seed, uint32_t salt, int64_t row_offset,
+                         void* stream);
+/* itts_linear_fwd with the rule on the output: y = act(x w^T + b) * m * scale. */
+int itts_linear_fwd_dropout(const float* d_x, int64_t ldx, const float* d_w, const float* d_b, float* d_y, int64_t ldy,
+                            int64_t M, int N, int K, int act, double p, uint64_t seed, uint32_t salt,
+                            int64_t row_offset, void* stream);
+/* itts_linear_bwd_input where the previous layer's output d_yprev [M, ldyp] (required) carries the rule (p, seed,
+ * salt, row_offset): dx = (dz w) * m * scale * act_prev'(y), y = d_yprev * (1 - p) where m = 1. */
+int itts_linear_bwd_input_dropout(const float* d_dz, int64_t lddz, const float* d_w, float* d_dx, int64_t lddx,
+                                  const float* d_yprev, int64_t ldyp, int act_prev, int64_t M, int N, int K, double p,
+                                  uint64_t seed, uint32_t salt, int64_t row_offset, void* stream);
+/* itts_linear_bwd with the input gradient of itts_linear_bwd_input_dropout (dw / db need nothing new: dz and x are
+ * the dropped values already); equal to the separate calls bit for bit. */
+int itts_linear_bwd_dropout(const float* d_dz, int64_t lddz, const float* d_x, int64_t ldx, const float* d_w,
+                            float* d_dw, float* d_db, float* d_dx, int64_t lddx, const float* d_yprev, int64_t ldyp,
+                            int act_prev, int64_t M, int N, int K, void* d_workspace, int accumulate, double p,
+                            uint64_t seed, uint32_t salt, int64_t row_offset, void* stream);
+/* itts_linear_fwd_sparse (below) with the rule on the output. */
+int itts_linear_fwd_sparse_dropout(const void* d_lists, const float* d_x, int64_t ldx, const float* d_w,
+                                   const float* d_b, float* d_y, int64_t ldy, int64_t M, int N, int K, int act,
+                                   double p, uint64_t seed, uint32_t salt, int64_t row_offset, void* stream);
+
 /* ---- dense layer on a sparse input (the min-max-normalised question vectors of layer 0: binary answers, mostly
  * exact zeros) -------------------------------------------------------------------------------------------------
  * Row lists of x [M, ldx]: per row the (k, x[m,k]) pairs with x[m,k] != 0 in ascending k (+-0.0 dropped; NaN and
@@ -1014,8 +1053,9 @@ int itts_gemm_path_counts(int64_t out[8]);
  *   a product      {kernel (1 register-staged, 2 ring, 3 ring pair launch), A_ROW, B_ROW, epilogue (as above), TN,
  *                   STAGES (staged; 0 otherwise), WM (ring: 1 = 64 x 128 tiles, 2 = 128 x 64; 0 otherwise), vecA, vecB,
  *                   the wide-store epilogue is the one taken, grouped tile order, split-K slabs, activation family
- *                   (0 none / Tanh / ReLU, 1 the others), tiles, workgroups, 0}; a pair launch gives two entries, the
- *                   weight-gradient product first
+ *                   (0 none / Tanh / ReLU, 1 the others), tiles, workgroups, 1 where the
+ *                   epilogue applied dropout (the _dropout entry points) and 0 otherwise}; a pair launch gives two
+ *                   entries, the weight-gradient product first
  *   a reduction    {4, float4 (1) or scalar (0) columns, merged with the bias, deferred (itts_defer_reductions),
  *                   slabs, 0 ...} */
 int itts_gemm_last_plan(int32_t* out, int max_entries);
