@@ -21,13 +21,16 @@ void set_error(const std::string& msg);
     }                                                                                     \
   } while (0)
 
-#define ITTS_REQUIRE(cond, msg)                                                           \
+// (`entry`: the entry point that the message names; a body that serves several of them says which one was called)
+#define ITTS_REQUIRE_AS(entry, cond, msg)                                                 \
   do {                                                                                    \
     if (!(cond)) {                                                                        \
-      ::itts::set_error(std::string(__func__) + ": " + (msg));                            \
+      ::itts::set_error(std::string(entry) + ": " + (msg));                               \
       return ITTS_E_INVALID;                                                              \
     }                                                                                     \
   } while (0)
+
+#define ITTS_REQUIRE(cond, msg) ITTS_REQUIRE_AS(__func__, cond, msg)
 
 #define ITTS_LAUNCH_CHECK() ITTS_HIP_CHECK(hipGetLastError())
 
@@ -125,6 +128,12 @@ int reduce_slabs(const float* slabs, int S, int64_t n, float* out, int accumulat
 // *loss = (float)(scale * sum of the nb partial sums), one launch of one workgroup in a fixed order (nn.hip): the
 // last step of every loss entry point.
 int loss_final_sum(const double* partial, int64_t nb, double scale, float* loss, hipStream_t s);
+
+// y = act(x w^T + b) of a dense layer (nn.hip): the body of itts_linear_fwd (DR = NoDrop) and itts_linear_fwd_dropout
+// (DR = DropRule, dropout.h), here for the sparse-input entry point's way to the dense product.
+template <class DR>
+int linear_fwd(const float* d_x, int64_t ldx, const float* d_w, const float* d_b, float* d_y, int64_t ldy, int64_t M,
+               int N, int K, int act, hipStream_t s, const DR& dr);
 
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 

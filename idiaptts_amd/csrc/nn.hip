@@ -880,17 +880,18 @@ static int choose_splitk(int64_t M, int N, int K) {
   return (int)std::min<int64_t>(s, 128);
 }
 
-}  // namespace itts
-
-using namespace itts;
-
-extern "C" int itts_linear_fwd(const float* d_x, int64_t ldx, const float* d_w, const float* d_b,
-                               float* d_y, int64_t ldy, int64_t M, int N, int K, int act,
-                               void* stream) {
+// ---- the products of a dense layer, each written once ------------------------------------------------------------
+// DR is NoDrop behind the plain entry point and DropRule behind its _dropout form (the rule: dropout.h), which a
+// refusal names.  A rule sits in the epilogue: on the output of the forward, on the previous layer's output in the
+// input gradient; the weight and bias gradients take none (their operands dz and x are the dropped values already).
+template <class DR>
+int linear_fwd(const float* d_x, int64_t ldx, const float* d_w, const float* d_b, float* d_y, int64_t ldy, int64_t M,
+               int N, int K, int act, hipStream_t s, const DR& dr) {
+  const char* const entry = DR::on ? "itts_linear_fwd_dropout" : "itts_linear_fwd";
   const PlanScope plan_scope;
-  ITTS_REQUIRE(d_w && (M == 0 || (d_x && d_y)), "null pointer");
-  ITTS_REQUIRE(M >= 0 && N > 0 && K > 0 && ldx >= K && ldy >= N, "bad sizes");
-  ITTS_REQUIRE(act >= ITTS_ACT_NONE && act <= ITTS_ACT_HARDSIGMOID, "unknown activation");
+  ITTS_REQUIRE_AS(entry, d_w && (M == 0 || (d_x && d_y)), "null pointer");
+  ITTS_REQUIRE_AS(entry, M >= 0 && N > 0 && K > 0 && ldx >= K && ldy >= N, "bad sizes");
+  ITTS_REQUIRE_AS(entry, act >= ITTS_ACT_NONE && act <= ITTS_ACT_HARDSIGMOID, "unknown activation");
   if (M == 0) return ITTS_OK;
   GemmArgs g{};
   g.A = d_x; g.lda = ldx; g.B = d_w; g.ldb = K; g.C = d_y; g.ldc = ldy;
@@ -899,8 +900,144 @@ extern "C" int itts_linear_fwd(const float* d_x, int64_t ldx, const float* d_w, 
   g.vecA = (ldx % 4 == 0) && aligned16(d_x);
   g.vecB = (K % 4 == 0) && aligned16(d_w);
   g.wide_out = (ldy % 4 == 0) && aligned16(d_y) && (!d_b || aligned16(d_b));
-  if (act_family(act) == AF_EXT) return launch_gemm<true, true, EPI_BIAS_ACT, AF_EXT>(g, 1, as_stream(stream));
-  return launch_gemm<true, true, EPI_BIAS_ACT>(g, 1, as_stream(stream));
+  if (act_family(act) == AF_EXT) return launch_gemm<true, true, EPI_BIAS_ACT, AF_EXT, DR>(g, 1, s, dr);
+  return launch_gemm<true, true, EPI_BIAS_ACT, AF_BASE, DR>(g, 1, s, dr);
+}
+template int linear_fwd<NoDrop>(const float*, int64_t, const float*, const float*, float*, int64_t, int64_t, int, int,
+                                int, hipStream_t, const NoDrop&);
+
+// dx[M,K] = dz[M,N] (row form, reduction N) x w[N,K] (col form: [k=N][out=K]), times the derivative of the previous
+// layer's activation where d_yprev, that layer's output, is given
+static GemmArgs input_grad_args(const float* d_dz, int64_t lddz, const float* d_w, float* d_dx, int64_t lddx,
+                                const float* d_yprev, int64_t ldyp, int act_prev, int64_t M, int N, int K) {
+  GemmArgs g{};
+  g.A = d_dz; g.lda = lddz; g.B = d_w; g.ldb = K; g.C = d_dx; g.ldc = lddx;
+  g.M = M; g.N = K; g.K = N; g.aux = d_yprev; g.ldaux = ldyp; g.act = act_prev;
+  g.kchunk = ((N + BK - 1) / BK) * BK; g.slab_stride = 0;
+  g.vecA = (lddz % 4 == 0) && aligned16(d_dz);
+  g.vecB = (K % 4 == 0) && aligned16(d_w);
+  g.wide_out = (lddx % 4 == 0) && aligned16(d_dx) && (!d_yprev || ((ldyp % 4 == 0) && aligned16(d_yprev)));
+  return g;
+}
+
+template <class DR>
+static int linear_bwd_input(const float* d_dz, int64_t lddz, const float* d_w, float* d_dx, int64_t lddx,
+                            const float* d_yprev, int64_t ldyp, int act_prev, int64_t M, int N, int K, hipStream_t s,
+                            const DR& dr) {
+  const char* const entry = DR::on ? "itts_linear_bwd_input_dropout" : "itts_linear_bwd_input";
+  const PlanScope plan_scope;
+  ITTS_REQUIRE_AS(entry, d_w && (M == 0 || (d_dz && d_dx)), "null pointer");
+  ITTS_REQUIRE_AS(entry, !DR::on || d_yprev, "the previous layer's output is needed where it carries dropout");
+  ITTS_REQUIRE_AS(entry, M >= 0 && N > 0 && K > 0 && lddz >= N && lddx >= K && (!DR::on || ldyp >= K), "bad sizes");
+  ITTS_REQUIRE_AS(entry, !d_yprev || (act_prev >= ITTS_ACT_NONE && act_prev <= ITTS_ACT_HARDSIGMOID),
+                  "unknown activation");
+  if (M == 0) return ITTS_OK;
+  const GemmArgs g = input_grad_args(d_dz, lddz, d_w, d_dx, lddx, d_yprev, ldyp, act_prev, M, N, K);
+  if (d_yprev) {
+    ITTS_REQUIRE_AS(entry, ldyp >= K, "ldyp too small");
+    if (act_family(act_prev) == AF_EXT) return launch_gemm<true, false, EPI_DACT, AF_EXT, DR>(g, 1, s, dr);
+    return launch_gemm<true, false, EPI_DACT, AF_BASE, DR>(g, 1, s, dr);
+  }
+  if constexpr (DR::on) return ITTS_OK;   // (not reached: a rule comes with d_yprev)
+  else return launch_gemm<true, false, EPI_STORE>(g, 1, s);
+}
+
+// The weight-gradient product dw[N,K] = dz^T x (A = dz as col form [k=M][out=N]; B = x as col form [k=M][out=K]) in
+// split-K slabs of the workspace, about S of them.  The bias gradient (column sums of dz) comes out of the same
+// launch: the workgroups of the first column tile add up their resident dz tiles.  When db follows dw in memory (the
+// flat gradient arenas) and both lengths are multiples of 4, one reduction serves both (merged).
+struct WgradPlan {
+  GemmArgs g;
+  int S_eff;
+  bool merged;
+};
+
+static WgradPlan wgrad_plan(const float* d_dz, int64_t lddz, const float* d_x, int64_t ldx, const float* d_dw,
+                            const float* d_db, int64_t M, int N, int K, void* d_workspace, int S) {
+  WgradPlan w{};
+  int64_t kchunk = (M + S - 1) / S;
+  kchunk = ((kchunk + BK - 1) / BK) * BK;
+  w.S_eff = (int)((M + kchunk - 1) / kchunk);
+  const int64_t n = (int64_t)N * K;
+  w.merged = d_db && d_db == d_dw + n && N % 4 == 0 && n % 4 == 0;
+  float* slabs = reinterpret_cast<float*>(d_workspace);
+  GemmArgs& g = w.g;
+  g.A = d_dz; g.lda = lddz; g.B = d_x; g.ldb = ldx; g.C = slabs; g.ldc = K;
+  g.M = N; g.N = K; g.K = M; g.kchunk = kchunk; g.slab_stride = w.merged ? n + N : n;
+  g.vecA = (lddz % 4 == 0) && aligned16(d_dz);
+  g.vecB = (ldx % 4 == 0) && aligned16(d_x);
+  if (d_db) {
+    g.bias_part = w.merged ? slabs + n : slabs + (int64_t)w.S_eff * n;
+    g.bias_part_stride = w.merged ? g.slab_stride : N;
+  }
+  return w;
+}
+
+// the slabs of wgrad_plan's product, summed into dw and db
+static int wgrad_reduce(const WgradPlan& w, float* d_dw, float* d_db, int accumulate, hipStream_t s) {
+  const int64_t N = w.g.M, n = N * w.g.N;
+  const int rc = launch_reduce_slabs(w.g.C, w.S_eff, w.merged ? n + N : n, d_dw, accumulate, s, w.merged);
+  if (rc || w.merged || !d_db) return rc;
+  return launch_reduce_slabs(w.g.bias_part, w.S_eff, N, d_db, accumulate, s);
+}
+
+// Weight gradient (+ bias gradient) and input gradient of one layer from one call: with operands
+// that allow the LDS-DMA kernel the two GEMMs share a launch (gemm_ring_pair_kernel), otherwise
+// this is itts_linear_bwd_weight followed by the input gradient above.  Same results either way
+// (bit for bit: the tiles, the split-K chunks and their order are those of the separate calls).
+template <class DR>
+static int linear_bwd(const float* d_dz, int64_t lddz, const float* d_x, int64_t ldx, const float* d_w, float* d_dw,
+                      float* d_db, float* d_dx, int64_t lddx, const float* d_yprev, int64_t ldyp, int act_prev,
+                      int64_t M, int N, int K, void* d_workspace, int accumulate, hipStream_t s, const DR& dr) {
+  const char* const entry = DR::on ? "itts_linear_bwd_dropout" : "itts_linear_bwd";
+  const PlanScope plan_scope;
+  ITTS_REQUIRE_AS(entry, d_w && d_dw && d_workspace && (M == 0 || (d_dz && d_x && d_dx)), "null pointer");
+  ITTS_REQUIRE_AS(entry, !DR::on || d_yprev, "the previous layer's output is needed where it carries dropout");
+  ITTS_REQUIRE_AS(entry, M >= 0 && N > 0 && K > 0 && lddz >= N && ldx >= K && lddx >= K && (!DR::on || ldyp >= K),
+                  "bad sizes");
+  ITTS_REQUIRE_AS(entry, !d_yprev || ldyp >= K, "ldyp too small");
+  ITTS_REQUIRE_AS(entry, !d_yprev || (act_prev >= ITTS_ACT_NONE && act_prev <= ITTS_ACT_HARDSIGMOID),
+                  "unknown activation");
+  const bool vec_ok = (lddz % 4 == 0) && aligned16(d_dz) && (ldx % 4 == 0) && aligned16(d_x) && (K % 4 == 0) &&
+                      aligned16(d_w);
+  bool fused = vec_ok && M > 0 && (lddx % 4 == 0) && aligned16(d_dx) &&
+               (!d_yprev || ((ldyp % 4 == 0) && aligned16(d_yprev)));
+  WgradPlan w{};
+  GemmArgs gx{};
+  if (fused) {
+    w = wgrad_plan(d_dz, lddz, d_x, ldx, d_dw, d_db, M, N, K, d_workspace, choose_splitk_ring(M, N, K));
+    gx = input_grad_args(d_dz, lddz, d_w, d_dx, lddx, d_yprev, ldyp, act_prev, M, N, K);
+    fused = ring_ok<false, false>(w.g, w.S_eff, EPI_STORE) &&
+            ring_ok<true, false>(gx, 1, d_yprev ? EPI_DACT : EPI_STORE);
+  }
+  if (!fused) {
+    int rc = itts_linear_bwd_weight(d_dz, lddz, d_x, ldx, d_dw, d_db, M, N, K, d_workspace, accumulate, s);
+    if (rc) return rc;
+    return linear_bwd_input<DR>(d_dz, lddz, d_w, d_dx, lddx, d_yprev, ldyp, act_prev, M, N, K, s, dr);
+  }
+  int rc = ITTS_OK;
+  const int wm = ring_wm(w.g.M, w.g.N);
+  if (d_yprev && act_family(act_prev) == AF_EXT)
+    rc = wm == 1 ? launch_ring_bwd_pair<1, EPI_DACT, AF_EXT, DR>(w.g, w.S_eff, gx, s, dr)
+                 : launch_ring_bwd_pair<2, EPI_DACT, AF_EXT, DR>(w.g, w.S_eff, gx, s, dr);
+  else if (d_yprev)
+    rc = wm == 1 ? launch_ring_bwd_pair<1, EPI_DACT, AF_BASE, DR>(w.g, w.S_eff, gx, s, dr)
+                 : launch_ring_bwd_pair<2, EPI_DACT, AF_BASE, DR>(w.g, w.S_eff, gx, s, dr);
+  else if constexpr (!DR::on)   // (a rule comes with d_yprev)
+    rc = wm == 1 ? launch_ring_bwd_pair<1, EPI_STORE>(w.g, w.S_eff, gx, s)
+                 : launch_ring_bwd_pair<2, EPI_STORE>(w.g, w.S_eff, gx, s);
+  if (rc) return rc;
+  return wgrad_reduce(w, d_dw, d_db, accumulate, s);
+}
+
+}  // namespace itts
+
+using namespace itts;
+
+extern "C" int itts_linear_fwd(const float* d_x, int64_t ldx, const float* d_w, const float* d_b,
+                               float* d_y, int64_t ldy, int64_t M, int N, int K, int act,
+                               void* stream) {
+  return linear_fwd(d_x, ldx, d_w, d_b, d_y, ldy, M, N, K, act, as_stream(stream), NoDrop{});
 }
 
 // ---- row gather: pack_padded_sequence / pad_packed_sequence / the h_{t-1} shift of the recurrent layers
@@ -1030,25 +1167,7 @@ extern "C" int itts_linear_bwd_input(const float* d_dz, int64_t lddz, const floa
                                      float* d_dx, int64_t lddx, const float* d_yprev,
                                      int64_t ldyp, int act_prev, int64_t M, int N, int K,
                                      void* stream) {
-  const PlanScope plan_scope;
-  ITTS_REQUIRE(d_w && (M == 0 || (d_dz && d_dx)), "null pointer");
-  ITTS_REQUIRE(M >= 0 && N > 0 && K > 0 && lddz >= N && lddx >= K, "bad sizes");
-  ITTS_REQUIRE(!d_yprev || (act_prev >= ITTS_ACT_NONE && act_prev <= ITTS_ACT_HARDSIGMOID), "unknown activation");
-  if (M == 0) return ITTS_OK;
-  // dx[M,K] = dz[M,N] (row form, reduction N) x w[N,K] (col form: [k=N][out=K])
-  GemmArgs g{};
-  g.A = d_dz; g.lda = lddz; g.B = d_w; g.ldb = K; g.C = d_dx; g.ldc = lddx;
-  g.M = M; g.N = K; g.K = N; g.aux = d_yprev; g.ldaux = ldyp; g.act = act_prev;
-  g.kchunk = ((N + BK - 1) / BK) * BK; g.slab_stride = 0;
-  g.vecA = (lddz % 4 == 0) && aligned16(d_dz);
-  g.vecB = (K % 4 == 0) && aligned16(d_w);
-  g.wide_out = (lddx % 4 == 0) && aligned16(d_dx) && (!d_yprev || ((ldyp % 4 == 0) && aligned16(d_yprev)));
-  if (d_yprev) {
-    ITTS_REQUIRE(ldyp >= K, "ldyp too small");
-    if (act_family(act_prev) == AF_EXT) return launch_gemm<true, false, EPI_DACT, AF_EXT>(g, 1, as_stream(stream));
-    return launch_gemm<true, false, EPI_DACT>(g, 1, as_stream(stream));
-  }
-  return launch_gemm<true, false, EPI_STORE>(g, 1, as_stream(stream));
+  return linear_bwd_input(d_dz, lddz, d_w, d_dx, lddx, d_yprev, ldyp, act_prev, M, N, K, as_stream(stream), NoDrop{});
 }
 
 extern "C" int64_t itts_linear_bwd_weight_workspace_bytes(int64_t M, int N, int K) {
@@ -1072,121 +1191,35 @@ extern "C" int itts_linear_bwd_weight(const float* d_dz, int64_t lddz, const flo
     return ITTS_OK;
   }
   const bool vec_ok = (lddz % 4 == 0) && aligned16(d_dz) && (ldx % 4 == 0) && aligned16(d_x) && (K % 4 == 0);
-  const int S = vec_ok ? choose_splitk_ring(M, N, K) : choose_splitk(M, N, K);
-  int64_t kchunk = (M + S - 1) / S;
-  kchunk = ((kchunk + BK - 1) / BK) * BK;
-  const int S_eff = (int)((M + kchunk - 1) / kchunk);
-  float* slabs = reinterpret_cast<float*>(d_workspace);
-  // dw[N,K] = dz^T x: A = dz as col form [k=M][out=N]; B = x as col form [k=M][out=K]
-  GemmArgs g{};
-  g.A = d_dz; g.lda = lddz; g.B = d_x; g.ldb = ldx; g.C = slabs; g.ldc = K;
-  g.M = N; g.N = K; g.K = M; g.kchunk = kchunk; g.slab_stride = (int64_t)N * K;
-  g.vecA = (lddz % 4 == 0) && aligned16(d_dz);
-  g.vecB = (ldx % 4 == 0) && aligned16(d_x);
-  const int64_t n = (int64_t)N * K;
-  if (d_db) {
-    // The bias gradient (column sums of dz) comes out of the same launch: the workgroups of the
-    // first column tile add up their resident dz tiles.  When db follows dw in memory (the flat
-    // gradient arenas) and both lengths are multiples of 4, one reduction serves both.
-    const bool merged = d_db == d_dw + n && N % 4 == 0 && n % 4 == 0;
-    const int64_t stride = merged ? n + N : n;
-    g.slab_stride = stride;
-    g.bias_part = merged ? slabs + n : slabs + (int64_t)S_eff * n;
-    g.bias_part_stride = merged ? stride : N;
-    int rc = launch_gemm<false, false, EPI_STORE>(g, S_eff, s);
-    if (rc) return rc;
-    if (merged) return launch_reduce_slabs(slabs, S_eff, n + N, d_dw, accumulate, s, true);
-    rc = launch_reduce_slabs(slabs, S_eff, n, d_dw, accumulate, s);
-    if (rc) return rc;
-    return launch_reduce_slabs(g.bias_part, S_eff, (int64_t)N, d_db, accumulate, s);
-  }
-  int rc = launch_gemm<false, false, EPI_STORE>(g, S_eff, s);
+  const WgradPlan w = wgrad_plan(d_dz, lddz, d_x, ldx, d_dw, d_db, M, N, K, d_workspace,
+                                 vec_ok ? choose_splitk_ring(M, N, K) : choose_splitk(M, N, K));
+  const int rc = launch_gemm<false, false, EPI_STORE>(w.g, w.S_eff, s);
   if (rc) return rc;
-  return launch_reduce_slabs(slabs, S_eff, n, d_dw, accumulate, s);
+  return wgrad_reduce(w, d_dw, d_db, accumulate, s);
 }
 
-// Weight gradient (+ bias gradient) and input gradient of one layer from one call: with operands
-// that allow the LDS-DMA kernel the two GEMMs share a launch (gemm_ring_pair_kernel), otherwise
-// this is itts_linear_bwd_weight followed by itts_linear_bwd_input.  Same results either way
-// (bit for bit: the tiles, the split-K chunks and their order are those of the separate calls).
 extern "C" int itts_linear_bwd(const float* d_dz, int64_t lddz, const float* d_x, int64_t ldx,
                                const float* d_w, float* d_dw, float* d_db, float* d_dx, int64_t lddx,
                                const float* d_yprev, int64_t ldyp, int act_prev, int64_t M, int N, int K,
                                void* d_workspace, int accumulate, void* stream) {
-  const PlanScope plan_scope;
-  ITTS_REQUIRE(d_w && d_dw && d_workspace && (M == 0 || (d_dz && d_x && d_dx)), "null pointer");
-  ITTS_REQUIRE(M >= 0 && N > 0 && K > 0 && lddz >= N && ldx >= K && lddx >= K, "bad sizes");
-  ITTS_REQUIRE(!d_yprev || ldyp >= K, "ldyp too small");
-  ITTS_REQUIRE(!d_yprev || (act_prev >= ITTS_ACT_NONE && act_prev <= ITTS_ACT_HARDSIGMOID), "unknown activation");
-  hipStream_t s = as_stream(stream);
-  const bool vec_ok = (lddz % 4 == 0) && aligned16(d_dz) && (ldx % 4 == 0) && aligned16(d_x) && (K % 4 == 0) &&
-                      aligned16(d_w);
-  const int64_t n = (int64_t)N * K;
-  const bool merged = d_db && d_db == d_dw + n && N % 4 == 0 && n % 4 == 0;
-  bool fused = vec_ok && M > 0 && (lddx % 4 == 0) && aligned16(d_dx) &&
-               (!d_yprev || ((ldyp % 4 == 0) && aligned16(d_yprev)));
-  GemmArgs gw{}, gx{};
-  int S_eff = 1;
-  if (fused) {
-    const int S = choose_splitk_ring(M, N, K);
-    int64_t kchunk = (M + S - 1) / S;
-    kchunk = ((kchunk + BK - 1) / BK) * BK;
-    S_eff = (int)((M + kchunk - 1) / kchunk);
-    float* slabs = reinterpret_cast<float*>(d_workspace);
-    gw.A = d_dz; gw.lda = lddz; gw.B = d_x; gw.ldb = ldx; gw.C = slabs; gw.ldc = K;
-    gw.M = N; gw.N = K; gw.K = M; gw.kchunk = kchunk; gw.vecA = gw.vecB = 1;
-    const int64_t stride = merged ? n + N : n;
-    gw.slab_stride = stride;
-    if (merged) { gw.bias_part = slabs + n; gw.bias_part_stride = stride; }
-    else if (d_db) { gw.bias_part = slabs + (int64_t)S_eff * n; gw.bias_part_stride = N; }
-    gx.A = d_dz; gx.lda = lddz; gx.B = d_w; gx.ldb = K; gx.C = d_dx; gx.ldc = lddx;
-    gx.M = M; gx.N = K; gx.K = N; gx.aux = d_yprev; gx.ldaux = ldyp; gx.act = act_prev;
-    gx.kchunk = ((N + BK - 1) / BK) * BK; gx.vecA = gx.vecB = 1;
-    fused = ring_ok<false, false>(gw, S_eff, EPI_STORE) && ring_ok<true, false>(gx, 1, d_yprev ? EPI_DACT : EPI_STORE);
-  }
-  if (!fused) {
-    int rc = itts_linear_bwd_weight(d_dz, lddz, d_x, ldx, d_dw, d_db, M, N, K, d_workspace, accumulate, stream);
-    if (rc) return rc;
-    return itts_linear_bwd_input(d_dz, lddz, d_w, d_dx, lddx, d_yprev, ldyp, act_prev, M, N, K, stream);
-  }
-  int rc;
-  const int wm = ring_wm(gw.M, gw.N);
-  if (d_yprev && act_family(act_prev) == AF_EXT)
-    rc = wm == 1 ? launch_ring_bwd_pair<1, EPI_DACT, AF_EXT>(gw, S_eff, gx, s)
-                 : launch_ring_bwd_pair<2, EPI_DACT, AF_EXT>(gw, S_eff, gx, s);
-  else if (d_yprev) rc = wm == 1 ? launch_ring_bwd_pair<1, EPI_DACT>(gw, S_eff, gx, s) : launch_ring_bwd_pair<2, EPI_DACT>(gw, S_eff, gx, s);
-  else rc = wm == 1 ? launch_ring_bwd_pair<1, EPI_STORE>(gw, S_eff, gx, s) : launch_ring_bwd_pair<2, EPI_STORE>(gw, S_eff, gx, s);
-  if (rc) return rc;
-  float* slabs = reinterpret_cast<float*>(d_workspace);
-  rc = launch_reduce_slabs(slabs, S_eff, merged ? n + N : n, d_dw, accumulate, s, merged);
-  if (rc || merged || !d_db) return rc;
-  return launch_reduce_slabs(slabs + (int64_t)S_eff * n, S_eff, (int64_t)N, d_db, accumulate, s);
+  return linear_bwd(d_dz, lddz, d_x, ldx, d_w, d_dw, d_db, d_dx, lddx, d_yprev, ldyp, act_prev, M, N, K, d_workspace,
+                    accumulate, as_stream(stream), NoDrop{});
 }
 
 // ---- dropout fused into the dense products (the rule: dropout.h) ---------------------------------
 // Each entry point is its plain counterpart with p == 0 (the same launches), and otherwise the same product with the
 // rule in the epilogue: on the output of the forward, on the previous layer's output in the input gradient.
+// (linear_fwd is sparse_rows.hip's as well, so it is instantiated by name: this form here, where the dropout kernels
+// have their place in the library)
+template int itts::linear_fwd<DropRule>(const float*, int64_t, const float*, const float*, float*, int64_t, int64_t, int,
+                                        int, int, hipStream_t, const DropRule&);
 extern "C" int itts_linear_fwd_dropout(const float* d_x, int64_t ldx, const float* d_w, const float* d_b, float* d_y,
                                        int64_t ldy, int64_t M, int N, int K, int act, double p, uint64_t seed,
                                        uint32_t salt, int64_t row_offset, void* stream) {
   ITTS_REQUIRE_DROP_P(p);
-  if (p == 0.0) return itts_linear_fwd(d_x, ldx, d_w, d_b, d_y, ldy, M, N, K, act, stream);
-  const PlanScope plan_scope;
-  ITTS_REQUIRE(d_w && (M == 0 || (d_x && d_y)), "null pointer");
-  ITTS_REQUIRE(M >= 0 && N > 0 && K > 0 && ldx >= K && ldy >= N, "bad sizes");
-  ITTS_REQUIRE(act >= ITTS_ACT_NONE && act <= ITTS_ACT_HARDSIGMOID, "unknown activation");
-  if (M == 0) return ITTS_OK;
-  GemmArgs g{};
-  g.A = d_x; g.lda = ldx; g.B = d_w; g.ldb = K; g.C = d_y; g.ldc = ldy;
-  g.M = M; g.N = N; g.K = K; g.bias = d_b; g.act = act;
-  g.kchunk = ((K + BK - 1) / BK) * BK; g.slab_stride = 0;
-  g.vecA = (ldx % 4 == 0) && aligned16(d_x);
-  g.vecB = (K % 4 == 0) && aligned16(d_w);
-  g.wide_out = (ldy % 4 == 0) && aligned16(d_y) && (!d_b || aligned16(d_b));
-  const DropRule dr = make_drop_rule(p, seed, salt, row_offset);
-  if (act_family(act) == AF_EXT)
-    return launch_gemm<true, true, EPI_BIAS_ACT, AF_EXT, DropRule>(g, 1, as_stream(stream), dr);
-  return launch_gemm<true, true, EPI_BIAS_ACT, AF_BASE, DropRule>(g, 1, as_stream(stream), dr);
+  if (p == 0.0) return linear_fwd(d_x, ldx, d_w, d_b, d_y, ldy, M, N, K, act, as_stream(stream), NoDrop{});
+  return linear_fwd(d_x, ldx, d_w, d_b, d_y, ldy, M, N, K, act, as_stream(stream),
+                    make_drop_rule(p, seed, salt, row_offset));
 }
 
 extern "C" int itts_linear_bwd_input_dropout(const float* d_dz, int64_t lddz, const float* d_w, float* d_dx,
@@ -1194,28 +1227,12 @@ extern "C" int itts_linear_bwd_input_dropout(const float* d_dz, int64_t lddz, co
                                              int N, int K, double p, uint64_t seed, uint32_t salt, int64_t row_offset,
                                              void* stream) {
   ITTS_REQUIRE_DROP_P(p);
-  if (p == 0.0) return itts_linear_bwd_input(d_dz, lddz, d_w, d_dx, lddx, d_yprev, ldyp, act_prev, M, N, K, stream);
-  const PlanScope plan_scope;
-  ITTS_REQUIRE(d_w && (M == 0 || (d_dz && d_dx)), "null pointer");
-  ITTS_REQUIRE(d_yprev, "the previous layer's output is needed where it carries dropout");
-  ITTS_REQUIRE(M >= 0 && N > 0 && K > 0 && lddz >= N && lddx >= K && ldyp >= K, "bad sizes");
-  ITTS_REQUIRE(act_prev >= ITTS_ACT_NONE && act_prev <= ITTS_ACT_HARDSIGMOID, "unknown activation");
-  if (M == 0) return ITTS_OK;
-  GemmArgs g{};
-  g.A = d_dz; g.lda = lddz; g.B = d_w; g.ldb = K; g.C = d_dx; g.ldc = lddx;
-  g.M = M; g.N = K; g.K = N; g.aux = d_yprev; g.ldaux = ldyp; g.act = act_prev;
-  g.kchunk = ((N + BK - 1) / BK) * BK; g.slab_stride = 0;
-  g.vecA = (lddz % 4 == 0) && aligned16(d_dz);
-  g.vecB = (K % 4 == 0) && aligned16(d_w);
-  g.wide_out = (lddx % 4 == 0) && aligned16(d_dx) && (ldyp % 4 == 0) && aligned16(d_yprev);
-  const DropRule dr = make_drop_rule(p, seed, salt, row_offset);
-  if (act_family(act_prev) == AF_EXT)
-    return launch_gemm<true, false, EPI_DACT, AF_EXT, DropRule>(g, 1, as_stream(stream), dr);
-  return launch_gemm<true, false, EPI_DACT, AF_BASE, DropRule>(g, 1, as_stream(stream), dr);
+  if (p == 0.0)
+    return linear_bwd_input(d_dz, lddz, d_w, d_dx, lddx, d_yprev, ldyp, act_prev, M, N, K, as_stream(stream), NoDrop{});
+  return linear_bwd_input(d_dz, lddz, d_w, d_dx, lddx, d_yprev, ldyp, act_prev, M, N, K, as_stream(stream),
+                          make_drop_rule(p, seed, salt, row_offset));
 }
 
-// dw / db as itts_linear_bwd_weight (their operands dz and x are already the dropped values), dx as
-// itts_linear_bwd_input_dropout; one launch for both where itts_linear_bwd has one, with the same tiles and chunks.
 extern "C" int itts_linear_bwd_dropout(const float* d_dz, int64_t lddz, const float* d_x, int64_t ldx, const float* d_w,
                                        float* d_dw, float* d_db, float* d_dx, int64_t lddx, const float* d_yprev,
                                        int64_t ldyp, int act_prev, int64_t M, int N, int K, void* d_workspace,
@@ -1223,58 +1240,10 @@ extern "C" int itts_linear_bwd_dropout(const float* d_dz, int64_t lddz, const fl
                                        void* stream) {
   ITTS_REQUIRE_DROP_P(p);
   if (p == 0.0)
-    return itts_linear_bwd(d_dz, lddz, d_x, ldx, d_w, d_dw, d_db, d_dx, lddx, d_yprev, ldyp, act_prev, M, N, K,
-                           d_workspace, accumulate, stream);
-  const PlanScope plan_scope;
-  ITTS_REQUIRE(d_w && d_dw && d_workspace && (M == 0 || (d_dz && d_x && d_dx)), "null pointer");
-  ITTS_REQUIRE(d_yprev, "the previous layer's output is needed where it carries dropout");
-  ITTS_REQUIRE(M >= 0 && N > 0 && K > 0 && lddz >= N && ldx >= K && lddx >= K && ldyp >= K, "bad sizes");
-  ITTS_REQUIRE(act_prev >= ITTS_ACT_NONE && act_prev <= ITTS_ACT_HARDSIGMOID, "unknown activation");
-  hipStream_t s = as_stream(stream);
-  const bool vec_ok = (lddz % 4 == 0) && aligned16(d_dz) && (ldx % 4 == 0) && aligned16(d_x) && (K % 4 == 0) &&
-                      aligned16(d_w);
-  const int64_t n = (int64_t)N * K;
-  const bool merged = d_db && d_db == d_dw + n && N % 4 == 0 && n % 4 == 0;
-  bool fused = vec_ok && M > 0 && (lddx % 4 == 0) && aligned16(d_dx) && (ldyp % 4 == 0) && aligned16(d_yprev);
-  GemmArgs gw{}, gx{};
-  int S_eff = 1;
-  if (fused) {   // the operands of itts_linear_bwd's pair, item for item
-    const int S = choose_splitk_ring(M, N, K);
-    int64_t kchunk = (M + S - 1) / S;
-    kchunk = ((kchunk + BK - 1) / BK) * BK;
-    S_eff = (int)((M + kchunk - 1) / kchunk);
-    float* slabs = reinterpret_cast<float*>(d_workspace);
-    gw.A = d_dz; gw.lda = lddz; gw.B = d_x; gw.ldb = ldx; gw.C = slabs; gw.ldc = K;
-    gw.M = N; gw.N = K; gw.K = M; gw.kchunk = kchunk; gw.vecA = gw.vecB = 1;
-    const int64_t stride = merged ? n + N : n;
-    gw.slab_stride = stride;
-    if (merged) { gw.bias_part = slabs + n; gw.bias_part_stride = stride; }
-    else if (d_db) { gw.bias_part = slabs + (int64_t)S_eff * n; gw.bias_part_stride = N; }
-    gx.A = d_dz; gx.lda = lddz; gx.B = d_w; gx.ldb = K; gx.C = d_dx; gx.ldc = lddx;
-    gx.M = M; gx.N = K; gx.K = N; gx.aux = d_yprev; gx.ldaux = ldyp; gx.act = act_prev;
-    gx.kchunk = ((N + BK - 1) / BK) * BK; gx.vecA = gx.vecB = 1;
-    fused = ring_ok<false, false>(gw, S_eff, EPI_STORE) && ring_ok<true, false>(gx, 1, EPI_DACT);
-  }
-  if (!fused) {
-    int rc = itts_linear_bwd_weight(d_dz, lddz, d_x, ldx, d_dw, d_db, M, N, K, d_workspace, accumulate, stream);
-    if (rc) return rc;
-    return itts_linear_bwd_input_dropout(d_dz, lddz, d_w, d_dx, lddx, d_yprev, ldyp, act_prev, M, N, K, p, seed, salt,
-                                         row_offset, stream);
-  }
-  const DropRule dr = make_drop_rule(p, seed, salt, row_offset);
-  int rc;
-  const int wm = ring_wm(gw.M, gw.N);
-  if (act_family(act_prev) == AF_EXT)
-    rc = wm == 1 ? launch_ring_bwd_pair<1, EPI_DACT, AF_EXT, DropRule>(gw, S_eff, gx, s, dr)
-                 : launch_ring_bwd_pair<2, EPI_DACT, AF_EXT, DropRule>(gw, S_eff, gx, s, dr);
-  else
-    rc = wm == 1 ? launch_ring_bwd_pair<1, EPI_DACT, AF_BASE, DropRule>(gw, S_eff, gx, s, dr)
-                 : launch_ring_bwd_pair<2, EPI_DACT, AF_BASE, DropRule>(gw, S_eff, gx, s, dr);
-  if (rc) return rc;
-  float* slabs = reinterpret_cast<float*>(d_workspace);
-  rc = launch_reduce_slabs(slabs, S_eff, merged ? n + N : n, d_dw, accumulate, s, merged);
-  if (rc || merged || !d_db) return rc;
-  return launch_reduce_slabs(slabs + (int64_t)S_eff * n, S_eff, (int64_t)N, d_db, accumulate, s);
+    return linear_bwd(d_dz, lddz, d_x, ldx, d_w, d_dw, d_db, d_dx, lddx, d_yprev, ldyp, act_prev, M, N, K, d_workspace,
+                      accumulate, as_stream(stream), NoDrop{});
+  return linear_bwd(d_dz, lddz, d_x, ldx, d_w, d_dw, d_db, d_dx, lddx, d_yprev, ldyp, act_prev, M, N, K, d_workspace,
+                    accumulate, as_stream(stream), make_drop_rule(p, seed, salt, row_offset));
 }
 
 // ---- elementwise dropout: out = in * m * scale (forward and backward alike), or the mask itself ----

@@ -284,42 +284,40 @@ static int launch_sparse_fwd(const void* d_lists, const float* d_w, const float*
   return ITTS_OK;
 }
 
-extern "C" int itts_linear_fwd_sparse(const void* d_lists, const float* d_x, int64_t ldx, const float* d_w,
-                                      const float* d_b, float* d_y, int64_t ldy, int64_t M, int N, int K, int act,
-                                      void* stream) {
-  ITTS_REQUIRE(d_w && (M == 0 || (d_lists && d_x && d_y)), "null pointer");
-  ITTS_REQUIRE(M >= 0 && N > 0 && K > 0 && K <= 65535 && ldx >= K && ldy >= N, "bad sizes");
-  ITTS_REQUIRE(act >= ITTS_ACT_NONE && act <= ITTS_ACT_HARDSIGMOID, "unknown activation");
+// DR: NoDrop behind itts_linear_fwd_sparse, DropRule (the rule of the dense layers, on the output) behind its _dropout
+// form
+template <class DR>
+static int linear_fwd_sparse(const void* d_lists, const float* d_x, int64_t ldx, const float* d_w, const float* d_b,
+                             float* d_y, int64_t ldy, int64_t M, int N, int K, int act, hipStream_t s, const DR& dr) {
+  const char* const entry = DR::on ? "itts_linear_fwd_sparse_dropout" : "itts_linear_fwd_sparse";
+  ITTS_REQUIRE_AS(entry, d_w && (M == 0 || (d_lists && d_x && d_y)), "null pointer");
+  ITTS_REQUIRE_AS(entry, M >= 0 && N > 0 && K > 0 && K <= 65535 && ldx >= K && ldy >= N, "bad sizes");
+  ITTS_REQUIRE_AS(entry, act >= ITTS_ACT_NONE && act <= ITTS_ACT_HARDSIGMOID, "unknown activation");
   if (M == 0) return ITTS_OK;
   if (K > kSparseMaxK) {   // the slab does not fit: the dense product, decided from the shape alone
     g_sparse_path[2].fetch_add(1, std::memory_order_relaxed);
-    return itts_linear_fwd(d_x, ldx, d_w, d_b, d_y, ldy, M, N, K, act, stream);
+    return itts::linear_fwd(d_x, ldx, d_w, d_b, d_y, ldy, M, N, K, act, s, dr);
   }
   g_sparse_path[1].fetch_add(1, std::memory_order_relaxed);
-  if (act_family(act) == AF_EXT) return launch_sparse_fwd<AF_EXT>(d_lists, d_w, d_b, d_y, ldy, M, N, K, act, as_stream(stream));
-  return launch_sparse_fwd<AF_BASE>(d_lists, d_w, d_b, d_y, ldy, M, N, K, act, as_stream(stream));
+  if (act_family(act) == AF_EXT) return launch_sparse_fwd<AF_EXT, DR>(d_lists, d_w, d_b, d_y, ldy, M, N, K, act, s, dr);
+  return launch_sparse_fwd<AF_BASE, DR>(d_lists, d_w, d_b, d_y, ldy, M, N, K, act, s, dr);
 }
 
-// itts_linear_fwd_sparse with the dropout rule of the dense layers on the output; p == 0 is the plain call.
+extern "C" int itts_linear_fwd_sparse(const void* d_lists, const float* d_x, int64_t ldx, const float* d_w,
+                                      const float* d_b, float* d_y, int64_t ldy, int64_t M, int N, int K, int act,
+                                      void* stream) {
+  return linear_fwd_sparse(d_lists, d_x, ldx, d_w, d_b, d_y, ldy, M, N, K, act, as_stream(stream), NoDrop{});
+}
+
 extern "C" int itts_linear_fwd_sparse_dropout(const void* d_lists, const float* d_x, int64_t ldx, const float* d_w,
                                               const float* d_b, float* d_y, int64_t ldy, int64_t M, int N, int K,
                                               int act, double p, uint64_t seed, uint32_t salt, int64_t row_offset,
                                               void* stream) {
   ITTS_REQUIRE_DROP_P(p);
-  if (p == 0.0) return itts_linear_fwd_sparse(d_lists, d_x, ldx, d_w, d_b, d_y, ldy, M, N, K, act, stream);
-  ITTS_REQUIRE(d_w && (M == 0 || (d_lists && d_x && d_y)), "null pointer");
-  ITTS_REQUIRE(M >= 0 && N > 0 && K > 0 && K <= 65535 && ldx >= K && ldy >= N, "bad sizes");
-  ITTS_REQUIRE(act >= ITTS_ACT_NONE && act <= ITTS_ACT_HARDSIGMOID, "unknown activation");
-  if (M == 0) return ITTS_OK;
-  if (K > kSparseMaxK) {   // the slab does not fit: the dense product, decided from the shape alone
-    g_sparse_path[2].fetch_add(1, std::memory_order_relaxed);
-    return itts_linear_fwd_dropout(d_x, ldx, d_w, d_b, d_y, ldy, M, N, K, act, p, seed, salt, row_offset, stream);
-  }
-  g_sparse_path[1].fetch_add(1, std::memory_order_relaxed);
-  const DropRule dr = make_drop_rule(p, seed, salt, row_offset);
-  if (act_family(act) == AF_EXT)
-    return launch_sparse_fwd<AF_EXT, DropRule>(d_lists, d_w, d_b, d_y, ldy, M, N, K, act, as_stream(stream), dr);
-  return launch_sparse_fwd<AF_BASE, DropRule>(d_lists, d_w, d_b, d_y, ldy, M, N, K, act, as_stream(stream), dr);
+  if (p == 0.0)
+    return linear_fwd_sparse(d_lists, d_x, ldx, d_w, d_b, d_y, ldy, M, N, K, act, as_stream(stream), NoDrop{});
+  return linear_fwd_sparse(d_lists, d_x, ldx, d_w, d_b, d_y, ldy, M, N, K, act, as_stream(stream),
+                           make_drop_rule(p, seed, salt, row_offset));
 }
 
 extern "C" int itts_sparse_path_counts(int64_t out[3]) {

@@ -218,19 +218,12 @@ class FlatFFModel:
         for i in range(len(self.layout) if n_layers is None else n_layers):
             out = self._rows_buffer("h%d" % i, M, self.layout[i][2])
             p = self.dropouts[i] if training else 0.0
+            drop = ops._drop_args(p, seed, i, 0) if p > 0.0 else None
             if i == 0 and sparse:
                 self._lists = ops.sparse_rows_build(h, lists=self._lists, want_record=False)
-                if p > 0.0:
-                    h = ops.linear_fwd_sparse_dropout(self._lists, h, self.weight_padded(i), self.bias(i), self.acts[i],
-                                                      p=p, seed=seed, salt=i, out=out)
-                else:
-                    h = ops.linear_fwd_sparse(self._lists, h, self.weight_padded(i), self.bias(i), self.acts[i],
-                                              out=out)
-            elif p > 0.0:
-                h = ops.linear_fwd_dropout(h, self.weight_padded(i), self.bias(i), self.acts[i], p=p, seed=seed, salt=i,
-                                           out=out)
+                h = ops._linear_fwd_sparse(self._lists, h, self.weight_padded(i), self.bias(i), self.acts[i], out, drop)
             else:
-                h = ops.linear_fwd(h, self.weight_padded(i), self.bias(i), self.acts[i], out=out)
+                h = ops._linear_fwd(h, self.weight_padded(i), self.bias(i), self.acts[i], out, drop)
             acts.append(h)
         return acts
 
@@ -320,13 +313,9 @@ class FlatFFModel:
             if i > 0:
                 # dW, db and the input gradient of the layer in one call (one launch)
                 dz_in = self._rows_buffer("dz%d" % (i & 1), M, self.layout[i][3])
-                if drops[i - 1] > 0.0:
-                    ops.linear_bwd_dropout(dz, inp, self.weight_padded(i), self.weight_padded(i, self.grads),
-                                           self.bias(i, self.grads), dz_in, yprev=hs[i - 1], act_prev=self.acts[i - 1],
-                                           p=drops[i - 1], seed=seed, salt=i - 1)
-                else:
-                    ops.linear_bwd(dz, inp, self.weight_padded(i), self.weight_padded(i, self.grads),
-                                   self.bias(i, self.grads), dz_in, yprev=hs[i - 1], act_prev=self.acts[i - 1])
+                drop = ops._drop_args(drops[i - 1], seed, i - 1, 0) if drops[i - 1] > 0.0 else None
+                ops._linear_bwd(dz, inp, self.weight_padded(i), self.weight_padded(i, self.grads),
+                                self.bias(i, self.grads), dz_in, hs[i - 1], self.acts[i - 1], False, drop)
             elif self._wgrad_sparse_now:
                 # without a plan (dims[0] > 512) the entry point runs the dense product and counts it
                 if self._col_plan is not None:

@@ -661,11 +661,8 @@ class LinearChainFunction(torch.autograd.Function):
             w = w.contiguous()
             if i == 0 and h.shape[1] != K and h.shape[1] == (K + 3) // 4 * 4:
                 w = torch.nn.functional.pad(w, (0, h.shape[1] - K))
-            if drops is not None and drops[i][0] > 0:
-                h = ops.linear_fwd_dropout(h, w, b, acts[i], p=drops[i][0], seed=seed, salt=drops[i][1],
-                                           out=_rows_padded(h.shape[0], N, h.device))
-            else:
-                h = ops.linear_fwd(h, w, b, acts[i], out=_rows_padded(h.shape[0], N, h.device))
+            drop = ops._drop_args(drops[i][0], seed, drops[i][1], 0) if drops is not None and drops[i][0] > 0 else None
+            h = ops._linear_fwd(h, w, b, acts[i], _rows_padded(h.shape[0], N, h.device), drop)
             ws.append(w)
             hs.append(h)
         ctx.save_for_backward(x, *hs, *ws)
@@ -700,11 +697,9 @@ class LinearChainFunction(torch.autograd.Function):
             db = torch.empty((N,), dtype=torch.float32, device=x.device)
             if i > 0:
                 dz_in = _rows_padded(M, K, x.device)
-                if drops is not None and drops[i - 1][0] > 0:
-                    ops.linear_bwd_dropout(dz, hs[i - 1], w, dw, db, dz_in, yprev=hs[i - 1], act_prev=ctx.acts[i - 1],
-                                           p=drops[i - 1][0], seed=seed, salt=drops[i - 1][1])
-                else:
-                    ops.linear_bwd(dz, hs[i - 1], w, dw, db, dz_in, yprev=hs[i - 1], act_prev=ctx.acts[i - 1])
+                drop = (ops._drop_args(drops[i - 1][0], seed, drops[i - 1][1], 0)
+                        if drops is not None and drops[i - 1][0] > 0 else None)
+                ops._linear_bwd(dz, hs[i - 1], w, dw, db, dz_in, hs[i - 1], ctx.acts[i - 1], False, drop)
                 grads[2 * i], grads[2 * i + 1] = dw, db
                 dz = dz_in
             else:

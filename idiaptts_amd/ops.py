@@ -453,7 +453,9 @@ def feature_stats(x, col0, width, want_cov, sums=None, second=None):
 
 
 # ------------------------------------------------------------------------------ dense layers
-def linear_fwd(x, w, b, act=ACT_NONE, out=None):
+# Each product below is written once, for the plain entry point and for its _dropout form: `drop` is None, or the rule
+# as _drop_args(p, seed, salt, row_offset) gives it, which goes in front of the stream.
+def _linear_fwd(x, w, b, act, out, drop):
     L = _lib.load()
     _need(x, torch.float32, "x")
     _need(w, torch.float32, "w")
@@ -463,9 +465,16 @@ def linear_fwd(x, w, b, act=ACT_NONE, out=None):
         raise ValueError("w must be contiguous [N, K]")
     if out is None:
         out = torch.empty((M, N), dtype=torch.float32, device=x.device)
-    _lib.check(L.itts_linear_fwd(_ptr(x), _rows(x, "x"), _ptr(w), _ptr(b), _ptr(out),
-                                 _rows(out, "out"), M, N, K, act, _stream()), "itts_linear_fwd")
+    args = (_ptr(x), _rows(x, "x"), _ptr(w), _ptr(b), _ptr(out), _rows(out, "out"), M, N, K, act, _stream())
+    if drop is None:
+        _lib.check(L.itts_linear_fwd(*args), "itts_linear_fwd")
+    else:
+        _lib.check(L.itts_linear_fwd_dropout(*args[:-1], *drop, args[-1]), "itts_linear_fwd_dropout")
     return out
+
+
+def linear_fwd(x, w, b, act=ACT_NONE, out=None):
+    return _linear_fwd(x, w, b, act, out, None)
 
 
 class SparseRows(object):
@@ -517,10 +526,7 @@ def sparse_rows_build(x, K=None, lists=None, want_record=True):
     return rows
 
 
-def linear_fwd_sparse(rows, x, w, b, act=ACT_NONE, out=None):
-    """ops.linear_fwd(x, w, b, act) through the row lists `rows` built from x (one fmaf chain per output over the
-    row's non-zeros in ascending k); x itself is read only where the shape sends the call to the dense product
-    (K > 512)."""
+def _linear_fwd_sparse(rows, x, w, b, act, out, drop):
     L = _lib.load()
     _need(x, torch.float32, "x")
     _need(w, torch.float32, "w")
@@ -532,9 +538,20 @@ def linear_fwd_sparse(rows, x, w, b, act=ACT_NONE, out=None):
         raise ValueError("the row lists were built for another shape")
     if out is None:
         out = torch.empty((M, N), dtype=torch.float32, device=x.device)
-    _lib.check(L.itts_linear_fwd_sparse(_ptr(rows.block), _ptr(x), _rows(x, "x"), _ptr(w), _ptr(b), _ptr(out),
-                                        _rows(out, "out"), M, N, K, act, _stream()), "itts_linear_fwd_sparse")
+    args = (_ptr(rows.block), _ptr(x), _rows(x, "x"), _ptr(w), _ptr(b), _ptr(out), _rows(out, "out"), M, N, K, act,
+            _stream())
+    if drop is None:
+        _lib.check(L.itts_linear_fwd_sparse(*args), "itts_linear_fwd_sparse")
+    else:
+        _lib.check(L.itts_linear_fwd_sparse_dropout(*args[:-1], *drop, args[-1]), "itts_linear_fwd_sparse_dropout")
     return out
+
+
+def linear_fwd_sparse(rows, x, w, b, act=ACT_NONE, out=None):
+    """ops.linear_fwd(x, w, b, act) through the row lists `rows` built from x (one fmaf chain per output over the
+    row's non-zeros in ascending k); x itself is read only where the shape sends the call to the dense product
+    (K > 512)."""
+    return _linear_fwd_sparse(rows, x, w, b, act, out, None)
 
 
 SparsePathCounts = collections.namedtuple("SparsePathCounts", "builds fwd_sparse fwd_dense")
@@ -725,18 +742,25 @@ def batch_pad_colsum(padded, lens, batch_first, out=None):
     return out
 
 
-def linear_bwd_input(dz, w, yprev=None, act_prev=ACT_NONE, out=None):
+def _linear_bwd_input(dz, w, yprev, act_prev, out, drop):
     L = _lib.load()
     _need(dz, torch.float32, "dz")
     M, N = dz.shape
     K = w.shape[1]
     if out is None:
         out = torch.empty((M, K), dtype=torch.float32, device=dz.device)
-    _lib.check(L.itts_linear_bwd_input(_ptr(dz), _rows(dz, "dz"), _ptr(w), _ptr(out),
-                                       _rows(out, "out"), _ptr(yprev),
-                                       _rows(yprev, "yprev") if yprev is not None else 0,
-                                       act_prev, M, N, K, _stream()), "itts_linear_bwd_input")
+    args = (_ptr(dz), _rows(dz, "dz"), _ptr(w), _ptr(out), _rows(out, "out"), _ptr(yprev),
+            _rows(yprev, "yprev") if yprev is not None else 0, int(act_prev if act_prev is not None else ACT_NONE),
+            M, N, K, _stream())
+    if drop is None:
+        _lib.check(L.itts_linear_bwd_input(*args), "itts_linear_bwd_input")
+    else:
+        _lib.check(L.itts_linear_bwd_input_dropout(*args[:-1], *drop, args[-1]), "itts_linear_bwd_input_dropout")
     return out
+
+
+def linear_bwd_input(dz, w, yprev=None, act_prev=ACT_NONE, out=None):
+    return _linear_bwd_input(dz, w, yprev, act_prev, out, None)
 
 
 _ws_cache = {}
@@ -1101,10 +1125,7 @@ def conv1d_bwd_weight(dz, x, kernel_size, padding, dilation, batch_first, dw=Non
     return dw, db
 
 
-def linear_bwd(dz, x, w, dw, db, dx, yprev=None, act_prev=ACT_NONE, accumulate=False):
-    """dw [N, K] (+ db [N]) and dx [M, K] of a linear layer from dz [M, N], its input x [M, K] and its
-    weight w [N, K] in one call (one launch when the buffers allow 16-byte rows); dx is multiplied by
-    the derivative of the previous layer's activation when yprev (that layer's output) is given."""
+def _linear_bwd(dz, x, w, dw, db, dx, yprev, act_prev, accumulate, drop):
     L = _lib.load()
     _need(dz, torch.float32, "dz")
     _need(x, torch.float32, "x")
@@ -1114,12 +1135,22 @@ def linear_bwd(dz, x, w, dw, db, dx, yprev=None, act_prev=ACT_NONE, accumulate=F
     if w.shape != (N, K) or not w.is_contiguous() or not dw.is_contiguous() or dw.shape != (N, K):
         raise ValueError("w and dw must be contiguous [N, K]")
     ws = _workspace(L.itts_linear_bwd_weight_workspace_bytes(M, N, K), dz.device)
-    _lib.check(L.itts_linear_bwd(_ptr(dz), _rows(dz, "dz"), _ptr(x), _rows(x, "x"), _ptr(w), _ptr(dw),
-                                 _ptr(db), _ptr(dx), _rows(dx, "dx"), _ptr(yprev),
-                                 _rows(yprev, "yprev") if yprev is not None else 0,
-                                 int(act_prev if act_prev is not None else ACT_NONE), M, N, K, _ptr(ws),
-                                 1 if accumulate else 0, _stream()), "itts_linear_bwd")
+    args = (_ptr(dz), _rows(dz, "dz"), _ptr(x), _rows(x, "x"), _ptr(w), _ptr(dw), _ptr(db), _ptr(dx), _rows(dx, "dx"),
+            _ptr(yprev), _rows(yprev, "yprev") if yprev is not None else 0,
+            int(act_prev if act_prev is not None else ACT_NONE), M, N, K, _ptr(ws), 1 if accumulate else 0,
+            _stream())
+    if drop is None:
+        _lib.check(L.itts_linear_bwd(*args), "itts_linear_bwd")
+    else:
+        _lib.check(L.itts_linear_bwd_dropout(*args[:-1], *drop, args[-1]), "itts_linear_bwd_dropout")
     return dw, db, dx
+
+
+def linear_bwd(dz, x, w, dw, db, dx, yprev=None, act_prev=ACT_NONE, accumulate=False):
+    """dw [N, K] (+ db [N]) and dx [M, K] of a linear layer from dz [M, N], its input x [M, K] and its
+    weight w [N, K] in one call (one launch when the buffers allow 16-byte rows); dx is multiplied by
+    the derivative of the previous layer's activation when yprev (that layer's output) is given."""
+    return _linear_bwd(dz, x, w, dw, db, dx, yprev, act_prev, accumulate, None)
 
 
 # ------------------------------------------------------------------------------ dropout (csrc/dropout.h)
@@ -1193,76 +1224,23 @@ def dropout_act_bwd(dy, d, act, p, seed, salt, row_offset=0, out=None):
 
 def linear_fwd_dropout(x, w, b, act=ACT_NONE, p=0.0, seed=0, salt=0, row_offset=0, out=None):
     """linear_fwd with dropout on the output, applied in the product's epilogue"""
-    L = _lib.load()
-    _need(x, torch.float32, "x")
-    _need(w, torch.float32, "w")
-    M, K = x.shape
-    N = w.shape[0]
-    if w.shape[1] != K or not w.is_contiguous():
-        raise ValueError("w must be contiguous [N, K]")
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.float32, device=x.device)
-    _lib.check(L.itts_linear_fwd_dropout(_ptr(x), _rows(x, "x"), _ptr(w), _ptr(b), _ptr(out), _rows(out, "out"), M, N,
-                                         K, act, *_drop_args(p, seed, salt, row_offset), _stream()),
-               "itts_linear_fwd_dropout")
-    return out
+    return _linear_fwd(x, w, b, act, out, _drop_args(p, seed, salt, row_offset))
 
 
 def linear_fwd_sparse_dropout(rows, x, w, b, act=ACT_NONE, p=0.0, seed=0, salt=0, row_offset=0, out=None):
     """linear_fwd_sparse with dropout on the output"""
-    L = _lib.load()
-    _need(x, torch.float32, "x")
-    _need(w, torch.float32, "w")
-    M, K = x.shape
-    N = w.shape[0]
-    if w.shape[1] != K or not w.is_contiguous():
-        raise ValueError("w must be contiguous [N, K]")
-    if rows.M != M or rows.K != K:
-        raise ValueError("the row lists were built for another shape")
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.float32, device=x.device)
-    _lib.check(L.itts_linear_fwd_sparse_dropout(_ptr(rows.block), _ptr(x), _rows(x, "x"), _ptr(w), _ptr(b), _ptr(out),
-                                                _rows(out, "out"), M, N, K, act,
-                                                *_drop_args(p, seed, salt, row_offset), _stream()),
-               "itts_linear_fwd_sparse_dropout")
-    return out
+    return _linear_fwd_sparse(rows, x, w, b, act, out, _drop_args(p, seed, salt, row_offset))
 
 
 def linear_bwd_input_dropout(dz, w, yprev, act_prev=ACT_NONE, p=0.0, seed=0, salt=0, row_offset=0, out=None):
     """linear_bwd_input where yprev, the previous layer's output, carries the dropout (p, seed, salt, row_offset)"""
-    L = _lib.load()
-    _need(dz, torch.float32, "dz")
-    M, N = dz.shape
-    K = w.shape[1]
-    if out is None:
-        out = torch.empty((M, K), dtype=torch.float32, device=dz.device)
-    _lib.check(L.itts_linear_bwd_input_dropout(_ptr(dz), _rows(dz, "dz"), _ptr(w), _ptr(out), _rows(out, "out"),
-                                               _ptr(yprev), _rows(yprev, "yprev") if yprev is not None else 0,
-                                               int(act_prev if act_prev is not None else ACT_NONE), M, N, K,
-                                               *_drop_args(p, seed, salt, row_offset), _stream()),
-               "itts_linear_bwd_input_dropout")
-    return out
+    return _linear_bwd_input(dz, w, yprev, act_prev, out, _drop_args(p, seed, salt, row_offset))
 
 
 def linear_bwd_dropout(dz, x, w, dw, db, dx, yprev, act_prev=ACT_NONE, p=0.0, seed=0, salt=0, row_offset=0,
                        accumulate=False):
     """linear_bwd where yprev, the previous layer's output, carries the dropout (p, seed, salt, row_offset)"""
-    L = _lib.load()
-    _need(dz, torch.float32, "dz")
-    _need(x, torch.float32, "x")
-    _need(w, torch.float32, "w")
-    M, N = dz.shape
-    K = x.shape[1]
-    if w.shape != (N, K) or not w.is_contiguous() or not dw.is_contiguous() or dw.shape != (N, K):
-        raise ValueError("w and dw must be contiguous [N, K]")
-    ws = _workspace(L.itts_linear_bwd_weight_workspace_bytes(M, N, K), dz.device)
-    _lib.check(L.itts_linear_bwd_dropout(_ptr(dz), _rows(dz, "dz"), _ptr(x), _rows(x, "x"), _ptr(w), _ptr(dw),
-                                         _ptr(db), _ptr(dx), _rows(dx, "dx"), _ptr(yprev),
-                                         _rows(yprev, "yprev") if yprev is not None else 0,
-                                         int(act_prev if act_prev is not None else ACT_NONE), M, N, K, _ptr(ws),
-                                         1 if accumulate else 0, *_drop_args(p, seed, salt, row_offset), _stream()),
-               "itts_linear_bwd_dropout")
-    return dw, db, dx
+    return _linear_bwd(dz, x, w, dw, db, dx, yprev, act_prev, accumulate, _drop_args(p, seed, salt, row_offset))
 
 
 def masked_mse(pred, target, row_valid, n_valid, loss_weight=1.0, want_grad=True, grad=None):

@@ -195,8 +195,10 @@ def test_input_gradient_and_fused_backward(gpu, kernel, act):
                 assert torch.equal(_bits(t), _bits(t0)), (what, "an input was written")
             check_out_frame(out, K, lay, kernel == "ring", what)
             # both gradients in one call: dw / db are the plain call's on the same operands, dx the separate call's
-            dw0, db0 = torch.empty(N, K, device=gpu), torch.empty(N, device=gpu)
-            dw1, db1 = torch.empty(N, K, device=gpu), torch.empty(N, device=gpu)
+            # (db right behind dw for both, as the flat gradient arenas hold them: whether one reduction serves the two
+            # depends on that, and two separate allocations may or may not come out adjacent)
+            (dw0, db0), (dw1, db1) = (torch.empty(N * K + N, device=gpu).split([N * K, N]) for _ in range(2))
+            dw0, dw1 = dw0.view(N, K), dw1.view(N, K)
             dx0, o0 = frame_out(M, K, lay, gpu)
             dx1, o1 = frame_out(M, K, lay, gpu)
             ops.linear_bwd(zv, dv, wv, dw0, db0, o0, yprev=dv, act_prev=act)
@@ -248,6 +250,24 @@ def test_p_zero_is_the_plain_entry_point(gpu):
         fn(dz, x, w, dw, db, dx, yprev=x, act_prev=ops.ACT_TANH, **kw)
         outs.append((dw, db, dx, ops.gemm_last_plan()))
     assert outs[0][3] == outs[1][3] and all(torch.equal(a, b_) for a, b_ in zip(outs[0][:3], outs[1][:3]))
+    # operands that cannot take the ring kernel: the separate weight and input gradient, for p == 0 as well
+    Mu, Nu, Ku = 65, 97, 16
+    (_, zu), (_, wu), (_, yu) = (frame_in(torch.rand(Mu, Nu, generator=g) - 0.25, "u", gpu),
+                                 flat_in(torch.rand(Nu, Ku, generator=g) - 0.5, "u", gpu),
+                                 frame_in(torch.tanh(torch.randn(Mu, Ku, generator=g)), "u", gpu))
+    outs = []
+    for fn_in, fn, kw in ((ops.linear_bwd_input, ops.linear_bwd, {}),
+                          (ops.linear_bwd_input_dropout, ops.linear_bwd_dropout, rule)):
+        _, dxi = frame_out(Mu, Ku, "u", gpu)
+        fn_in(zu, wu, yu, ops.ACT_TANH, out=dxi, **kw)
+        plan_in = ops.gemm_last_plan()
+        dw, db, (_, dx) = torch.empty(Nu, Ku, device=gpu), torch.empty(Nu, device=gpu), frame_out(Mu, Ku, "u", gpu)
+        fn(zu, yu, wu, dw, db, dx, yprev=yu, act_prev=ops.ACT_TANH, **kw)
+        outs.append((dxi.clone(), dw, db, dx.clone(), plan_in, ops.gemm_last_plan()))
+    kinds = [getattr(e, "kernel", "reduce") for e in outs[0][5]]
+    assert _one(outs[0][4]).kernel == "staged" and kinds == ["staged", "reduce", "reduce", "staged"], outs[0][4:]
+    assert outs[0][4:] == outs[1][4:] and all(torch.equal(_bits(a), _bits(b_)) for a, b_ in zip(outs[0][:4], outs[1][:4]))
+    assert torch.equal(_bits(outs[0][0]), _bits(outs[0][3])), "fused and separate input gradients differ"
     assert torch.equal(ops.dropout_apply(dz, 0.0, 1, 2), dz)
     assert torch.equal(ops.dropout_act_bwd(dz, y0, ops.ACT_TANH, 0.0, 1, 2), ops.act_bwd(dz, y0, ops.ACT_TANH))
 
