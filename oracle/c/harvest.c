@@ -203,11 +203,74 @@ static void refined_f0(const double* x, int xl, double fs, double pos, double f0
 }
 
 /* ---- contour fixing ------------------------------------------------------------------------- */
+/* Counters next to the decisions of the contour code (they change no result): how often the last
+ * orc_harvest_debug call took each branch, and how close each thresholded decision came to its
+ * threshold.  The tests use them to prove that their inputs reach a branch, and that no decision
+ * is close enough to flip under the rounding differences of another implementation. */
+#define HB_LIST(X)                                                                              \
+  X(step2_removes_short_section)     /* FixStep2 zeroes a section shorter than 6 frames */      \
+  X(extend_stops_after_4_misses)                                                                \
+  X(extend_runs_100_frames)                                                                     \
+  X(extend_cut_by_contour_end)       /* either side: fewer than 100 frames were left */         \
+  X(extend_meets_contour_start)      /* ... backwards, down to frame 0 */                       \
+  X(extend_meets_contour_finish)     /* ... forwards, up to frame T - 1 */                      \
+  X(sub_rejects_section)             /* ExtendSub: 2200 / mean >= ed - st */                    \
+  X(sub_real_swap)                   /* selected at an index other than its own */              \
+  X(sub_selects_nothing)             /* count == 0 although sections exist */                   \
+  X(sub_first_rejected_later_selected) /* selected channel 0 is not section 0 */                \
+  X(sub_carried_mean_decides)        /* the section's own mean would have decided otherwise */  \
+  X(merge_disjoint)                                                                             \
+  X(merge_contained)                                                                            \
+  X(merge_overlap_first_wins)        /* s1 > s2 */                                              \
+  X(merge_overlap_second_wins)                                                                  \
+  X(merge_order_not_identity)                                                                   \
+  X(merge_channel0_later_in_order)   /* channel 0 is not the first of the sorted order */       \
+  X(merge_channel0_after_rewrite)    /* ... nor the second: boundary[0..1] was rewritten */     \
+  X(merge_score_tie)                 /* s1 == s2 exactly */                                     \
+  X(step4_bridges_gap)                                                                          \
+  X(smooth_more_than_3_sections)                                                                \
+  /* sizes, not branches */                                                                     \
+  X(sections)                        /* sections entering FixStep3 */                           \
+  X(selected_sections)               /* ExtendSub's count */                                    \
+  X(smooth_sections)                 /* sections of the smoothing call */
+#define HM_LIST(X)                                                                              \
+  X(step1_slope)                     /* | |f - ref| / ref          - 0.008 | */                 \
+  X(step1_previous)                  /* | |f - prev| / prev        - 0.008 | */                 \
+  X(extend_select)                   /* | |ref - cand| / ref       - 0.18  | */                 \
+  X(sub_length)                      /* | 2200 / mean - (ed - st) | / (ed - st) */              \
+  X(merge_score)                     /* | s1 - s2 | / max(s1, s2), exact ties left out */
+#define HB_ENUM(n) HB_##n,
+#define HM_ENUM(n) HM_##n,
+#define HB_NAME(n) #n,
+enum { HB_LIST(HB_ENUM) HB_COUNT };
+enum { HM_LIST(HM_ENUM) HM_COUNT };
+static const char* const HB_NAMES[] = {HB_LIST(HB_NAME)};
+static const char* const HM_NAMES[] = {HM_LIST(HB_NAME)};
+static int g_branch[HB_COUNT];
+static double g_margin[HM_COUNT];
+static int g_in_extend = 0;
+
+static void margin(int which, double distance) {
+  if (distance < g_margin[which]) g_margin[which] = distance;  /* a NaN never enters */
+}
+
+int orc_harvest_branch_names(const char** names, int cap) {
+  for (int i = 0; i < HB_COUNT && i < cap; ++i) names[i] = HB_NAMES[i];
+  return HB_COUNT;
+}
+void orc_harvest_branch_counts(int* counts) { memcpy(counts, g_branch, sizeof(g_branch)); }
+int orc_harvest_margin_names(const char** names, int cap) {
+  for (int i = 0; i < HM_COUNT && i < cap; ++i) names[i] = HM_NAMES[i];
+  return HM_COUNT;
+}
+void orc_harvest_margins(double* margins) { memcpy(margins, g_margin, sizeof(g_margin)); }
+
 static double select_best_f0(double ref, const double* cands, int nc, double allowed, double* err) {
   double best = 0.0;
   *err = allowed;
   for (int i = 0; i < nc; ++i) {
     const double t = fabs(ref - cands[i]) / ref;
+    if (g_in_extend && cands[i] != 0.0) margin(HM_extend_select, fabs(t - allowed));
     if (t > *err) continue;
     best = cands[i];
     *err = t;
@@ -244,6 +307,8 @@ static int extend_f0(int origin, int last, int shift, const double* cand, int ld
   const int distance = abs(last - origin);
   int count = 0;
   double dummy;
+  int broke = 0;
+  g_in_extend = 1;
   for (int i = 0; i <= distance; ++i) {
     const int at = origin + shift * i + shift;
     ext[at] = select_best_f0(tmp, cand + (size_t)at * ldc, nc, allowed, &dummy);
@@ -254,7 +319,19 @@ static int extend_f0(int origin, int last, int shift, const double* cand, int ld
       count = 0;
       shifted = at;
     }
-    if (count == threshold) break;
+    if (count == threshold) {
+      broke = 1;
+      break;
+    }
+  }
+  g_in_extend = 0;
+  if (broke) {
+    g_branch[HB_extend_stops_after_4_misses]++;
+  } else if (distance == 100) {
+    g_branch[HB_extend_runs_100_frames]++;
+  } else {
+    g_branch[HB_extend_cut_by_contour_end]++;
+    g_branch[shift < 0 ? HB_extend_meets_contour_start : HB_extend_meets_contour_finish]++;
   }
   return shifted;
 }
@@ -268,12 +345,20 @@ static double search_score(double f0, const double* cands, const double* scores,
 
 static int merge_sub(const double* f1, int st1, int ed1, const double* f2, int st2, int ed2,
                      const double* cand, const double* scr, int ldc, int nc, double* merged) {
-  if (st1 <= st2 && ed1 >= ed2) return ed1;
+  if (st1 <= st2 && ed1 >= ed2) {
+    g_branch[HB_merge_contained]++;
+    return ed1;
+  }
   double s1 = 0.0, s2 = 0.0;
   for (int i = st2; i <= ed1; ++i) {
     s1 += search_score(f1[i], cand + (size_t)i * ldc, scr + (size_t)i * ldc, nc);
     s2 += search_score(f2[i], cand + (size_t)i * ldc, scr + (size_t)i * ldc, nc);
   }
+  if (s1 == s2)
+    g_branch[HB_merge_score_tie]++;
+  else
+    margin(HM_merge_score, fabs(s1 - s2) / (s1 > s2 ? s1 : s2));
+  g_branch[s1 > s2 ? HB_merge_overlap_first_wins : HB_merge_overlap_second_wins]++;
   if (s1 > s2)
     for (int i = ed1; i <= ed2; ++i) merged[i] = f2[i];
   else
@@ -287,6 +372,7 @@ static void fix_step3(const double* in, int T, int nc, const double* cand, const
   int* bl = (int*)malloc(sizeof(int) * (T + 2));
   const int nb = boundary_list(in, T, bl);
   const int ns = nb / 2;
+  g_branch[HB_sections] = ns;
   if (ns == 0) {
     free(bl);
     return;
@@ -308,9 +394,19 @@ static void fix_step3(const double* in, int T, int nc, const double* cand, const
   double mean = 0.0;
   for (int i = 0; i < ns; ++i) {
     const int st = bl[i * 2], ed = bl[i * 2 + 1];
+    const double carried = mean;
     for (int j = st; j < ed; ++j) mean += mc[i][j];
     mean /= ed - st;
+    {
+      const double own = mean - carried / (ed - st);
+      if ((2200.0 / own < ed - st) != (2200.0 / mean < ed - st))
+        g_branch[HB_sub_carried_mean_decides]++;
+    }
+    margin(HM_sub_length, fabs(2200.0 / mean - (ed - st)) / (ed - st));
+    if (!(2200.0 / mean < ed - st)) g_branch[HB_sub_rejects_section]++;
     if (2200.0 / mean < ed - st) {
+      if (i != count) g_branch[HB_sub_real_swap]++;
+      if (count == 0 && i != 0) g_branch[HB_sub_first_rejected_later_selected]++;
       double* tp = mc[count];
       mc[count] = mc[i];
       mc[i] = tp;
@@ -323,6 +419,8 @@ static void fix_step3(const double* in, int T, int nc, const double* cand, const
       count++;
     }
   }
+  g_branch[HB_selected_sections] = count;
+  if (count == 0) g_branch[HB_sub_selects_nothing]++;
   if (count != 0) {
     /* MergeF0 */
     int* order = (int*)malloc(sizeof(int) * count);
@@ -336,10 +434,18 @@ static void fix_step3(const double* in, int T, int nc, const double* cand, const
         } else {
           break;
         }
+    for (int i = 0; i < count; ++i)
+      if (order[i] != i) {
+        g_branch[HB_merge_order_not_identity]++;
+        break;
+      }
     for (int i = 0; i < T; ++i) out[i] = mc[0][i];
     for (int i = 1; i < count; ++i) {
       const int o = order[i];
+      if (o == 0) g_branch[HB_merge_channel0_later_in_order]++;
+      if (o == 0 && i >= 2) g_branch[HB_merge_channel0_after_rewrite]++;
       if (bl[o * 2] - bl[1] > 0) {
+        g_branch[HB_merge_disjoint]++;
         for (int j = bl[o * 2]; j <= bl[o * 2 + 1]; ++j) out[j] = mc[o][j];
         bl[0] = bl[o * 2];
         bl[1] = bl[o * 2 + 1];
@@ -372,7 +478,9 @@ static void fix_contour(const double* cand, const double* scr, int T, int nc, in
   for (int i = 2; i < T; ++i) {
     if (tmp[i] == 0.0) continue;
     const double ref = tmp[i - 1] * 2 - tmp[i - 2];
-    best[i] = (fabs((tmp[i] - ref) / ref) > 0.008 && fabs(tmp[i] - tmp[i - 1]) / tmp[i - 1] > 0.008)
+    margin(HM_step1_slope, fabs(fabs((tmp[i] - ref) / ref) - 0.008));
+    margin(HM_step1_previous, fabs(fabs(tmp[i] - tmp[i - 1]) / tmp[i - 1] - 0.008));
+    best[i] =(fabs((tmp[i] - ref) / ref) > 0.008 && fabs(tmp[i] - tmp[i - 1]) / tmp[i - 1] > 0.008)
                   ? 0.0
                   : tmp[i];
   }
@@ -381,6 +489,7 @@ static void fix_contour(const double* cand, const double* scr, int T, int nc, in
   int nb = boundary_list(best, T, bl);
   for (int i = 0; i < nb / 2; ++i) {
     if (bl[i * 2 + 1] - bl[i * 2] >= 6) continue;
+    g_branch[HB_step2_removes_short_section]++;
     for (int j = bl[i * 2]; j <= bl[i * 2 + 1]; ++j) tmp[j] = 0.0;
   }
   /* FixStep3 (0.18) */
@@ -391,6 +500,7 @@ static void fix_contour(const double* cand, const double* scr, int T, int nc, in
   for (int i = 0; i < nb / 2 - 1; ++i) {
     const int distance = bl[(i + 1) * 2] - bl[i * 2 + 1] - 1;
     if (distance >= 9) continue;
+    g_branch[HB_step4_bridges_gap]++;
     const double t0 = best[bl[i * 2 + 1]] + 1;
     const double t1 = best[bl[(i + 1) * 2]] - 1;
     const double c = (t1 - t0) / (distance + 1.0);
@@ -413,6 +523,8 @@ static void smooth_contour(const double* f0, int T, double* out) {
   int* bl = (int*)malloc(sizeof(int) * (n + 2));
   for (int i = 0; i < T; ++i) c[i + lag] = f0[i];
   const int nb = boundary_list(c, n, bl);
+  g_branch[HB_smooth_sections] = nb / 2;
+  if (nb / 2 > 3) g_branch[HB_smooth_more_than_3_sections]++;
   for (int s = 0; s < nb / 2; ++s) {
     const int st = bl[s * 2], ed = bl[s * 2 + 1];
     for (int j = 0; j < st; ++j) xs[j] = c[st];
@@ -449,6 +561,8 @@ int orc_harvest_debug(const double* x, int xl, int fs, double frame_period, doub
   const double target_fs = 8000.0;
   const int r = hmax(hmin(orc_mround(fs / target_fs), 12), 1);
   const double cio = 40.0;
+  memset(g_branch, 0, sizeof(g_branch));
+  for (int i = 0; i < HM_COUNT; ++i) g_margin[i] = INFINITY;
   const double af = f0_floor * 0.9, ac = f0_ceil * 1.1;
   const int nch = 1 + (int)(log(ac / af) / log(2.0) * cio);
   double* bnd = (double*)malloc(sizeof(double) * nch);

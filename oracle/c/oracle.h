@@ -25,6 +25,12 @@ int orc_harvest(const double* x, int xl, int fs, double frame_period, double f0_
 int orc_harvest_debug(const double* x, int xl, int fs, double frame_period, double f0_floor,
                       double f0_ceil, double* f0_out, double* tp_out, double* raw_out,
                       double* cand_out, double* score_out, double* best_out, int* dims);
+/* what the contour code of the last orc_harvest_debug call decided: counts per branch and the
+ * smallest distance of every thresholded decision from its threshold (names: harvest.c) */
+int orc_harvest_branch_names(const char** names, int cap);
+void orc_harvest_branch_counts(int* counts);
+int orc_harvest_margin_names(const char** names, int cap);
+void orc_harvest_margins(double* margins);
 
 /* WORLD's randn() (common.cpp / matlabfunctions.cpp): xorshift128 with the fixed seed that
  * randn_reseed() restores at the start of CheapTrick / D4C / Synthesis; one normal deviate is

@@ -90,7 +90,8 @@ def harvest_num_frames(n, fs, frame_period=5.0):
 
 def harvest(x, fs, frame_period=5.0, f0_floor=71.0, f0_ceil=800.0, debug=False, mirror_write=True):
     """pyworld.harvest(x, fs, f0_floor, f0_ceil, frame_period) -> (f0, t); with `debug` also the
-    per-stage arrays (1 ms grid).  mirror_write=False drops the spectrum bins that
+    per-stage arrays (1 ms grid) and what the contour code decided (`branches`, `margins`:
+    _harvest_decisions).  mirror_write=False drops the spectrum bins that
     GetFilteredSignal overwrites while it multiplies (test decomposition only)."""
     _fn("orc_harvest_set_mirror_write", None, [c_int])(1 if mirror_write else 0)
     x = np.ascontiguousarray(x, dtype=np.float64)
@@ -116,8 +117,25 @@ def harvest(x, fs, frame_period=5.0, f0_floor=71.0, f0_ceil=800.0, debug=False, 
     assert fn(_p(x), len(x), fs, frame_period, f0_floor, f0_ceil, _p(f0), _p(tp), _p(raw),
               _p(cand), _p(score), _p(best), _p(dims)) == 0
     assert dims[0] == nch and dims[1] == T1 and dims[2] == maxc
+    branches, margins = _harvest_decisions()
     return f0, tp, dict(raw=raw, cand=cand, score=score, best=best, n_cand=int(dims[4]),
-                        y_length=int(dims[3]))
+                        y_length=int(dims[3]), branches=branches, margins=margins)
+
+
+def _harvest_decisions():
+    """What the contour code of the last orc_harvest_debug call decided: `branches`, name -> count
+    (three names are sizes: sections, selected_sections, smooth_sections), and `margins`, name ->
+    smallest distance of that thresholded decision from its threshold (inf: never taken)."""
+    names = (ctypes.c_char_p * 64)()
+    nb = _fn("orc_harvest_branch_names", c_int, [c_void_p, c_int])(names, 64)
+    counts = np.zeros(nb, dtype=np.int32)
+    _fn("orc_harvest_branch_counts", None, [c_void_p])(_p(counts))
+    branches = {names[i].decode(): int(counts[i]) for i in range(nb)}
+    nm = _fn("orc_harvest_margin_names", c_int, [c_void_p, c_int])(names, 64)
+    values = np.zeros(nm)
+    _fn("orc_harvest_margins", None, [c_void_p])(_p(values))
+    margins = {names[i].decode(): float(values[i]) for i in range(nm)}
+    return branches, margins
 
 
 def harvest_waveform(x, fs):
