@@ -41,6 +41,7 @@
 
 #include "common.h"
 #include "context.h"
+#include "rawwave.h"
 
 namespace itts {
 namespace {
@@ -201,15 +202,7 @@ void launch_mol(const MolArgs& a, int B, hipStream_t s) {
 }
 
 // ---- mu-law --------------------------------------------------------------------------------------------------
-// (((sign(x) * log(1 + mu |x|) / log(1 + mu)) + 1) * (mu / 2)) truncated toward zero, every operation rounded on its
-// own as numpy does (no fused multiply-add)
-__device__ __forceinline__ int64_t mulaw_index(double x, double mu, double log1pmu) {
-  const double sgn = (double)((x > 0.0) - (x < 0.0));
-  const double lg = log(__dadd_rn(1.0, __dmul_rn(mu, fabs(x))));
-  const double q = __ddiv_rn(__dmul_rn(sgn, lg), log1pmu);
-  return (int64_t)__dmul_rn(__dadd_rn(q, 1.0), mu / 2.0);
-}
-
+// (the index itself: mulaw_index, rawwave.h)
 __global__ __launch_bounds__(RW_THREADS) void mulaw_encode_kernel(const double* __restrict__ x, int64_t n, double mu,
                                                                   double log1pmu, int64_t* __restrict__ idx) {
   const int64_t i = (int64_t)blockIdx.x * RW_THREADS + threadIdx.x;
@@ -262,12 +255,8 @@ struct LinArgs {
   int D, m, sig0;
 };
 
-// scipy's interp1d(kind="linear") at numpy.linspace(0, T - 1, m T), operation by operation: x_j = j * ((T - 1) /
-// (m T - 1)); the interval is the one numpy.searchsorted(side="left") names, lo = ceil(x_j) - 1 clipped to 0 .. T - 2
-// (an x_j that is a whole number belongs to the interval on its left, at its end); slope = y_hi - y_lo in the INPUT's
-// precision (scipy subtracts the float32 rows before it divides by the float64 abscissae), then slope * (x_j - lo) +
-// y_lo in float64, product and sum rounded on their own.  The last row is the input's last row (there scipy's
-// slope * 1 + y_lo can miss y_hi by an ulp).
+// one element of the output a lane: row j = e / D of the signal's m T rows, column d (the arithmetic: lin_pos and
+// lin_value, rawwave.h)
 template <typename TI, typename TO>
 __global__ __launch_bounds__(RW_THREADS) void sample_linearly_kernel(LinArgs a) {
   const int sig = a.sig0 + blockIdx.y;
@@ -279,18 +268,7 @@ __global__ __launch_bounds__(RW_THREADS) void sample_linearly_kernel(LinArgs a) 
   const int d = (int)(e - j * a.D);
   const TI* x = reinterpret_cast<const TI*>(a.x) + begin * a.D + d;
   TO* y = reinterpret_cast<TO*>(a.y) + begin * a.m * a.D;
-  double v;
-  if (j == n_out - 1) {
-    v = (double)x[(T - 1) * a.D];
-  } else {
-    const double step = (double)(T - 1) / (double)(n_out - 1);
-    const double pos = __dmul_rn((double)j, step);
-    const int64_t lo = max((int64_t)0, min((int64_t)ceil(pos) - 1, T - 2));
-    const TI ylo = x[lo * a.D], yhi = x[(lo + 1) * a.D];
-    const TI slope = yhi - ylo;
-    v = __dadd_rn(__dmul_rn((double)slope, pos - (double)lo), (double)ylo);
-  }
-  y[e] = (TO)v;
+  y[e] = (TO)lin_value(x, a.D, lin_pos(j, T, n_out));
 }
 
 // offsets of a batch: ascending from 0; the longest signal

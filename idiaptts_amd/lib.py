@@ -245,6 +245,8 @@ _SIGNATURES = {
     "itts_wavenet_generate": (c_int, [_P] * 10 + [POINTER(c_int), c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_int, c_double, _P, c_int64, _P, POINTER(c_int), c_int, c_int64, c_int, _P,
                                       c_int64, _P, _P, _P]),
+    "itts_vocoder_windows": (c_int, [_P, c_int64, _P, c_int64, c_int, c_int, c_int, POINTER(c_int64), c_int, c_int64,
+                                     _P, _P, _P]),
     "itts_fixed_attention_plan": (c_int, [c_int, c_int64, c_int, c_int, c_int, c_int, POINTER(c_int64)]
                                   + [POINTER(c_int)] * 6),
     "itts_fixed_attention_fwd": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, c_int, c_int64, c_int, c_int,

@@ -2288,6 +2288,50 @@ def sample_linearly(x, offsets, m, dtype=torch.float32):
     return y, [o * m for o in offsets]
 
 
+VOCODER_WINDOW_FIELDS = 5
+
+
+def vocoder_windows(x, feat, windows, W, m, mu=255, target=None, cond=None):
+    """A training batch of the vocoder from the resident corpus, one launch (itts_vocoder_windows): `x` float64 [n]
+    samples and `feat` float32 [rows, cin] conditioning frames, the utterances back to back (`feat` None: no
+    conditioning); `windows` host int64 [B, 5] = (first sample in x, len, first frame row of the utterance, its T
+    frames, place a of the first sample in the utterance).  Returns (target [B, mu + 1, W] one-hot, or [B, 1, W]
+    samples with mu None / 0; cond [B, cin, W] or None): columns past a window's len are zeros, every element is
+    written.  `target` / `cond`: contiguous float32 buffers of those shapes to write into."""
+    import numpy as np
+    L = _lib.load()
+    mu = 0 if mu is None else int(mu)
+    W, m = int(W), int(m)
+    win = np.ascontiguousarray(np.asarray(windows, dtype=np.int64).reshape(-1, VOCODER_WINDOW_FIELDS))
+    B = win.shape[0]
+    _need(x, torch.float64, "x")
+    x = x.reshape(-1).contiguous()
+    cin = 0
+    if feat is not None:
+        _need(feat, torch.float32, "feat")
+        if feat.dim() != 2:
+            raise ValueError("feat must be [rows, cin], got {}".format(tuple(feat.shape)))
+        feat = feat.contiguous()
+        cin = feat.shape[1]
+    outs = []
+    for buf, name, shape in ((target, "target", (B, mu + 1, max(W, 0))), (cond, "cond", (B, cin, max(W, 0)))):
+        if name == "cond" and cin == 0:
+            outs.append(None)
+            continue
+        if buf is None:
+            buf = torch.empty(shape, dtype=torch.float32, device=x.device)
+        _need(buf, torch.float32, name)
+        if tuple(buf.shape) != shape or not buf.is_contiguous():
+            raise ValueError("{} must be a contiguous float32 {}".format(name, list(shape)))
+        outs.append(buf)
+    target, cond = outs
+    _lib.check(L.itts_vocoder_windows(_ptr(x), x.numel(), _ptr(feat) if cin else None,
+                                      feat.shape[0] if cin else 0, cin, m, mu,
+                                      (ctypes.c_int64 * win.size).from_buffer(win) if win.size else None, B, W,
+                                      _ptr(target), _ptr(cond), _stream()), "itts_vocoder_windows")
+    return target, cond
+
+
 # ---------------------------------------------------------------------------------------- WaveNet
 def _gate_rows(t, name, width=None):
     _need(t, torch.float32, name)

@@ -325,6 +325,14 @@ class ExponentialMovingAverage(object):
 
     def __init__(self, model, decay):
         import copy
+        from torch.nn.utils.weight_norm import WeightNorm
+        # torch.nn.utils.weight_norm keeps the derived weight g v / |v| as a plain attribute with a grad_fn, which
+        # deepcopy refuses (the WaveNet vocoder's convolutions); its forward pre-hook recomputes it on every call, so
+        # a detached value in its place changes nothing
+        for module in model.modules():
+            for hook in module._forward_pre_hooks.values():
+                if isinstance(hook, WeightNorm):
+                    setattr(module, hook.name, hook.compute_weight(module).detach())
         self.model = copy.deepcopy(model)
         self.decay = decay
         self.shadow = {}
@@ -539,7 +547,8 @@ class ModularModelHandlerPyTorch(object):
         return data, lengths
 
     def set_dataset(self, hparams, dataset_train, dataset_val, collate_fn=None):
-        if hparams.get_value("resident_dataset", False):
+        # (a dataset that batches itself on the device -- VocoderWindowSampler -- has nothing for the resident path)
+        if hparams.get_value("resident_dataset", False) and not self._batches_itself(dataset_train):
             return self._set_resident_dataset(hparams, dataset_train, dataset_val, collate_fn)
         self._resident = None
         self._set_loaders(hparams, dataset_train, dataset_val, collate_fn)
@@ -572,10 +581,15 @@ class ModularModelHandlerPyTorch(object):
         # in another mode is the exception): the frame-independent layers may then skip them (nn/functional.py)
         stock = collate_fn is None or collate_fn is self.prepare_batch \
             or getattr(collate_fn, "__func__", None) is ModularModelHandlerPyTorch.prepare_batch
-        self._stock_padding = bool(stock) and all(
+        self._stock_padding = bool(stock) and not self._batches_itself(dataset_train) and all(
             r.min_frames is None or getattr(r, "pad_mode", "constant") == "constant"
             for ds in (dataset_train, dataset_val) if ds is not None
             for r in getattr(ds, "datareaders", ()))
+
+    @staticmethod
+    def _batches_itself(dataset):
+        """True for an object that is its own loader (data_preparation/VocoderCorpus.py: VocoderWindowSampler)."""
+        return callable(getattr(dataset, "as_batch_loader", None))
 
     @staticmethod
     def _items_draw_random_numbers(dataset):
@@ -589,6 +603,9 @@ class ModularModelHandlerPyTorch(object):
     def _get_dataloader(self, batch_size, dataset, batch_first=True, collate_fn=None,
                         common_divisor=1, num_workers=1, pin_memory=True, shuffle=False,
                         worker_kind="process", device_cache=False, device_cache_bytes=None, host_cache_bytes=None):
+        if self._batches_itself(dataset):
+            # its batches are (data, lengths) pairs on the device already: no collate function, no cache, no workers
+            return dataset.as_batch_loader(batch_size=batch_size, shuffle=shuffle)
         stock = collate_fn is None or collate_fn is self.prepare_batch
         collate_fn = self.prepare_batch if collate_fn is None else collate_fn
         rank, world = parallel.dp_rank_world()

@@ -96,3 +96,73 @@ class WaveNetWrapper(nn.Module):
 
     def parameters(self):
         return self.model.parameters()
+
+
+class WaveNetVocoder(nn.Module):
+    """The wrapper as a dict-in / dict-out module, the form ModularModelHandlerPyTorch drives
+    (`model(data, lengths, max_lengths)`; the reference has no such module: its WaveNetVocoderTrainer predates the
+    modular handler).  `data[input_names[0]]` is the conditioning [B, cin, T] at the sample rate (not read when the
+    network has cin_channels 0), `data[target_name]` the one-hot / scalar target [B, C, T]; the logits [B, out_channels,
+    T] go to `data[output_names[0]]` with the target's lengths.  `inference` generates lengths[input_names[0]] *
+    len_in_out_multiplier samples a row and writes what WaveNetWrapper.forward(target=None) returns.
+    The state dict is the wrapper's under `model.` (`model.model.first_conv.weight_g`, ...)."""
+
+    class Config:
+        def __init__(self, wavenet_config, input_names=None, target_name="target", output_names=None,
+                     name="WaveNetVocoder", batch_first=True):
+            self.wavenet_config = wavenet_config
+            self.input_names = ["conditioning"] if input_names is None else list(input_names)
+            self.target_name = target_name
+            self.output_names = ["pred_target"] if output_names is None else list(output_names)
+            self.name = name
+            self.batch_first = batch_first
+
+        def create_model(self):
+            return WaveNetVocoder(self)
+
+    def __init__(self, config):
+        super().__init__()
+        if not config.batch_first:
+            raise NotImplementedError("WaveNetVocoder batch_first=False is not implemented: the network takes "
+                                      "[B, C, T].")
+        if len(config.input_names) != 1 or len(config.output_names) != 1:
+            raise ValueError("WaveNetVocoder takes one input name (the conditioning) and one output name, got {} and "
+                             "{}.".format(config.input_names, config.output_names))
+        self.config = config
+        self.input_names, self.output_names = list(config.input_names), list(config.output_names)
+        self.target_name, self.name, self.batch_first = config.target_name, config.name, config.batch_first
+        self.model = config.wavenet_config.create_model()
+
+    @property
+    def use_cond(self):
+        return self.model.model.cin_channels > 0
+
+    def init_hidden(self, batch_size=1):
+        return None
+
+    def _write(self, data, lengths, max_lengths, output, like):
+        name = self.output_names[0]
+        data[name] = output
+        lengths[name] = lengths[like]
+        max_lengths[name] = max_lengths[like] if like in max_lengths else output.shape[2]
+
+    def forward(self, data, lengths, max_lengths, **kwargs):
+        target = data.get(self.target_name)
+        if target is None:
+            return self.inference(data, lengths, max_lengths, **kwargs)
+        cond = data[self.input_names[0]] if self.use_cond else None
+        output, _ = self.model(cond, target, lengths[self.target_name])
+        self._write(data, lengths, max_lengths, output, self.target_name)
+
+    def inference(self, data, lengths, max_lengths, uniforms=None, generator=None):
+        first = self.input_names[0]
+        cond = data[first] if self.use_cond else None
+        output, _ = self.model(cond, None, lengths[first], uniforms=uniforms, generator=generator)
+        name = self.output_names[0]
+        data[name] = output
+        lengths[name] = torch.as_tensor(self.model._lengths(lengths[first]), dtype=torch.long)
+        max_lengths[name] = output.shape[2]
+
+
+# (the adapter's config by the wrapper's name as well: WaveNetWrapper.NamedConfig(wavenet_config, ...))
+WaveNetWrapper.NamedConfig = WaveNetVocoder.Config

@@ -1200,6 +1200,27 @@ int itts_wavenet_generate(const float* d_wf, const float* d_bf, const float* d_w
                           const float* d_u, const int* h_lengths, int B, int64_t T_out, int initial_class,
                           float* d_state, int64_t state_floats, void* d_out, float* d_logits, void* stream);
 
+/* ---- training batches of the vocoder from a device-resident corpus (csrc/vocoder_batch.hip; what
+ *      model_trainers/WaveNetVocoderTrainer.py:99-122, :141-173 gets from two readers, max_frames and a collate).
+ *
+ * itts_vocoder_windows: one launch writes the targets and the conditioning of B windows of W columns.  d_x [n_x]
+ *   float64 samples, the utterances back to back; d_feat [n_rows, cin] float32 conditioning frames, back to back.
+ *   h_windows [B, 5] host int64, per window: the index in d_x of its first sample; its length len, 1 .. W; the first
+ *   row of its utterance in d_feat; the utterance's T >= 2 frames; the place a of the first sample in the utterance,
+ *   a + len <= m T.  Sample a + j pairs with row a + j of itts_sample_linearly of the WHOLE utterance (m T rows), so a
+ *   window's conditioning equals the slice of the up-sampled utterance, bit for bit.  For j < len:
+ *     mu >= 1: d_target [B, mu + 1, W] (class-strided, as itts_softmax_xent_strided takes it) gets a 1 at the class
+ *              of itts_mulaw_encode_f64 and zeros elsewhere;  mu == 0: d_target [B, 1, W] = (float) x;
+ *     d_cond [B, cin, W] = the interpolated features (NULL with cin == 0; d_feat, n_rows and the last three window
+ *     fields are then not looked at).
+ *   Columns j >= len are zeros.  Every element of both outputs is written; lanes run along the columns, a lane
+ *   computes its class and its place among the frames once and writes its column.  A window's bits depend on its five
+ *   numbers alone (not on B or its place in the batch); no atomics: repeated calls give identical bits.  B == 0
+ *   succeeds and does nothing.  Envelope (anything else: ITTS_E_INVALID with a message naming the value, before any
+ *   device work): mu 0 .. 4095, cin 0 .. 128, m >= 1, W >= 1, B <= 65535, every window inside d_x and d_feat. */
+int itts_vocoder_windows(const double* d_x, int64_t n_x, const float* d_feat, int64_t n_rows, int cin, int m, int mu,
+                         const int64_t* h_windows, int B, int64_t W, float* d_target, float* d_cond, void* stream);
+
 /* ---- Fixed (duration-derived) attention of the encoder-decoder model (csrc/fixed_attention.hip) ------------------
  * float32; pitches (ld*) are floats from one row to the next, utterance steps (utt*) floats from one utterance to the
  * next, last extents have unit stride.  16-byte accesses where every pitch, step and base of a side (phoneme side: A
