@@ -152,6 +152,11 @@ _SIGNATURES = {
     "itts_layernorm_workspace_bytes": (c_int64, [c_int64, c_int]),
     "itts_layernorm_bwd": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P, _P, c_int64, _P, _P, c_int64,
                                    c_int, c_int, _P, _P]),
+    "itts_attention_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
+    "itts_attention_fwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int64, c_int64, c_double, c_uint64,
+                                   c_uint32, _P]),
+    "itts_attention_bwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int64, c_int64, c_double,
+                                   c_uint64, c_uint32, _P]),
     "itts_allpass_warp_fwd": (c_int, [_P, c_int64, _P, _P, _P, _P, c_int64, c_int64, c_int, c_int, _P]),
     "itts_allpass_warp_bwd": (c_int, [_P, c_int64, _P, c_int64, _P, _P, _P, _P, c_int64, _P, c_int64, c_int, c_int,
                                       _P]),

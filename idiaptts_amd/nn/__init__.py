@@ -1,3 +1,3 @@
 from .modules import (GRU, LSTM, RNN, AllPassWarp, GradientScaling, LinearAct, MeanPooling,  # noqa: F401
-                      MLPGLayer, SelectLastPooling, VanillaVAE)
+                      MLPGLayer, SelectLastPooling, TransformerEncoderLayer, VanillaVAE)
 from .wavenet import WaveNet  # noqa: F401

@@ -187,6 +187,28 @@ class LayerNormActFunction(torch.autograd.Function):
         return (dx if ctx.needs_input_grad[0] else None), dw, db, None, None, None
 
 
+class AttentionFunction(torch.autograd.Function):
+    """o = softmax(q k^T / sqrt(dh)) v per utterance and head on the in-projection's output qkv ([B, T, 3 D] when
+    batch_first, else [T, B, 3 D]): torch.nn.MultiheadAttention between its two projections, inside
+    torch.nn.TransformerEncoderLayer (rnn_dyn/FFWrapper.py:62-73 builds it by name).  klen: int32 [B] keys per
+    utterance on the device, or None for all T.  (p, seed, salt): dropout on the probabilities, p = 0 for none.
+    Saves qkv, o and the [B, nhead, T] log-sum-exp: no [T, T] tensor and no mask (csrc/attention.hip)."""
+
+    @staticmethod
+    def forward(ctx, qkv, klen, nhead, batch_first, p, seed, salt):
+        qkv = qkv.contiguous()
+        ctx.args = (int(nhead), klen, bool(batch_first), float(p), int(seed), int(salt))
+        o, lse = ops.attention_forward(qkv, *ctx.args)
+        ctx.save_for_backward(qkv, o, lse)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv, o, lse = ctx.saved_tensors
+        dqkv = ops.attention_backward(do.contiguous(), qkv, o, lse, *ctx.args)
+        return dqkv, None, None, None, None, None, None
+
+
 class AllPassWarpFunction(torch.autograd.Function):
     """y = all-pass warp of x by alpha (layers/AllPassWarp.py forward, with layers/AllPassWarpLayer.py's
     de-normalisation before and normalisation after inside the same kernel).  x: [.., .., D] with D = nb * N,

@@ -10,9 +10,10 @@ import torch
 from torch import nn
 
 from .. import ops
-from .functional import (AllPassWarpFunction, Conv1dActFunction, GRULayerFunction, LayerNormActFunction,
-                         LinearActFunction, LSTMLayerFunction, MlpgFunction, PackedBatch, RNNLayerFunction, StatesToCallerOrder,
-                         TimePoolFunction, VAEReparamFunction, grad_scaling)
+from .functional import (AllPassWarpFunction, AttentionFunction, ChainDropout, Conv1dActFunction, DropoutFunction,
+                         GRULayerFunction, LayerNormActFunction, LinearActFunction, LinearChainFunction, LSTMLayerFunction,
+                         MlpgFunction, PackedBatch, RNNLayerFunction, StatesToCallerOrder, TimePoolFunction,
+                         VAEReparamFunction, default_dropout_stream, grad_scaling)
 
 
 class LinearAct(nn.Linear):
@@ -89,6 +90,112 @@ class LayerNormAct(nn.LayerNorm):
             return y if self.act == ops.ACT_NONE else getattr(nn, ops.ACT_TORCH_NAME[self.act])()(y)
         return LayerNormActFunction.apply(input_, self.weight, self.bias, self.normalized_shape[0], self.eps,
                                           self.act)
+
+
+class _SelfAttentionParameters(nn.Module):
+    """The parameters of torch.nn.MultiheadAttention for self-attention with one embedding width, under its names
+    (`in_proj_weight`, `in_proj_bias`, `out_proj.weight`, `out_proj.bias`), created and initialised in its order:
+    the out-projection as a Linear, then xavier_uniform_ on the in-projection and zeros in both biases."""
+
+    def __init__(self, embed_dim, num_heads):
+        super().__init__()
+        self.embed_dim, self.num_heads = embed_dim, num_heads
+        self.in_proj_weight = nn.Parameter(torch.empty((3 * embed_dim, embed_dim)))
+        self.in_proj_bias = nn.Parameter(torch.empty(3 * embed_dim))
+        self.out_proj = nn.Linear(embed_dim, embed_dim)
+        nn.init.xavier_uniform_(self.in_proj_weight)
+        nn.init.constant_(self.in_proj_bias, 0.0)
+        nn.init.constant_(self.out_proj.bias, 0.0)
+
+    def extra_repr(self):
+        return "embed_dim={}, num_heads={}".format(self.embed_dim, self.num_heads)
+
+
+class TransformerEncoderLayer(nn.Module):
+    """torch.nn.TransformerEncoderLayer (same constructor arguments, parameter names, shapes and initial values,
+    so its state dicts and the reference's load key for key) on the HIP kernels: the in-projection is one GEMM to
+    [rows, 3 d_model], the attention core runs csrc/attention.hip (no [T, T] tensor), the out-projection is a GEMM,
+    the feed-forward is one LinearChainFunction node with ReLU and its dropouts fused, both norms run the LayerNorm
+    row kernel.  `norm_first` reorders, nothing else.
+
+    forward(x, lengths=None, mask_padding=False): x is [B, T, d_model] when batch_first, else [T, B, d_model].
+    Without lengths or with mask_padding=False every position of the padded tensor is a key (what the reference
+    computes: it passes no mask); with mask_padding=True the keys of utterance b are its first lengths[b] positions
+    (torch's src_key_padding_mask).  Every query position is computed either way.
+
+    `dropout` applies, as in torch, to the attention probabilities, behind the attention and the feed-forward
+    branches, and inside the feed-forward; in train() only.  Masks follow the counter rule of csrc/dropout.h: one
+    seed per forward from `nn.functional.DropoutStream`, and the salts 4 * salt + 0 .. 3 for the four places, `salt`
+    being the block's index in its model.
+
+    Refused by name (NotImplementedError): an activation other than "relu" (GELU needs the stored pre-activation),
+    a callable activation, bias=False, and sizes outside the kernel's envelope (ops.attention_check_envelope)."""
+
+    salt = 0
+
+    def __init__(self, d_model, nhead, dim_feedforward=2048, dropout=0.1, activation="relu", layer_norm_eps=1e-5,
+                 batch_first=False, norm_first=False, bias=True):
+        super().__init__()
+        if d_model % nhead != 0:
+            raise ValueError("d_model = {} must be divisible by nhead = {}".format(d_model, nhead))
+        if not isinstance(activation, str):
+            raise NotImplementedError("TransformerEncoderLayer activation {!r}: a callable activation is not "
+                                      "implemented, only \"relu\"".format(activation))
+        if activation != "relu":
+            raise NotImplementedError("TransformerEncoderLayer activation={!r} is not implemented, only \"relu\" "
+                                      "(the backward of GELU needs the stored pre-activation)".format(activation))
+        if not bias:
+            raise NotImplementedError("TransformerEncoderLayer bias=False is not implemented")
+        if not 0.0 <= float(dropout) < 1.0:
+            raise ValueError("TransformerEncoderLayer dropout must be in [0, 1), got {}".format(dropout))
+        ops.attention_check_envelope(d_model, nhead)
+        self.d_model, self.nhead, self.dim_feedforward = d_model, nhead, dim_feedforward
+        self.p = float(dropout)
+        self.batch_first, self.norm_first = bool(batch_first), bool(norm_first)
+        self.self_attn = _SelfAttentionParameters(d_model, nhead)
+        self.linear1 = LinearAct(d_model, dim_feedforward, act="relu")
+        self.linear2 = LinearAct(dim_feedforward, d_model)
+        self.norm1 = LayerNormAct(d_model, eps=layer_norm_eps)
+        self.norm2 = LayerNormAct(d_model, eps=layer_norm_eps)
+
+    def extra_repr(self):
+        return "d_model={}, nhead={}, dim_feedforward={}, dropout={}, batch_first={}, norm_first={}".format(
+            self.d_model, self.nhead, self.dim_feedforward, self.p, self.batch_first, self.norm_first)
+
+    def key_lengths(self, x, lengths):
+        """int32 [B] on x's device (what the kernel reads), clipped to the padded extent"""
+        T = x.shape[1 if self.batch_first else 0]
+        if torch.is_tensor(lengths) and lengths.dtype == torch.int32 and lengths.device == x.device:
+            return lengths
+        return torch.as_tensor(lengths).to(device=x.device, dtype=torch.int32).clamp(1, T).contiguous()
+
+    def _attention(self, x, klen, p, seed):
+        sa = self.self_attn
+        qkv = LinearActFunction.apply(x, sa.in_proj_weight, sa.in_proj_bias, ops.ACT_NONE)
+        a = AttentionFunction.apply(qkv, klen, self.nhead, self.batch_first, p, seed, 4 * self.salt)
+        a = LinearActFunction.apply(a, sa.out_proj.weight, sa.out_proj.bias, ops.ACT_NONE)
+        return DropoutFunction.apply(a, p, seed, 4 * self.salt + 1) if p > 0.0 else a
+
+    def _feed_forward(self, x, p, seed):
+        acts = (self.linear1.act, self.linear2.act)
+        if p > 0.0:
+            acts = ChainDropout(acts, ((p, 4 * self.salt + 2), (p, 4 * self.salt + 3)), seed)
+        rows = LinearChainFunction.apply(x.reshape(-1, x.shape[-1]), acts, self.linear1.weight, self.linear1.bias,
+                                         self.linear2.weight, self.linear2.bias)
+        return rows.reshape(x.shape)
+
+    def forward(self, x, lengths=None, mask_padding=False):
+        if x.dim() != 3 or x.shape[2] != self.d_model:
+            raise ValueError("TransformerEncoderLayer over d_model = {} got an input of shape {}"
+                             .format(self.d_model, tuple(x.shape)))
+        klen = self.key_lengths(x, lengths) if mask_padding and lengths is not None else None
+        p = self.p if self.training else 0.0
+        seed = default_dropout_stream().next() if p > 0.0 else 0
+        if self.norm_first:
+            x = x + self._attention(self.norm1(x), klen, p, seed)
+            return x + self._feed_forward(self.norm2(x), p, seed)
+        x = self.norm1(x + self._attention(x, klen, p, seed))
+        return self.norm2(x + self._feed_forward(x, p, seed))
 
 
 class AllPassWarp(nn.Module):

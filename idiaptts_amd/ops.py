@@ -1313,6 +1313,81 @@ def layer_norm_bwd(dy, x, mean, rstd, gamma, y=None, act=ACT_NONE, want_gamma=Tr
     return dx, dgamma, dbeta
 
 
+# the envelope of csrc/attention.hip (AT_*)
+ATTENTION_MIN_HEAD_DIM, ATTENTION_MAX_HEAD_DIM, ATTENTION_HEAD_DIM_STEP = 4, 128, 4
+ATTENTION_MAX_WIDTH, ATTENTION_MAX_TIME, ATTENTION_MAX_BATCH_HEADS = 1024, 32768, 65535
+
+
+def attention_check_envelope(d_model, nhead, T=None, B=None):
+    """NotImplementedError naming the value that the attention kernels do not take (d_model = nhead * dh)"""
+    dh = d_model // nhead
+    if (d_model != nhead * dh or dh % ATTENTION_HEAD_DIM_STEP
+            or not ATTENTION_MIN_HEAD_DIM <= dh <= ATTENTION_MAX_HEAD_DIM):
+        raise NotImplementedError("attention with head width d_model / nhead = {} / {}: the kernel takes multiples "
+                                  "of {} in {} .. {}".format(d_model, nhead, ATTENTION_HEAD_DIM_STEP,
+                                                             ATTENTION_MIN_HEAD_DIM, ATTENTION_MAX_HEAD_DIM))
+    if d_model > ATTENTION_MAX_WIDTH:
+        raise NotImplementedError("attention over d_model = {}: the kernel takes at most {}"
+                                  .format(d_model, ATTENTION_MAX_WIDTH))
+    if T is not None and not 1 <= T <= ATTENTION_MAX_TIME:
+        raise NotImplementedError("attention over T = {} positions: the kernel takes 1 .. {}"
+                                  .format(T, ATTENTION_MAX_TIME))
+    if B is not None and B * nhead > ATTENTION_MAX_BATCH_HEADS:
+        raise NotImplementedError("attention over B * nhead = {} * {}: the kernel takes at most {}"
+                                  .format(B, nhead, ATTENTION_MAX_BATCH_HEADS))
+
+
+def _attention_operands(qkv, nhead, klen, batch_first):
+    _need(qkv, torch.float32, "qkv")
+    if qkv.dim() != 3 or not qkv.is_contiguous() or qkv.shape[2] % 3:
+        raise ValueError("qkv must be a contiguous [B, T, 3 D] / [T, B, 3 D] tensor")
+    B, T = (qkv.shape[0], qkv.shape[1]) if batch_first else (qkv.shape[1], qkv.shape[0])
+    D = qkv.shape[2] // 3
+    attention_check_envelope(D, nhead, T if B else None, B)
+    if klen is not None:
+        _need(klen, torch.int32, "klen")
+        if klen.shape != (B,) or not klen.is_contiguous():
+            raise ValueError("klen must be a contiguous [{}] vector".format(B))
+    strides = (T, 1) if batch_first else (1, B)
+    return B, T, D, strides
+
+
+def attention_forward(qkv, nhead, klen=None, batch_first=True, p=0.0, seed=0, salt=0):
+    """softmax(q k^T / sqrt(dh)) v per utterance and head (torch.nn.MultiheadAttention between its projections):
+    qkv [B, T, 3 D] (batch_first) or [T, B, 3 D] as the in-projection writes it, klen [B] int32 keys per utterance
+    (None: T); every query t < T attends keys 0 .. klen[b] - 1.  p > 0: dropout on the probabilities, mask from
+    (seed, salt, (b * nhead + h) * T + t, key).  Returns (o in qkv's layout with D columns, lse [B, nhead, T])."""
+    L = _lib.load()
+    B, T, D, (sb, st) = _attention_operands(qkv, nhead, klen, batch_first)
+    o = torch.empty(qkv.shape[:2] + (D,), dtype=torch.float32, device=qkv.device)
+    lse = torch.empty((B, nhead, T), dtype=torch.float32, device=qkv.device)
+    if B * T:
+        pp, seed, salt, _ = _drop_args(p, seed, salt, 0)
+        _lib.check(L.itts_attention_fwd(_ptr(qkv), _ptr(o), _ptr(klen), _ptr(lse), B, T, nhead, D // nhead, sb, st,
+                                        pp, seed, salt, _stream()), "itts_attention_fwd")
+    return o, lse
+
+
+def attention_backward(do, qkv, o, lse, nhead, klen=None, batch_first=True, p=0.0, seed=0, salt=0):
+    """dqkv (qkv's shape: dq | dk | dv) of attention_forward from do, the forward's operands and outputs and the
+    same dropout rule; nothing but qkv, o and lse is stored between the two, and repeated calls give the same bits."""
+    L = _lib.load()
+    B, T, D, (sb, st) = _attention_operands(qkv, nhead, klen, batch_first)
+    for name, t in (("do", do), ("o", o)):
+        _need(t, torch.float32, name)
+        if t.shape != qkv.shape[:2] + (D,) or not t.is_contiguous():
+            raise ValueError("{} must be contiguous with the shape of the forward's output".format(name))
+    _need(lse, torch.float32, "lse")
+    if lse.shape != (B, nhead, T) or not lse.is_contiguous():
+        raise ValueError("lse must be the forward's [B, nhead, T] log-sum-exp")
+    dqkv = torch.empty_like(qkv)
+    if B * T:
+        pp, seed, salt, _ = _drop_args(p, seed, salt, 0)
+        _lib.check(L.itts_attention_bwd(_ptr(do), _ptr(qkv), _ptr(o), _ptr(klen), _ptr(lse), _ptr(dqkv), B, T, nhead,
+                                        D // nhead, sb, st, pp, seed, salt, _stream()), "itts_attention_bwd")
+    return dqkv
+
+
 ALLPASS_MAX_SIZE = 64            # kAllpassMaxN of csrc/allpass.h
 
 

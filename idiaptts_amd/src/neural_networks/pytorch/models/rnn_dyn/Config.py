@@ -2,8 +2,11 @@
 (idiaptts/src/neural_networks/pytorch/models/rnn_dyn/Config.py:12-138), restricted to the layer
 types on the accelerated path: Linear (+ activation, RNNDyn.LINEAR_NONLINS) groups, LSTM / GRU / RNN groups, Conv1d
 groups, LayerNorm (+ activation) groups, the pooling groups PoolLast / PoolMean (`LayerConfig("PoolLast",
-batch_first=True)`) and the VAE / VanillaVAE group (`LayerConfig("VAE", out_dim=latent_dim)`, last group only);
-LayerNorm, the pooling groups and VAE have no spelling in the legacy model string (the reference's grammar has none)."""
+batch_first=True)`), the VAE / VanillaVAE group (`LayerConfig("VAE", out_dim=latent_dim)`, last group only) and
+self-attention groups (`LayerConfig("TransformerEncoderLayer", num_layers=n, d_model=D, nhead=H, dim_feedforward=F,
+batch_first=..)`, with this package's own `mask_padding` and `layer_dropout`: RNNDyn.TransformerWrapper);
+LayerNorm, the pooling groups, VAE and TransformerEncoderLayer have no spelling in the legacy model string (the
+reference's grammar has none)."""
 import copy
 import re
 from typing import List

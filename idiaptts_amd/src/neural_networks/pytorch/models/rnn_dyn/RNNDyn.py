@@ -5,7 +5,9 @@ TransposingWrapper.py).
 state_dict() keys and shapes equal the reference's, so its checkpoints load unchanged:
 FF group `<i>.module.<k>.weight/bias` with k = index of the Linear (or LayerNorm) inside the nn.Sequential
 (non-linearity / dropout modules keep their slots), VAE group `<i>.module.0.linear.weight` (pooling groups have no
-parameters), RNN group `<i>.module.weight_ih_l0[_reverse]`, `<i>.h_0`, `<i>.c_0`, Conv1d group `<i>.module.<k>.weight/bias` as FF groups; the group index starts at 1
+parameters), RNN group `<i>.module.weight_ih_l0[_reverse]`, `<i>.h_0`, `<i>.c_0`, Conv1d group `<i>.module.<k>.weight/bias` as FF groups,
+TransformerEncoderLayer group `<i>.module.<k>.self_attn.in_proj_weight`, `.self_attn.out_proj.weight`, `.linear1`, `.linear2`,
+`.norm1`, `.norm2` with k = index of the block; the group index starts at 1
 because `emb_groups` takes slot 0 of the ModuleList.
 """
 import copy
@@ -17,7 +19,7 @@ from idiaptts_amd import ops
 from idiaptts_amd.nn.functional import (ChainDropout, DropoutFunction, LinearChainFunction, ValidRows,
                                         default_dropout_stream, padding_is_identical, padding_rows_identical)
 from idiaptts_amd.nn.modules import (GRU, LSTM, RNN, Conv1dAct, LayerNormAct, LinearAct, MeanPooling, SelectLastPooling,
-                                     VanillaVAE)
+                                     TransformerEncoderLayer, VanillaVAE)
 
 # the torch.nn activations a Linear group fuses (default arguments, as the reference's `getattr(nn, nonlin)()`)
 LINEAR_NONLINS = tuple(ops.ACT_TORCH_NAME.values())
@@ -379,6 +381,84 @@ class CNNWrapper(nn.Module):
         return output, kwargs
 
 
+class TransformerWrapper(nn.Module):
+    """A self-attention layer group: `LayerConfig("TransformerEncoderLayer", num_layers=n, d_model=.., nhead=..,
+    dim_feedforward=.., batch_first=..)`, which the reference's FFWrapper builds as `num_layers` times
+    `torch.nn.TransformerEncoderLayer(**kwargs)` in an nn.Sequential named `module` (FFWrapper.py:62-73): the same
+    state-dict keys, here on nn.modules.TransformerEncoderLayer.  A `LayerConfig(dropout=p)` puts a Dropout(p) behind
+    each block, as FFWrapper does.  The group takes the padded tensor and the lengths, never the valid rows.
+
+    Two keyword arguments are this package's own (the reference would hand them to torch and fail):
+    mask_padding (default False): False reproduces the reference, which passes no mask, so padded positions are keys
+        and an utterance's output depends on how far its batch is padded; True restricts the keys of every utterance
+        to its own length (torch's src_key_padding_mask) and is the recommended setting.
+    layer_dropout (default 0.1): the dropout inside the block, in [0, 1).  LayerConfig's own `dropout` never reaches
+        torch's constructor in the reference, so its blocks always train with torch's default of 0.1; the default
+        here is the same, and 0 turns it off.
+
+    d_model must be the group's input width and a `batch_first` among the kwargs must be the model's (the reference
+    silently attends across the batch axis otherwise); without one the model's layout is used.  A `nonlin` is
+    refused: the block has its own activation."""
+
+    OWN_KWARGS = ("mask_padding", "layer_dropout")
+
+    def __init__(self, in_dim, layer_config, batch_first=True):
+        super().__init__()
+        if layer_config.type != "TransformerEncoderLayer":
+            raise NotImplementedError("Layer type {} is not a self-attention group.".format(layer_config.type))
+        if layer_config.nonlin is not None:
+            raise NotImplementedError("TransformerEncoderLayer group nonlin={}: not implemented, the block applies "
+                                      "its own activation.".format(layer_config.nonlin))
+        kwargs = dict(layer_config.kwargs)
+        self.mask_padding = bool(kwargs.pop("mask_padding", False))
+        layer_dropout = float(kwargs.pop("layer_dropout", 0.1))
+        if not 0.0 <= layer_dropout < 1.0:
+            raise ValueError("TransformerEncoderLayer group layer_dropout={} is outside [0, 1).".format(layer_dropout))
+        if "d_model" not in kwargs or "nhead" not in kwargs:
+            raise ValueError("TransformerEncoderLayer group ({}): d_model and nhead are required.".format(layer_config))
+        if kwargs["d_model"] != in_dim:
+            raise ValueError("TransformerEncoderLayer group d_model={} does not match the group's input of {} "
+                             "features.".format(kwargs["d_model"], in_dim))
+        if bool(kwargs.setdefault("batch_first", bool(batch_first))) != bool(batch_first):
+            raise ValueError("TransformerEncoderLayer group batch_first={} in a model with batch_first={}: the block "
+                             "would attend across the batch axis.".format(kwargs["batch_first"], batch_first))
+        self.batch_first = batch_first
+        layers = []
+        for _ in range(layer_config.num_layers):
+            layers.append(TransformerEncoderLayer(dropout=layer_dropout, **kwargs))
+            if layer_config.dropout > 0.0:
+                layers.append(Dropout(layer_config.dropout))
+        self.module = nn.Sequential(*layers)
+        self.out_dim = in_dim
+        self.number_layers(0)
+
+    def number_layers(self, first):
+        """The blocks take the indices first, first + 1, ... as their salts, a dropout behind a block that block's
+        index; returns the next index."""
+        idx = first - 1
+        for m in self.module:
+            if isinstance(m, Dropout):
+                m.salt = max(idx, 0)
+            else:
+                idx += 1
+                m.salt = idx
+        return idx + 1
+
+    def init_hidden(self, batch_size=1):
+        pass
+
+    def forward(self, input_, **kwargs):
+        lengths = kwargs.get("seq_lengths_input") if self.mask_padding else None
+        if lengths is not None:
+            lengths = self.module[0].key_lengths(input_, lengths)       # one upload for all blocks
+        for m in self.module:
+            if isinstance(m, TransformerEncoderLayer):
+                input_ = m(input_, lengths=lengths, mask_padding=lengths is not None)
+            else:
+                input_ = m(input_)
+        return input_, kwargs
+
+
 class RNNDyn(nn.ModuleList):
 
     def __init__(self, config):
@@ -402,6 +482,8 @@ class RNNDyn(nn.ModuleList):
                     raise NotImplementedError("{} groups are outside the accelerated path (SURVEY.md "
                                               "section 2).".format(layer_config.type))
                 layer = CNNWrapper(in_dim, layer_config, config.batch_first)
+            elif layer_config.type == "TransformerEncoderLayer":
+                layer = TransformerWrapper(in_dim, layer_config, config.batch_first)
             else:
                 layer = FFWrapper(in_dim, layer_config, config.batch_first)
             in_dim = layer.out_dim
@@ -412,7 +494,7 @@ class RNNDyn(nn.ModuleList):
             self.append(layer)
             self.layer_groups.append(layer)
             # the salt of a dropout is the index in the model of the layer in front of it
-            if isinstance(layer, FFWrapper):
+            if isinstance(layer, (FFWrapper, TransformerWrapper)):
                 n_layers = layer.number_layers(n_layers)
             else:
                 n_layers += layer_config.num_layers
@@ -444,11 +526,12 @@ class RNNDyn(nn.ModuleList):
                 rows, chain = (rows[0], run_linear_chain(rows[1], chain)), []
 
         # After a Conv1d group the padding positions no longer hold one common row (those just past each length mix
-        # in valid frames), so no later group may stand one representative row in for them.
-        after_conv = False
+        # in valid frames), and after a self-attention group neither (every position attends its own utterance's
+        # keys), so no later group may stand one representative row in for them.
+        padding_mixed = False
         for group_idx, module in enumerate(self.layer_groups):
             affected = [emb for emb in self.emb_groups.values() if self._affects(emb, group_idx)]
-            if isinstance(module, FFWrapper) and not affected and not after_conv:
+            if isinstance(module, FFWrapper) and not affected and not padding_mixed:
                 if rows is None:
                     vr = module.valid_rows_for(input_, kwargs)
                     if vr is not None:
@@ -466,8 +549,8 @@ class RNNDyn(nn.ModuleList):
                 input_, rows = rows[0].unpack(rows[1]), None
             for emb in affected:
                 input_ = torch.cat((input_, embeddings[emb.name]), dim=2)
-            after_conv = after_conv or isinstance(module, CNNWrapper)
-            if after_conv and padding_is_identical():
+            padding_mixed = padding_mixed or isinstance(module, (CNNWrapper, TransformerWrapper))
+            if padding_mixed and padding_is_identical():
                 with padding_rows_identical(False):
                     input_, kwargs = module(input_, **kwargs)
             else:

@@ -1,5 +1,5 @@
 from .Config import Config, config_from_legacy_string  # noqa: F401
-from .RNNDyn import CNNWrapper, FFWrapper, RNNDyn, RNNWrapper  # noqa: F401
+from .RNNDyn import CNNWrapper, FFWrapper, RNNDyn, RNNWrapper, TransformerWrapper  # noqa: F401
 
 
 def convert_legacy_to_config(in_dim, hparams):

@@ -643,6 +643,36 @@ int itts_layernorm_bwd(const float* d_dy, int64_t lddy, const float* d_x, int64_
                        const float* d_gamma, float* d_dx, int64_t lddx, float* d_dgamma,
                        float* d_dbeta, int64_t N, int D, int act, void* d_workspace, void* stream);
 
+/* ---- multi-head self-attention (torch.nn.MultiheadAttention inside torch.nn.TransformerEncoderLayer, which the
+ *      reference reaches through rnn_dyn/FFWrapper.py:62-73; csrc/attention.hip) ---------------------------------
+ * o = softmax(q k^T * scale) v per utterance b and head h, all float32, without a [T, T] tensor in global memory
+ * (online softmax over key tiles of 32).  d_qkv [rows, 3 D] holds q | k | v per row as the in-projection writes
+ * it, head h in columns h * dh .. (h + 1) * dh of each third, D = H * dh; d_o [rows, D].  Row of (b, t) =
+ * b * stride_b + t * stride_t, so [B, T, .] (stride_b = T, stride_t = 1) and [T, B, .] (1, B) both work.
+ * d_klen [B] (int32, device): query t of utterance b attends keys 0 .. klen[b] - 1, for EVERY t < T;
+ * 1 <= klen[b] <= T (not checked on the device: a larger value is clamped to T, a smaller one to 1).  Rows of
+ * k / v at and beyond klen[b] are never used (they may hold NaN).  NULL d_klen: klen = T.  scale = 1 / sqrt(dh).
+ * d_lse [B, H, T] (itts_attention_workspace_bytes) receives ln sum_k exp(score) per query for the backward.
+ * p > 0: dropout on the softmax probabilities before P v (DropRule of csrc/dropout.h: key = seed, salt = salt),
+ * element (row = (b * H + h) * T + t, col = key): the mask depends on b, h, t and T, so utterances of a batch
+ * draw independent masks, as in torch; p == 0 runs the kernel without a generator.
+ * The order of every sum depends on klen[b] and the tile sizes only: the same bits for any B, T and position.
+ * Envelope (else ITTS_E_INVALID before any device work): dh a multiple of 4 in 4 .. 128 (computed at
+ * the next multiple of 32), D <= 1024,
+ * 1 <= T <= 32768, B * H <= 65535, strides >= 1; B == 0 succeeds and does nothing. */
+int64_t itts_attention_workspace_bytes(int B, int H, int T);
+int itts_attention_fwd(const float* d_qkv, float* d_o, const int32_t* d_klen, float* d_lse, int B, int T, int H,
+                       int dh, int64_t stride_b, int64_t stride_t, double p, uint64_t seed, uint32_t salt,
+                       void* stream);
+/* d_dqkv [rows, 3 D] = (dq | dk | dv) from d_do [rows, D], the forward's d_qkv, d_o and d_lse and the same rule.
+ * Every element of the B * T addressed rows is written exactly once (dk / dv rows at and beyond klen[b]: zero).
+ * P is recomputed from q, k and the log-sum-exp; the mask is recomputed.  Three launches: delta = rowsum(do * o);
+ * dk / dv, one workgroup per 128 keys sweeping the query tiles; dq, one workgroup per 128 queries sweeping the key
+ * tiles.  No atomics and no waiting between workgroups: repeated calls give identical bits. */
+int itts_attention_bwd(const float* d_do, const float* d_qkv, const float* d_o, const int32_t* d_klen,
+                       const float* d_lse, float* d_dqkv, int B, int T, int H, int dh, int64_t stride_b,
+                       int64_t stride_t, double p, uint64_t seed, uint32_t salt, void* stream);
+
 /* ---- all-pass frequency warping, the VTLN layer (csrc/allpass.hip) ------------------------------------------
  * Rows of D = nb * N floats are nb blocks of N cepstral coefficients, each warped by the row's own factor:
  * y_b = x_b' W(alpha), W the N x N all-pass matrix of the recursion W[0][0] = 1, W[0][c] = 0,
