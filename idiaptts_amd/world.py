@@ -326,6 +326,9 @@ def mel_inverse_tables(fs, n_fft, n_mels, dtype=np.float32):
         filt[m] = (np.searchsorted(j, m - 1, "left"), np.searchsorted(j, m, "left"), np.searchsorted(j, m, "right"))
     pinv_t = np.zeros((n_mels, KP))
     pinv_t[:, :K] = np.linalg.pinv(A).T
+    # a bin in no filter (0 Hz, the Nyquist bin) is a zero column of A and a zero row of pinv(A); the SVD leaves
+    # 1e-17 there, which no iteration would move (its gradient is 0): all-negative bands would not invert to 0
+    pinv_t[:, :K][:, ~A.any(axis=0)] = 0.0
     inv_l = 1.0 / float(np.linalg.eigvalsh(A @ A.T)[-1])
     return bin_j, bin_w, filt, pinv_t, inv_l
 

@@ -11,10 +11,10 @@ import numpy as np
 
 def window(n_fft, win_length=None):
     """Periodic Hann window of win_length points (scipy.signal.get_window("hann", fftbins=True)), zero-padded to
-    n_fft and centred (librosa.util.pad_center)."""
+    n_fft and centred (librosa.util.pad_center).  A window of one point is 1 (scipy's rule for every window)."""
     win_length = n_fft if win_length is None else win_length
     n = np.arange(win_length)
-    w = 0.5 - 0.5 * np.cos(2.0 * np.pi * n / win_length)
+    w = 0.5 - 0.5 * np.cos(2.0 * np.pi * n / win_length) if win_length > 1 else np.ones(1)
     lpad = (n_fft - win_length) // 2
     return np.pad(w, (lpad, n_fft - win_length - lpad))
 
