@@ -3,10 +3,11 @@
 // zero.  The dense product multiplies by those zeros; here every row of x becomes a list of its (k, value) pairs once
 // per batch (sparse_rows_build_kernel), and the forward product walks the lists against a slab of w^T held in LDS
 // (sparse_linear_fwd_kernel): per non-zero one 16-byte LDS read and four fmaf give four outputs.
-//   * roofline: instruction issue.  A list slot of four rows costs a wave about seven instructions (two DPP
-//     broadcasts, the slab address, a ds_read_b128, two packed fmaf and its share of the loads and loop), and the
-//     walk runs to the longest of four lists; the LDS reads themselves (nnz x N x 4 bytes at 256 B/clk/CU) take
-//     under a fifth of the kernel's time.
+//   * roofline: instruction issue and LDS reads side by side.  A list slot of four rows costs a wave four vector
+//     instructions (the slab address, an add that carries the DPP broadcast of the entry's byte offset; the broadcast
+//     of the value; two packed fmaf) and one ds_read_b128 (4 LDS cycles), and the walk runs to the longest of four
+//     lists.  No wave waits for memory inside an ordinary group: what a group needs is requested a group ahead, and
+//     the wait for it leaves the wave's own store of y in flight ("Load schedule and slot").
 //   * what does not depend on the density: the slab fill (w read along k, 16 bytes a lane where w's rows allow it),
 //     the store of y and the activation.
 #include <algorithm>
@@ -25,7 +26,14 @@ constexpr int kFwdWaves = 16;         // one workgroup per CU (LDS), four waves 
 constexpr int kRowsPerWave = 4;       // a quarter wave per row: 16 lanes x 4 columns
 constexpr int kStep = 8;              // list slots per trip of the walk; the build pads every list to whole trips
 constexpr int kFetch = 16;            // list entries per load: one per lane of a quarter wave
+constexpr int kAhead = 48;            // entries of every row that are requested a group of rows ahead of their walk
+constexpr int kAheadFetches = kAhead / kFetch;
+constexpr int kSlabRowBytes = kSlabCols * 4;
 constexpr int kFillTrips = kSparseMaxK / 4 / kFwdWaves;   // 16-byte loads of a lane in the slab fill
+static_assert(kAhead % kFetch == 0 && kFetch == 2 * kStep, "the walk takes a fetch as two trips");
+
+typedef float floatx4 __attribute__((ext_vector_type(4)));
+typedef int intx2 __attribute__((ext_vector_type(2)));
 
 static std::atomic<int64_t> g_sparse_path[3];
 
@@ -84,20 +92,30 @@ __global__ __launch_bounds__(256) void sparse_rows_build_kernel(const uint32_t* 
   }
 }
 
-// Slot J of the 16 list entries a quarter wave holds, entry j in its lane j: the DPP row broadcast hands lane J's
-// (k, value) to the quarter's 16 lanes, which read their 16 bytes of slab row k and do four fmaf (two packed ones).
+// Slot J of the 16 list entries a quarter wave holds, entry j in its lane j, e.x already the byte offset of slab row
+// k (slab_offsets): the DPP row broadcast hands lane J's (offset, value) to the quarter's 16 lanes, which read their
+// 16 bytes of the slab row and do four fmaf.  Four VALU instructions: the offset's broadcast rides on the add of the
+// lane's own offset (v_add_u32_dpp), the value's is a v_mov_b32_dpp, and two v_pk_fma_f32.  row_newbcast writes every
+// lane, so the broadcasts need no defined `old`: bound_ctrl spares the v_mov that would zero it.
 template <int J>
-__device__ __forceinline__ void walk_slot(const float4* slab4, int i16, int2 e, float4& acc) {
-  const int k = __builtin_amdgcn_update_dpp(0, e.x, 0x150 + J, 0xf, 0xf, false);   // row_newbcast:J
-  const float v = __int_as_float(__builtin_amdgcn_update_dpp(0, e.y, 0x150 + J, 0xf, 0xf, false));
-  const float4 wk = slab4[k * (kSlabCols / 4) + i16];
+__device__ __forceinline__ void walk_slot(const char* slab, int lane_off, int2 e, float4& acc) {
+  const int off = __builtin_amdgcn_update_dpp(0, e.x, 0x150 + J, 0xf, 0xf, true);   // row_newbcast:J
+  const float v = __int_as_float(__builtin_amdgcn_update_dpp(0, e.y, 0x150 + J, 0xf, 0xf, true));
+  const float4 wk = *reinterpret_cast<const float4*>(slab + (off + lane_off));
   acc.x = fmaf(v, wk.x, acc.x); acc.y = fmaf(v, wk.y, acc.y);
   acc.z = fmaf(v, wk.z, acc.z); acc.w = fmaf(v, wk.w, acc.w);
 }
 template <int FIRST, int... U>
-__device__ __forceinline__ void walk_trip(const float4* slab4, int i16, int2 e, float4& acc,
+__device__ __forceinline__ void walk_trip(const char* slab, int lane_off, int2 e, float4& acc,
                                           std::integer_sequence<int, U...>) {
-  (walk_slot<FIRST + U>(slab4, i16, e, acc), ...);
+  (walk_slot<FIRST + U>(slab, lane_off, e, acc), ...);
+}
+// the 16 entries of one fetch: k -> byte offset of slab row k, once per fetched entry
+__device__ __forceinline__ int2 slab_offsets(int2 e) { return make_int2(e.x * kSlabRowBytes, e.y); }
+// the two trips of a fetch, for a quarter whose list has `left` entries from this fetch's first on
+__device__ __forceinline__ void walk_fetch(const char* slab, int lane_off, int2 e, int left, float4& acc) {
+  if (left > 0) walk_trip<0>(slab, lane_off, e, acc, std::make_integer_sequence<int, kStep>());
+  if (left > kStep) walk_trip<kStep>(slab, lane_off, e, acc, std::make_integer_sequence<int, kStep>());
 }
 
 // Workgroup = (64-column slab of w^T in LDS, row range); wave = four rows at a time, one per quarter wave; lane = four
@@ -108,10 +126,11 @@ __device__ __forceinline__ void walk_trip(const float4* slab4, int i16, int2 e, 
 // and does four fmaf (two packed ones).  The neutral entries that fill a list's last trip read the slab's extra
 // all-zero row K with a zero value: acc + 0 * 0.  The slab's rows are 64 floats apart, so the four rows a
 // ds_read_b128 touches all start on bank 0 and every 16 lanes the hardware serves together cover the 64 banks once,
-// whatever the four k are.  The walk runs to the longest of the four lists in trips of kStep slots, its loads one
-// fetch of kFetch entries ahead, and a quarter whose list has ended sits the trips out; the first fetch and the
-// counts of the next four rows are requested before the current rows are walked.  One fmaf chain per output, in
-// ascending k, from +0; the bias is added last.
+// whatever the four k are.  The walk runs to the longest of the four lists in trips of kStep slots, and a quarter
+// whose list has ended sits the trips out.  The counts and the first kAhead entries of the next four rows are
+// requested before the current rows are walked and waited for behind the current rows' store, by a wait that leaves
+// that store in flight; only rows longer than kAhead fetch inside their walk, one fetch of kFetch entries ahead.  One
+// fmaf chain per output, in ascending k, from +0; the bias is added last.
 // (A list entry with k > K would read LDS out of range, which returns zeros; the lists come from the build.)
 // DR: the dropout rule of the dense layers on the output (dropout.h: a lane's four columns are one Philox call), or
 // NoDrop, which carries nothing.
@@ -164,10 +183,42 @@ __global__ __launch_bounds__(kFwdWaves * 64) void sparse_linear_fwd_kernel(
   // rows behind the range re-read the last row and are never used: no branch around a load
   auto row_of = [&](int64_t group) { return m_begin + (group * kRowsPerWave + q); };
   const int i16 = lane & 15;
-  auto fetch = [&](int64_t m, int j0) { return entries[std::min<int64_t>(m, M - 1) * pitch + (j0 + i16)]; };
+  const int last_fetch = (int)pitch - kFetch;   // a fetch never leaves its row: a short pitch re-reads its last block
+  auto fetch = [&](int64_t m, int j0) {
+    return entries[std::min<int64_t>(m, M - 1) * pitch + (std::min(j0, last_fetch) + i16)];
+  };
+  // What a group of four rows needs before its walk: the counts and the first kAhead entries of every row, requested
+  // before the group in front of it is walked.  The four loads are hidden from the compiler's wait counting: counted
+  // by the compiler, the wait for them is a vmcnt(0) (paths with different numbers of loads meet before it), which
+  // also waits for the y store issued behind them.  Vector memory operations retire in order, so wait_ahead<KEEP>
+  // names the registers (nothing reads or moves them between the request and the wait) and leaves only the KEEP
+  // operations issued behind the requests in flight.  Every load and store the compiler counts itself -- the fetches
+  // of a row longer than kAhead, the stores -- is issued behind the requests of its group, so its own waits hold.
+  struct Ahead {
+    int cnt;
+    intx2 e[kAheadFetches];
+  };
+  static_assert(kAheadFetches == 3, "request_ahead and wait_ahead name three fetches");
+  auto request_ahead = [&](int64_t group, Ahead& a) {
+    const int64_t m = std::min<int64_t>(row_of(group), M - 1);
+    const int* pc = counts + m;
+    const int2* pe = entries + m * pitch + i16;
+    const int2 *p0 = pe, *p1 = pe + std::min(kFetch, last_fetch), *p2 = pe + std::min(2 * kFetch, last_fetch);
+    asm volatile("global_load_dword %0, %1, off" : "=v"(a.cnt) : "v"(pc) : "memory");
+    asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(a.e[0]) : "v"(p0) : "memory");
+    asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(a.e[1]) : "v"(p1) : "memory");
+    asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(a.e[2]) : "v"(p2) : "memory");
+  };
+  auto wait_ahead = [&](auto keep, Ahead& a) {
+    // (the s_nop: a 16-byte store may sit right in front, whose data registers the code behind the wait rewrites)
+    asm volatile("s_nop 1\n\ts_waitcnt vmcnt(%4)"
+                 : "+v"(a.cnt), "+v"(a.e[0]), "+v"(a.e[1]), "+v"(a.e[2])
+                 : "n"(decltype(keep)::value)
+                 : "memory");
+  };
   int64_t group = wave;
-  int2 first = fetch(row_of(group), 0);
-  int cnt_next = counts[std::min<int64_t>(row_of(group), M - 1)];
+  Ahead next;
+  request_ahead(group, next);
   __syncthreads();
 
   float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -178,26 +229,61 @@ __global__ __launch_bounds__(kFwdWaves * 64) void sparse_linear_fwd_kernel(
     if (n + 2 < N) bv.z = bias[n + 2];
     if (n + 3 < N) bv.w = bias[n + 3];
   }
-  const bool vec_store = wide_out && n + 4 <= store_cols;
-  const int last_fetch = (int)pitch - kFetch;
+  const char* slab_bytes = reinterpret_cast<const char*>(slab4);
+  const int lane_off = i16 * 16;
+  // (the bias is used here so that the compiler waits for it here, and not at its uses in every group's epilogue)
+  asm volatile("" ::"v"(bv.x), "v"(bv.y), "v"(bv.z), "v"(bv.w));
+  wait_ahead(std::integral_constant<int, 0>{}, next);   // nothing is known to lie behind the first group's requests
 
-  for (; m_begin + group * kRowsPerWave < m_end; group += kFwdWaves) {
-    const int64_t m = row_of(group);
-    const int cnt = m < m_end ? cnt_next : 0;
-    int2 cur = first;
-    first = fetch(row_of(group + kFwdWaves), 0);
-    cnt_next = counts[std::min<int64_t>(row_of(group + kFwdWaves), M - 1)];
-    int longest = std::max(cnt, __shfl_xor(cnt, 16, 64));
-    longest = __builtin_amdgcn_readfirstlane(std::max(longest, __shfl_xor(longest, 32, 64)));
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    // a quarter whose list has ended sits the trips out (the loads stay outside the branch and inside the row)
-    for (int j0 = 0; j0 < longest; j0 += kFetch) {
-      const int2 nxt = fetch(m, std::min(j0 + kFetch, last_fetch));
-      if (j0 < cnt) walk_trip<0>(slab4, i16, cur, acc, std::make_integer_sequence<int, kStep>());
-      if (j0 + kStep < cnt) walk_trip<kStep>(slab4, i16, cur, acc, std::make_integer_sequence<int, kStep>());
-      cur = nxt;
-    }
-    if (m < m_end) {
+  // WIDE: y's rows are 16-byte aligned and a lane's four columns are stored whole or not at all (store_cols is a
+  // multiple of four then).  The store is a buffer store that every wave issues exactly once per group, outside any
+  // branch -- a lane with nothing to store carries an offset beyond the buffer, which the hardware drops -- so exactly
+  // one store lies behind a group's requests when the next group is about to start, and the wait there, vmcnt(1),
+  // leaves it in flight: no wave waits for its own output.  The buffer is this range's rows of y; the host keeps a
+  // range below 2 GB.
+  // Not WIDE (a pitch or pointer of y that is not 16-byte aligned): up to four dword stores a lane, behind branches, so
+  // their number is not known and the wait is a full one (vmcnt(0)), which also waits for the stores.
+  auto run = [&](auto wide) {
+    constexpr bool WIDE = decltype(wide)::value;
+    const int64_t range_rows = std::max<int64_t>(m_end - m_begin, 1);
+    const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(
+        y + m_begin * ldy, 0, WIDE ? (int)(((range_rows - 1) * ldy + store_cols) * 4) : 0, 0x00020000);
+    for (; m_begin + group * kRowsPerWave < m_end; group += kFwdWaves) {
+      const int64_t m = row_of(group);
+      const Ahead cur = next;
+      request_ahead(group + kFwdWaves, next);
+      const int cnt = m < m_end ? cur.cnt : 0;
+      int longest = std::max(cnt, __shfl_xor(cnt, 16, 64));
+      longest = __builtin_amdgcn_readfirstlane(std::max(longest, __shfl_xor(longest, 32, 64)));
+      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+      // the first kAhead entries, from registers; a quarter whose list has ended sits the trips out
+      auto walk_ahead = [&]() {
+#pragma unroll
+        for (int f = 0; f < kAheadFetches; ++f)
+          if (f * kFetch < longest)
+            walk_fetch(slab_bytes, lane_off, slab_offsets(make_int2(cur.e[f].x, cur.e[f].y)), cnt - f * kFetch, acc);
+      };
+      if (longest <= kAhead) {
+        walk_ahead();   // the ordinary group: no wait for vector memory between its requests and its store
+      } else {
+        // Rows longer than kAhead: the fetches behind the first kAhead entries are loads the compiler counts, the
+        // first requested here, the others one fetch ahead of their walk, each waited for before its walk.  This is a
+        // branch of its own, with its own copy of the walk above, and every path through it uses every register it
+        // loads into (`landed`): a load that could be pending where the two branches meet again, or at the next
+        // group, puts a full wait into the ordinary group's walk.
+        auto landed = [](int2 e) { asm volatile("" ::"v"(e.x), "v"(e.y)); };
+        int2 more = fetch(m, kAhead);
+        walk_ahead();
+        int j0 = kAhead;
+        for (; j0 + kFetch < longest; j0 += kFetch) {
+          const int2 nxt = fetch(m, j0 + kFetch);
+          landed(more);
+          walk_fetch(slab_bytes, lane_off, slab_offsets(more), cnt - j0, acc);
+          more = nxt;
+        }
+        landed(more);
+        walk_fetch(slab_bytes, lane_off, slab_offsets(more), cnt - j0, acc);
+      }
       float4 o;
       o.x = n < N ? act_fwd_af<AF>(acc.x + bv.x, act) : 0.f;
       o.y = n + 1 < N ? act_fwd_af<AF>(acc.y + bv.y, act) : 0.f;
@@ -208,17 +294,26 @@ __global__ __launch_bounds__(kFwdWaves * 64) void sparse_linear_fwd_kernel(
         o.x = dr.apply(o.x, dw.w[0]); o.y = dr.apply(o.y, dw.w[1]);
         o.z = dr.apply(o.z, dw.w[2]); o.w = dr.apply(o.w, dw.w[3]);
       }
-      float* yr = y + m * ldy + n;
-      if (vec_store) {
-        *reinterpret_cast<float4*>(yr) = o;
+      if constexpr (WIDE) {
+        const bool stores = m < m_end && n + 4 <= store_cols;
+        const uint32_t vo = stores ? (uint32_t)(((m - m_begin) * ldy + n) * 4) : 0xfffffff0u;
+        floatx4 ov = {o.x, o.y, o.z, o.w};
+        __builtin_amdgcn_raw_buffer_store_b128(ov, yrs, vo, 0, 0);
+        wait_ahead(std::integral_constant<int, 1>{}, next);
       } else {
+        if (m < m_end) {
+        float* yr = y + m * ldy + n;
         if (n < store_cols) yr[0] = o.x;
         if (n + 1 < store_cols) yr[1] = o.y;
         if (n + 2 < store_cols) yr[2] = o.z;
         if (n + 3 < store_cols) yr[3] = o.w;
+        }
+        wait_ahead(std::integral_constant<int, 0>{}, next);
       }
     }
-  }
+  };
+  if (wide_out) run(std::true_type{});
+  else run(std::false_type{});
 }
 
 }  // namespace itts
@@ -272,9 +367,11 @@ static int launch_sparse_fwd(const void* d_lists, const float* d_w, const float*
   const char* base = static_cast<const char*>(d_lists);
   const int slabs = (N + kSlabCols - 1) / kSlabCols;
   // one workgroup per CU where the shape allows it; a range is worth its slab fill from about 64 rows on
-  const int64_t ranges = std::max<int64_t>(1, std::min<int64_t>(fwd_compute_units() / slabs, (M + 63) / 64));
+  int64_t ranges = std::max<int64_t>(1, std::min<int64_t>(fwd_compute_units() / slabs, (M + 63) / 64));
   // the pad columns inside a 16-byte row pitch are written as zeros, as the dense epilogue does
-  const bool wide_out = (ldy % 4 == 0) && aligned16(d_y);
+  const bool wide_out = (ldy % 4 == 0) && aligned16(d_y) && ldy < (int64_t(1) << 28);
+  // the 16-byte stores address a range's rows of y with 32-bit byte offsets: more ranges where y is that large
+  if (wide_out) ranges = std::max(ranges, (M * ldy * 4 >> 31) + 1);
   const int store_cols = wide_out ? (int)std::min<int64_t>((N + 3) / 4 * 4, ldy) : N;
   hipLaunchKernelGGL((sparse_linear_fwd_kernel<AF, DR>), dim3((unsigned)(slabs * ranges)), dim3(kFwdWaves * 64),
                      (size_t)(K + 1) * kSlabCols * 4, s, reinterpret_cast<const int*>(base + l.counts_off),

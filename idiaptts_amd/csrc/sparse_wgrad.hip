@@ -320,8 +320,9 @@ typedef float floatx16 __attribute__((ext_vector_type(16)));
 // the quarter's 16 lanes, which read their 16 bytes of that dz row and do four fmaf.
 template <int J>
 __device__ __forceinline__ void col_slot(const char* buf, int lane_off, int2 e, float4& acc) {
-  const int off = __builtin_amdgcn_update_dpp(0, e.x, 0x150 + J, 0xf, 0xf, false);   // row_newbcast:J
-  const float v = __int_as_float(__builtin_amdgcn_update_dpp(0, e.y, 0x150 + J, 0xf, 0xf, false));
+  // (row_newbcast writes every lane: with bound_ctrl nothing zeroes the destinations first)
+  const int off = __builtin_amdgcn_update_dpp(0, e.x, 0x150 + J, 0xf, 0xf, true);   // row_newbcast:J
+  const float v = __int_as_float(__builtin_amdgcn_update_dpp(0, e.y, 0x150 + J, 0xf, 0xf, true));
   const float4 d = *reinterpret_cast<const float4*>(buf + off + lane_off);
   acc.x = fmaf(v, d.x, acc.x); acc.y = fmaf(v, d.y, acc.y);
   acc.z = fmaf(v, d.z, acc.z); acc.w = fmaf(v, d.w, acc.w);
