@@ -260,6 +260,12 @@ _SIGNATURES = {
                                          c_int64, c_int64, _P]),
     "itts_rnn_cell_step": (c_int, [c_int, c_int, _P, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_int, c_int,
                                    _P, c_int64, _P, c_int64, _P]),
+    "itts_dtw_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
+    "itts_dtw_plan": (c_int, [c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "itts_dtw_align": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, c_int, POINTER(ctypes.c_int32),
+                               POINTER(ctypes.c_int32), c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int64, _P,
+                               c_int64, _P]),
+    "itts_dtw_step_probe": (c_int, [c_int, c_int, _P, _P]),
 }
 
 

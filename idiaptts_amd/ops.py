@@ -2700,3 +2700,148 @@ def rnn_cell_step(kind, gi, gh, h, c=None, b_hh=None, act=ACT_TANH):
                                     _ptr(b_hh), _ptr(h), _rows(h, "h"), _ptr(c), _rows(c, "c") if c is not None else 0,
                                     B, H, _ptr(h_out), H, _ptr(c_out), H, _stream()), "itts_rnn_cell_step")
     return h_out, c_out
+
+
+# ------------------------------------------------------------------------------- dynamic time warping
+DTW_MAX_T, DTW_MAX_D = 4096, 128                # csrc/dtw.hip
+# bytes of decisions (one per cell of the padded grids) a single itts_dtw_align call may hold; dtw_align splits the
+# batch into groups under it (256 pairs of 1 600 x 1 600 frames are 0.66 GB: one group)
+DTW_WORKSPACE_CAP = 1 << 30
+
+
+def _dtw_check_sizes(T1, T2, D):
+    for name, v in (("T1", T1), ("T2", T2)):
+        if not 1 <= int(v) <= DTW_MAX_T:
+            raise ValueError("dtw: {} = {} is outside 1 .. {}".format(name, int(v), DTW_MAX_T))
+    if not 1 <= int(D) <= DTW_MAX_D:
+        raise ValueError("dtw: D = {} is outside 1 .. {}".format(int(D), DTW_MAX_D))
+
+
+def dtw_plan(T1, T2, D):
+    """What a DTW of a [T1, D] against a [T2, D] sequence uses (itts_dtw_plan; no device work): the forward kernel's
+    tile edges `col_block` and `rows_per_pass`, and `cell_bytes_x8`, 8 x the bytes of decisions stored per cell."""
+    _dtw_check_sizes(T1, T2, D)
+    W, R, c8 = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    if _lib.load().itts_dtw_plan(int(T1), int(T2), int(D), ctypes.byref(W), ctypes.byref(R), ctypes.byref(c8)) != 0:
+        raise ValueError("dtw_plan: ({}, {}, {}) is outside the envelope".format(T1, T2, D))
+    return {"col_block": W.value, "rows_per_pass": R.value, "cell_bytes_x8": c8.value}
+
+
+def dtw_step_probe(mode, steps):
+    """Queues `steps` empty steps of a dependency chain in one workgroup (itts_dtw_step_probe; mode "barrier": 256
+    threads, one workgroup barrier a step; "shift": one wave, one lane shift a step) and returns the 256 doubles it
+    leaves; the caller times it (scripts/bench_dtw.py)."""
+    out = torch.empty(256, dtype=torch.float64, device="cuda")
+    _lib.check(_lib.load().itts_dtw_step_probe({"barrier": 0, "shift": 1}[mode], int(steps), _ptr(out), _stream()),
+               "itts_dtw_step_probe")
+    return out
+
+
+def _dtw_side(t, lens, name):
+    """(tensors or padded tensor, lengths, D) of one side of dtw_align, sizes checked (ValueError) on the host."""
+    if isinstance(t, (list, tuple)):
+        if len(t) < 1:
+            raise ValueError("dtw_align: {} holds B = 0 sequences".format(name))
+        for u in t:
+            if u.dim() != 2:
+                raise ValueError("dtw_align: every sequence of {} must be [T, D], got {}".format(name, tuple(u.shape)))
+        D = int(t[0].shape[1])
+        for b, u in enumerate(t):
+            if int(u.shape[1]) != D:
+                raise ValueError("dtw_align: {}[{}] has D = {}, {}[0] has D = {}".format(name, b, int(u.shape[1]), name, D))
+        given = [int(u.shape[0]) for u in t]
+        if lens is not None and [int(v) for v in lens] != given:
+            raise ValueError("dtw_align: {}_lens = {} do not match the sequences' lengths {}".format(
+                name, [int(v) for v in lens], given))
+        return list(t), given, D
+    if t.dim() != 3:
+        raise ValueError("dtw_align: {} must be [B, T, D] or a list of [T, D], got {}".format(name, tuple(t.shape)))
+    if lens is None:
+        raise ValueError("dtw_align: {}_lens is needed with a padded {}".format(name, name))
+    lens = [int(v) for v in (lens.tolist() if hasattr(lens, "tolist") else lens)]
+    if int(t.shape[0]) < 1 or len(lens) != int(t.shape[0]):
+        raise ValueError("dtw_align: {} holds B = {} sequences, {}_lens {}".format(name, int(t.shape[0]), name, len(lens)))
+    for b, v in enumerate(lens):
+        if v > int(t.shape[1]):
+            raise ValueError("dtw_align: {}_lens[{}] = {} is longer than the buffer's {} frames".format(
+                name, b, v, int(t.shape[1])))
+    return t, lens, int(t.shape[2])
+
+
+def _dtw_groups(t1, t2, cap):
+    """Consecutive pairs whose padded decision grids fit `cap` bytes together (a pair on its own always goes)."""
+    groups, g0, m1, m2 = [], 0, 0, 0
+    for b in range(len(t1)):
+        n1, n2 = max(m1, t1[b]), max(m2, t2[b])
+        if b > g0 and (b - g0 + 1) * n1 * n2 > cap:
+            groups.append((g0, b))
+            g0, n1, n2 = b, t1[b], t2[b]
+        m1, m2 = n1, n2
+    groups.append((g0, len(t1)))
+    return groups
+
+
+def dtw_align(x, x_lens, y, y_lens, band=None, return_path=True):
+    """Dynamic time warping of B pairs (itts_dtw_align): x / y padded [B, T, D] tensors with their lengths, or lists of
+    [T, D] tensors (lengths None); float32 or float64 (anything else, or a mixed pair, is widened to float64).  Local
+    distance: the Euclidean norm; steps (1,1), (1,0), (0,1), ties in that order; all arithmetic float64.  band = r
+    admits |j - round(i (T2-1)/(T1-1))| <= r only (None: no band).
+    -> cost float64 [B], length int32 [B], path int32 [B, Lmax, 2] (rows behind length[b] are -1; None without
+    return_path).  A pair whose band does not connect its corners has cost inf and length 0.  The batch is cut into
+    groups of at most DTW_WORKSPACE_CAP bytes of decisions; a pair's result does not depend on the grouping."""
+    x, t1, D = _dtw_side(x, x_lens, "x")
+    y, t2, Dy = _dtw_side(y, y_lens, "y")
+    if D != Dy:
+        raise ValueError("dtw_align: x has D = {}, y has D = {}".format(D, Dy))
+    if len(t1) != len(t2):
+        raise ValueError("dtw_align: x holds B = {} sequences, y {}".format(len(t1), len(t2)))
+    for b in range(len(t1)):
+        _dtw_check_sizes(t1[b], t2[b], D)
+    if band is not None and int(band) < 0:
+        raise ValueError("dtw_align: band = {} is negative (None: no band)".format(band))
+    band = -1 if band is None else min(int(band), 2 * DTW_MAX_T)
+    B = len(t1)
+    first = x[0] if isinstance(x, list) else x
+    firsty = y[0] if isinstance(y, list) else y
+    dtype = first.dtype if first.dtype == firsty.dtype and first.dtype in (torch.float32, torch.float64) \
+        else torch.float64
+
+    def padded(t, name):
+        if isinstance(t, list):
+            for u in t:
+                if not u.is_cuda:
+                    raise _lib.IttsError("{} must live on the GPU (no CPU fallback)".format(name))
+            t = torch.nn.utils.rnn.pad_sequence([u.to(dtype) for u in t], batch_first=True)
+        elif not t.is_cuda:
+            raise _lib.IttsError("{} must live on the GPU (no CPU fallback)".format(name))
+        t = t.to(dtype)
+        return t if t.stride(2) == 1 else t.contiguous()
+
+    x, y = padded(x, "x"), padded(y, "y")
+    L = _lib.load()
+    dev = x.device
+    cost = torch.empty(B, dtype=torch.float64, device=dev)
+    length = torch.empty(B, dtype=torch.int32, device=dev)
+    paths = []
+    for g0, g1 in _dtw_groups(t1, t2, DTW_WORKSPACE_CAP):
+        n, m1, m2 = g1 - g0, max(t1[g0:g1]), max(t2[g0:g1])
+        nbytes = L.itts_dtw_workspace_bytes(n, m1, m2)
+        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        rows = m1 + m2 - 1
+        path = torch.empty((n, rows, 2), dtype=torch.int32, device=dev) if return_path else None
+        h1 = (ctypes.c_int32 * n)(*t1[g0:g1])
+        h2 = (ctypes.c_int32 * n)(*t2[g0:g1])
+        xg, yg = x[g0:g1], y[g0:g1]
+        _lib.check(L.itts_dtw_align(_ptr(xg), x.stride(1), x.stride(0), _ptr(yg), y.stride(1), y.stride(0),
+                                    1 if dtype == torch.float64 else 0, h1, h2, n, m1, m2, D, band, _ptr(cost[g0:g1]),
+                                    _ptr(length[g0:g1]), _ptr(path), rows, _ptr(work), nbytes, _stream()),
+                   "itts_dtw_align")
+        paths.append(path)
+    if not return_path:
+        return cost, length, None
+    lmax = max(int(length.max().item()), 1)
+    out = torch.full((B, lmax, 2), -1, dtype=torch.int32, device=dev)
+    for (g0, g1), path in zip(_dtw_groups(t1, t2, DTW_WORKSPACE_CAP), paths):
+        keep = min(lmax, path.shape[1])
+        out[g0:g1, :keep] = path[:, :keep]
+    return cost, length, out

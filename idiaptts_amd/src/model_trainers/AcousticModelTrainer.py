@@ -153,9 +153,28 @@ class AcousticModelTrainer(ModularTrainer):
         """{label name: (MCD, F0 RMSE, VDE, BAP distortion) averaged over the ids}; `data` holds
         the post-processed (de-normalised, MLPG-smoothed) network outputs per id, the originals
         are loaded from hparams.world_dir (reference :402-432)."""
+        alignment = getattr(hparams, "metrics_alignment", "truncate")
+        if alignment not in ("truncate", "dtw"):
+            raise ValueError("hparams.metrics_alignment = {!r} is not one of 'truncate', 'dtw'".format(alignment))
         dict_original_post = self.get_output_dict(
             data.keys(), hparams, chunk_size=hparams.get_value("n_frames_per_step", default=1))
         metric_dict = {}
+        if alignment == "dtw":
+            # outputs whose lengths are not the originals' (predicted durations): every score along the DTW path of
+            # the two coded spectra, all ids of a label aligned by one call
+            for label_name in next(iter(data.values())).keys():
+                outs = [WorldFeatLabelGen.convert_to_world_features(
+                    sample=labels[label_name], contains_deltas=False,
+                    num_coded_sps=hparams.num_coded_sps, num_bap=hparams.num_bap) for labels in data.values()]
+                orgs = [WorldFeatLabelGen.convert_to_world_features(
+                    sample=dict_original_post[id_name], contains_deltas=hparams.add_deltas,
+                    num_coded_sps=hparams.num_coded_sps, num_bap=hparams.num_bap) for id_name in data.keys()]
+                per_id = Metrics.get_metrics_dtw_batch(orgs, outs)
+                for id_name, scores in zip(data.keys(), per_id):
+                    self.logger.info("{} {}: MCD {:.3f} dB, F0 RMSE {:.2f} Hz, VDE {:.3f} %, "
+                                     "BAP {:.3f} dB".format(label_name, id_name, *scores))
+                metric_dict[label_name] = list(np.mean(np.array(per_id, dtype=np.float64), axis=0))
+            return metric_dict
         for label_name in next(iter(data.values())).keys():
             per_id = []
             for id_name, labels in data.items():

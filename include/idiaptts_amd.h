@@ -1287,6 +1287,42 @@ int itts_rnn_cell_step(int kind, int act, const float* d_gi, int64_t ldgi, const
                        const float* d_b_hh, const float* d_h, int64_t ldh, const float* d_c, int64_t ldc, int B, int H,
                        float* d_h_out, int64_t ldho, float* d_c_out, int64_t ldco, void* stream);
 
+/* ---- Dynamic time warping of pairs of feature sequences (csrc/dtw.hip; the scores of Metrics.get_metrics_dtw; the
+ *      reference has no counterpart) ---------------------------------------------------------------------------------
+ * Pair b: x[b] [T1_b, D], y[b] [T2_b, D], float32 (is_f64 = 0) or float64 (is_f64 = 1), padded to [B, T1max, D] and
+ * [B, T2max, D]; ld* are elements from one frame to the next, utt* from one pair to the next, D has unit stride.
+ * Nothing behind a length (or behind D in a row) is read.  All arithmetic is float64:
+ *   d(i, j) = sqrt(sum_k (x[i, k] - y[j, k])^2);  C(0, 0) = d(0, 0);
+ *   C(i, j) = d(i, j) + min(C(i-1, j-1), C(i-1, j), C(i, j-1)), a predecessor outside the grid or the band = +inf;
+ *   on equal values the diagonal is taken, then (i-1, j), then (i, j-1).
+ * band = r >= 0 admits cell (i, j) only if |j - centre(i)| <= r, centre(i) = (2 i (T2-1) + (T1-1)) / (2 (T1-1)) in
+ * integer (floor) division, i.e. round-half-up of i (T2-1) / (T1-1); with T1 == 1 the one path is the whole row and
+ * every cell is admitted.  So (0, 0) and (T1-1, T2-1) are always admitted.  band < 0: no band.  A band that does not
+ * connect the two (r below the jump of centre(i) from one row to the next, when T2 > T1) gives cost = +inf.
+ * Outputs: d_cost [B] = C(T1-1, T2-1); d_length [B] = cells on the path, L (0 when the cost is not finite);
+ *   d_path [B, path_rows, 2] int32 (or NULL: no path is written), rows (i, j) from (0, 0) to (T1-1, T2-1), rows
+ *   L .. path_rows - 1 set to -1; path_rows >= T1max + T2max - 1.
+ * d_work: itts_dtw_workspace_bytes(B, T1max, T2max) bytes = B T1max T2max, one byte per cell (0 diagonal, 1 (i-1, j),
+ *   2 (i, j-1)); the only per-cell HBM traffic, cells outside the band are not written; -1 outside the envelope.
+ * One workgroup per pair and one wave per pair for the backtrack; no workgroup waits on another, no atomics: a pair's
+ * bits depend on its own rows, its lengths and the band alone, repeated calls give identical bits.  h_t1 / h_t2 are
+ * host arrays (copied to the device through scope-owned scratch).
+ * Envelope: B >= 1, 1 <= T1_b <= T1max <= 4096, 1 <= T2_b <= T2max <= 4096, 1 <= D <= 128; anything else is
+ *   ITTS_E_INVALID with a message naming the value, before any device work.
+ * itts_dtw_plan (no device work; 0, or -1 outside the envelope): the columns of a block, the rows of a pass (the tile
+ *   edges of the forward kernel) and 8 x the bytes stored per cell. */
+int64_t itts_dtw_workspace_bytes(int B, int T1max, int T2max);
+int itts_dtw_plan(int T1, int T2, int D, int* col_block, int* rows_per_pass, int* cell_bytes_x8);
+int itts_dtw_align(const void* d_x, int64_t ldx, int64_t uttx, const void* d_y, int64_t ldy, int64_t utty, int is_f64,
+                   const int32_t* h_t1, const int32_t* h_t2, int B, int T1max, int T2max, int D, int band,
+                   double* d_cost, int32_t* d_length, int32_t* d_path, int64_t path_rows, void* d_work,
+                   int64_t work_bytes, void* stream);
+/* itts_dtw_step_probe: a measuring aid (scripts/bench_dtw.py).  One workgroup runs `steps` steps of a dependency chain
+ *   with nothing else in them and writes its 256 doubles to d_out: mode 0, 256 threads pass a value to their neighbour
+ *   through LDS with one workgroup barrier a step; mode 1, one wave passes it by a lane shift (the forward kernel's
+ *   step).  (T1 + T2 - 1) x the time of a step is what no tiling of the recurrence gets under. */
+int itts_dtw_step_probe(int mode, int steps, double* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
